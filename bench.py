@@ -6,12 +6,16 @@ launched under torch.distributed.run (one rank per GPU, RCCL). A "step" is one p
 query (lidf_query_f32) over one synthetic 240x320 frame with 64 candidates per ray resident in HBM
 on every rank (BASELINE.json configs[1]; weak scaling: each rank owns one frame), followed — for
 N>1 — by the RCCL all-gather of the per-rank depth maps (the only collective on the path).
-Rank 0 prints ONE JSON line with the metric, the MFMA roofline of the dominant kernel (HIP events
-recorded by the library around lidf_points_fused_kernel on the launch stream) and, at N=1, the CPU
-baseline (the oracle port on the host cores over the same frame in 614,400-point slabs, ~20 s) and
-the kernel's average duration by rocprofv3 --kernel-trace of this same command, run as a child
-process after the timed region (roofline.kernel_ms_rocprof_live; --no-rocprof to skip).
-`python bench.py --gpus N` without a launcher re-executes itself under torch.distributed.run.
+Rank 0 prints ONE JSON line with the metric and the MFMA roofline of the dominant kernel (HIP events
+recorded by the library around lidf_points_fused_kernel on the launch stream).
+A plain run sets up, warms up, times --steps steps and prints that line; nothing else.
+--full adds what takes runs of its own, after the timed region: at N=1 the same workload through the
+split-f16 kernel and with offsets for the selected pairs only, the CPU baseline (the oracle port on
+the host cores over the same frame in 614,400-point slabs, ~20 s) with the parity record against it,
+and the kernels' average durations by rocprofv3 --kernel-trace (+ counter passes) of this same
+command, run as child processes (roofline.kernel_ms_rocprof_live, profile; --no-rocprof to skip).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (dump_outputs).
+`python bench.py --gpus N` without a launcher runs itself under torch.distributed.run.
 """
 import argparse
 import ctypes as C
@@ -196,6 +200,28 @@ def parity_record(got, ref, scene, depth):
             "tolerance": 1e-4, "ok": bool(max(mx.values()) <= 1e-4 and float(d.mean()) <= 1e-4)}
 
 
+# --dump-outputs: an output with more rows is written as this fixed, seeded sample of its rows (the
+# per-pair outputs of the headline frame hold 4.9 M rows: 118 MB in all)
+DUMP_ROWS = 1 << 19
+
+
+def dump_outputs(d, arrays):
+    """Write `arrays` (name -> tensor) as <d>/<name>.npy: float32, integer tensors as float64 (exact below
+    2^53). An array of n > DUMP_ROWS rows keeps DUMP_ROWS of them, drawn by a generator seeded with n alone,
+    so that two runs with the same arguments keep the same rows; their indices go to <d>/rows_of_<n>.npy."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().cpu()
+        n = a.shape[0] if a.dim() else 1
+        if n > DUMP_ROWS:
+            idx = torch.randint(n, (DUMP_ROWS,), generator=torch.Generator().manual_seed(n)).sort().values
+            a = a[idx]
+            np.save(os.path.join(d, "rows_of_%d.npy" % n), idx.double().numpy())
+        a = a.float() if a.is_floating_point() else a.double()
+        np.save(os.path.join(d, name + ".npy"), a.numpy())
+
+
 def _short(name):
     """Kernel name without its argument list (rocprofv3 reports the demangled signature)."""
     return name.split("(")[0].replace("void ", "").strip()
@@ -243,15 +269,15 @@ def live_profile(argv, dominant, steps=6, warmup=2, pmc=False, timeout=300, per_
     if os.environ.get("LIDF_BENCH_NO_ROCPROF") == "1":
         return None
     keep, skip = [], False
-    for a in argv:            # the workload flags of this run without its step counts
+    for a in argv:            # the workload flags of this run without its step counts and output options
         if skip:
             skip = False
             continue
-        if a in ("--steps", "--warmup", "--gpus"):
+        if a in ("--steps", "--warmup", "--gpus", "--dump-outputs"):
             skip = True
             continue
-        if a.startswith(("--steps=", "--warmup=", "--gpus=")) or a in ("--no-cpu-baseline", "--no-rocprof", "--pmc",
-                                                                        "--no-split-f16"):
+        if a.startswith(("--steps=", "--warmup=", "--gpus=", "--dump-outputs=")) or a in (
+                "--no-cpu-baseline", "--no-rocprof", "--pmc", "--no-split-f16", "--full"):
             continue
         keep.append(a)
     out = None
@@ -596,17 +622,19 @@ def secondary(args):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     kern_ms = e0.elapsed_time(e1) / args.steps  # one dominant kernel per step on torch's stream
-    # the host's share of a step (enqueue only: the device is idle at every start, nothing waits inside step()):
-    # a step whose host time approaches its device time reads the box's CPU, not the kernels
-    host = 0.0
-    nh = min(args.steps, 10)
-    for _ in range(nh):
+    host_ms = None
+    if args.full:
+        # the host's share of a step (enqueue only: the device is idle at every start, nothing waits inside
+        # step()): a step whose host time approaches its device time reads the box's CPU, not the kernels
+        host = 0.0
+        nh = min(args.steps, 10)
+        for _ in range(nh):
+            torch.cuda.synchronize()
+            th = time.perf_counter()
+            step()
+            host += time.perf_counter() - th
         torch.cuda.synchronize()
-        th = time.perf_counter()
-        step()
-        host += time.perf_counter() - th
-    torch.cuda.synchronize()
-    host_ms = host / max(nh, 1) * 1e3
+        host_ms = host / max(nh, 1) * 1e3
     hbm = args.workload == "embed"
     split_rows = args.workload == "decoders" and args.precision == "f16x3"
     # frac = issued MFMA FLOP / time / peak where the instruction count is known (decoders); the
@@ -647,13 +675,13 @@ def secondary(args):
     marker = {"train-refine": ("lidf_pnet_bwd_b_kernel", 2), "train-query": ("lidf_points_fused_train_kernel", 1),
               "train": ("lidf_points_kernel<5>", 2)}.get(args.workload)
     profiled = any(k.startswith(("ROCP_", "ROCPROF")) for k in os.environ)
-    if marker and not args.no_rocprof and not profiled:
+    if args.full and marker and not args.no_rocprof and not profiled:
         live = live_profile(sys.argv[1:], marker[0], steps=6, warmup=2, per_step=marker[1])
     emit({
         "metric": "Mpoints/sec, %s" % args.workload, "value": round(P * args.steps / elapsed / 1e6, 2),
         "unit": "Mpoints/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
-        "host_enqueue_ms_per_step": round(host_ms, 4),
+        "host_enqueue_ms_per_step": round(host_ms, 4) if host_ms is not None else None,
         "scaling": "weak", "vs_baseline": None,
         "dtype": DTYPE_F16X3 if (args.workload == "decoders" and args.precision == "f16x3") else "f32",
         "data": "synthetic",
@@ -862,7 +890,7 @@ def e2e(args):
     # time, the kernels of a step, and the issued-FLOP fractions of its three matrix kernels
     live = None
     profiled = any(k.startswith(("ROCP_", "ROCPROF")) for k in os.environ)
-    if not args.no_rocprof and not profiled and max(1, args.streams) == 1 and not use_dist:
+    if args.full and not args.no_rocprof and not profiled and max(1, args.streams) == 1 and not use_dist:
         live = live_profile(sys.argv[1:], "lidf_points_fused_kernel" if args.precision == "f32" else "lidf_points_h_kernel",
                             pmc=args.pmc)
     roof = None
@@ -963,25 +991,32 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--samples", type=int, default=64, help="candidates per ray (N)")
     ap.add_argument("--frames", type=int, default=1, help="frames per rank per step")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the legs that take runs of their own: the split-f16 and "
+                         "offsets-selected legs, the CPU baseline and parity record, the rocprofv3 children, the host "
+                         "enqueue time of the secondary workloads (off by default: a plain run measures the steps "
+                         "alone); --no-cpu-baseline / --no-rocprof / --no-split-f16 / --pmc select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="query workloads: write the outputs of the last timed step (the arrays lidf_query returns, "
+                         "the depth maps, stage 2's pred_pos_refine) as DIR/<name>.npy, at most 64 MB in all")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-rocprof", action="store_true",
-                    help="skip the rocprofv3 legs of an N = 1 run (roofline.kernel_ms_rocprof_live and the "
+                    help="--full: skip the rocprofv3 legs of an N = 1 run (roofline.kernel_ms_rocprof_live and the "
                          "\"profile\" block: per-kernel durations and launches per step by rocprofv3 --kernel-trace "
                          "of this same command, run as a child process after the timed region)")
     ap.add_argument("--no-split-f16", action="store_true",
-                    help="query workload: skip the secondary legs of the default f32 run (the same workload through "
+                    help="--full, query workload: skip the secondary legs of the f32 run (the same workload through "
                          "the split-f16 kernel -> \"split_f16\", and with offsets for the selected pairs only -> "
                          "\"offsets_selected\") and the extra step that keeps outputs for the parity record. The "
                          "rocprofv3 children of a run pass it, so that profile.* and hbm.* are numbers of the timed "
                          "f32 step alone")
     ap.add_argument("--pmc", action="store_true",
-                    help="also run the two HBM counter passes (rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE) of "
-                         "this command -> roofline.traffic, hbm.bytes_counter; the default headline run does so "
-                         "by itself")
+                    help="--full: also run the two HBM counter passes (rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE) "
+                         "of this command -> roofline.traffic, hbm.bytes_counter; the headline run does so by itself")
     ap.add_argument("--precision", default="f32", choices=["f32", "f16x3"],
                     help="arithmetic of the decoders' matrix products: f32 (default, the headline) or "
                          "f16x3 = three f16-piece products per term with f32 accumulation (f32-level "
-                         "accuracy, LidfQueryArgs.precision); the default f32 run also reports the "
+                         "accuracy, LidfQueryArgs.precision); an f32 run with --full also reports the "
                          "f16x3 rate and its deviation from the f32 outputs as \"split_f16\"")
     ap.add_argument("--pairs", default="dense", choices=["dense", "ragged", "n1", "scene"],
                     help="candidate list of the query workload: dense = N per ray (the headline shape); "
@@ -1046,6 +1081,8 @@ def main():
     if args.config is not None:
         preset = {1: (1, 64, "query"), 2: (4, 64, "query"), 3: (1, 64, "query+refine"), 4: (4, 256, "query")}
         args.frames, args.samples, args.workload = preset[args.config]
+    if args.dump_outputs and args.workload not in ("query", "query+refine"):
+        ap.error("--dump-outputs: query workloads only (--workload query / query+refine)")
     if args.workload == "e2e" and (args.gpus > 1 or "RANK" in os.environ):
         # A frame forks onto a side stream; RCCL brings streams of its own, and with HIP's default of 4 hardware
         # queues the two streams of a frame can land on one queue (the frame then runs 6 % slower than without a
@@ -1060,9 +1097,11 @@ def main():
         port = sk.getsockname()[1]
         sk.close()
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
-                                  "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1",
-                                  "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        import subprocess
+        r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
+                            "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1",
+                            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        sys.exit(r.returncode)
     claim_stdout()
     if args.workload in ("decoders", "embed", "train", "train-query", "train-refine"):
         return secondary(args)
@@ -1203,7 +1242,7 @@ def main():
     t0 = time.perf_counter()
     for i in range(args.steps):
         state["step"] = i
-        lane_step(i, None if gf != 64 else pairs[i])
+        last = lane_step(i, None if gf != 64 else pairs[i])
     state["step"] = None
     torch.cuda.synchronize()
     barrier()
@@ -1224,6 +1263,11 @@ def main():
         pts = torch.tensor([scene["P"]], device=dev, dtype=torch.int64)
         dist.all_reduce(pts)                                # points of the whole job (shards may differ)
         points_all = int(pts.item())
+    if args.dump_outputs and rank == 0:   # what the caller of the last timed step received (its lane's depth maps)
+        keys = ("pred_offset", "pred_prob_end", "pair_pred_pos", "pred_prob_end_softmax", "max_pair_id", "pred_pos",
+                "pred_pos_refine")
+        dump_outputs(args.dump_outputs, dict({k: last[k] for k in keys if last.get(k) is not None},
+                                             depth=depths[(args.steps - 1) % S]))
 
     # (widths other than the shipped ones run layer by layer: no single dominant kernel to time)
     kern_ms = sum(ev.elapsed_ms(a, b) for a, b in pairs) / args.steps if gf == 64 else float("nan")
@@ -1241,7 +1285,7 @@ def main():
         gather_ok = bool(t.item())
     split = None
     hip_f32 = None
-    legs = not args.no_split_f16
+    legs = args.full and not args.no_split_f16
     sel_leg = None
     if world == 1 and refine is None and dense and gf == 64 and legs and not args.no_cpu_baseline:
         hip_f32 = step()   # outputs of the measured configuration, kept for the parity record
@@ -1320,7 +1364,7 @@ def main():
         profiled = any(k.startswith(("ROCP_", "ROCPROF")) for k in os.environ)   # already under a profiler
         headline = (dense and B == 1 and N == 64 and refine is None and not h16 and S == 1 and gf == 64
                     and args.offsets == "all")
-        if world == 1 and not use_dist and not args.no_rocprof and not profiled:
+        if args.full and world == 1 and not use_dist and not args.no_rocprof and not profiled:
             live = live_profile(sys.argv[1:], kname, pmc=args.pmc or (headline and not args.no_cpu_baseline),
                                 per_step=(2 if (args.offsets == "selected" and gf == 64 and not h16) else
                                           chain_launches_per_step(gf, P) if gf != 64 else 1))
@@ -1503,7 +1547,7 @@ def main():
                                                               "the decoders layer by layer (LIDF_CHAIN16=0)", B, N))
             line["metric"] = "Mpoints/sec implicit-MLP query at imnet_gf %d (%s)" % (gf, "chain launch" if chained
                                                                                     else "layer by layer")
-        if world == 1 and not args.no_cpu_baseline and dense and gf == 64:
+        if args.full and world == 1 and not args.no_cpu_baseline and dense and gf == 64:
             cb, ref = cpu_baseline(scene)
             line["cpu_baseline"] = cb
             if hip_f32 is not None:

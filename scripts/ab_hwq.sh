@@ -3,11 +3,11 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/abq; mkdir -p $O
 cd $R
 for rep in 1 2 3; do for q in def 2 3 4 8; do
   unset GPU_MAX_HW_QUEUES; [ $q != def ] && export GPU_MAX_HW_QUEUES=$q
-  python bench.py --workload e2e --e2e-mode frame --streams 3 --steps 300 --warmup 30 --no-rocprof > $O/s3_q${q}_$rep.json 2>/dev/null
+  python bench.py --full --workload e2e --e2e-mode frame --streams 3 --steps 300 --warmup 30 --no-rocprof > $O/s3_q${q}_$rep.json 2>/dev/null
 done; done
 unset GPU_MAX_HW_QUEUES
 for rep in 1 2 3; do for s in 2 4 6; do
-  python bench.py --workload e2e --e2e-mode frame --streams $s --steps 300 --warmup 30 --no-rocprof > $O/s${s}_qdef_$rep.json 2>/dev/null
+  python bench.py --full --workload e2e --e2e-mode frame --streams $s --steps 300 --warmup 30 --no-rocprof > $O/s${s}_qdef_$rep.json 2>/dev/null
 done; done
 python - <<'PY'
 import json, glob, os

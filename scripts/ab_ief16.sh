@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
 for v in new old new old; do
   if [ $v = new ]; then unset LIDF_IEF16; else export LIDF_IEF16=0; fi
-  rm -rf /tmp/p_$v; rocprofv3 --kernel-trace --stats -d /tmp/p_$v -o r -- python $R/bench.py --workload e2e --e2e-mode frame --steps 20 --warmup 3 --no-rocprof > /dev/null 2>&1
+  rm -rf /tmp/p_$v; rocprofv3 --kernel-trace --stats -d /tmp/p_$v -o r -- python $R/bench.py --full --workload e2e --e2e-mode frame --steps 20 --warmup 3 --no-rocprof > /dev/null 2>&1
   python - <<PY
 import sqlite3
 cur=sqlite3.connect('/tmp/p_$v/r_results.db').cursor()

@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT; ALT=$1; PAT=${2:-lidf}; W=${3:-train-query}
 cd /tmp && export TMPDIR=/tmp
 for v in new old new old; do
   if [ $v = new ]; then unset LIDF_HIP_LIB; else export LIDF_HIP_LIB=$R/$ALT; fi
-  rm -rf /tmp/p_$v; rocprofv3 --kernel-trace --stats -d /tmp/p_$v -o r -- python $R/bench.py --workload $W --steps 10 --warmup 3 > /dev/null 2>&1
+  rm -rf /tmp/p_$v; rocprofv3 --kernel-trace --stats -d /tmp/p_$v -o r -- python $R/bench.py --full --workload $W --steps 10 --warmup 3 > /dev/null 2>&1
   python - <<PY
 import sqlite3
 cur=sqlite3.connect('/tmp/p_$v/r_results.db').cursor()

@@ -11,8 +11,8 @@
 #   plain-omp1     no process group, OMP_NUM_THREADS=1
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/ab_pg; mkdir -p $O
 N=${1:-2000}; W=${2:-300}
-run_plain() { python $R/bench.py --workload e2e --e2e-mode frame --steps $N --warmup $W --no-rocprof "$@"; }
-run_tr() { python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port $((29700 + RANDOM % 200)) $R/bench.py --workload e2e --gpus 1 --steps $N --warmup $W --no-rocprof "$@"; }
+run_plain() { python $R/bench.py --full --workload e2e --e2e-mode frame --steps $N --warmup $W --no-rocprof "$@"; }
+run_tr() { python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port $((29700 + RANDOM % 200)) $R/bench.py --full --workload e2e --gpus 1 --steps $N --warmup $W --no-rocprof "$@"; }
 for rep in 1 2; do
   run_plain > $O/plain_$rep.json 2>/dev/null
   run_tr > $O/nccl_$rep.json 2>/dev/null

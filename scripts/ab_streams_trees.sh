@@ -8,10 +8,10 @@ for rep in 1 2 3; do for v in new old; do
   D=$R; [ $v = old ] && D=$R/_old
   for q in def 8; do
     unset GPU_MAX_HW_QUEUES; [ $q != def ] && export GPU_MAX_HW_QUEUES=$q
-    (cd $D && python bench.py --workload e2e --e2e-mode frame --streams 3 --steps $N --warmup $W --no-rocprof > $O/s3_${v}_q${q}_$rep.json 2>/dev/null)
+    (cd $D && python bench.py --full --workload e2e --e2e-mode frame --streams 3 --steps $N --warmup $W --no-rocprof > $O/s3_${v}_q${q}_$rep.json 2>/dev/null)
   done
   unset GPU_MAX_HW_QUEUES
-  (cd $D && python bench.py --workload e2e --e2e-mode frame --steps $N --warmup $W --no-rocprof > $O/s1_${v}_$rep.json 2>/dev/null)
+  (cd $D && python bench.py --full --workload e2e --e2e-mode frame --steps $N --warmup $W --no-rocprof > $O/s1_${v}_$rep.json 2>/dev/null)
 done; done
 python - <<'PY'
 import glob, json, os
@@ -27,7 +27,7 @@ cd /tmp && export TMPDIR=/tmp
 for v in new old; do
   D=$R; [ $v = old ] && D=$R/_old
   rm -rf /tmp/p_ic_$v
-  (cd $D && rocprofv3 --kernel-trace --pmc SQC_ICACHE_REQ SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_BUSY_CYCLES -d /tmp/p_ic_$v -o r -- python bench.py --workload e2e --e2e-mode frame --no-side-stream --steps 6 --warmup 3 --no-rocprof > /dev/null 2>&1)
+  (cd $D && rocprofv3 --kernel-trace --pmc SQC_ICACHE_REQ SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_BUSY_CYCLES -d /tmp/p_ic_$v -o r -- python bench.py --full --workload e2e --e2e-mode frame --no-side-stream --steps 6 --warmup 3 --no-rocprof > /dev/null 2>&1)
   python - $v <<'PY'
 import sqlite3, sys, glob
 v = sys.argv[1]

@@ -9,10 +9,10 @@ for v in split whole old; do
   unset LIDF_HIP_LIB LIDF_TAIL_SPLIT
   [ $v = whole ] && export LIDF_TAIL_SPLIT=0
   [ $v = old ] && [ -f $R/liblidf_old.so ] && export LIDF_HIP_LIB=$R/liblidf_old.so
-  python bench.py --pairs scene --steps 200 --warmup 20 --no-cpu-baseline --no-rocprof > $O/scene_${v}_$rep.json 2>/dev/null
-  python bench.py --workload e2e --e2e-mode frame --steps 300 --warmup 30 --no-rocprof > $O/e2e_f1_${v}_$rep.json 2>/dev/null
-  python bench.py --workload e2e --e2e-mode frame --frames 4 --steps 80 --warmup 8 --no-rocprof > $O/e2e_f4_${v}_$rep.json 2>/dev/null
-  python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-rocprof --no-split-f16 > $O/headline_${v}_$rep.json 2>/dev/null
+  python bench.py --full --pairs scene --steps 200 --warmup 20 --no-cpu-baseline --no-rocprof > $O/scene_${v}_$rep.json 2>/dev/null
+  python bench.py --full --workload e2e --e2e-mode frame --steps 300 --warmup 30 --no-rocprof > $O/e2e_f1_${v}_$rep.json 2>/dev/null
+  python bench.py --full --workload e2e --e2e-mode frame --frames 4 --steps 80 --warmup 8 --no-rocprof > $O/e2e_f4_${v}_$rep.json 2>/dev/null
+  python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-rocprof --no-split-f16 > $O/headline_${v}_$rep.json 2>/dev/null
 done; done
 python - <<'PY'
 import json, glob, os

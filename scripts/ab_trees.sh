@@ -7,7 +7,7 @@ for ARGS in "$@"; do
   i=$((i+1))
   for rep in 1 2; do for v in new old; do
     D=$R; [ $v = old ] && D=$R/_old
-    (cd $D && python bench.py $ARGS --no-rocprof > $O/a${i}_${v}_$rep.json 2>/dev/null)
+    (cd $D && python bench.py --full $ARGS --no-rocprof > $O/a${i}_${v}_$rep.json 2>/dev/null)
   done; done
 done
 python - "$@" <<'PY'

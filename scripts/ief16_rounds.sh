@@ -3,7 +3,7 @@
 R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
 for f in 1 2 3 4; do
-  rm -rf /tmp/p_$f; rocprofv3 --kernel-trace --stats -d /tmp/p_$f -o r -- python $R/bench.py --workload query+refine --frames $f --samples 4 --steps 12 --warmup 3 --no-rocprof --no-cpu-baseline --no-split-f16 > /tmp/o_$f.log 2>&1 || tail -3 /tmp/o_$f.log
+  rm -rf /tmp/p_$f; rocprofv3 --kernel-trace --stats -d /tmp/p_$f -o r -- python $R/bench.py --full --workload query+refine --frames $f --samples 4 --steps 12 --warmup 3 --no-rocprof --no-cpu-baseline --no-split-f16 > /tmp/o_$f.log 2>&1 || tail -3 /tmp/o_$f.log
   python - <<PY
 import sqlite3
 cur=sqlite3.connect('/tmp/p_$f/r_results.db').cursor()

@@ -1,6 +1,6 @@
 O=gpurun_out/s2; mkdir -p $O; R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
-rm -rf /tmp/p_e4; rocprofv3 --kernel-trace --stats -d /tmp/p_e4 -o r -- python $R/bench.py --workload e2e --frames 4 --steps 10 --warmup 3 > $R/$O/e2e4_prof.json 2>/dev/null
+rm -rf /tmp/p_e4; rocprofv3 --kernel-trace --stats -d /tmp/p_e4 -o r -- python $R/bench.py --full --workload e2e --frames 4 --steps 10 --warmup 3 > $R/$O/e2e4_prof.json 2>/dev/null
 cd $R
 python - <<PY
 import sqlite3

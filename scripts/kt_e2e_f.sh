@@ -1,7 +1,7 @@
 # per-kernel time of the evaluation path at $1 frames per call, one stream (no overlap: durations add up)
 R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
-rm -rf /tmp/p_ef; rocprofv3 --kernel-trace --stats -d /tmp/p_ef -o r -- python $R/bench.py --workload e2e --e2e-mode frame --frames $1 --no-side-stream --steps 12 --warmup 3 --no-rocprof > /tmp/ef.json 2>/dev/null
+rm -rf /tmp/p_ef; rocprofv3 --kernel-trace --stats -d /tmp/p_ef -o r -- python $R/bench.py --full --workload e2e --e2e-mode frame --frames $1 --no-side-stream --steps 12 --warmup 3 --no-rocprof > /tmp/ef.json 2>/dev/null
 python - "$1" <<'PY'
 import sqlite3, sys, json
 F=int(sys.argv[1])

@@ -1,7 +1,7 @@
 # per-kernel time of the query at another decoder width ($1 = gf), one step of 4,915,200 pairs
 R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
-rm -rf /tmp/p_gf; rocprofv3 --kernel-trace --stats -d /tmp/p_gf -o r -- python $R/bench.py --imnet-gf $1 --steps 3 --warmup 1 --no-rocprof --no-cpu-baseline --no-split-f16 > /dev/null 2>&1
+rm -rf /tmp/p_gf; rocprofv3 --kernel-trace --stats -d /tmp/p_gf -o r -- python $R/bench.py --full --imnet-gf $1 --steps 3 --warmup 1 --no-rocprof --no-cpu-baseline --no-split-f16 > /dev/null 2>&1
 python - <<'PY'
 import sqlite3
 cur=sqlite3.connect('/tmp/p_gf/r_results.db').cursor()

@@ -1,7 +1,7 @@
 # kernel-trace of the headline step: per-kernel average durations -> gpurun_out/s2/kt_<tag>.txt
 TAG=${1:-x}; O=gpurun_out/s2; mkdir -p $O; R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
-rm -rf /tmp/p_kt; rocprofv3 --kernel-trace --stats -d /tmp/p_kt -o r -- python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline > $R/$O/bench_$TAG.json 2>/dev/null
+rm -rf /tmp/p_kt; rocprofv3 --kernel-trace --stats -d /tmp/p_kt -o r -- python $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline > $R/$O/bench_$TAG.json 2>/dev/null
 cd $R
 python - <<PY > $O/kt_$TAG.txt
 import sqlite3

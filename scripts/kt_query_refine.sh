@@ -1,6 +1,6 @@
 O=gpurun_out/s2; mkdir -p $O; R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
-rm -rf /tmp/p_qr; rocprofv3 --kernel-trace --stats -d /tmp/p_qr -o r -- python $R/bench.py --workload query+refine --steps 10 --warmup 3 --no-cpu-baseline > $R/$O/qr_prof.json 2>/dev/null
+rm -rf /tmp/p_qr; rocprofv3 --kernel-trace --stats -d /tmp/p_qr -o r -- python $R/bench.py --full --workload query+refine --steps 10 --warmup 3 --no-cpu-baseline > $R/$O/qr_prof.json 2>/dev/null
 cd $R
 python - <<PY
 import sqlite3

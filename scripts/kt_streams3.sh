@@ -3,7 +3,7 @@ R=$GRAFT_REPO_ROOT; cd /tmp; export TMPDIR=/tmp
 for v in new old new old; do
   D=$R; [ $v = old ] && D=$R/_old
   rm -rf /tmp/k3_$v
-  (cd $D && rocprofv3 --kernel-trace --stats -d /tmp/k3_$v -o r -- python bench.py --workload e2e --e2e-mode frame --streams 3 --steps 200 --warmup 20 --no-rocprof > /dev/null 2>&1)
+  (cd $D && rocprofv3 --kernel-trace --stats -d /tmp/k3_$v -o r -- python bench.py --full --workload e2e --e2e-mode frame --streams 3 --steps 200 --warmup 20 --no-rocprof > /dev/null 2>&1)
   python - <<PY
 import sqlite3
 cur=sqlite3.connect('/tmp/k3_$v/r_results.db').cursor()

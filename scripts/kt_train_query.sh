@@ -2,7 +2,7 @@
 # and the launches of the last step in time order
 O=gpurun_out/s2; mkdir -p $O; R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
-rm -rf /tmp/p_tq; rocprofv3 --kernel-trace --stats -d /tmp/p_tq -o r -- python $R/bench.py --workload train-query --steps 10 --warmup 3 --no-rocprof > $R/$O/tq_prof.json 2>/dev/null
+rm -rf /tmp/p_tq; rocprofv3 --kernel-trace --stats -d /tmp/p_tq -o r -- python $R/bench.py --full --workload train-query --steps 10 --warmup 3 --no-rocprof > $R/$O/tq_prof.json 2>/dev/null
 cd $R
 python - <<PY
 import sqlite3

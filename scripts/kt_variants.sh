@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/ktv; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 for v in $VALS; do
   export $VAR=$v
-  rm -rf /tmp/p_v; rocprofv3 --kernel-trace --stats -d /tmp/p_v -o r -- python $R/bench.py --workload e2e --e2e-mode frame --no-side-stream --steps 30 --warmup 3 --no-rocprof > $O/bench_$v.json 2>/dev/null
+  rm -rf /tmp/p_v; rocprofv3 --kernel-trace --stats -d /tmp/p_v -o r -- python $R/bench.py --full --workload e2e --e2e-mode frame --no-side-stream --steps 30 --warmup 3 --no-rocprof > $O/bench_$v.json 2>/dev/null
   python - "$v" "$PAT" <<'PY'
 import sqlite3, sys, json, os
 cur = sqlite3.connect('/tmp/p_v/r_results.db').cursor()

@@ -2,7 +2,7 @@
 # clock = SQ_BUSY_CYCLES / 32 (XCD x SE) / duration, MFMA busy = SQ_VALU_MFMA_BUSY_CYCLES / 1024 SIMDs / (clock x duration)
 O=gpurun_out/s2; mkdir -p $O; R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
-rm -rf /tmp/p_tp; rocprofv3 --kernel-trace --pmc SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES -d /tmp/p_tp -o r -- python $R/bench.py --workload ${1:-train-query} --steps 4 --warmup 2 > /dev/null 2>&1
+rm -rf /tmp/p_tp; rocprofv3 --kernel-trace --pmc SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES -d /tmp/p_tp -o r -- python $R/bench.py --full --workload ${1:-train-query} --steps 4 --warmup 2 > /dev/null 2>&1
 cd $R
 python - <<PY
 import sqlite3

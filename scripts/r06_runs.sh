@@ -7,7 +7,7 @@ O=gpurun_out/r6p; mkdir -p $O
 R=$GRAFT_REPO_ROOT
 PARTS="${@:-head e2e train misc prof}"
 has() { [[ " $PARTS " == *" $1 "* ]]; }
-B="python bench.py"
+B="python bench.py --full"
 if has head; then
   $B --steps 20 --warmup 5 > $O/bench_n1.json 2> $O/err.txt
   $B --config 2 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_config2.json 2>> $O/err.txt
@@ -28,7 +28,7 @@ if has e2e; then
   $B --workload e2e --e2e-mode frame --offsets selected --streams 6 --steps 2000 --warmup 300 > $O/bench_e2e_frame_f1_selected_streams6.json 2>> $O/err.txt
   $B --workload e2e --e2e-mode frame --frames 16 --offsets selected --steps 100 --warmup 10 --no-rocprof > $O/bench_e2e_frame_f16_selected.json 2>> $O/err.txt
   # the same stream under a 1-rank RCCL group, the SAME protocol
-  python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29654 bench.py --workload e2e --gpus 1 --steps 2000 --warmup 300 --no-rocprof > $O/bench_e2e_rccl_n1.json 2>> $O/err.txt
+  python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29654 bench.py --full --workload e2e --gpus 1 --steps 2000 --warmup 300 --no-rocprof > $O/bench_e2e_rccl_n1.json 2>> $O/err.txt
 fi
 if has train; then
   for w in train train-query train-refine; do $B --workload $w --steps 40 --warmup 10 > $O/bench_$w.json 2>> $O/err.txt; done
@@ -43,14 +43,14 @@ if has misc; then
   LIDF_CHAIN16=0 $B --imnet-gf 128 --steps 3 --warmup 1 --no-cpu-baseline --no-rocprof > $O/bench_gf128_layers.json 2>> $O/err.txt
   LIDF_CHAIN16=0 $B --imnet-gf 32 --steps 5 --warmup 2 --no-cpu-baseline --no-rocprof > $O/bench_gf32_layers.json 2>> $O/err.txt
   for w in decoders embed; do $B --workload $w --steps $( [ $w = embed ] && echo 2000 || echo 40 ) --warmup $( [ $w = embed ] && echo 300 || echo 10 ) > $O/bench_$w.json 2>> $O/err.txt; done
-  python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29655 bench.py --gpus 1 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_n1_rccl.json 2>> $O/err.txt
-  python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29656 bench.py --gpus 1 --shard rays --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_n1_rccl_rays.json 2>> $O/err.txt
+  python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29655 bench.py --full --gpus 1 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_n1_rccl.json 2>> $O/err.txt
+  python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29656 bench.py --full --gpus 1 --shard rays --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_n1_rccl_rays.json 2>> $O/err.txt
 fi
 if has prof; then
   cd /tmp && export TMPDIR=/tmp
   H="--steps 10 --warmup 2 --no-cpu-baseline --no-rocprof --no-split-f16"
   P="--steps 3 --warmup 1 --no-cpu-baseline --no-rocprof --no-split-f16"
-  kt() { rm -rf /tmp/p_$1; rocprofv3 --kernel-trace --stats -d /tmp/p_$1 -o r -- python $R/bench.py "${@:2}" > /dev/null 2>&1; cp /tmp/p_$1/r_results.db $R/$O/$1.db 2>/dev/null || cp $(find /tmp/p_$1 -name '*_results.db' | head -1) $R/$O/$1.db; }
+  kt() { rm -rf /tmp/p_$1; rocprofv3 --kernel-trace --stats -d /tmp/p_$1 -o r -- python $R/bench.py --full "${@:2}" > /dev/null 2>&1; cp /tmp/p_$1/r_results.db $R/$O/$1.db 2>/dev/null || cp $(find /tmp/p_$1 -name '*_results.db' | head -1) $R/$O/$1.db; }
   kt kt $H
   kt kt_refine --config 3 $H
   kt kt_e2e --workload e2e --e2e-mode frame --steps 10 --warmup 3 --no-rocprof
@@ -59,7 +59,7 @@ if has prof; then
   kt kt_train_query --workload train-query --steps 10 --warmup 3 --no-rocprof
   kt kt_train --workload train --steps 10 --warmup 3 --no-rocprof
   kt kt_train_pair --workload train --decoder-pair --steps 10 --warmup 3 --no-rocprof
-  pmc() { rm -rf /tmp/p_$1; rocprofv3 "${@:3}" -d /tmp/p_$1 -o r -- python $R/bench.py $2 > /dev/null 2>&1; cp $(find /tmp/p_$1 -name '*_results.db' | head -1) $R/$O/$1.db; }
+  pmc() { rm -rf /tmp/p_$1; rocprofv3 "${@:3}" -d /tmp/p_$1 -o r -- python $R/bench.py --full $2 > /dev/null 2>&1; cp $(find /tmp/p_$1 -name '*_results.db' | head -1) $R/$O/$1.db; }
   pmc fetch "$P" --pmc FETCH_SIZE
   pmc write "$P" --pmc WRITE_SIZE
   pmc mfma "$P" --pmc SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES

@@ -2,7 +2,7 @@
 # launch on the same queue. usage: timeline_step.sh <workload> <marker kernel substring> [bench flags]
 R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
-rm -rf /tmp/p_tl; rocprofv3 --kernel-trace --stats -d /tmp/p_tl -o r -- python $R/bench.py --workload $1 --steps 6 --warmup 3 --no-rocprof "${@:3}" > /dev/null 2>&1
+rm -rf /tmp/p_tl; rocprofv3 --kernel-trace --stats -d /tmp/p_tl -o r -- python $R/bench.py --full --workload $1 --steps 6 --warmup 3 --no-rocprof "${@:3}" > /dev/null 2>&1
 python - "$2" <<'PY'
 import sqlite3, sys
 cur=sqlite3.connect('/tmp/p_tl/r_results.db').cursor()

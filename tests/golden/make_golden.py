@@ -9,8 +9,9 @@ Python modules are imported and executed, and only their inputs/outputs are stor
   g2_decoders.npz   IMNet / IEF forward outputs on closed-form weights  (models/implicit_net.py:60-152)
   g3_pipeline.npz   LIDF.get_miss_ray -> compute_ray_aabb -> get_embedding -> get_pred trace on a
                     2 x 16 x 24 synthetic batch                           (models/pipeline.py:203-466)
-  g5_decoder_grads.npz  autograd gradients of the reference IMNet / IEF (input rows and every
-                    parameter) for a closed-form upstream gradient   (models/implicit_net.py:60-152)
+  g5_decoder_grads_<case>.npz  autograd gradients of the reference IMNet / IEF (input rows and every
+                    parameter) for a closed-form upstream gradient, one file per decoder case
+                                                                       (models/implicit_net.py:60-152)
   g6_miss_ray.npz   LIDF.get_miss_ray on float masks (holes, an empty image, -0.0, tiny values)
                                                                        (models/pipeline.py:203-269)
   g7_refine_select.npz  the same two refine iterations with refine.use_all_pix = False
@@ -152,7 +153,7 @@ def g5_decoder_grads():
         return lo
 
     for kind, d, n_iter, sig in (("IMNET", 385, 1, False), ("IEF", 385, 2, False), ("IEF", 334, 3, True)):
-        seed = 51 + 10 * len(out)
+        seed = 51 + 10 * sum(len(case) for case in out.values())   # (10 x the arrays stored before this case)
         while True:
             p = closed_form_params(kind, d, seed=seed)
             x = closed_form((96, d), 0.5698402910, 0.1 * d, 1.0)
@@ -169,12 +170,14 @@ def g5_decoder_grads():
         y = m(x)
         (y * wgt).sum().backward()
         key = "%s_%d_%d_%d" % (kind, d, n_iter, int(sig))
-        out[key + "_seed"] = np.int64(seed)
-        out[key + "_y"] = y.detach().numpy()
-        out[key + "_g_input"] = x.grad.numpy()
+        case = out[key] = {}
+        case[key + "_seed"] = np.int64(seed)
+        case[key + "_y"] = y.detach().numpy()
+        case[key + "_g_input"] = x.grad.numpy()
         for k, v in m.named_parameters():
-            out[key + "_g_" + k] = v.grad.numpy()
-    np.savez_compressed(os.path.join(HERE, "g5_decoder_grads.npz"), **out)
+            case[key + "_g_" + k] = v.grad.numpy()
+    for key, case in out.items():   # one file per case: each stays under 1 MiB
+        np.savez_compressed(os.path.join(HERE, "g5_decoder_grads_%s.npz" % key), **case)
 
 
 def g2_decoders():

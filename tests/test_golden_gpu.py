@@ -78,8 +78,8 @@ def test_g3_pipeline_hip(cuda, precision):
 def test_g5_decoder_grads_hip(cuda):
     """The library's training path (forward with kept activations + backward) against the
     gradients of the reference's own IMNet / IEF modules."""
-    from test_oracle_golden import g5_cases, g5_inputs
-    g = load("g5_decoder_grads.npz")
+    from test_oracle_golden import G5, g5_cases, g5_inputs
+    g = load(*G5)
     for key, kind, d, n_iter, sig, seed in g5_cases(g):
         m = make_module(kind, closed_form_params(kind, d, seed=seed), d, cuda, n_iter=n_iter,
                         use_sigmoid=sig).train()

@@ -11,8 +11,12 @@ from util import closed_form, closed_form_params, orc
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
-def load(name):
-    return {k: v for k, v in np.load(os.path.join(G, name)).items()}
+# g5 is stored one case per file (each fixture stays under 1 MiB)
+G5 = tuple("g5_decoder_grads_%s.npz" % c for c in ("IMNET_385_1_0", "IEF_385_2_0", "IEF_334_3_1"))
+
+
+def load(*names):
+    return {k: v for name in names for k, v in np.load(os.path.join(G, name)).items()}
 
 
 def test_g1_embed():
@@ -170,7 +174,7 @@ def g5_inputs(d):
 
 def test_g5_decoder_grads():
     """Autograd of the oracle's restatement against the reference modules' own gradients."""
-    g = load("g5_decoder_grads.npz")
+    g = load(*G5)
     n = 0
     for key, kind, d, n_iter, sig, seed in g5_cases(g):
         p = {k: v.clone().requires_grad_(True) for k, v in closed_form_params(kind, d, seed=seed).items()}
