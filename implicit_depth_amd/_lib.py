@@ -55,7 +55,7 @@ class LidfQueryArgs(C.Structure):
 
 class LidfDecoderGrads(C.Structure):
     """struct LidfDecoderGrads (include/lidf_hip.h)."""
-    _fields_ = [(k, C.c_void_p) for k in ("w1", "b1", "w2", "b2", "w3", "b3", "w4", "b4", "wenc", "benc")]
+    _fields_ = LidfDecoder._fields_[:10]   # w1 .. benc
 
 
 class LidfQueryTrainArgs(C.Structure):
@@ -77,8 +77,7 @@ class LidfPointNet(C.Structure):
 
 class LidfPointNetGrads(C.Structure):
     """struct LidfPointNetGrads (include/lidf_hip.h)."""
-    _fields_ = [(n, C.c_void_p) for n in (
-        "w_p1", "b_p1", "w_p2", "b_p2", "w_v1", "b_v1", "w_p3", "b_p3", "w_p4", "b_p4", "w_v2", "b_v2")]
+    _fields_ = LidfPointNet._fields_[:12]   # w_p1 .. b_v2
 
 
 class LidfRefineArgs(C.Structure):
@@ -370,6 +369,24 @@ def check(status):
 def ptr(t):
     """Device pointer of a torch tensor (None -> NULL)."""
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def param_ptr(t, keep):
+    """Device pointer of a float32 parameter for a weight struct: the tensor, or its contiguous copy, is appended
+    to `keep`, which the caller holds until every launch that reads the struct is ordered on its streams."""
+    import torch
+    t = t.detach()
+    if t.dtype != torch.float32:
+        raise RuntimeError("lidf_hip: float32 parameters required")
+    t = t.contiguous()
+    keep.append(t)
+    return t.data_ptr()
+
+
+def workspace(nbytes, device):
+    """An uninitialised byte workspace of at least one byte (a zero-byte request still gets a valid pointer)."""
+    import torch
+    return torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=device)
 
 
 def current_stream(device=None):

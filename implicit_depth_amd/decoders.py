@@ -129,42 +129,55 @@ def _init_offset_value(mod):
     return v
 
 
+_LAYERS = ("linear_1", "linear_2", "linear_3", "linear_4", "offset_enc")
+
+
+def decoder_params(mod):
+    """The parameters of an IMNet / IEF in the order of LidfDecoder's pointer fields (w1, b1, ..., w4, b4, then
+    an IEF's wenc, benc): the order every training node passes and returns them in."""
+    return [t for name in _LAYERS if hasattr(mod, name) for t in (getattr(mod, name).weight, getattr(mod, name).bias)]
+
+
+def n_passes(mod):
+    """Passes of the trunk per row: an IEF's n_iter, 1 for an IMNet."""
+    return int(mod.n_iter) if isinstance(mod, IEF) else 1
+
+
 def _decoder_struct(mod, keep, tensors=None):
     """Fill a LidfDecoder from a module's parameters; `keep` collects the contiguous tensors
-    whose storage the struct borrows for the duration of the call. `tensors` (state-dict names ->
-    tensors) overrides the module's live parameters: autograd's backward passes what its forward
-    saved, so that an in-place update between the two is caught by torch's version check."""
-    def p(name):
-        t = tensors[name] if tensors is not None else _get(mod, name)
-        t = t.detach()
-        if t.dtype != torch.float32:
-            raise RuntimeError("lidf_hip: float32 parameters required")
-        t = t.contiguous()
-        keep.append(t)
-        return t.data_ptr()
-
+    whose storage the struct borrows for the duration of the call. `tensors` (in decoder_params
+    order) overrides the module's live parameters: autograd's backward passes what its forward
+    saved, so that an in-place update between the two is caught by torch's version check.
+    An IMNet leaves wenc / benc NULL."""
     d = _lib.LidfDecoder()
-    d.w1, d.b1 = p("linear_1.weight"), p("linear_1.bias")
-    d.w2, d.b2 = p("linear_2.weight"), p("linear_2.bias")
-    d.w3, d.b3 = p("linear_3.weight"), p("linear_3.bias")
-    d.w4, d.b4 = p("linear_4.weight"), p("linear_4.bias")
+    for (field, _), t in zip(d._fields_, decoder_params(mod) if tensors is None else tensors):
+        setattr(d, field, _lib.param_ptr(t, keep))
     is_ief = isinstance(mod, IEF)
-    if is_ief:
-        d.wenc, d.benc = p("offset_enc.weight"), p("offset_enc.bias")
-        d.n_iter = int(mod.n_iter)
-        d.init_offset = _init_offset_value(mod)
-    else:
-        d.wenc, d.benc = None, None
-        d.n_iter = 1
-        d.init_offset = 0.0
+    d.n_iter = n_passes(mod)
+    d.init_offset = _init_offset_value(mod) if is_ief else 0.0
     d.is_ief = 1 if is_ief else 0
     d.use_sigmoid = 1 if mod.use_sigmoid else 0
     return d
 
 
-def _get(mod, name):
-    layer, attr = name.split(".")
-    return getattr(getattr(mod, layer), attr)
+def _grad_struct(params):
+    """Fresh float32 gradients shaped like `params` (decoder_params order) and the LidfDecoderGrads that points
+    at them; an IMNet's wenc / benc stay NULL."""
+    grads = [torch.empty(p.shape, dtype=torch.float32, device=p.device) for p in params]
+    gs = _lib.LidfDecoderGrads()
+    for (field, _), g in zip(gs._fields_, grads):
+        setattr(gs, field, g.data_ptr())
+    return grads, gs
+
+
+def _rows(inp_feat):
+    """[n, D] rows as the kernels read them: unit column stride, row stride >= D (a copy otherwise); returns the
+    rows and their leading dimension."""
+    x = inp_feat.detach()
+    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        x = x.contiguous()
+    n, d = x.shape
+    return x, (x.stride(0) if n > 1 else d)
 
 
 def is_shipped(mod):
@@ -193,11 +206,8 @@ def decoders_forward(inp_feat, prob_dec=None, offset_dec=None, precision="f32"):
         raise RuntimeError("inp_feat must be a CUDA tensor (no CPU path)")
     if inp_feat.dtype != torch.float32 or inp_feat.dim() != 2:
         raise RuntimeError("inp_feat must be float32 [n, D]")
-    x = inp_feat.detach()
-    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
-        x = x.contiguous()
+    x, ld = _rows(inp_feat)
     n, d = x.shape
-    ld = x.stride(0) if n > 1 else d
     keep = []
     dp = do = None
     for m in (prob_dec, offset_dec):
@@ -218,7 +228,7 @@ def decoders_forward(inp_feat, prob_dec=None, offset_dec=None, precision="f32"):
     out_o = torch.empty((n, 1), dtype=torch.float32, device=x.device) if do is not None else None
     L = _lib.lib()
     wsb = L.lidf_decoders_workspace_bytes(n, d)
-    ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=x.device)
+    ws = _lib.workspace(wsb, x.device)
     with torch.cuda.device(x.device):
         fn = L.lidf_decoders_split_f32 if precision == "f16x3" else L.lidf_decoders_f32
         _lib.check(fn(
@@ -228,30 +238,21 @@ def decoders_forward(inp_feat, prob_dec=None, offset_dec=None, precision="f32"):
     return out_p, out_o
 
 
-_PARAM_ORDER = ("linear_1.weight", "linear_1.bias", "linear_2.weight", "linear_2.bias",
-                "linear_3.weight", "linear_3.bias", "linear_4.weight", "linear_4.bias",
-                "offset_enc.weight", "offset_enc.bias")
-
-
 class _DecoderTrainFn(torch.autograd.Function):
     """IMNet / IEF on [n, D] rows with a HIP forward that keeps the activations and a HIP backward
     (what autograd derives for models/implicit_net.py:81-98 / :131-152)."""
 
     @staticmethod
     def forward(ctx, mod, inp_feat, *params):
-        x = inp_feat.detach()
-        if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
-            x = x.contiguous()
+        x, ld = _rows(inp_feat)
         n, d = x.shape
-        ld = x.stride(0) if n > 1 else d
         keep = []
         dec = _decoder_struct(mod, keep)
         L = _lib.lib()
-        n_pass = int(mod.n_iter) if isinstance(mod, IEF) else 1
         f32 = dict(dtype=torch.float32, device=x.device)
-        act = torch.empty((max(L.lidf_decoder_train_act_floats(n, n_pass), 1),), **f32)
+        act = torch.empty((max(L.lidf_decoder_train_act_floats(n, n_passes(mod)), 1),), **f32)
         wsb = L.lidf_decoder_train_workspace_bytes(n, d)
-        ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=x.device)
+        ws = _lib.workspace(wsb, x.device)
         out = torch.empty((n, 1), **f32)
         with torch.cuda.device(x.device):
             _lib.check(L.lidf_decoder_forward_train_f32(
@@ -260,21 +261,18 @@ class _DecoderTrainFn(torch.autograd.Function):
         # the parameters are saved (not re-read from the module in backward): torch's version
         # counters then catch an in-place update between forward and backward
         ctx.mod, ctx.ld, ctx.ws, ctx.wsb = mod, ld, ws, wsb
-        ctx.names = [k for k in _PARAM_ORDER if _has(mod, k)]
         ctx.save_for_backward(x, act, *params)
         return out
 
     @staticmethod
     def backward(ctx, g_out):
-        mod = ctx.mod
-        x, act = ctx.saved_tensors[0], ctx.saved_tensors[1]
-        saved = dict(zip(ctx.names, ctx.saved_tensors[2:]))
+        x, act, *params = ctx.saved_tensors
         n, d = x.shape
         keep = []
-        dec = _decoder_struct(mod, keep, saved)
+        dec = _decoder_struct(ctx.mod, keep, params)
         f32 = dict(dtype=torch.float32, device=x.device)
         g = g_out.detach().reshape(-1).contiguous().float()
-        gtens, gs = _grad_struct(ctx.names, saved, f32)
+        grads, gs = _grad_struct(params)
         d_inp = torch.empty((n, d), **f32) if ctx.needs_input_grad[1] else None
         with torch.cuda.device(x.device):
             _lib.check(_lib.lib().lidf_decoder_backward_f32(
@@ -282,21 +280,7 @@ class _DecoderTrainFn(torch.autograd.Function):
                 _lib.ptr(d_inp), d, C.byref(gs), _lib.ptr(ctx.ws), ctx.wsb,
                 _lib.current_stream(x.device)))
         # frozen parameters get no gradient tensor
-        return (None, d_inp) + tuple(gtens[k] if ctx.needs_input_grad[2 + i] else None
-                                     for i, k in enumerate(ctx.names))
-
-
-def _has(mod, name):
-    layer, _ = name.split(".")
-    return hasattr(mod, layer)
-
-
-def _grad_struct(names, saved, f32):
-    gtens = {k: torch.empty_like(saved[k], **f32).contiguous() for k in names}
-    gs = _lib.LidfDecoderGrads()
-    for field, k in zip(("w1", "b1", "w2", "b2", "w3", "b3", "w4", "b4", "wenc", "benc"), _PARAM_ORDER):
-        setattr(gs, field, gtens[k].data_ptr() if k in gtens else None)
-    return gtens, gs
+        return (None, d_inp) + tuple(gr if ctx.needs_input_grad[2 + i] else None for i, gr in enumerate(grads))
 
 
 class _DecoderPairTrainFn(torch.autograd.Function):
@@ -307,23 +291,19 @@ class _DecoderPairTrainFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, prob, off, inp_feat, n_prob, *params):
-        x = inp_feat.detach()
-        if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
-            x = x.contiguous()
+        x, ld = _rows(inp_feat)
         n, d = x.shape
-        ld = x.stride(0) if n > 1 else d
         keep = []
         L = _lib.lib()
         f32 = dict(dtype=torch.float32, device=x.device)
         wsb = L.lidf_decoder_pair_workspace_bytes(n, d)
         one = L.lidf_decoder_train_workspace_bytes(n, d)
-        ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=x.device)
+        ws = _lib.workspace(wsb, x.device)
         outs, acts = [], []
         with torch.cuda.device(x.device):
             for which, mod in enumerate((prob, off)):
                 dec = _decoder_struct(mod, keep)
-                n_pass = int(mod.n_iter) if isinstance(mod, IEF) else 1
-                act = torch.empty((max(L.lidf_decoder_train_act_floats(n, n_pass), 1),), **f32)
+                act = torch.empty((max(L.lidf_decoder_train_act_floats(n, n_passes(mod)), 1),), **f32)
                 out = torch.empty((n, 1), **f32)
                 _lib.check(L.lidf_decoder_forward_train_f32(
                     _lib.ptr(x), n, d, ld, C.byref(dec), _lib.ptr(out), _lib.ptr(act),
@@ -331,39 +311,33 @@ class _DecoderPairTrainFn(torch.autograd.Function):
                     _lib.current_stream(x.device)))
                 outs.append(out)
                 acts.append(act)
-        ctx.prob, ctx.off, ctx.ld, ctx.ws, ctx.wsb = prob, off, ld, ws, wsb
-        ctx.names_p = [k for k in _PARAM_ORDER if _has(prob, k)]
-        ctx.names_o = [k for k in _PARAM_ORDER if _has(off, k)]
-        assert n_prob == len(ctx.names_p)
+        ctx.prob, ctx.off, ctx.ld, ctx.ws, ctx.wsb, ctx.n_prob = prob, off, ld, ws, wsb, n_prob
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(x, acts[0], acts[1], *params)
         return outs[0], outs[1]
 
     @staticmethod
     def backward(ctx, g_p, g_o):
-        x, act_p, act_o = ctx.saved_tensors[:3]
-        np_ = len(ctx.names_p)
-        saved_p = dict(zip(ctx.names_p, ctx.saved_tensors[3:3 + np_]))
-        saved_o = dict(zip(ctx.names_o, ctx.saved_tensors[3 + np_:]))
+        x, act_p, act_o, *params = ctx.saved_tensors
+        params_p, params_o = params[:ctx.n_prob], params[ctx.n_prob:]
         n, d = x.shape
         keep = []
         f32 = dict(dtype=torch.float32, device=x.device)
         # an output the loss did not use: a zero gradient (every sum of that decoder's backward is then zero)
         g_p = torch.zeros((n,), **f32) if g_p is None else g_p.detach().reshape(-1).contiguous().float()
         g_o = torch.zeros((n,), **f32) if g_o is None else g_o.detach().reshape(-1).contiguous().float()
-        dp = _decoder_struct(ctx.prob, keep, saved_p)
-        do = _decoder_struct(ctx.off, keep, saved_o)
-        gt_p, gs_p = _grad_struct(ctx.names_p, saved_p, f32)
-        gt_o, gs_o = _grad_struct(ctx.names_o, saved_o, f32)
+        dp = _decoder_struct(ctx.prob, keep, params_p)
+        do = _decoder_struct(ctx.off, keep, params_o)
+        gt_p, gs_p = _grad_struct(params_p)
+        gt_o, gs_o = _grad_struct(params_o)
         d_inp = torch.empty((n, d), **f32) if ctx.needs_input_grad[2] else None
         with torch.cuda.device(x.device):
             _lib.check(_lib.lib().lidf_decoder_pair_backward_f32(
                 _lib.ptr(x), n, d, ctx.ld, C.byref(dp), C.byref(do), _lib.ptr(act_p), _lib.ptr(act_o),
                 _lib.ptr(g_p), _lib.ptr(g_o), _lib.ptr(d_inp), d, C.byref(gs_p), C.byref(gs_o),
                 _lib.ptr(ctx.ws), ctx.wsb, _lib.current_stream(x.device)))
-        grads = [gt_p[k] for k in ctx.names_p] + [gt_o[k] for k in ctx.names_o]
         return (None, None, d_inp, None) + tuple(g if ctx.needs_input_grad[4 + i] else None
-                                                 for i, g in enumerate(grads))
+                                                 for i, g in enumerate(gt_p + gt_o))
 
 
 def decoders_forward_train(inp_feat, prob_dec, offset_dec):
@@ -380,8 +354,7 @@ def decoders_forward_train(inp_feat, prob_dec, offset_dec):
             raise RuntimeError("inp_feat must be float32 [n, %d]" % m.inp_dim)
     if not (prob_dec._needs_autograd(inp_feat) or offset_dec._needs_autograd(inp_feat)):
         return decoders_forward(inp_feat, prob_dec, offset_dec)     # nothing to differentiate: the inference launch
-    pp = [_get(prob_dec, k) for k in _PARAM_ORDER if _has(prob_dec, k)]
-    po = [_get(offset_dec, k) for k in _PARAM_ORDER if _has(offset_dec, k)]
+    pp, po = decoder_params(prob_dec), decoder_params(offset_dec)
     return _DecoderPairTrainFn.apply(prob_dec, offset_dec, inp_feat, len(pp), *pp, *po)
 
 
@@ -395,7 +368,7 @@ class _DecoderBase(nn.Module):
             return generic.decoder_forward_train(self, inp_feat)
         if inp_feat.dtype != torch.float32 or inp_feat.dim() != 2 or inp_feat.shape[1] != self.inp_dim:
             raise RuntimeError("inp_feat must be float32 [n, %d]" % self.inp_dim)
-        return _DecoderTrainFn.apply(self, inp_feat, *[_get(self, k) for k in _PARAM_ORDER if _has(self, k)])
+        return _DecoderTrainFn.apply(self, inp_feat, *decoder_params(self))
 
     def _needs_autograd(self, inp_feat):
         if not torch.is_grad_enabled():

@@ -25,23 +25,36 @@ def _segment_max(x, idx, n):
     return out.scatter_reduce(0, idx.view(-1, 1).expand_as(x), x, reduce="amax", include_self=True)
 
 
-def pointnet_struct(mod, keep):
-    def p(t):
-        t = t.detach()
-        if t.dtype != torch.float32:
-            raise RuntimeError("lidf_hip: float32 parameters required")
-        t = t.contiguous()
-        keep.append(t)
-        return t.data_ptr()
+_PN_ORDER = ("point_lin1", "point_lin2", "vox_lin1", "point_lin3", "point_lin4", "vox_lin2")
 
+
+def pointnet_params(mod):
+    """[w, b] x (point_lin1, point_lin2, vox_lin1, point_lin3, point_lin4, vox_lin2): the order of LidfPointNet's
+    pointer fields, in which the training nodes pass and return them."""
+    return [t for name in _PN_ORDER for t in (getattr(mod, name).weight, getattr(mod, name).bias)]
+
+
+def _pn_struct_from(tensors, keep):
+    """LidfPointNet from tensors in pointnet_params order; `keep` collects the contiguous tensors the struct
+    borrows."""
     s = _lib.LidfPointNet()
-    s.w_p1, s.b_p1 = p(mod.point_lin1.weight), p(mod.point_lin1.bias)
-    s.w_p2, s.b_p2 = p(mod.point_lin2.weight), p(mod.point_lin2.bias)
-    s.w_v1, s.b_v1 = p(mod.vox_lin1.weight), p(mod.vox_lin1.bias)
-    s.w_p3, s.b_p3 = p(mod.point_lin3.weight), p(mod.point_lin3.bias)
-    s.w_p4, s.b_p4 = p(mod.point_lin4.weight), p(mod.point_lin4.bias)
-    s.w_v2, s.b_v2 = p(mod.vox_lin2.weight), p(mod.vox_lin2.bias)
+    for (field, _), t in zip(s._fields_, tensors):
+        setattr(s, field, _lib.param_ptr(t, keep))
     return s
+
+
+def pointnet_struct(mod, keep):
+    return _pn_struct_from(pointnet_params(mod), keep)
+
+
+def _pn_grad_struct(params):
+    """Fresh float32 gradients shaped like `params` (pointnet_params order) and the LidfPointNetGrads that points
+    at them."""
+    grads = [torch.empty(p.shape, dtype=torch.float32, device=p.device) for p in params]
+    gs = _lib.LidfPointNetGrads()
+    for (field, _), g in zip(gs._fields_, grads):
+        setattr(gs, field, g.data_ptr())
+    return grads, gs
 
 
 def packed_pointnet(mod, s, dev):
@@ -74,25 +87,6 @@ def check_pointnet(mod, what="this entry"):
                            "layer by layer (PointNet2Stage.forward without autograd)" % what)
 
 
-_PN_ORDER = ("point_lin1", "point_lin2", "vox_lin1", "point_lin3", "point_lin4", "vox_lin2")
-_PN_FIELDS = ("p1", "p2", "v1", "p3", "p4", "v2")
-
-
-def _pn_struct_from(tensors, keep):
-    """LidfPointNet from a list [w, b] x (point_lin1, point_lin2, vox_lin1, point_lin3, point_lin4,
-    vox_lin2)."""
-    s = _lib.LidfPointNet()
-    for i, f in enumerate(_PN_FIELDS):
-        for j, pre in enumerate(("w_", "b_")):
-            t = tensors[2 * i + j].detach()
-            if t.dtype != torch.float32:
-                raise RuntimeError("lidf_hip: float32 parameters required")
-            t = t.contiguous()
-            keep.append(t)
-            setattr(s, pre + f, t.data_ptr())
-    return s
-
-
 class _PointNetTrainFn(torch.autograd.Function):
     """PointNet2Stage.forward under autograd (models/pointnet.py:22-38): HIP forward that keeps the
     activations (lidf_pointnet_forward_train_f32) and HIP backward (lidf_pointnet_backward_f32)."""
@@ -107,7 +101,7 @@ class _PointNetTrainFn(torch.autograd.Function):
         f32 = dict(dtype=torch.float32, device=x.device)
         act = torch.empty((max(L.lidf_pointnet_train_act_floats(n, n_vox), 1),), **f32)
         wsb = L.lidf_pointnet_train_workspace_bytes(n, n_vox)
-        ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=x.device)
+        ws = _lib.workspace(wsb, x.device)
         out = torch.empty((n_vox, 128), **f32)
         with torch.cuda.device(x.device):
             _lib.check(L.lidf_pointnet_forward_train_f32(C.byref(s), _lib.ptr(x), _lib.ptr(idx), n, n_vox,
@@ -126,11 +120,7 @@ class _PointNetTrainFn(torch.autograd.Function):
         s = _pn_struct_from(params, keep)
         f32 = dict(dtype=torch.float32, device=x.device)
         g = g_out.detach().contiguous().float()
-        grads = [torch.empty_like(p, **f32).contiguous() for p in params]
-        gs = _lib.LidfPointNetGrads()
-        for i, f in enumerate(_PN_FIELDS):
-            setattr(gs, "w_" + f, grads[2 * i].data_ptr())
-            setattr(gs, "b_" + f, grads[2 * i + 1].data_ptr())
+        grads, gs = _pn_grad_struct(params)
         d_inp = torch.empty((n, 6), **f32) if ctx.needs_input_grad[0] else None
         with torch.cuda.device(x.device):
             _lib.check(_lib.lib().lidf_pointnet_backward_f32(
@@ -174,9 +164,8 @@ class PointNet2Stage(nn.Module):
                 return generic.pointnet_forward_train(self, inp_feat, vox2point_idx, int(n_vox))
             return generic.pointnet_forward(self, inp_feat, vox2point_idx, int(n_vox))
         if needs_grad:   # the library's training path: forward that keeps activations + backward
-            params = [t for name in _PN_ORDER for t in (getattr(self, name).weight, getattr(self, name).bias)]
             return _PointNetTrainFn.apply(inp_feat, vox2point_idx.detach().to(torch.int32).contiguous(),
-                                          int(n_vox), *params)
+                                          int(n_vox), *pointnet_params(self))
         x = inp_feat.detach()
         x = x.contiguous()
         idx = vox2point_idx.detach().to(torch.int32).contiguous()
@@ -187,7 +176,7 @@ class PointNet2Stage(nn.Module):
         keep.append(packed_pointnet(self, s, x.device))
         L = _lib.lib()
         wsb = L.lidf_pointnet_workspace_bytes(n, n_vox)
-        ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=x.device)
+        ws = _lib.workspace(wsb, x.device)
         with torch.cuda.device(x.device):
             _lib.check(L.lidf_pointnet_f32(C.byref(s), _lib.ptr(x), _lib.ptr(idx), n, n_vox,
                                            _lib.ptr(out), _lib.ptr(ws), wsb,

@@ -21,7 +21,7 @@ import os
 import torch
 
 from . import _lib
-from .decoders import _decoder_struct
+from .decoders import _decoder_struct, _grad_struct, decoder_params, n_passes
 
 
 def _i32(t, name):
@@ -95,7 +95,7 @@ def _compact_mask(mask, intr):
     L = _lib.lib()
     n = bs * h * w
     wsb = L.lidf_miss_ray_workspace_bytes(n)
-    ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(wsb, dev)
     cnt = torch.zeros((1,), dtype=torch.int32, device=dev)
     mt = MASK_DTYPES[mask.dtype]
     with torch.cuda.device(dev):
@@ -208,7 +208,7 @@ def compute_ray_aabb(ray_dir, voxel_bound, ray_bid, voxel_bid, voxel_coord=None,
         gwb = L.lidf_ray_aabb_grid_workspace_bytes(int(batch), rx, ry, rz)
         if gwb == 0:
             raise RuntimeError("unsupported grid dimensions %s x batch %s" % (grid_dims, batch))
-        gws = torch.empty((gwb,), dtype=torch.uint8, device=dev)
+        gws = _lib.workspace(gwb, dev)
     count = torch.empty((max(R, 1),), dtype=torch.int32, device=dev)
     pair_off = torch.zeros((R + 1,), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
@@ -226,7 +226,7 @@ def compute_ray_aabb(ray_dir, voxel_bound, ray_bid, voxel_bid, voxel_coord=None,
                                                      _lib.ptr(ray_bid), _lib.ptr(voxel_bid), R, V,
                                                      _lib.ptr(count), st))
             wsb = L.lidf_exclusive_scan_workspace_bytes(R)
-            ws = torch.empty((wsb,), dtype=torch.uint8, device=dev)
+            ws = _lib.workspace(wsb, dev)
             _lib.check(L.lidf_exclusive_scan_i32(_lib.ptr(count), R, _lib.ptr(pair_off),
                                                  _lib.ptr(ws), wsb, st))
         P = int(pair_off[-1].item())  # host needs P to size the outputs (as nonzero() does)
@@ -368,7 +368,7 @@ def lidf_query(ray_dir, ray_pix, ray_bid, pair_off, pair_ray, pair_vox, pair_t, 
     L = _lib.lib()
     wsb = L.lidf_query_workspace_bytes(R, V, B * 32 * h * w)
     if workspace is None or workspace.numel() < wsb:
-        workspace = torch.empty((wsb,), dtype=torch.uint8, device=dev)
+        workspace = _lib.workspace(wsb, dev)
     keep = []
     dp = _decoder_struct(prob_dec, keep)
     do = _decoder_struct(offset_dec, keep)
@@ -433,7 +433,7 @@ def ray_features(feat_grid, ray_dir, ray_pix, ray_bid, roi_inp_bbox=8, multires_
     out = torch.empty((R, 128 + 3 + 6 * multires_views), dtype=torch.float32, device=ray_dir.device)
     L = _lib.lib()
     wsb = L.lidf_ray_features_workspace_bytes(B, h, w, R)   # box-sum image: 4 gathers per channel
-    ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=ray_dir.device)
+    ws = _lib.workspace(wsb, ray_dir.device)
     with torch.cuda.device(ray_dir.device):
         _lib.check(L.lidf_ray_features_f32(
             _lib.ptr(feat_grid), B, h, w, _lib.ptr(ray_dir), _lib.ptr(ray_pix), _lib.ptr(ray_bid),
@@ -525,7 +525,7 @@ def lidf_refine(ray_dir, ray_pix, ray_bid, ray_flat, pred_pos, max_pair_id, pair
             raise RuntimeError("rayfeat must be [R,%d]" % (128 + Ed))
     L = _lib.lib()
     wsb = L.lidf_refine_workspace_bytes(R, Nv, V)
-    ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(wsb, dev)
     keep = []
     pn = pointnet_struct(pnet_model, keep)
     from .pointnet import packed_pointnet
@@ -663,7 +663,7 @@ def get_occ_vox_bound(valid_xyz, valid_bid, batch, xmin=(-1.0, -1.0, 0.0), xmax=
     counts = torch.zeros((2,), dtype=torch.int32, device=dev)
     L = _lib.lib()
     wsb = L.lidf_voxelize_workspace_bytes(N, ncell)
-    ws = torch.empty((wsb,), dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(wsb, dev)
     xm = (C.c_float * 3)(*[float(v) for v in lo.tolist()])
     rr = (C.c_int32 * 3)(*r)
     with torch.cuda.device(dev):
@@ -757,7 +757,7 @@ class _RayFeaturesFn(torch.autograd.Function):
         g = g.detach().contiguous().float()
         d_feat = torch.empty(ctx.shape, dtype=torch.float32, device=g.device)
         wsb = B * 129 * h * w * 4    # scratch image of the parked gradients + rays-per-pixel table
-        ws = torch.empty((wsb,), dtype=torch.uint8, device=g.device)
+        ws = _lib.workspace(wsb, g.device)
         with torch.cuda.device(g.device):
             _lib.check(_lib.lib().lidf_ray_features_backward_f32(
                 _lib.ptr(g), _lib.ptr(ray_pix), _lib.ptr(ray_bid), g.shape[0], B, h, w, ctx.bbox,
@@ -799,169 +799,6 @@ class _BuildRowsFn(torch.autograd.Function):
                 _lib.ptr(g), _lib.ptr(pair_off), _lib.ptr(pair_vox), R, P, V, L, Lv,
                 _lib.ptr(d_vox), _lib.ptr(d_ray), _lib.current_stream(g.device)))
         return (d_vox, d_ray) + (None,) * 9
-
-
-class _QueryDecoderFn(torch.autograd.Function):
-    """One decoder of the query in the factorised form (lidf_query_decoder_forward_train_f32 /
-    lidf_query_decoder_backward_f32): inputs vox_feat [V,128] and rayfeat [R,128+Ed], no [P,385]
-    rows; gradients for both and for every parameter."""
-
-    @staticmethod
-    def forward(ctx, mod, vox_feat, rayfeat, pe, pair_off, pair_ray, pair_vox, multires,
-                multires_views, *params):
-        from . import decoders as _dec
-        vf, rf = vox_feat.detach().contiguous(), rayfeat.detach().contiguous()
-        P, R, V = pair_ray.shape[0], rf.shape[0], vf.shape[0]
-        keep = []
-        dec = _dec._decoder_struct(mod, keep)
-        a = _lib.LidfQueryTrainArgs()
-        a.n_pairs, a.n_rays, a.n_vox = P, R, V
-        a.pair_off, a.pair_ray, a.pair_vox = pair_off.data_ptr(), pair_ray.data_ptr(), pair_vox.data_ptr()
-        a.pe, a.multires, a.multires_views = pe.data_ptr(), multires, multires_views
-        a.vox_feat, a.rayfeat, a.dec = vf.data_ptr(), rf.data_ptr(), C.pointer(dec)
-        L = _lib.lib()
-        n_pass = int(mod.n_iter) if isinstance(mod, _dec.IEF) else 1
-        f32 = dict(dtype=torch.float32, device=vf.device)
-        act = torch.empty((max(L.lidf_query_decoder_act_floats(P, R, V, n_pass), 1),), **f32)
-        wsb = L.lidf_query_decoder_workspace_bytes(P, R, V)
-        ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=vf.device)
-        out = torch.empty((P, 1), **f32)
-        with torch.cuda.device(vf.device):
-            _lib.check(L.lidf_query_decoder_forward_train_f32(
-                C.byref(a), _lib.ptr(out), _lib.ptr(act), _lib.ptr(ws), wsb,
-                _lib.current_stream(vf.device)))
-        ctx.mod, ctx.ws = mod, ws
-        ctx.cfg = (multires, multires_views, wsb)
-        ctx.names = [k for k in _dec._PARAM_ORDER if _dec._has(mod, k)]
-        ctx.save_for_backward(vf, rf, pe, pair_off, pair_ray, pair_vox, act, *params)
-        return out
-
-    @staticmethod
-    def backward(ctx, g_out):
-        from . import decoders as _dec
-        mod, ws = ctx.mod, ctx.ws
-        vf, rf, pe, pair_off, pair_ray, pair_vox, act = ctx.saved_tensors[:7]
-        saved = dict(zip(ctx.names, ctx.saved_tensors[7:]))
-        multires, multires_views, wsb = ctx.cfg
-        keep = []
-        dec = _dec._decoder_struct(mod, keep, saved)
-        a = _lib.LidfQueryTrainArgs()
-        a.n_pairs, a.n_rays, a.n_vox = pair_ray.shape[0], rf.shape[0], vf.shape[0]
-        a.pair_off, a.pair_ray, a.pair_vox = pair_off.data_ptr(), pair_ray.data_ptr(), pair_vox.data_ptr()
-        a.pe, a.multires, a.multires_views = pe.data_ptr(), multires, multires_views
-        a.vox_feat, a.rayfeat, a.dec = vf.data_ptr(), rf.data_ptr(), C.pointer(dec)
-        f32 = dict(dtype=torch.float32, device=vf.device)
-        g = g_out.detach().reshape(-1).contiguous().float()
-        names = ctx.names
-        gt = {k: torch.empty_like(saved[k], **f32).contiguous() for k in names}
-        gs = _lib.LidfDecoderGrads()
-        for field, k in zip(("w1", "b1", "w2", "b2", "w3", "b3", "w4", "b4", "wenc", "benc"), _dec._PARAM_ORDER):
-            setattr(gs, field, gt[k].data_ptr() if k in gt else None)
-        d_vox = torch.empty_like(vf) if ctx.needs_input_grad[1] else None
-        d_ray = torch.empty_like(rf) if ctx.needs_input_grad[2] else None
-        with torch.cuda.device(vf.device):
-            _lib.check(_lib.lib().lidf_query_decoder_backward_f32(
-                C.byref(a), _lib.ptr(act), _lib.ptr(g), _lib.ptr(d_vox), _lib.ptr(d_ray), 0,
-                C.byref(gs), _lib.ptr(ws), wsb, _lib.current_stream(vf.device)))
-        return (None, d_vox, d_ray) + (None,) * 6 + tuple(
-            gt[k] if ctx.needs_input_grad[9 + i] else None for i, k in enumerate(names))
-
-
-class _QueryDecodersFn(torch.autograd.Function):
-    """Both decoders of the query in the factorised form: forward = ONE launch of the per-point
-    kernel with the activations kept (lidf_query_forward_train_f32; the positional encodings are
-    formed in registers), backward = lidf_query_decoder_backward_f32 per decoder, the second one
-    adding into the first one's d vox_feat / d rayfeat."""
-
-    @staticmethod
-    def forward(ctx, prob_mod, off_mod, vox_feat, rayfeat, pe, pair_off, pair_ray, pair_vox, pair_t,
-                ray_dir, vox_center, pos_rel, multires, multires_views, n_prob, *params):
-        from . import decoders as _dec
-        vf, rf = vox_feat.detach().contiguous(), rayfeat.detach().contiguous()
-        P, R, V = pair_ray.shape[0], rf.shape[0], vf.shape[0]
-        keep = []
-        dp, do = _dec._decoder_struct(prob_mod, keep), _dec._decoder_struct(off_mod, keep)
-        a = _lib.LidfQueryTrainArgs()
-        a.n_pairs, a.n_rays, a.n_vox = P, R, V
-        a.pair_off, a.pair_ray, a.pair_vox = pair_off.data_ptr(), pair_ray.data_ptr(), pair_vox.data_ptr()
-        a.pe, a.multires, a.multires_views = pe.data_ptr(), multires, multires_views
-        a.vox_feat, a.rayfeat, a.dec = vf.data_ptr(), rf.data_ptr(), C.pointer(dp)
-        L = _lib.lib()
-        f32 = dict(dtype=torch.float32, device=vf.device)
-        passes = [int(m.n_iter) if isinstance(m, _dec.IEF) else 1 for m in (prob_mod, off_mod)]
-        acts = [torch.empty((max(L.lidf_query_decoder_act_floats(P, R, V, n), 1),), **f32) for n in passes]
-        wsb = L.lidf_query_forward_train_workspace_bytes(R, V)
-        ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=vf.device)
-        outs = [torch.empty((P, 1), **f32) for _ in range(2)]
-        with torch.cuda.device(vf.device):
-            _lib.check(L.lidf_query_forward_train_f32(
-                C.byref(a), C.byref(do), _lib.ptr(pair_t), _lib.ptr(ray_dir),
-                _lib.ptr(vox_center) if vox_center is not None else None, 1 if pos_rel else 0,
-                _lib.ptr(outs[0]), _lib.ptr(outs[1]), _lib.ptr(acts[0]), _lib.ptr(acts[1]), _lib.ptr(ws), wsb,
-                _lib.current_stream(vf.device)))
-        ctx.mods = (prob_mod, off_mod)
-        ctx.cfg = (multires, multires_views, n_prob)
-        ctx.names = [[k for k in _dec._PARAM_ORDER if _dec._has(m, k)] for m in (prob_mod, off_mod)]
-        ctx.save_for_backward(vf, rf, pe, pair_off, pair_ray, pair_vox, acts[0], acts[1], *params)
-        return outs[0], outs[1]
-
-    @staticmethod
-    def backward(ctx, g_prob, g_off):
-        from . import decoders as _dec
-        vf, rf, pe, pair_off, pair_ray, pair_vox, act_p, act_o = ctx.saved_tensors[:8]
-        params = ctx.saved_tensors[8:]
-        multires, multires_views, n_prob = ctx.cfg
-        P, R, V = pair_ray.shape[0], rf.shape[0], vf.shape[0]
-        f32 = dict(dtype=torch.float32, device=vf.device)
-        L = _lib.lib()
-        wsb = L.lidf_query_decoder_workspace_bytes(P, R, V)
-        ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=vf.device)
-        d_vox = torch.empty_like(vf) if ctx.needs_input_grad[2] else None
-        d_ray = torch.empty_like(rf) if ctx.needs_input_grad[3] else None
-        g_pred = g_pred.contiguous().float() if g_pred is not None else None
-        grads_out = []
-        for i, (mod, act, g_out, names, ps) in enumerate((
-                (ctx.mods[0], act_p, g_prob, ctx.names[0], params[:n_prob]),
-                (ctx.mods[1], act_o, g_off, ctx.names[1], params[n_prob:]))):
-            saved = dict(zip(names, ps))
-            keep = []
-            dec = _dec._decoder_struct(mod, keep, saved)
-            a = _lib.LidfQueryTrainArgs()
-            a.n_pairs, a.n_rays, a.n_vox = P, R, V
-            a.pair_off, a.pair_ray, a.pair_vox = pair_off.data_ptr(), pair_ray.data_ptr(), pair_vox.data_ptr()
-            a.pe, a.multires, a.multires_views = pe.data_ptr(), multires, multires_views
-            a.vox_feat, a.rayfeat, a.dec = vf.data_ptr(), rf.data_ptr(), C.pointer(dec)
-            g = (g_out if g_out is not None else torch.zeros((P, 1), **f32)).detach().reshape(-1).contiguous().float()
-            gt = {k: torch.empty_like(saved[k], **f32).contiguous() for k in names}
-            gs = _lib.LidfDecoderGrads()
-            for field, k in zip(("w1", "b1", "w2", "b2", "w3", "b3", "w4", "b4", "wenc", "benc"), _dec._PARAM_ORDER):
-                setattr(gs, field, gt[k].data_ptr() if k in gt else None)
-            with torch.cuda.device(vf.device):
-                _lib.check(L.lidf_query_decoder_backward_f32(
-                    C.byref(a), _lib.ptr(act), _lib.ptr(g), _lib.ptr(d_vox), _lib.ptr(d_ray), 1 if i else 0,
-                    C.byref(gs), _lib.ptr(ws), wsb, _lib.current_stream(vf.device)))
-            grads_out += [gt[k] for k in names]
-        base = 15
-        return (None, None, d_vox, d_ray) + (None,) * 11 + tuple(
-            g if ctx.needs_input_grad[base + i] else None for i, g in enumerate(grads_out))
-
-
-def _query_decoders(prob_mod, off_mod, vox_feat, rayfeat, pe, pair_off, pair_ray, pair_vox, pair_t,
-                    ray_dir, vox_center, pos_rel, multires, multires_views):
-    from . import decoders as _dec
-    _dec._check_supported(prob_mod), _dec._check_supported(off_mod)
-    pp = [_dec._get(prob_mod, k) for k in _dec._PARAM_ORDER if _dec._has(prob_mod, k)]
-    po = [_dec._get(off_mod, k) for k in _dec._PARAM_ORDER if _dec._has(off_mod, k)]
-    return _QueryDecodersFn.apply(prob_mod, off_mod, vox_feat, rayfeat, pe, pair_off, pair_ray, pair_vox,
-                                  pair_t, ray_dir, vox_center, pos_rel, multires, multires_views, len(pp),
-                                  *pp, *po)
-
-
-def _query_decoder(mod, vox_feat, rayfeat, pe, pair_off, pair_ray, pair_vox, multires, multires_views):
-    from . import decoders as _dec
-    _dec._check_supported(mod)
-    return _QueryDecoderFn.apply(mod, vox_feat, rayfeat, pe, pair_off, pair_ray, pair_vox, multires,
-                                 multires_views, *[_dec._get(mod, k) for k in _dec._PARAM_ORDER if _dec._has(mod, k)])
 
 
 class _QueryTailFn(torch.autograd.Function):
@@ -1021,6 +858,17 @@ def _train_side_stream(dev):
     return s
 
 
+def _query_train_args(vf, rf, pe, pair_off, pair_ray, pair_vox, multires, multires_views, dec):
+    """LidfQueryTrainArgs of the factorised query over vox_feat `vf` [V,128] and rayfeat `rf` [R,128+Ed] for the
+    decoder struct `dec` (the argument block holds a reference to it)."""
+    a = _lib.LidfQueryTrainArgs()
+    a.n_pairs, a.n_rays, a.n_vox = pair_ray.shape[0], rf.shape[0], vf.shape[0]
+    a.pair_off, a.pair_ray, a.pair_vox = pair_off.data_ptr(), pair_ray.data_ptr(), pair_vox.data_ptr()
+    a.pe, a.multires, a.multires_views = pe.data_ptr(), multires, multires_views
+    a.vox_feat, a.rayfeat, a.dec = vf.data_ptr(), rf.data_ptr(), C.pointer(dec)
+    return a
+
+
 class _QueryTrainFn(torch.autograd.Function):
     """get_pred of the training step as ONE autograd node: both decoders (lidf_query_forward_train_f32, one launch
     of the per-point kernel with the activations kept) and the per-pair / per-ray tail (lidf_query_tail_f32).
@@ -1029,35 +877,30 @@ class _QueryTrainFn(torch.autograd.Function):
     nor pair_pred_pos received a gradient, dL/d pred_offset is non-zero at the selected pair of every ray only,
     and offset_dec's backward runs over those R rows (lidf_query_decoder_backward_rows_f32) — the same gradients,
     an eighth of the rows at 8 pairs per ray. A loss that touches pred_offset or pair_pred_pos takes the dense
-    backward (lidf_query_tail_backward_f32 + lidf_query_decoder_backward_f32)."""
+    backward (lidf_query_tail_backward_f32 + lidf_query_decoder_backward_f32).
+    selected (offsets="selected"): offset_dec runs on the selected pair of every ray only, forward and backward
+    (lidf_query_forward_train_selected_f32); pred_offset / pair_pred_pos are zero at every other pair."""
 
     @staticmethod
     def forward(ctx, prob_mod, off_mod, vox_feat, rayfeat, pe, pair_off, pair_ray, pair_vox, pair_t,
                 ray_dir, vox_center, pos_rel, multires, multires_views, r0, r1, part, mid_in, selected, n_prob,
                 *params):
-        from . import decoders as _dec
         vf, rf = vox_feat.detach().contiguous(), rayfeat.detach().contiguous()
         dev = vf.device
         P, R, V = pair_ray.shape[0], rf.shape[0], vf.shape[0]
-        if selected:
-            return _QueryTrainFn._forward_selected(ctx, prob_mod, off_mod, vf, rf, pe, pair_off, pair_ray, pair_vox,
-                                                   pair_t, ray_dir, vox_center, pos_rel, multires, multires_views,
-                                                   r0, r1, part, mid_in, n_prob, params)
         keep = []
-        dp, do = _dec._decoder_struct(prob_mod, keep), _dec._decoder_struct(off_mod, keep)
-        a = _lib.LidfQueryTrainArgs()
-        a.n_pairs, a.n_rays, a.n_vox = P, R, V
-        a.pair_off, a.pair_ray, a.pair_vox = pair_off.data_ptr(), pair_ray.data_ptr(), pair_vox.data_ptr()
-        a.pe, a.multires, a.multires_views = pe.data_ptr(), multires, multires_views
-        a.vox_feat, a.rayfeat, a.dec = vf.data_ptr(), rf.data_ptr(), C.pointer(dp)
+        dp, do = _decoder_struct(prob_mod, keep), _decoder_struct(off_mod, keep)
+        a = _query_train_args(vf, rf, pe, pair_off, pair_ray, pair_vox, multires, multires_views, dp)
         L = _lib.lib()
         f32 = dict(dtype=torch.float32, device=dev)
-        passes = [int(m.n_iter) if isinstance(m, _dec.IEF) else 1 for m in (prob_mod, off_mod)]
-        acts = [torch.empty((max(L.lidf_query_decoder_act_floats(P, R, V, n), 1),), **f32) for n in passes]
+        passes = [n_passes(prob_mod), n_passes(off_mod)]
+        act_p = torch.empty((max(L.lidf_query_decoder_act_floats(P, R, V, passes[0]), 1),), **f32)
+        act_o = torch.empty((max(L.lidf_query_decoder_act_floats(R if selected else P, R, V, passes[1]), 1),), **f32)
         wsb = L.lidf_query_forward_train_workspace_bytes(R, V)
-        ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=dev)
-        prob, off = torch.empty((P, 1), **f32), torch.empty((P, 1), **f32)
-        pos = torch.empty((P, 3), **f32)
+        ws = _lib.workspace(wsb, dev)
+        prob = torch.empty((P, 1), **f32)
+        new = torch.zeros if selected else torch.empty   # (selected: written at the selected pairs only)
+        off, pos = new((P, 1), **f32), new((P, 3), **f32)
         sm = torch.empty((P,), **f32)
         mid = torch.empty((R,), dtype=torch.int64, device=dev)
         pred = torch.empty((R, 3), **f32)
@@ -1065,63 +908,24 @@ class _QueryTrainFn(torch.autograd.Function):
             mid_in = mid_in.to(torch.int64).contiguous()
         with torch.cuda.device(dev):
             st = _lib.current_stream(dev)
-            _lib.check(L.lidf_query_forward_train_f32(
-                C.byref(a), C.byref(do), _lib.ptr(pair_t), _lib.ptr(ray_dir),
-                _lib.ptr(vox_center) if vox_center is not None else None, 1 if pos_rel else 0,
-                _lib.ptr(prob), _lib.ptr(off), _lib.ptr(acts[0]), _lib.ptr(acts[1]), _lib.ptr(ws), wsb, st))
-            _lib.check(L.lidf_query_tail_f32(
-                _lib.ptr(off), _lib.ptr(prob), _lib.ptr(pair_off), _lib.ptr(pair_ray), _lib.ptr(pair_t),
-                _lib.ptr(ray_dir), R, P, r0, r1, part, _lib.ptr(mid_in), _lib.ptr(pos), _lib.ptr(sm),
-                _lib.ptr(mid), _lib.ptr(pred), st))
+            if selected:
+                _lib.check(L.lidf_query_forward_train_selected_f32(
+                    C.byref(a), C.byref(do), _lib.ptr(pair_t), _lib.ptr(ray_dir), _lib.ptr(vox_center),
+                    1 if pos_rel else 0, r0, r1, part, _lib.ptr(mid_in), _lib.ptr(prob), _lib.ptr(sm), _lib.ptr(mid),
+                    _lib.ptr(off), _lib.ptr(pos), _lib.ptr(pred), _lib.ptr(act_p), _lib.ptr(act_o), _lib.ptr(ws),
+                    wsb, st))
+            else:
+                _lib.check(L.lidf_query_forward_train_f32(
+                    C.byref(a), C.byref(do), _lib.ptr(pair_t), _lib.ptr(ray_dir), _lib.ptr(vox_center),
+                    1 if pos_rel else 0, _lib.ptr(prob), _lib.ptr(off), _lib.ptr(act_p), _lib.ptr(act_o),
+                    _lib.ptr(ws), wsb, st))
+                _lib.check(L.lidf_query_tail_f32(
+                    _lib.ptr(off), _lib.ptr(prob), _lib.ptr(pair_off), _lib.ptr(pair_ray), _lib.ptr(pair_t),
+                    _lib.ptr(ray_dir), R, P, r0, r1, part, _lib.ptr(mid_in), _lib.ptr(pos), _lib.ptr(sm),
+                    _lib.ptr(mid), _lib.ptr(pred), st))
         sel = mid_in if mid_in is not None else mid
         ctx.mods = (prob_mod, off_mod)
-        ctx.cfg = (multires, multires_views, n_prob, r0, r1, part, passes, False)
-        ctx.names = [[k for k in _dec._PARAM_ORDER if _dec._has(m, k)] for m in (prob_mod, off_mod)]
-        ctx.save_for_backward(vf, rf, pe, pair_off, pair_ray, pair_vox, ray_dir, sel, acts[0], acts[1], *params)
-        ctx.set_materialize_grads(False)
-        mid_out = mid if mid_in is None else sel.clone()   # (a copy: never the caller's tensor as an output)
-        ctx.mark_non_differentiable(sm, mid_out)
-        return prob, off, pos, sm, mid_out, pred
-
-    @staticmethod
-    def _forward_selected(ctx, prob_mod, off_mod, vf, rf, pe, pair_off, pair_ray, pair_vox, pair_t, ray_dir,
-                          vox_center, pos_rel, multires, multires_views, r0, r1, part, mid_in, n_prob, params):
-        """offsets="selected": offset_dec runs on the selected pair of every ray only, forward and backward
-        (lidf_query_forward_train_selected_f32); pred_offset / pair_pred_pos are zero at every other pair."""
-        from . import decoders as _dec
-        dev = vf.device
-        P, R, V = pair_ray.shape[0], rf.shape[0], vf.shape[0]
-        keep = []
-        dp, do = _dec._decoder_struct(prob_mod, keep), _dec._decoder_struct(off_mod, keep)
-        a = _lib.LidfQueryTrainArgs()
-        a.n_pairs, a.n_rays, a.n_vox = P, R, V
-        a.pair_off, a.pair_ray, a.pair_vox = pair_off.data_ptr(), pair_ray.data_ptr(), pair_vox.data_ptr()
-        a.pe, a.multires, a.multires_views = pe.data_ptr(), multires, multires_views
-        a.vox_feat, a.rayfeat, a.dec = vf.data_ptr(), rf.data_ptr(), C.pointer(dp)
-        L = _lib.lib()
-        f32 = dict(dtype=torch.float32, device=dev)
-        passes = [int(m.n_iter) if isinstance(m, _dec.IEF) else 1 for m in (prob_mod, off_mod)]
-        act_p = torch.empty((max(L.lidf_query_decoder_act_floats(P, R, V, passes[0]), 1),), **f32)
-        act_o = torch.empty((max(L.lidf_query_decoder_act_floats(R, R, V, passes[1]), 1),), **f32)
-        wsb = L.lidf_query_forward_train_workspace_bytes(R, V)
-        ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=dev)
-        prob = torch.empty((P, 1), **f32)
-        off, pos = torch.zeros((P, 1), **f32), torch.zeros((P, 3), **f32)
-        sm = torch.empty((P,), **f32)
-        mid = torch.empty((R,), dtype=torch.int64, device=dev)
-        pred = torch.empty((R, 3), **f32)
-        if mid_in is not None:
-            mid_in = mid_in.to(torch.int64).contiguous()
-        with torch.cuda.device(dev):
-            _lib.check(L.lidf_query_forward_train_selected_f32(
-                C.byref(a), C.byref(do), _lib.ptr(pair_t), _lib.ptr(ray_dir),
-                _lib.ptr(vox_center) if vox_center is not None else None, 1 if pos_rel else 0, r0, r1, part,
-                _lib.ptr(mid_in), _lib.ptr(prob), _lib.ptr(sm), _lib.ptr(mid), _lib.ptr(off), _lib.ptr(pos),
-                _lib.ptr(pred), _lib.ptr(act_p), _lib.ptr(act_o), _lib.ptr(ws), wsb, _lib.current_stream(dev)))
-        sel = mid_in if mid_in is not None else mid
-        ctx.mods = (prob_mod, off_mod)
-        ctx.cfg = (multires, multires_views, n_prob, r0, r1, part, passes, True)
-        ctx.names = [[k for k in _dec._PARAM_ORDER if _dec._has(m, k)] for m in (prob_mod, off_mod)]
+        ctx.cfg = (multires, multires_views, n_prob, r0, r1, part, passes, selected)
         ctx.save_for_backward(vf, rf, pe, pair_off, pair_ray, pair_vox, ray_dir, sel, act_p, act_o, *params)
         ctx.set_materialize_grads(False)
         mid_out = mid if mid_in is None else sel.clone()   # (a copy: never the caller's tensor as an output)
@@ -1130,9 +934,7 @@ class _QueryTrainFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_prob, g_off, g_pos, g_sm, g_mid, g_pred):
-        from . import decoders as _dec
-        vf, rf, pe, pair_off, pair_ray, pair_vox, ray_dir, sel, act_p, act_o = ctx.saved_tensors[:10]
-        params = ctx.saved_tensors[10:]
+        vf, rf, pe, pair_off, pair_ray, pair_vox, ray_dir, sel, act_p, act_o, *params = ctx.saved_tensors
         multires, multires_views, n_prob, r0, r1, part, passes, selected = ctx.cfg
         P, R, V = pair_ray.shape[0], rf.shape[0], vf.shape[0]
         dev = vf.device
@@ -1160,9 +962,15 @@ class _QueryTrainFn(torch.autograd.Function):
         wsb = L.lidf_query_decoder_workspace_bytes(P, R, V)
         if rows_only:
             wsb = max(wsb, L.lidf_query_decoder_rows_workspace_bytes(R, V, multires, passes[1]))
-        ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=dev)
+        ws = _lib.workspace(wsb, dev)
         d_vox = torch.empty_like(vf) if ctx.needs_input_grad[2] else None
         d_ray = torch.empty_like(rf) if ctx.needs_input_grad[3] else None
+        # both decoders' weight and gradient structs, built here on the caller's stream before the side stream
+        # forks: `keep` holds the contiguous copies the structs borrow until after the join below
+        keep = []
+        decs = [_decoder_struct(m, keep, ps) for m, ps in zip(ctx.mods, (params[:n_prob], params[n_prob:]))]
+        args = [_query_train_args(vf, rf, pe, pair_off, pair_ray, pair_vox, multires, multires_views, d) for d in decs]
+        grads, gstructs = zip(_grad_struct(params[:n_prob]), _grad_struct(params[n_prob:]))
         # offset_dec's backward over the selected rows is ~40 launches on R rows (76,800 where prob_dec's walk
         # 614,400): latency, not work. The two backwards are independent until their input gradients are added, so
         # that one runs on a side stream beside prob_dec's (its own workspace and d_vox / d_ray, added at the join;
@@ -1172,30 +980,14 @@ class _QueryTrainFn(torch.autograd.Function):
         side = _train_side_stream(dev) if two else None
         ws2 = d_vox2 = d_ray2 = None
         if two:
-            ws2 = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=dev)
+            ws2 = _lib.workspace(wsb, dev)
             d_vox2 = torch.empty_like(vf) if d_vox is not None else None
             d_ray2 = torch.empty_like(rf) if d_ray is not None else None
             side.wait_stream(torch.cuda.current_stream(dev))
-        grads_out = [None, None]
         with torch.cuda.device(dev):
             st = _lib.current_stream(dev)
-            order = ((1, ctx.mods[1], act_o, ctx.names[1], params[n_prob:]),
-                     (0, ctx.mods[0], act_p, ctx.names[0], params[:n_prob]))
-            if not two:
-                order = order[::-1]
-            for i, mod, act, names, ps in order:
-                saved = dict(zip(names, ps))
-                keep = []
-                dec = _dec._decoder_struct(mod, keep, saved)
-                a = _lib.LidfQueryTrainArgs()
-                a.n_pairs, a.n_rays, a.n_vox = P, R, V
-                a.pair_off, a.pair_ray, a.pair_vox = pair_off.data_ptr(), pair_ray.data_ptr(), pair_vox.data_ptr()
-                a.pe, a.multires, a.multires_views = pe.data_ptr(), multires, multires_views
-                a.vox_feat, a.rayfeat, a.dec = vf.data_ptr(), rf.data_ptr(), C.pointer(dec)
-                gt = {k: torch.empty_like(saved[k], **f32).contiguous() for k in names}
-                gs = _lib.LidfDecoderGrads()
-                for field, k in zip(("w1", "b1", "w2", "b2", "w3", "b3", "w4", "b4", "wenc", "benc"), _dec._PARAM_ORDER):
-                    setattr(gs, field, gt[k].data_ptr() if k in gt else None)
+            for i in ((1, 0) if two else (0, 1)):
+                a, gs, act = args[i], gstructs[i], (act_p, act_o)[i]
                 if i == 1 and rows_only:
                     with torch.cuda.stream(side) if two else contextlib.nullcontext():
                         _lib.check(L.lidf_query_decoder_backward_rows_f32(
@@ -1209,9 +1001,8 @@ class _QueryTrainFn(torch.autograd.Function):
                         g = g_prob if g_prob is not None else torch.zeros((P, 1), **f32)
                     else:   # the tail's adjoint for every pair, + what the loss put on pred_offset itself
                         g = torch.empty((P,), **f32)
-                        gpos = g_pos.contiguous().float() if g_pos is not None else None
                         _lib.check(L.lidf_query_tail_backward_f32(
-                            _lib.ptr(gpos), _lib.ptr(g_pred), _lib.ptr(sel), _lib.ptr(pair_ray), _lib.ptr(ray_dir),
+                            _lib.ptr(g_pos), _lib.ptr(g_pred), _lib.ptr(sel), _lib.ptr(pair_ray), _lib.ptr(ray_dir),
                             R, P, r0, r1, part, _lib.ptr(g), st))
                         if g_off is not None:
                             g = g + g_off.reshape(-1)
@@ -1219,17 +1010,14 @@ class _QueryTrainFn(torch.autograd.Function):
                     _lib.check(L.lidf_query_decoder_backward_f32(
                         C.byref(a), _lib.ptr(act), _lib.ptr(g), _lib.ptr(d_vox), _lib.ptr(d_ray), 1 if i else 0,
                         C.byref(gs), _lib.ptr(ws), wsb, st))
-                grads_out[i] = [gt[k] for k in names]
         if two:   # join: offset_dec's share of the input gradients
             torch.cuda.current_stream(dev).wait_stream(side)
             if d_vox is not None:
                 d_vox += d_vox2
             if d_ray is not None:
                 d_ray += d_ray2
-        grads_out = grads_out[0] + grads_out[1]
-        base = 20
         return (None, None, d_vox, d_ray) + (None,) * 16 + tuple(
-            g if ctx.needs_input_grad[base + i] else None for i, g in enumerate(grads_out))
+            g if ctx.needs_input_grad[20 + i] else None for i, g in enumerate(grads[0] + grads[1]))
 
 
 def lidf_query_train(ray_dir, ray_pix, ray_bid, pair_off, pair_ray, pair_vox, pair_t, feat_grid,
@@ -1295,10 +1083,9 @@ def lidf_query_train(ray_dir, ray_pix, ray_bid, pair_off, pair_ray, pair_vox, pa
     if factorised:
         if two:
             torch.cuda.current_stream(dev).wait_stream(side)
-        from . import decoders as _dec
-        _dec._check_supported(prob_dec), _dec._check_supported(offset_dec)
-        pp = [_dec._get(prob_dec, k) for k in _dec._PARAM_ORDER if _dec._has(prob_dec, k)]
-        po = [_dec._get(offset_dec, k) for k in _dec._PARAM_ORDER if _dec._has(offset_dec, k)]
+        from .decoders import _check_supported
+        _check_supported(prob_dec), _check_supported(offset_dec)
+        pp, po = decoder_params(prob_dec), decoder_params(offset_dec)
         pred_prob, pred_offset, pair_pred_pos, sm, mid, pred_pos = _QueryTrainFn.apply(
             prob_dec, offset_dec, vox_feat, rayfeat, pe, pair_off, pair_ray, pair_vox, pair_t, ray_dir, vox_center,
             pos_rel, multires, multires_views, float(offset_range[0]), float(offset_range[1]), float(part_size),
@@ -1368,6 +1155,9 @@ def _refine_train_args(cfg, x, rf, pn, do, out, end_voxel, ws, cells):
     return q
 
 
+_PN_PARAMS = 12   # PointNet2Stage's parameters lead the node's *params (pointnet_params order), the decoder's follow
+
+
 class _RefineTrainFn(torch.autograd.Function):
     """RefineNet.forward 'train' as ONE autograd node: lidf_refine_train_forward_f32 keeps what
     lidf_refine_train_backward_f32 needs in one `act` buffer (weight streams of the step, the per-ray layer-1
@@ -1377,7 +1167,6 @@ class _RefineTrainFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred_pos, rayfeat, cfg, *params):
-        from .decoders import _decoder_struct
         from .pointnet import _pn_struct_from
         t = cfg["tensors"]
         dev = pred_pos.device
@@ -1385,16 +1174,12 @@ class _RefineTrainFn(torch.autograd.Function):
         B, _, h, w = t["rgb_img"].shape
         T, L_, Lv = cfg["forward_times"], cfg["multires"], cfg["multires_views"]
         dec = cfg["offset_dec"]
-        npn = 12
-        pn_params, dec_params = params[:npn], params[npn:]
         keep = []
-        pn = _pn_struct_from(pn_params, keep)
-        do = _decoder_struct(dec, keep, tensors=dict(zip(cfg["dec_names"], dec_params)))
+        pn = _pn_struct_from(params[:_PN_PARAMS], keep)
+        do = _decoder_struct(dec, keep, params[_PN_PARAMS:])
         L = _lib.lib()
-        npass = dec.n_iter if do.is_ief else 1
-        act = torch.empty((max(L.lidf_refine_train_act_bytes(R, Nv, V, L_, Lv, npass, T), 1),), dtype=torch.uint8,
-                          device=dev)
-        ws = torch.empty((max(L.lidf_refine_train_workspace_bytes(R, Nv, V, L_), 1),), dtype=torch.uint8, device=dev)
+        act = _lib.workspace(L.lidf_refine_train_act_bytes(R, Nv, V, L_, Lv, n_passes(dec), T), dev)
+        ws = _lib.workspace(L.lidf_refine_train_workspace_bytes(R, Nv, V, L_), dev)
         out = torch.empty((R, 3), dtype=torch.float32, device=dev)
         end_voxel = torch.empty((R,), dtype=torch.int32, device=dev)
         x = pred_pos.detach().contiguous()
@@ -1414,42 +1199,29 @@ class _RefineTrainFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_pos, _g_end):
-        from .decoders import _decoder_struct
-        from .pointnet import _PN_FIELDS, _pn_struct_from
+        from .pointnet import _pn_grad_struct, _pn_struct_from
         cfg = ctx.cfg
-        x, rf, act = ctx.saved_tensors[:3]
-        params = ctx.saved_tensors[3:]
-        npn = 12
+        x, rf, act, *params = ctx.saved_tensors
         dev = x.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        grads = [torch.empty(p.shape, **f32) for p in params]
-        gp = _lib.LidfPointNetGrads()
-        for i, f in enumerate(_PN_FIELDS):
-            setattr(gp, "w_" + f, grads[2 * i].data_ptr())
-            setattr(gp, "b_" + f, grads[2 * i + 1].data_ptr())
-        gd = _lib.LidfDecoderGrads()
-        _map = {"linear_1.weight": "w1", "linear_1.bias": "b1", "linear_2.weight": "w2", "linear_2.bias": "b2",
-                "linear_3.weight": "w3", "linear_3.bias": "b3", "linear_4.weight": "w4", "linear_4.bias": "b4",
-                "offset_enc.weight": "wenc", "offset_enc.bias": "benc"}
-        for name, gr in zip(cfg["dec_names"], grads[npn:]):
-            setattr(gd, _map[name], gr.data_ptr())
+        grads_pn, gp = _pn_grad_struct(params[:_PN_PARAMS])
+        grads_dec, gd = _grad_struct(params[_PN_PARAMS:])
         d_pos = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         d_rf = torch.empty_like(rf) if ctx.needs_input_grad[1] else None
         g = g_pos.detach().contiguous().float()
         # (the argument block is rebuilt from the SAVED tensors: same buffers as the forward's)
         keep = []
-        pn = _pn_struct_from(params[:npn], keep)
-        do = _decoder_struct(cfg["offset_dec"], keep, tensors=dict(zip(cfg["dec_names"], params[npn:])))
+        pn = _pn_struct_from(params[:_PN_PARAMS], keep)
+        do = _decoder_struct(cfg["offset_dec"], keep, params[_PN_PARAMS:])
         R, Nv, V = x.shape[0], cfg["tensors"]["valid_inp"].shape[0], cfg["tensors"]["voxel_bound"].shape[0]
-        ws = torch.empty((max(_lib.lib().lidf_refine_train_workspace_bytes(R, Nv, V, cfg["multires"]), 1),),
-                         dtype=torch.uint8, device=dev)
+        ws = _lib.workspace(_lib.lib().lidf_refine_train_workspace_bytes(R, Nv, V, cfg["multires"]), dev)
         q = _refine_train_args(cfg, x, rf, pn, do, None, None, ws, ctx.cells)
         q.cell_table_ready = 1 if ctx.cells is not None else 0
         with torch.cuda.device(dev):
             _lib.check(_lib.lib().lidf_refine_train_backward_f32(
                 C.byref(q), cfg["forward_times"], _lib.ptr(act), act.numel(), _lib.ptr(g), _lib.ptr(d_pos),
                 _lib.ptr(d_rf), C.byref(gp), C.byref(gd), _lib.current_stream(dev)))
-        return (d_pos, d_rf, None) + tuple(gr if ctx.needs_input_grad[3 + i] else None for i, gr in enumerate(grads))
+        return (d_pos, d_rf, None) + tuple(gr if ctx.needs_input_grad[3 + i] else None
+                                           for i, gr in enumerate(grads_pn + grads_dec))
 
 
 def lidf_refine_train(ray_dir, ray_pix, ray_bid, ray_flat, pred_pos, max_pair_id, pair_vox, voxel_bound,
@@ -1473,7 +1245,7 @@ def lidf_refine_train(ray_dir, ray_pix, ray_bid, ray_flat, pred_pos, max_pair_id
     (pipeline.py:937). grid: as lidf_refine (the end voxels through the cell table).
     Returns pred_pos_refine [R,3] (with grad) and the last end_voxel_id [R] i32."""
     from .decoders import is_shipped
-    from .pointnet import _PN_ORDER, is_shipped as pnet_shipped
+    from .pointnet import is_shipped as pnet_shipped, pointnet_params
     E, Ed = 3 + 6 * multires, 3 + 6 * multires_views
     if not (is_shipped(offset_dec) and pnet_shipped(pnet_model) and feat_grid.shape[1] == 32
             and multires > 0 and offset_dec.inp_dim == 256 + E + Ed):
@@ -1513,13 +1285,10 @@ def lidf_refine_train(ray_dir, ray_pix, ray_bid, ray_flat, pred_pos, max_pair_id
     cur = pred_pos
     if perturb_noise is not None:
         cur = cur + float(perturb_noise) * ray_dir
-    dec_names = [n for n, _ in offset_dec.named_parameters()]
-    params = [t for name in _PN_ORDER for t in (getattr(pnet_model, name).weight, getattr(pnet_model, name).bias)]
-    params += [p for _, p in offset_dec.named_parameters()]
     cfg = dict(tensors={k: v.detach() for k, v in ts.items()}, forward_times=int(forward_times), multires=multires,
                multires_views=multires_views, pos_rel=pos_rel, pnet_pos_rel=pnet_pos_rel, offset_range=offset_range,
-               offset_dec=offset_dec, dec_names=dec_names, grid=grid)
-    pos, end_voxel = _RefineTrainFn.apply(cur, rayfeat, cfg, *params)
+               offset_dec=offset_dec, grid=grid)
+    pos, end_voxel = _RefineTrainFn.apply(cur, rayfeat, cfg, *pointnet_params(pnet_model), *decoder_params(offset_dec))
     return pos, end_voxel
 
 

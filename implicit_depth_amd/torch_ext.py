@@ -28,5 +28,5 @@ def ext():
 
 def decoder_weights(mod):
     """[w1,b1,...,w4,b4(,offset_enc.weight,offset_enc.bias)] of an IMNet / IEF module."""
-    from .decoders import _PARAM_ORDER, _get, _has
-    return [_get(mod, k).detach().contiguous() for k in _PARAM_ORDER if _has(mod, k)]
+    from .decoders import decoder_params
+    return [t.detach().contiguous() for t in decoder_params(mod)]

@@ -24,7 +24,7 @@ import torch  # noqa: E402
 from util import make_module, orc, to_dev  # noqa: E402
 from implicit_depth_amd import _lib  # noqa: E402
 from implicit_depth_amd import decoders as _dec  # noqa: E402
-from implicit_depth_amd.query import ray_features  # noqa: E402
+from implicit_depth_amd.query import _query_train_args, ray_features  # noqa: E402
 
 dev = torch.device("cuda:0")
 scene = orc.synthetic_scene(1, 240, 320, 8, seed=1235)
@@ -41,11 +41,7 @@ for kind in ("IMNET", "IEF"):
     mod = make_module(kind, scene["prob_p" if kind == "IMNET" else "off_p"], 385, dev).train()
     keep = []
     dec = _dec._decoder_struct(mod, keep)
-    a = _lib.LidfQueryTrainArgs()
-    a.n_pairs, a.n_rays, a.n_vox = P, R, V
-    a.pair_off, a.pair_ray, a.pair_vox = s["pair_off"].data_ptr(), s["pair_ray"].data_ptr(), s["pair_vox"].data_ptr()
-    a.pe, a.multires, a.multires_views = pe.data_ptr(), 8, 4
-    a.vox_feat, a.rayfeat, a.dec = s["vox_feat"].data_ptr(), rf.data_ptr(), C.pointer(dec)
+    a = _query_train_args(s["vox_feat"], rf, pe, s["pair_off"], s["pair_ray"], s["pair_vox"], 8, 4, dec)
     npass = 2 if kind == "IEF" else 1
     act = torch.empty((L.lidf_query_decoder_act_floats(P, R, V, npass),), device=dev)
     wsb = L.lidf_query_decoder_workspace_bytes(P, R, V)

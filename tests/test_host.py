@@ -389,3 +389,66 @@ def test_cpu_tensors_refused_unless_composite_is_allowed(monkeypatch):
     # gradients flow through the composite definition (a caller's CPU unit test of a training step)
     mods[0](x).sum().backward()
     assert mods[0].linear_1.weight.grad is not None
+
+
+_DEC_FIELDS = {"w1": "linear_1.weight", "b1": "linear_1.bias", "w2": "linear_2.weight", "b2": "linear_2.bias",
+               "w3": "linear_3.weight", "b3": "linear_3.bias", "w4": "linear_4.weight", "b4": "linear_4.bias",
+               "wenc": "offset_enc.weight", "benc": "offset_enc.bias"}
+_PN_FIELDS = {"w_p1": "point_lin1.weight", "b_p1": "point_lin1.bias", "w_p2": "point_lin2.weight",
+              "b_p2": "point_lin2.bias", "w_v1": "vox_lin1.weight", "b_v1": "vox_lin1.bias",
+              "w_p3": "point_lin3.weight", "b_p3": "point_lin3.bias", "w_p4": "point_lin4.weight",
+              "b_p4": "point_lin4.bias", "w_v2": "vox_lin2.weight", "b_v2": "vox_lin2.bias"}
+
+
+def test_weight_and_gradient_structs_point_at_their_parameters():
+    """The ctypes marshalling of the training nodes, on CPU modules: every pointer field of a weight struct is the
+    data_ptr() of the parameter it names (an IMNet's wenc / benc are NULL), and the gradient structs point every
+    field at the gradient tensor of that same parameter."""
+    from implicit_depth_amd import IEF, IMNet, PointNet2Stage
+    from implicit_depth_amd.decoders import _decoder_struct, _grad_struct, decoder_params
+    from implicit_depth_amd.pointnet import _pn_grad_struct, pointnet_params, pointnet_struct
+    cases = [(IMNet(385, 1, 64), _DEC_FIELDS, _decoder_struct, decoder_params, _grad_struct),
+             (IEF("cpu", 385, 1, 64, n_iter=2), _DEC_FIELDS, _decoder_struct, decoder_params, _grad_struct),
+             (PointNet2Stage(6, 128, 32), _PN_FIELDS, pointnet_struct, pointnet_params, _pn_grad_struct)]
+    for mod, fields, struct, params, grad_struct in cases:
+        what = type(mod).__name__
+        named = dict(mod.named_parameters())
+        keep = []
+        s = struct(mod, keep)
+        for f, n in fields.items():
+            assert getattr(s, f) == (named[n].data_ptr() if n in named else None), (what, f)
+        if what != "PointNet2Stage":
+            assert (s.is_ief, s.n_iter) == ((1, 2) if what == "IEF" else (0, 1)), what
+            # the backward's form: the saved tensors in decoder_params order
+            s2 = _decoder_struct(mod, [], decoder_params(mod))
+            assert all(getattr(s2, f) == getattr(s, f) for f in fields), what
+        ps = params(mod)
+        assert sorted(map(id, ps)) == sorted(map(id, named.values())), what
+        grads, gs = grad_struct(ps)
+        name_of = {id(p): n for n, p in named.items()}
+        grad_of = {name_of[id(p)]: g for p, g in zip(ps, grads)}
+        for n, p in named.items():
+            assert grad_of[n].shape == p.shape and grad_of[n].dtype == torch.float32, (what, n)
+        for f, n in fields.items():
+            assert getattr(gs, f) == (grad_of[n].data_ptr() if n in named else None), (what, f)
+        assert len({g.data_ptr() for g in grads}) == len(grads), what
+
+
+def test_non_contiguous_parameter_is_marshalled_as_a_kept_copy():
+    """A parameter held non-contiguously reaches the struct as a contiguous copy with equal values, and that copy
+    is in `keep` (the caller holds it until the launches that read it are ordered)."""
+    from implicit_depth_amd import IEF, IMNet, PointNet2Stage
+    from implicit_depth_amd.decoders import _decoder_struct
+    from implicit_depth_amd.pointnet import pointnet_struct
+    for mod, field, layer, struct in ((IMNet(385, 1, 64), "w2", "linear_2", _decoder_struct),
+                                      (IEF("cpu", 385, 1, 64, n_iter=2), "w2", "linear_2", _decoder_struct),
+                                      (PointNet2Stage(6, 128, 32), "w_p3", "point_lin3", pointnet_struct)):
+        lin = getattr(mod, layer)
+        lin.weight = torch.nn.Parameter(lin.weight.detach().t().contiguous().t())
+        assert not lin.weight.is_contiguous()
+        keep = []
+        s = struct(mod, keep)
+        ptr = getattr(s, field)
+        assert ptr != lin.weight.data_ptr()
+        held = [t for t in keep if t.data_ptr() == ptr]
+        assert len(held) == 1 and held[0].is_contiguous() and torch.equal(held[0], lin.weight.detach())
