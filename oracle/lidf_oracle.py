@@ -16,6 +16,12 @@ Pinning status:
   * roi_align (torchvision 0.7.0) and torch_scatter: sources are NOT in the reference tree and
     neither package is installed -> PARITY UNPINNED for those two; restated from their documented
     semantics and property-tested.
+
+Precision: by default every function computes on float32 CPU tensors, as above. The differentiable path (embed,
+the decoders, roi_align_fast, scatter_softmax / scatter_max, query, pointnet2stage) follows the dtype and device of
+its inputs instead, so the same restatement evaluated on float64 (GPU) tensors is the high-precision reference of
+tests/test_f64_gpu.py. Discrete steps (ray_aabb / pcl_aabb, an arg-max given as max_pair_id) keep their float32
+definition. refine_step and lidf_forward are float32 CPU only (they go through numpy).
 """
 import math
 
@@ -52,27 +58,41 @@ def _out_act(y, use_sigmoid):
     return torch.max(torch.min(y, y * 0.01 + 0.99), y * 0.01)  # implicit_net.py:96
 
 
-def _mlp4(p, x):
-    l1 = F.leaky_relu(F.linear(x, p["linear_1.weight"], p["linear_1.bias"]), 0.02)
-    l2 = F.leaky_relu(F.linear(l1, p["linear_2.weight"], p["linear_2.bias"]), 0.02)
-    l3 = F.leaky_relu(F.linear(l2, p["linear_3.weight"], p["linear_3.bias"]), 0.02)
+def _mlp4(p, x, preacts=None):
+    z1 = F.linear(x, p["linear_1.weight"], p["linear_1.bias"])
+    l1 = F.leaky_relu(z1, 0.02)
+    z2 = F.linear(l1, p["linear_2.weight"], p["linear_2.bias"])
+    l2 = F.leaky_relu(z2, 0.02)
+    z3 = F.linear(l2, p["linear_3.weight"], p["linear_3.bias"])
+    l3 = F.leaky_relu(z3, 0.02)
+    if preacts is not None:
+        preacts += [z1, z2, z3]
     return F.linear(l3, p["linear_4.weight"], p["linear_4.bias"])
 
 
-def imnet_forward(p, x, use_sigmoid=False):
-    return _out_act(_mlp4(p, x), use_sigmoid)
+# preacts (tests only): a list that receives every kink-bearing pre-activation in evaluation order — the three
+# hidden layers of every pass, then the output activation's argument (the IMNet's logit, the IEF's running offset)
+def imnet_forward(p, x, use_sigmoid=False, preacts=None):
+    y = _mlp4(p, x, preacts)
+    if preacts is not None:
+        preacts.append(y)
+    return _out_act(y, use_sigmoid)
 
 
-def ief_forward(p, x, n_iter, use_sigmoid=False, init_offset=0.001):
-    off = torch.full((x.shape[0], 1), init_offset, dtype=torch.float32)  # implicit_net.py:104,132
+def ief_forward(p, x, n_iter, use_sigmoid=False, init_offset=0.001, preacts=None):
+    off = torch.full((x.shape[0], 1), init_offset, dtype=x.dtype, device=x.device)  # implicit_net.py:104,132
     for _ in range(n_iter):
         feat = F.linear(off, p["offset_enc.weight"], p["offset_enc.bias"])
-        off = off + _mlp4(p, torch.cat([x, feat], 1))
+        off = off + _mlp4(p, torch.cat([x, feat], 1), preacts)
+    if preacts is not None:
+        preacts.append(off)
     return _out_act(off, use_sigmoid)
 
 
-def decoder_forward(p, x, kind, n_iter=2, use_sigmoid=False):
-    return ief_forward(p, x, n_iter, use_sigmoid) if kind == "IEF" else imnet_forward(p, x, use_sigmoid)
+def decoder_forward(p, x, kind, n_iter=2, use_sigmoid=False, preacts=None):
+    if kind == "IEF":
+        return ief_forward(p, x, n_iter, use_sigmoid, preacts=preacts)
+    return imnet_forward(p, x, use_sigmoid, preacts=preacts)
 
 
 def init_decoder(kind, inp_dim, seed, scale=1.0, gf=64):
@@ -288,8 +308,8 @@ def _axis_taps(start, binsz, g, size):
     """Per-axis bilinear taps of the RoIAlign sample points: start/binsz [n] f32, g samples per
     bin. Returns (lo, hi) int64 [n,2,g] and (wlo, whi) f32 [n,2,g] following bilinear_interpolate's
     edge rules (outside [-1, size] -> zero weight; clamp at 0; last row/col collapse)."""
-    ph = torch.arange(2, dtype=torch.float32).view(1, 2, 1)
-    i = (torch.arange(g, dtype=torch.float32) + 0.5).view(1, 1, g)
+    ph = torch.arange(2, dtype=start.dtype, device=start.device).view(1, 2, 1)
+    i = (torch.arange(g, dtype=start.dtype, device=start.device) + 0.5).view(1, 1, g)
     c = (start.view(-1, 1, 1) + ph * binsz.view(-1, 1, 1)) + (i * binsz.view(-1, 1, 1)) / float(g)
     dead = (c < -1.0) | (c > float(size))
     c = c.clamp(min=0.0)
@@ -297,8 +317,8 @@ def _axis_taps(start, binsz, g, size):
     edge = lo >= size - 1
     lo = torch.where(edge, torch.full_like(lo, size - 1), lo)
     hi = torch.where(edge, lo, lo + 1)
-    c = torch.where(edge, lo.float(), c)
-    l = c - lo.float()
+    c = torch.where(edge, lo.to(c.dtype), c)
+    l = c - lo.to(c.dtype)
     wlo, whi = 1.0 - l, l
     wlo = torch.where(dead, torch.zeros_like(wlo), wlo)
     whi = torch.where(dead, torch.zeros_like(whi), whi)
@@ -312,7 +332,8 @@ def roi_align_fast(feat, boxes, chunk=4096):
     per-box Python loop would dominate (cpu_baseline, larger tests)."""
     B, C, H, W = feat.shape
     K = boxes.shape[0]
-    out = torch.zeros(K, C, 2, 2)
+    boxes = boxes.to(device=feat.device, dtype=feat.dtype)   # (integer corners: exact in any float type)
+    out = torch.zeros(K, C, 2, 2, dtype=feat.dtype, device=feat.device)
     bid = boxes[:, 0].long()
     rsw, rsh = boxes[:, 1] - 0.5, boxes[:, 2] - 0.5
     roi_w, roi_h = (boxes[:, 3] - 0.5) - rsw, (boxes[:, 4] - 0.5) - rsh
@@ -329,8 +350,8 @@ def roi_align_fast(feat, boxes, chunk=4096):
                 xlo, xhi, wxl, wxh = _axis_taps(rsw[ids], bw[ids], g_w, W)
                 n = ids.numel()
                 bsel = bid[ids].view(n, 1, 1, 1)
-                csel = torch.arange(C).view(1, C, 1, 1)
-                acc = torch.zeros(n, C, 2, 2)
+                csel = torch.arange(C, device=feat.device).view(1, C, 1, 1)
+                acc = torch.zeros(n, C, 2, 2, dtype=feat.dtype, device=feat.device)
                 for yi, wy in ((ylo, wyl), (yhi, wyh)):
                     for xi, wx in ((xlo, wxl), (xhi, wxh)):
                         v = feat[bsel, csel, yi.reshape(n, 1, 2 * g_h, 1), xi.reshape(n, 1, 1, 2 * g_w)]
@@ -356,18 +377,18 @@ def roi_boxes(img_ind, bid, h, w, roi_inp_bbox=8):
 # ----------------------------------------------------------------------------------------------
 def scatter_softmax(src, index, dim_size=None):
     n = int(index.max()) + 1 if dim_size is None and index.numel() else (dim_size or 0)
-    mx = torch.full((n,), -float("inf"), dtype=src.dtype)
+    mx = torch.full((n,), -float("inf"), dtype=src.dtype, device=src.device)
     mx = mx.scatter_reduce(0, index, src, reduce="amax", include_self=True)
     e = (src - mx[index]).exp()
-    s = torch.zeros(n, dtype=src.dtype).index_add_(0, index, e)
+    s = torch.zeros(n, dtype=src.dtype, device=src.device).index_add_(0, index, e)
     return e / s[index]
 
 
 def scatter_max(src, index, dim_size):
     out = torch.zeros(dim_size, dtype=src.dtype)
     arg = torch.full((dim_size,), src.shape[0], dtype=torch.long)
-    s = src.detach().numpy()   # values only: the arg-max carries no gradient
-    idx = index.numpy()
+    s = src.detach().cpu().numpy()   # values only: the arg-max carries no gradient
+    idx = index.cpu().numpy()
     best = {}
     for i in range(s.shape[0]):
         r = int(idx[i])
@@ -376,7 +397,7 @@ def scatter_max(src, index, dim_size):
     for r, (v, i) in best.items():
         out[r] = float(v)
         arg[r] = i
-    return out, arg
+    return out.to(src.device), arg.to(src.device)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -426,10 +447,11 @@ def build_inp_embed(ray_dir, ray_pix, ray_bid, pair_ray, pair_vox, pair_t, feat_
 def query(ray_dir, ray_pix, ray_bid, pair_ray, pair_vox, pair_t, pair_off, feat_grid, vox_feat,
           prob_p, off_p, off_kind="IEF", n_iter=2, use_sigmoid=False, multires=8, multires_views=4,
           roi_inp_bbox=8, offset_range=(0.0, 1.0), part_size=0.25, vox_center=None, pos_rel=False,
-          chunk=262144, fast_roi=False, roi_out_bbox=2, max_pair_id=None):
+          chunk=262144, fast_roi=False, roi_out_bbox=2, max_pair_id=None, rows=None):
     """get_embedding + get_pred (models/pipeline.py:338-466) + depth z. Pairs are ray-major.
     roi_out_bbox: model.roi_out_bbox (:387), 2 in every shipped config. max_pair_id [R] int64: the selection by
-    ground-truth labels of training while epoch < maxpool_label_epo (:444-446) instead of the arg-max."""
+    ground-truth labels of training while epoch < maxpool_label_epo (:444-446) instead of the arg-max.
+    rows (tests only): a list that receives the decoder input rows [chunk, D] of every chunk, in pair order."""
     R = ray_dir.shape[0]
     P = pair_ray.shape[0]
     boxes = roi_boxes(ray_pix.long(), ray_bid.long(), feat_grid.shape[2], feat_grid.shape[3],
@@ -439,9 +461,10 @@ def query(ray_dir, ray_pix, ray_bid, pair_ray, pair_vox, pair_t, pair_off, feat_
     else:
         ray_rgb = roi_align(feat_grid, boxes, output_size=roi_out_bbox).reshape(R, -1)
     e_dir_ray = embed(ray_dir, multires_views)
-    pred_offset = torch.empty(P, 1)
-    pred_prob = torch.empty(P, 1)
-    pair_pred_pos = torch.empty(P, 3)
+    dt, dev = vox_feat.dtype, vox_feat.device   # float32 CPU by default; float64 / GPU tensors follow
+    pred_offset = torch.empty(P, 1, dtype=dt, device=dev)
+    pred_prob = torch.empty(P, 1, dtype=dt, device=dev)
+    pair_pred_pos = torch.empty(P, 3, dtype=dt, device=dev)
     for s in range(0, P, chunk):
         sl = slice(s, min(P, s + chunk))
         pr, pv, pt = pair_ray[sl], pair_vox[sl], pair_t[sl]
@@ -455,6 +478,8 @@ def query(ray_dir, ray_pix, ray_bid, pair_ray, pair_vox, pair_t, pair_off, feat_
             ie, il = enter, leave
         inp = torch.cat((vox_feat[pv], ray_rgb[pr], embed(ie, multires), embed(il, multires),
                          e_dir_ray[pr]), -1)
+        if rows is not None:
+            rows.append(inp)
         po = decoder_forward(off_p, inp, off_kind, n_iter, use_sigmoid)
         pp = imnet_forward(prob_p, inp, use_sigmoid)
         # pipeline.py:437-439
@@ -465,10 +490,10 @@ def query(ray_dir, ray_pix, ray_bid, pair_ray, pair_vox, pair_t, pair_off, feat_
     if P > 0:
         sm = scatter_softmax(pred_prob[:, 0], pair_ray, dim_size=R)
     else:
-        sm = torch.empty(0)
+        sm = torch.empty(0, dtype=dt, device=dev)
     if max_pair_id is None:
         _, max_pair_id = scatter_max(sm, pair_ray, dim_size=R)
-    dummy = torch.cat((pair_pred_pos, torch.zeros(1, 3)), 0)  # pipeline.py:452-454
+    dummy = torch.cat((pair_pred_pos, torch.zeros(1, 3, dtype=dt, device=dev)), 0)  # pipeline.py:452-454
     pred_pos = dummy[max_pair_id]
     return {
         "pred_offset": pred_offset, "pred_prob_end": pred_prob, "pair_pred_pos": pair_pred_pos,
@@ -510,7 +535,7 @@ def occupied_voxels(valid_xyz, valid_bid, xmin=(-1.0, -1.0, 0.0), xmax=(1.0, 1.0
 # ----------------------------------------------------------------------------------------------
 def _scatter_max_rows(x, idx, n):
     """torch_scatter.scatter(x, idx, dim=0, reduce='max'); rows without points are 0 (x >= 0)."""
-    out = torch.zeros(n, x.shape[1], dtype=x.dtype)
+    out = torch.zeros(n, x.shape[1], dtype=x.dtype, device=x.device)
     return out.scatter_reduce(0, idx.view(-1, 1).expand_as(x), x, reduce="amax", include_self=True)
 
 

@@ -94,3 +94,119 @@ def make_pointnet(params, device):
     m = PointNet2Stage(input_channels=6, output_channels=128, gf_dim=32)
     m.load_state_dict({k: v.clone() for k, v in params.items()})
     return m.to(device).eval()
+
+
+# ----------------------------------------------------------------------------------------------
+# float64 yardstick: the HIP f32 path against a float64 evaluation of the oracle, with the oracle's own
+# float32 error on the same inputs as the unit (tests/test_f64_gpu.py, tests/test_f64_criterion.py)
+# ----------------------------------------------------------------------------------------------
+F64_K = 4.0          # the kernel may be this many times less accurate than the f32 torch evaluation
+F64_FLOOR_ULPS = 4   # plus this many units of 2^-24 of the tensor's largest magnitude
+
+
+def f64(obj, device=None):
+    """float64 copy of a tensor or of a dict of tensors (integer tensors keep their type)."""
+    if isinstance(obj, dict):
+        return {k: f64(v, device) for k, v in obj.items()}
+    if not torch.is_tensor(obj):
+        return obj
+    t = obj.detach().to(device) if device is not None else obj.detach()
+    return t.double() if t.is_floating_point() else t
+
+
+def inv_out_act(v):
+    """Exact inverse of the decoders' output activation max(min(y, 0.01y + 0.99), 0.01y) (implicit_net.py:96),
+    in float64: v < 0 -> 100 v, v > 1 -> 100 (v - 0.99). The activation divides any logit error by 100 outside
+    [0, 1]; comparing logits keeps that error visible."""
+    v = v.double()
+    return torch.where(v < 0, 100.0 * v, torch.where(v > 1, 100.0 * (v - 0.99), v))
+
+
+def f64_errors(got, ref64, ref32):
+    """(max|got - ref64|, max|ref32 - ref64|, ||got - ref64|| / ||ref64||, ||ref32 - ref64|| / ||ref64||, max|ref64|)."""
+    r = ref64.double().reshape(-1)
+    g = got.detach().double().to(r.device).reshape(-1)
+    s = ref32.detach().double().to(r.device).reshape(-1)
+    nr = max(r.norm().item(), 1e-300)
+    return ((g - r).abs().max().item(), (s - r).abs().max().item(), (g - r).norm().item() / nr,
+            (s - r).norm().item() / nr, r.abs().max().item())
+
+
+def assert_f64_close(what, got, ref64, ref32, k=F64_K, floor_ulps=F64_FLOOR_ULPS, report=None):
+    """The HIP result must be no less accurate than the float32 oracle it replaces, within a factor k, both
+    elementwise and normwise, against the float64 oracle on the same inputs:
+        max|got - ref64|          <= k max|ref32 - ref64|           + floor_ulps 2^-24 max|ref64|
+        ||got - ref64|| / ||ref64|| <= k ||ref32 - ref64|| / ||ref64|| + floor_ulps 2^-24
+    Returns (and appends to `report`, a list) the measured errors; the assertion message carries both errors
+    and their ratio."""
+    assert tuple(got.shape) == tuple(ref64.shape) == tuple(ref32.shape), (what, got.shape, ref64.shape, ref32.shape)
+    if ref64.numel() == 0:
+        return None
+    e_max, e32_max, e_nrm, e32_nrm, scale = f64_errors(got, ref64, ref32)
+    u = 2.0 ** -24
+    row = {"what": what, "max": e_max, "max32": e32_max, "ratio_max": e_max / max(e32_max, u * scale, 1e-300),
+           "nrm": e_nrm, "nrm32": e32_nrm, "ratio_nrm": e_nrm / max(e32_nrm, u, 1e-300)}
+    if report is not None:
+        report.append(row)
+    msg = ("%s: HIP vs float64 max %.3g / normwise %.3g; f32 oracle vs float64 max %.3g / normwise %.3g; "
+           "ratio %.2f / %.2f (k = %g)" % (what, e_max, e_nrm, e32_max, e32_nrm, row["ratio_max"],
+                                           row["ratio_nrm"], k))
+    print(msg)
+    assert e_max == e_max and e_max <= k * e32_max + floor_ulps * u * scale, msg
+    assert e_nrm <= k * e32_nrm + floor_ulps * u, msg
+    return row
+
+
+def decoder_preacts(p, x, kind, n_iter=2):
+    """Every kink-bearing pre-activation of orc.decoder_forward(p, x, kind, n_iter), taken from the oracle itself
+    (its preacts list): the three hidden layers of every pass, and the output clamp's argument (the IEF's running
+    offset, the IMNet's logit)."""
+    zs = []
+    with torch.no_grad():
+        orc.decoder_forward(p, x, kind, n_iter, preacts=zs)
+    return zs[:-1], zs[-1]
+
+
+def kink_rows(p, x, kind, n_iter=2, use_sigmoid=False, rel=1.5e-6):
+    """[n] bool: rows of the float64 evaluation where any hidden pre-activation lies within rel x (its layer's
+    max|z|) of the leaky-ReLU kink at 0, or the output clamp's argument within rel x max|y| of its kinks at 0
+    and 1. Such a row's gradient depends on which side of the kink rounding puts it (slope 1 or 0.02), in
+    any precision; gradient checks give it zero upstream gradient on both sides. (rel: the f32 oracle's own
+    pre-activation error against float64 is 0.5-0.9e-6 x max|z| on the IEF at 385 inputs.)"""
+    zs, y = decoder_preacts(p, x, kind, n_iter)
+    bad = torch.zeros(x.shape[0], dtype=torch.bool, device=x.device)
+    for z in zs:
+        bad |= (z.abs() < rel * z.abs().max()).any(1)
+    if not use_sigmoid:
+        d = rel * max(y.abs().max().item(), 1.0)
+        bad |= ((y.abs() < d) | ((y - 1.0).abs() < d)).any(1)
+    return bad
+
+
+def oracle_grads(p, x, kind, w, dt, n_iter=2, use_sigmoid=False):
+    """Oracle decoder output and gradients of sum(y * w) at dtype dt, on x's device: {param: grad, "input": grad}.
+    Parameters and input are fresh leaves (a copy even where x already has dtype dt), so two calls on the same x
+    never share an input gradient."""
+    pc = {k: v.detach().to(x.device, dt, copy=True).requires_grad_(True) for k, v in p.items()}
+    xc = x.detach().to(dt, copy=True).requires_grad_(True)
+    y = orc.decoder_forward(pc, xc, kind, n_iter, use_sigmoid)
+    (y.reshape(-1) * w.to(dt)).sum().backward()
+    g = {k: v.grad for k, v in pc.items()}
+    g["input"] = xc.grad
+    return y.detach(), g
+
+
+def tf32_off():
+    """Context manager: full-precision float32 matmuls (no TF32) for the references, restored on exit."""
+    import contextlib
+
+    @contextlib.contextmanager
+    def cm():
+        old = (torch.backends.cuda.matmul.allow_tf32, torch.backends.cudnn.allow_tf32)
+        torch.backends.cuda.matmul.allow_tf32 = False
+        torch.backends.cudnn.allow_tf32 = False
+        try:
+            yield
+        finally:
+            torch.backends.cuda.matmul.allow_tf32, torch.backends.cudnn.allow_tf32 = old
+    return cm()
