@@ -3,184 +3,8 @@
 #include <string.h>
 #include <stdlib.h>
 
-#include "lidf_device.h"
+#include "lidf_launch.h"
 #include "lidf_hip.h"
-
-extern "C" {
-hipError_t lidf_launch_pack(const StreamLayout&, const NetW&, const NetW&, const L1Map&, float*,
-                            float*, hipStream_t);
-hipError_t lidf_launch_points(int mode, const PointsArgs&, int grid, hipStream_t);
-hipError_t lidf_launch_l1only_pair(const PointsArgs&, const PointsArgs&, const PointsArgs*, int cus, hipStream_t);
-hipError_t lidf_launch_refine_step(const RefineStepArgs&, long long, hipStream_t);
-hipError_t lidf_launch_pack_h(const StreamLayout&, const NetW&, const NetW&, const L1Map&, float*,
-                              float*, hipStream_t);
-hipError_t lidf_launch_points_h(const PointsArgs&, int cus, hipStream_t);
-StreamLayout lidf_make_layout_rows_h(int nets, int D, int l1only);
-hipError_t lidf_launch_pack_rows_h(const StreamLayout&, const NetW&, const NetW&, const L1Map&, float*,
-                                   float*, hipStream_t);
-hipError_t lidf_launch_rows_h(const PointsArgs&, int grid, hipStream_t);
-hipError_t lidf_launch_embed(const float*, long long, int, float*, hipStream_t);
-hipError_t lidf_launch_rayfeat(const float*, float*, int, int, int, const float*, const int*,
-                               const int*, long long, int, int, float*, int, hipStream_t);
-hipError_t lidf_launch_ray_reduce(const float*, const float*, const int*, long long, long long,
-                                  const int*, const int*, long long, float*, long long*, float*,
-                                  float*, hipStream_t);
-hipError_t lidf_launch_ray_dirs(const float*, int, int, int, float*, hipStream_t);
-hipError_t lidf_launch_ray_aabb_dense(const float*, const float*, const int*, const int*,
-                                      long long, long long, int*, float*, hipStream_t);
-hipError_t lidf_launch_ray_aabb_grid_build(const float*, const int*, const int*, long long, int, int, int,
-                                           int, int*, unsigned*, float*, hipStream_t);
-hipError_t lidf_launch_ray_aabb_grid(bool, const float*, const int*, long long, int, int, int, int,
-                                     const int*, const unsigned*, const float*, int*, const int*, int*,
-                                     int*, float*, hipStream_t);
-hipError_t lidf_launch_ray_aabb_compact(bool, const float*, const float*, const int*, const int*,
-                                        long long, long long, int*, const int*, int*, int*, float*,
-                                        hipStream_t);
-hipError_t lidf_launch_pcl_aabb_dense(const float*, const float*, const int*, const int*,
-                                      long long, long long, int*, hipStream_t);
-hipError_t lidf_launch_pcl_aabb_last(const float*, const float*, const int*, const int*,
-                                     long long, long long, int*, hipStream_t);
-hipError_t lidf_launch_scan(const int*, long long, int*, int*, hipStream_t);
-hipError_t lidf_launch_miss_count(const void*, int, long long, int*, int*, int*, int*, hipStream_t);
-hipError_t lidf_launch_miss_fill(const void*, int, long long, const int*, const float*, int, int, int*,
-                                 int*, int*, float*, long long*, long long*, long long*, hipStream_t);
-hipError_t lidf_launch_linear(int nt, const LinearArgs&, int grid, hipStream_t);
-hipError_t lidf_launch_chain16(int gf, const Chain16Args&, int cus, hipStream_t);
-hipError_t lidf_launch_wgrad(const float*, long long, int, const float*, long long, int, long long,
-                             float*, int, float*, float*, size_t, hipStream_t);
-hipError_t lidf_launch_pack_pointnet(const float*, const float*, const float*, const float*, const float*,
-                                     const float*, const float*, float*, const LidfPackGuardState*,
-                                     hipStream_t);
-hipError_t lidf_launch_rayfeat_dev(const float*, float*, int, int, int, const float*, const int*,
-                                   const int*, long long, const int*, int, int, float*, int, hipStream_t);
-hipError_t lidf_launch_rayfeat_phase(const float*, float*, int, int, int, const float*, const int*,
-                                     const int*, long long, const int*, int, int, float*, int, int, hipStream_t);
-hipError_t lidf_launch_ray_reduce_dev(const float*, const float*, const int*, long long, long long,
-                                      const int*, const int*, const int*, const int*, long long, float*,
-                                      long long*, float*, float*, hipStream_t, const int*, const float*, int*,
-                                      int*, float*);
-hipError_t lidf_launch_selected_finish(const long long*, const float*, const float*, long long, long long,
-                                       const int*, const int*, const int*, const int*, long long, float*,
-                                       float*, float*, float*, hipStream_t);
-hipError_t lidf_launch_scan_dev(const int*, long long, const int*, int*, int*, int*, hipStream_t);
-hipError_t lidf_launch_ray_aabb_compact_dev(bool, const float*, const float*, const int*, const int*,
-                                            long long, long long, const int*, const int*, int*,
-                                            const int*, int*, int*, float*, long long, hipStream_t);
-hipError_t lidf_launch_pointnet_chain_dev(int, const float*, const float*, const int*, const float*,
-                                          float*, long long, int, long long, const int*,
-                                          const int*, const int*, const int*, int, hipStream_t);
-hipError_t lidf_launch_vox2(const Vox2Args&, hipStream_t);
-size_t lidf_group_idx_bytes(long long, long long);
-hipError_t lidf_launch_group_idx(const int*, long long, const int*, long long, void*, const int**, const int**,
-                                 hipStream_t);
-hipError_t lidf_launch_ief16(const Ief16Args&, int, hipStream_t);
-int lidf_pointnet_lds_max_voxels(void);
-size_t lidf_pointnet_sort_bytes(long long, long long);
-hipError_t lidf_launch_sort_idx(const int*, long long, const int*, long long, void*, const int**,
-                                const int**, hipStream_t);
-hipError_t lidf_launch_pointnet_chain_sorted(int, const float*, const float*, const int*, const float*,
-                                             float*, long long, long long, const int*, const int*, int,
-                                             hipStream_t);
-hipError_t lidf_launch_refine_prep_dev(const float*, const long long*, const int*, long long, const float*,
-                                       const int*, long long, const int*, const int*, const float*,
-                                       long long, int, long long, float*, int*, int*,
-                                       const unsigned char*, const int*, const int*, hipStream_t,
-                                       const CellLookup*);
-hipError_t lidf_launch_refine_rows_dev(const float*, const int*, const float*, const float*, int, int, int,
-                                       int, long long, const int*, float*, int, int, hipStream_t);
-hipError_t lidf_launch_refine_finish_dev(const float*, const float*, const float*, float, float, long long,
-                                         const int*, float*, const int*, const int*, long long, float*,
-                                         hipStream_t);
-hipError_t lidf_launch_frame_head(const float*, const float*, const float*, const float*, const float*, int,
-                                  int, int, int, const GridSpec&, void*, int*, int*, int*, float*,
-                                  float*, int*, int*, int*, int*, int*, int*, float*, float*, float*,
-                                  const int*, const int*, long long, hipStream_t);
-size_t lidf_frame_head_blocks(long long);
-size_t lidf_frame_head_lb_bytes(long long);
-hipError_t lidf_launch_frame_cells(const int*, long long, const GridSpec&, int*, int*, float*, int*, float*,
-                                   int*, int*, hipStream_t);
-size_t lidf_ray_aabb_onepass_lb_bytes(long long);
-hipError_t lidf_launch_ray_aabb_onepass(const float*, const float*, const int*, const int*, long long, int*,
-                                        void*, int*, int*, int*, float*, long long, const int*, hipStream_t);
-hipError_t lidf_launch_roi_align(const float*, int, int, int, const int*, const int*, long long, int, int,
-                                 float*, long long, hipStream_t);
-hipError_t lidf_launch_frame_points(const float*, const float*, const int*, const int*, const int*,
-                                    const GridSpec&, long long, const int*, int*, int*, float*, float*,
-                                    float*, hipStream_t);
-hipError_t lidf_launch_vox_cells_bid(const int*, const int*, long long, const GridSpec&, int*, float*, int*,
-                                     hipStream_t);
-hipError_t lidf_launch_frame_select(const float*, const int*, const int*, long long, long long, const int*,
-                                    unsigned char*, hipStream_t);
-hipError_t lidf_launch_fingerprint(const float* const*, const long long*, int, unsigned long long,
-                                   LidfPackGuardState*, hipStream_t);
-hipError_t lidf_launch_fingerprint_multi(const float* const*, const long long*, const int*, int,
-                                         const unsigned long long*, int, void*, int, hipStream_t);
-size_t lidf_pointnet_chain_stream_bytes(void);
-hipError_t lidf_launch_pointnet_chain(int, const float*, const float*, const int*, const float*, float*,
-                                      float*, long long, long long, int, hipStream_t);
-size_t lidf_pointnet_pool_scratch_bytes(long long);
-hipError_t lidf_launch_dgrad_chain(const float*, const float*, const float*, const unsigned*,
-                                   const unsigned*, long long, float, float*, float*, int, float*, int, hipStream_t);
-size_t lidf_dgrad_stream_bytes(void);
-hipError_t lidf_launch_pack_dgrad(const float*, const float*, float*, hipStream_t);
-hipError_t lidf_launch_pnet_gather_segsum(const float*, const int*, long long, const int*, const int*, long long,
-                                          long long, float*, float*, hipStream_t);
-hipError_t lidf_launch_l4_backward(const float*, const float*, const float*, float, long long, float*,
-                                   float*, float*, float*, hipStream_t);
-hipError_t lidf_launch_ief_tail(const float*, const float*, const float*, int, const float*,
-                                const float*, long long, int, float*, float*, float*, float*, float*,
-                                float*, float*, hipStream_t);
-hipError_t lidf_launch_ief_first_pass(const float*, float*, float, const float*, int, const float*,
-                                      const float*, float*, float*, float*, hipStream_t);
-hipError_t lidf_launch_out_act(const float*, long long, int, float*, const float*, float*,
-                               hipStream_t);
-hipError_t lidf_launch_build_rows(const int*, const int*, const float*, const float*, const float*, int,
-                                  const float*, const float*, int, int, int, long long, float*, int,
-                                  hipStream_t);
-hipError_t lidf_launch_rows_backward(const float*, int, int, const int*, const int*, long long,
-                                     long long, int, float*, float*, int, hipStream_t);
-hipError_t lidf_launch_rayfeat_backward(const float*, int, const int*, const int*, long long, int, int,
-                                        int, int, float*, float*, int*, hipStream_t);
-hipError_t lidf_launch_pe_rows(const int*, const int*, const float*, const float*, const float*, int, int,
-                               long long, float*, hipStream_t);
-hipError_t lidf_launch_seg_sum_ray(const float*, int, const int*, long long, float*, hipStream_t);
-hipError_t lidf_launch_seg_sum_idx(const float*, const int*, long long, long long, float*, void*, size_t,
-                                   hipStream_t);
-size_t lidf_seg_sum_idx_ws_bytes(long long, long long);
-hipError_t lidf_launch_pair_pos(const float*, const int*, const float*, const float*, long long, float,
-                                float, float, float, float*, hipStream_t);
-hipError_t lidf_launch_ray_select(const float*, const long long*, long long, long long, float*,
-                                  hipStream_t);
-hipError_t lidf_launch_pair_pos_backward(const float*, const float*, const long long*, const int*,
-                                         const float*, long long, float, float*, hipStream_t);
-hipError_t lidf_launch_relu_mask(const float*, const float*, long long, float*, hipStream_t);
-hipError_t lidf_launch_segmax_arg(const float*, const int*, const float*, long long, int, int*, hipStream_t);
-hipError_t lidf_launch_segmax_backward(const float*, const int*, const int*, const float*, long long, int,
-                                       int, float*, hipStream_t);
-hipError_t lidf_launch_seg_sum_rows(const float*, const int*, long long, int, float*, hipStream_t);
-hipError_t lidf_launch_embed_backward(const float*, const float*, long long, int, float*, hipStream_t);
-hipError_t lidf_launch_depth_metrics(const float*, const float*, const void*, int, int, int, int, int,
-                                     float*, void*, hipStream_t);
-size_t lidf_depth_metrics_ws_bytes(void);
-hipError_t lidf_launch_vox_mark(const float*, const int*, long long, const GridSpec&, int*, int*,
-                                int*, hipStream_t);
-hipError_t lidf_launch_vox_cells(const int*, const int*, long long, const GridSpec&, int*, float*,
-                                 hipStream_t);
-hipError_t lidf_launch_vox_points(const float*, const int*, const int*, const int*, long long,
-                                  const GridSpec&, int*, int*, float*, hipStream_t);
-hipError_t lidf_launch_refine_prep(const float*, const long long*, const int*, long long,
-                                   const float*, const int*, long long, const int*, const int*,
-                                   const float*, long long, const float*, int, int, int, int, int,
-                                   long long, float*, int*, float*, int, int*, const unsigned char*,
-                                   hipStream_t, const CellLookup*);
-hipError_t lidf_launch_refine_gather(const float*, const int*, long long, float*, int, hipStream_t);
-hipError_t lidf_launch_refine_gather_dev(const float*, const int*, long long, const int*, float*, int,
-                                         hipStream_t);
-hipError_t lidf_launch_refine_rows(const float*, const int*, const float*, const float*, int, int, int, int,
-                                   long long, float*, int, hipStream_t);
-hipError_t lidf_launch_refine_finish(const float*, const float*, const float*, float, float,
-                                     long long, float*, hipStream_t);
-}
 
 #define LIDF_API extern "C" __attribute__((visibility("default")))
 #define CHECK_HIP(x)                       \
@@ -191,8 +15,6 @@ hipError_t lidf_launch_refine_finish(const float*, const float*, const float*, f
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static size_t linex_stream_bytes(int k);
 
-extern "C" hipError_t lidf_launch_zero_segments(float* const* ptrs, const long long* counts, int n,
-                                                hipStream_t st);
 // Zero up to two buffers of 4-byte words with ONE kernel launch (the frame path: a kernel node of a
 // captured graph instead of memset nodes, and one launch where hipMemsetAsync would be one per buffer).
 static hipError_t zero_words(void* a, size_t words_a, void* b, size_t words_b, hipStream_t st) {
@@ -215,9 +37,6 @@ static inline StreamLayout guarded(StreamLayout lay) {
 }
 // Pack-only API calls collect the streams of a module and pack them with one launch per
 // LIDF_PACK_JOBS streams (lidf_pack_multi_kernel) instead of one launch per stream.
-extern "C" hipError_t lidf_launch_pack_multi(const PackJobs&, hipStream_t);
-extern "C" hipError_t lidf_launch_pack(const StreamLayout&, const NetW&, const NetW&, const L1Map&, float*,
-                                       float*, hipStream_t);
 static thread_local PackJobs* tl_jobs = nullptr;
 static hipError_t flush_jobs(PackJobs& j, hipStream_t st) {
     const hipError_t e = lidf_launch_pack_multi(j, st);
@@ -255,7 +74,6 @@ static int cu_count(int* out) {
     return LIDF_OK;
 }
 
-extern "C" hipError_t lidf_launch_zero_segments(float* const*, const long long*, int, hipStream_t);
 // the gradient buffers of one decoder start at zero: one launch over the ten arrays
 static hipError_t zero_decoder_grads(const LidfDecoderGrads* g, int ld1, int is_ief, hipStream_t st) {
     float* const p[10] = {g->w1, g->b1, g->w2, g->b2, g->w3, g->b3, g->w4, g->b4,
@@ -2990,8 +2808,6 @@ LIDF_API int lidf_query_forward_train_f32(const LidfQueryTrainArgs* q, const Lid
 // The training forward with offset_dec on the selected pair of every ray only (the training counterpart of
 // LidfQueryArgs.offsets_selected): prob_dec on every pair with its activations kept, the per-ray softmax / arg-max,
 // offset_dec on the one-pair-per-ray list with ITS activations kept (R rows), positions.
-extern "C" hipError_t lidf_launch_sel_from_ids(const long long*, const int*, const float*, long long, long long, int*,
-                                               int*, float*, hipStream_t);
 LIDF_API int lidf_query_forward_train_selected_f32(const LidfQueryTrainArgs* q, const LidfDecoder* offset_dec,
                                                      const float* pair_t, const float* ray_dir,
                                                      const float* vox_center, int32_t pos_rel, float offset_range0,
@@ -3289,9 +3105,6 @@ LIDF_API size_t lidf_query_decoder_rows_workspace_bytes(int64_t n_rays, int64_t 
     if (n_rays < 0 || n_vox < 0 || multires < 0 || multires > 16 || n_pass <= 0) return 0;
     return qrows_ws(n_rays, n_vox, 2 * (3 + 6 * multires), n_pass).total;
 }
-extern "C" hipError_t lidf_launch_gather_sel_rows(const float*, long long, int, const long long*, long long,
-                                                  const int*, const float*, int, const float*, const float*,
-                                                  const float*, float, float*, int*, float*, float*, int*, hipStream_t);
 LIDF_API int lidf_query_decoder_backward_rows_f32(const LidfQueryTrainArgs* q, const float* act, int32_t act_is_rows,
                                                     const int64_t* rows, const float* g_pred_pos,
                                                     const float* g_offset_rows, const float* ray_dir, float scale,

@@ -2,27 +2,6 @@
 // lidf_pointnet_train.hip (included by lidf_api.hip behind the layer-by-layer training path, which stays as the
 // path for voxel tables beyond the sort's 16,384 rows and as the A/B reference: LIDF_PNET_TRAIN_CHAIN=0).
 
-extern "C" {
-void lidf_sort_idx_layout(long long, long long, size_t*, int*, size_t*);
-size_t lidf_sort_idx_ws_bytes(long long, long long);
-hipError_t lidf_launch_sort_idx(const int*, long long, const int*, long long, void*, const int**, const int**,
-                                hipStream_t);
-hipError_t lidf_launch_pnet_train_fwd(int, const float*, const float*, const int*, const int*, const int*,
-                                      const float*, float*, int*, float*, float*, float*, void*, long long, long long,
-                                      int, hipStream_t);
-hipError_t lidf_launch_pnet_unpack(const void*, long long, float*, int*, hipStream_t);
-int lidf_pnet_chunk_rows(void);
-hipError_t lidf_launch_pnet_tables(const int*, int, long long, const int*, int*, int*, hipStream_t);
-hipError_t lidf_launch_pnet_bwd_a(const float*, const int*, const int*, const float*, const int*, const float*,
-                                  float*, float*, long long, int, hipStream_t);
-hipError_t lidf_launch_pnet_bwd_b(const float*, const int*, const int*, const int*, const float*, const float*,
-                                  const int*, const float*, const float*, float*, float*, float*, long long, int,
-                                  hipStream_t);
-hipError_t lidf_launch_pnet_dw4(const float*, const int*, const float*, long long, float*, float*, hipStream_t);
-hipError_t lidf_launch_pnet_segsum(const float*, const int*, const int*, long long, long long, float*, float*,
-                                   hipStream_t);
-}
-
 static bool pnetc_enabled() {
     static int on = -1;
     if (on < 0) {

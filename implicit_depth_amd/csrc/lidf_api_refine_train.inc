@@ -16,15 +16,6 @@
 //             after the loop the per-ray part once on the sum of S over the iterations.
 // Parameter gradients accumulate inside the call (every kernel that writes one adds into it).
 
-extern "C" {
-hipError_t lidf_launch_refine_train_goff(const float*, const float*, float, long long, const float*, int, float*,
-                                         hipStream_t);
-hipError_t lidf_launch_refine_train_dcur(const float*, const float*, const int*, const float*, int, const float*, int,
-                                         const float*, long long, float*, hipStream_t);
-hipError_t lidf_launch_add_inplace(float*, const float*, long long, hipStream_t);
-hipError_t lidf_launch_iota(int*, long long, hipStream_t);
-}
-
 struct RtLay {
     // `act`: [weight streams | raypart | ray index | per-iteration blocks]
     size_t s_pnf[7], s_pnb[PNET_BWD_SLOTS], s_pnchain, s_pnbwd, s_vox, s_ray, s_chain, s_dvox, s_dpe, s_dgrad;

@@ -2,7 +2,7 @@
 // positional encoding, per-ray ROIAlign + direction embedding, per-ray softmax/argmax/select,
 // ray generation, ray/voxel and point/voxel box tests, exclusive scan.
 // Built with -ffp-contract=off: these restate f32 arithmetic of the reference op by op.
-#include "lidf_device.h"
+#include "lidf_launch.h"
 
 // ------------------------------------------------------------------------------------------------
 // Positional encoding — Embedder.embed (models/implicit_net.py:38-39).
@@ -413,12 +413,6 @@ extern "C" hipError_t lidf_launch_roi_align(const float* feat, int Cn, int H, in
 
 // `box` (scratch, B*32*H*W floats, followed by R+1 ints for the clamped-box list) may be NULL:
 // every ray then takes the general path inside the main kernel.
-extern "C" hipError_t lidf_launch_rayfeat_dev(const float* feat, float* box, int B, int H, int W,
-                                              const float* ray_dir, const int* ray_pix,
-                                              const int* ray_bid, long long R, const int* R_dev,
-                                              int half, int Lv, float* out, int ld, hipStream_t st);
-extern "C" hipError_t lidf_launch_zero_segments(float* const* ptrs, const long long* counts, int n,
-                                                hipStream_t st);
 extern "C" hipError_t lidf_launch_rayfeat(const float* feat, float* box, int B, int H, int W,
                                           const float* ray_dir, const int* ray_pix,
                                           const int* ray_bid, long long R, int half, int Lv,
@@ -930,27 +924,6 @@ extern "C" hipError_t lidf_launch_ray_aabb_compact(bool fill, const float* ray_d
     return hipGetLastError();
 }
 
-extern "C" hipError_t lidf_launch_ray_aabb_compact_dev(bool fill, const float* ray_dir,
-                                                       const float* vbound, const int* ray_bid,
-                                                       const int* vox_bid, long long R_cap,
-                                                       long long V_cap, const int* R_dev,
-                                                       const int* V_dev, int* count,
-                                                       const int* pair_off, int* pair_ray,
-                                                       int* pair_vox, float* pair_t, long long pair_cap,
-                                                       hipStream_t st) {
-    if (R_cap <= 0) return hipSuccess;
-    dim3 grid((unsigned)((R_cap + 255) / 256)), block(256);
-    if (fill)
-        hipLaunchKernelGGL(lidf_ray_aabb_compact_kernel<true>, grid, block, 0, st, ray_dir, vbound,
-                           ray_bid, vox_bid, R_cap, V_cap, count, pair_off, pair_ray, pair_vox, pair_t,
-                           R_dev, V_dev, pair_cap);
-    else
-        hipLaunchKernelGGL(lidf_ray_aabb_compact_kernel<false>, grid, block, 0, st, ray_dir, vbound,
-                           ray_bid, vox_bid, R_cap, V_cap, count, pair_off, pair_ray, pair_vox, pair_t,
-                           R_dev, V_dev, 0LL);
-    return hipGetLastError();
-}
-
 // The compact list in ONE launch with device-side sizes (the sync-free frame path; rounds 2-3: count ->
 // three scan launches -> cut at the capacity -> fill): a workgroup of 256 rays counts its hits — keeping
 // the first AABB_HITS voxel indices of every ray in LDS —, obtains the number of pairs before it by a
@@ -1458,20 +1431,6 @@ extern "C" hipError_t lidf_launch_scan(const int* in, long long n, int* out, int
     hipLaunchKernelGGL(lidf_scan_top_kernel, dim3(1), dim3(256), 0, st, sums, nb);
     hipLaunchKernelGGL(lidf_scan_final_kernel, dim3((unsigned)nb), dim3(256), 0, st, in, n, sums,
                        out, (const int*)nullptr, (int*)nullptr);
-    return hipGetLastError();
-}
-
-// The same scan over the first *n_dev entries of a buffer of capacity n_cap (the sync-free frame
-// path): the launch is sized for n_cap, entries beyond *n_dev are neither read nor written, and the
-// grand total out[*n_dev] is also stored to *total_out when given.
-extern "C" hipError_t lidf_launch_scan_dev(const int* in, long long n_cap, const int* n_dev, int* out,
-                                           int* sums, int* total_out, hipStream_t st) {
-    if (n_cap <= 0) n_cap = 1;
-    const long long nb = (n_cap + SCAN_ITEMS - 1) / SCAN_ITEMS;
-    hipLaunchKernelGGL(lidf_scan_sums_kernel, dim3((unsigned)nb), dim3(256), 0, st, in, n_cap, sums, n_dev);
-    hipLaunchKernelGGL(lidf_scan_top_kernel, dim3(1), dim3(256), 0, st, sums, nb);
-    hipLaunchKernelGGL(lidf_scan_final_kernel, dim3((unsigned)nb), dim3(256), 0, st, in, n_cap, sums,
-                       out, n_dev, total_out);
     return hipGetLastError();
 }
 

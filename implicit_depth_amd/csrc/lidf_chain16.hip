@@ -21,7 +21,7 @@
 //            W2[16 To + j][16 T + 4 g + 0..3]; ceil(T3 / 4) bias quads of layer 3; for T < T2: T3 quads
 //            W3[16 To + j][16 T + 4 g + ..]; padding to a multiple of the ring (lidf_chain16_pass_quads).
 // aux: w4 [gf] | b4 [1].
-#include "lidf_device.h"
+#include "lidf_launch.h"
 
 #define C16_RING 8
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)

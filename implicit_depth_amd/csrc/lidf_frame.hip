@@ -13,7 +13,7 @@
 // points inside the grid, [4] NV0 valid pixels, [5] NVS valid points kept by the stride, [6] NV + R,
 // [7] overflow flags (bit 0: more pairs than max_pairs — the list was cut).
 // Built with -ffp-contract=off: the f32 expressions follow the reference op by op.
-#include "lidf_device.h"
+#include "lidf_launch.h"
 
 #define FRAME_ITEMS 1024   // pixels per workgroup: 256 threads x 4 consecutive pixels
 

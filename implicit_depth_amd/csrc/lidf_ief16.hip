@@ -27,7 +27,7 @@
 //   (biases as matrix steps, not loads: vector memory returns in order, a load of a bias vector at the head of
 //   a pass waits behind the ring's requests and the ring behind it — measured 10 % of the launch)
 // aux: w4 [64] | b4 [1] (read once per wavefront).
-#include "lidf_device.h"
+#include "lidf_launch.h"
 
 // (a ring of 16 quads — a lone sub-tile consumes a quad in 128 cycles — measured no faster than 8)
 #define IEF16_RING 8

@@ -12,7 +12,7 @@
 // torch_scatter.scatter(..., reduce='max') (models/pointnet.py:27,35): values are post-ReLU
 // (>= 0), so integer atomicMax on the bit pattern is an exact, order-independent float max, and a
 // zero-initialised pool reproduces torch_scatter's 0 for a voxel without points.
-#include "lidf_device.h"
+#include "lidf_launch.h"
 #include <cstdlib>
 
 #include "lidf_linear_kernel.inc"
@@ -156,9 +156,6 @@ extern "C" hipError_t lidf_launch_vox2(const Vox2Args& a, hipStream_t st) {
 }
 
 // the SPLIT / XCOL instantiations: lidf_linear_s.hip, lidf_linear_x.hip, lidf_linear_sx.hip
-extern "C" void lidf_launch_linear_s(int nt, dim3 g, dim3 b, hipStream_t st, const LinearArgs& a);
-extern "C" void lidf_launch_linear_x(int nt, dim3 g, dim3 b, hipStream_t st, const LinearArgs& a);
-extern "C" void lidf_launch_linear_sx(int nt, dim3 g, dim3 b, hipStream_t st, const LinearArgs& a);
 
 // nt = accumulator tiles; a.xcol: the stream carries nt + 1 quads per k-quad, the last one the extra column's
 extern "C" hipError_t lidf_launch_linear(int nt, const LinearArgs& a_in, int grid, hipStream_t st) {

@@ -30,7 +30,7 @@
 //    land on the same few hundred addresses and were 80 % of the PointNet's time.
 //  * otherwise as in lidf_linear.hip: the wave reduces per distinct voxel of its 32 rows, one lane
 //    issues global integer atomic maxima where a plain read does not already prove them unnecessary.
-#include "lidf_device.h"
+#include "lidf_launch.h"
 
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 #define SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
@@ -58,7 +58,7 @@ struct PnetChainArgs {
     const int* n_dev;
     const int* V_dev;
     // voxel-sorted walk (large tables): point p of the launch is perm[p], the points are grouped by
-    // voxel (lidf_launch_pointnet_sort), points left out of the pooling are not in perm; the number of
+    // voxel (lidf_launch_sort_idx / _group_idx), points left out of the pooling are not in perm; the number of
     // points is *n_perm. The global-atomic pooling then meets one or two voxels per wavefront.
     const int* perm;
     const int* n_perm;
@@ -517,10 +517,6 @@ extern "C" hipError_t lidf_launch_pointnet_chain_dev(int stage, const float* str
 // scan, placement through per-voxel cursors. Points with a negative voxel are left out.
 // scratch: lidf_pointnet_sort_bytes(n, V) bytes.
 // ------------------------------------------------------------------------------------------------
-extern "C" size_t lidf_sort_idx_ws_bytes(long long P, long long V);
-extern "C" hipError_t lidf_launch_sort_idx(const int* idx, long long P, const int* n_dev, long long V,
-                                           void* ws, const int** perm_out, const int** n_perm_out,
-                                           hipStream_t st);
 extern "C" int lidf_pointnet_lds_max_voxels(void) { return PN_LDS_LIMIT / 516; }
 // scratch of the sort (0: the table is too large for it — the unsorted global-atomic path is taken)
 extern "C" size_t lidf_pointnet_sort_bytes(long long n, long long V) { return lidf_sort_idx_ws_bytes(n, V); }

@@ -25,7 +25,7 @@
 // The dense weight gradients (dW3[:, 64:], dW2, dW1 over the points; the per-voxel layers over V rows) stay
 // launches of lidf_wgrad2_kernel: their contraction runs over the points, which the chains hold in the lane
 // dimension.
-#include "lidf_device.h"
+#include "lidf_launch.h"
 
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 #define SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)

@@ -23,7 +23,7 @@
 // is kept minimal: leaky-relu in 2 instructions per register, sin/cos on the transcendental unit
 // behind an exact range reduction in revolutions, the per-ray layer-1 partial added by a rank-1
 // MFMA instead of 128 v_add per net, no staging through LDS.
-#include "lidf_device.h"
+#include "lidf_launch.h"
 
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 #define SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)

@@ -27,7 +27,7 @@
 // per workgroup through LDS in chunks of 16 quads (3 rotating buffers, one s_barrier per chunk,
 // global loads issued one chunk ahead), and each wavefront keeps a 4-quad register ring of
 // ds_read_b128 in flight.
-#include "lidf_device.h"
+#include "lidf_launch.h"
 #include <stdio.h>
 #include <stdlib.h>
 

@@ -1,6 +1,6 @@
 // lidf_refine.hip — per-ray kernels of the stage-2 refinement query
 // (RefineNet.get_pred_refine, models/pipeline.py:922-1030), built with -ffp-contract=off.
-#include "lidf_device.h"
+#include "lidf_launch.h"
 
 // inside test of extensions/pcl_aabb/pcl_aabb_cuda_kernel.cu:23-44 (inclusive bounds)
 __device__ __forceinline__ bool inside_box(float x, float y, float z, const float* vb) {
@@ -9,20 +9,6 @@ __device__ __forceinline__ bool inside_box(float x, float y, float z, const floa
     if ((z < vb[2]) || (z > vb[5])) return false;
     return true;
 }
-
-extern "C" hipError_t lidf_launch_refine_prep_dev(const float*, const long long*, const int*, long long,
-                                                  const float*, const int*, long long, const int*,
-                                                  const int*, const float*, long long, int, long long,
-                                                  float*, int*, int*, const unsigned char*, const int*,
-                                                  const int*, hipStream_t, const CellLookup*);
-extern "C" hipError_t lidf_launch_refine_rows_dev(const float*, const int*, const float*, const float*, int,
-                                                  int, int, int, long long, const int*, float*, int, int,
-                                                  hipStream_t);
-extern "C" hipError_t lidf_launch_refine_finish_dev(const float*, const float*, const float*, float, float,
-                                                    long long, const int*, float*, const int*, const int*,
-                                                    long long, float*, hipStream_t);
-extern "C" hipError_t lidf_launch_zero_segments(float* const* ptrs, const long long* counts, int n,
-                                                hipStream_t st);
 
 // One thread per ray:
 //   end_voxel = max( voxel of the arg-max pair (0 for a ray without pairs: the dummy row,
@@ -413,13 +399,6 @@ extern "C" hipError_t lidf_launch_refine_prep_dev(const float* pred_pos, const l
     return hipGetLastError();
 }
 
-extern "C" hipError_t lidf_launch_refine_rows(const float* pred_pos, const int* end_voxel,
-                                              const float* vbound, const float* rayfeat, int ld_rf,
-                                              int Lv, int L, int pos_rel, long long R,
-                                              float* inp_embed, int ld_e, hipStream_t st) {
-    return lidf_launch_refine_rows_dev(pred_pos, end_voxel, vbound, rayfeat, ld_rf, Lv, L, pos_rel, R, nullptr,
-                                       inp_embed, ld_e, 0, st);
-}
 extern "C" hipError_t lidf_launch_refine_rows_dev(const float* pred_pos, const int* end_voxel,
                                                   const float* vbound, const float* rayfeat, int ld_rf,
                                                   int Lv, int L, int pos_rel, long long R,

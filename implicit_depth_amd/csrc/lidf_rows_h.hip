@@ -11,7 +11,7 @@
 // 16 quads, 3 buffers, one barrier per chunk, 4-deep ds_read ring).
 //
 // Stream per decoder: [layer 1: NKS k-steps x (8 tiles x (hi, lo))] [pass: 176 quads, pass_desc()].
-#include "lidf_device.h"
+#include "lidf_launch.h"
 
 namespace rowsh {
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));

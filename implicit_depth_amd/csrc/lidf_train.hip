@@ -3,7 +3,7 @@
 // training path keeps every layer's activation (lidf_decoder_forward_train_f32), the backward
 // (lidf_decoder_backward_f32) runs the input-gradient chain through lidf_linear_kernel with the
 // transposed weights and the leaky-ReLU mask as epilogue, and reduces the weight gradients here.
-#include "lidf_device.h"
+#include "lidf_launch.h"
 #include <stdlib.h>
 
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
@@ -1383,7 +1383,6 @@ extern "C" hipError_t lidf_launch_seg_sum_ray(const float* S, int F, const int* 
 // and the chunk sums are added up per index in order. out[v,:] is written (zero for an index
 // without pairs), no atomics, no pre-zeroing.
 #define SEG_CH 128
-extern "C" hipError_t lidf_launch_scan(const int*, long long, int*, int*, hipStream_t);
 
 struct SegPlan {
     long long nblk, per_blk, nscan, max_chunks;

@@ -94,6 +94,48 @@ def test_struct_layouts_match_header(tmp_path):
             assert int(seen["%s.%s" % (n, f)]) == getattr(cls, f).offset, (n, f)
 
 
+def test_launchers_are_declared_once_in_lidf_launch_h():
+    """The kernel files' host launchers are extern "C": the linker matches them by name alone. Their
+    only prototypes live in csrc/lidf_launch.h, which every .hip file includes, so that the compiler
+    checks each definition against what its callers see. No .hip / .inc file carries a prototype of
+    its own, and what lidf_api.hip calls, the kernel files define and the header declares agree."""
+    import glob
+    csrc = os.path.join(ROOT, "implicit_depth_amd", "csrc")
+
+    def code(path):   # without comments and preprocessor lines (the LIDF_API macro spells extern "C")
+        s = open(path).read()
+        s = re.sub(r"/\*.*?\*/", "", s, flags=re.S)
+        s = re.sub(r"//[^\n]*", "", s)
+        return re.sub(r"^[ \t]*#(?:[^\n]*\\\n)*[^\n]*", "", s, flags=re.M)
+
+    hips = sorted(glob.glob(os.path.join(csrc, "*.hip")))
+    incs = sorted(glob.glob(os.path.join(csrc, "*.inc")))
+    assert len(hips) >= 17 and len(incs) >= 3
+    header = code(os.path.join(csrc, "lidf_launch.h"))
+    assert len(re.findall(r'extern\s+"C"', header)) == 1
+    declared = set(re.findall(r"\b(lidf_\w+)\s*\(", header))
+    assert len(declared) >= 100
+
+    defined = set()
+    for p in hips + incs:
+        s, name = code(p), os.path.basename(p)
+        if p.endswith(".hip"):
+            assert '#include "lidf_launch.h"' in open(p).read(), name
+        assert not re.search(r'extern\s+"C"\s*\{', s), name + ': extern "C" block'
+        for m in re.finditer(r'extern\s+"C"([^;{]*)([;{])', s):
+            fn = re.search(r"\b(\w+)\s*\(", m.group(1)).group(1)
+            assert m.group(2) == "{", "%s: prototype of %s (it belongs in lidf_launch.h)" % (name, fn)
+            defined.add(fn)
+    assert defined == declared, sorted(defined ^ declared)   # nothing declared and gone, nothing undeclared
+
+    callers = [os.path.join(csrc, "lidf_api.hip")] + [p for p in incs if "lidf_api_" in os.path.basename(p)]
+    assert len(callers) == 3
+    called = set()
+    for p in callers:
+        called |= set(re.findall(r"\b(lidf_launch_\w+)\s*\(", code(p)))
+    assert len(called) >= 80 and called <= declared, sorted(called - declared)
+
+
 def test_torch_extension_shim_loads():
     """The pybind11 shim over the C ABI is built in-tree and imports without a GPU."""
     from implicit_depth_amd import torch_ext
