@@ -3415,5 +3415,83 @@ static int pointnet_backward_layers(const LidfPointNet* w, const float* inp, con
                                   0, cus, st);
 }
 
+// ---- Stage-1 training step: labels and loss (lidf_loss.hip) -------------------------------------
+LIDF_API int lidf_pair_labels_f32(const float* xyz, int32_t batch, int32_t height, int32_t width,
+                                  const int32_t* ray_bid, const int32_t* ray_flat, int64_t n_rays,
+                                  const int32_t* pair_off, const int32_t* pair_vox, int64_t n_pairs,
+                                  const float* voxel_bound, int64_t n_vox, float* gt_pos, int64_t* pcl_label,
+                                  float* pcl_label_float, int64_t* gt_max_pair_id, int32_t* n_label,
+                                  int32_t* pix2ray, lidf_stream_t stream) {
+    if (n_rays < 0 || n_pairs < 0 || n_vox < 0 || batch < 0 || height < 0 || width < 0 || !n_label)
+        return LIDF_ERR_BAD_ARG;
+    if (n_rays > 0x7ffffffeLL || n_pairs > 0x7ffffffeLL) return LIDF_ERR_UNSUPPORTED;
+    const long long npix = (long long)batch * height * width;
+    if (npix > 0x7ffffffeLL) return LIDF_ERR_UNSUPPORTED;
+    if (n_rays > 0 && (!xyz || !ray_bid || !ray_flat || !pair_off || !gt_pos || !gt_max_pair_id || npix == 0))
+        return LIDF_ERR_BAD_ARG;
+    if (n_pairs > 0 && (n_rays == 0 || n_vox == 0 || !pair_vox || !voxel_bound || !pcl_label || !pcl_label_float))
+        return LIDF_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    CHECK_HIP(hipMemsetAsync(n_label, 0, sizeof(int32_t), st));
+    if (pix2ray && npix > 0) CHECK_HIP(hipMemsetAsync(pix2ray, 0xff, (size_t)npix * sizeof(int32_t), st));
+    CHECK_HIP(lidf_launch_pair_labels(xyz, ray_bid, ray_flat, (long long)height * width, pair_off, pair_vox,
+                                      voxel_bound, n_rays, n_pairs, gt_pos, (long long*)pcl_label, pcl_label_float,
+                                      (long long*)gt_max_pair_id, n_label, pix2ray, st));
+    return LIDF_OK;
+}
+
+LIDF_API size_t lidf_stage1_loss_workspace_bytes(int64_t n_rays) {
+    return n_rays > 0 ? lidf_stage1_loss_partial_bytes(n_rays) : 0;
+}
+
+static int loss_args(const LidfLossArgs* a, LossArgs* k) {
+    if (!a || a->n_rays < 0 || a->n_pairs < 0 || a->batch < 0 || a->height < 0 || a->width < 0)
+        return LIDF_ERR_BAD_ARG;
+    if (a->n_rays > 0x7ffffffeLL || a->n_pairs > 0x7ffffffeLL ||
+        (long long)a->batch * a->height * a->width > 0x7ffffffeLL)
+        return LIDF_ERR_UNSUPPORTED;
+    if (a->n_rays > 0 && (!a->xyz || !a->ray_bid || !a->ray_flat || !a->pair_off || !a->pix2ray || !a->gt_pos ||
+                          !a->gt_max_pair_id || !a->n_label || !a->pred_pos))
+        return LIDF_ERR_BAD_ARG;
+    if (a->n_pairs > 0 && (!a->pcl_label || !a->pred_prob)) return LIDF_ERR_BAD_ARG;
+    memset(k, 0, sizeof(*k));
+    k->R = a->n_rays, k->P = a->n_pairs, k->hw = (long long)a->height * a->width;
+    k->B = a->batch, k->H = a->height, k->W = a->width;
+    k->xyz = a->xyz, k->ray_bid = a->ray_bid, k->ray_flat = a->ray_flat, k->pair_off = a->pair_off;
+    k->pix2ray = a->pix2ray, k->gt_pos = a->gt_pos, k->label = (const long long*)a->pcl_label;
+    k->gt_maxid = (const long long*)a->gt_max_pair_id, k->n_label = a->n_label;
+    k->pred_pos = a->pred_pos, k->logit = a->pred_prob;
+    k->pos_w = a->pos_w, k->prob_w = a->prob_w, k->surf_w = a->surf_norm_w, k->smooth_w = a->smooth_w;
+    k->surf_on = a->surf_norm_on != 0, k->smooth_on = a->smooth_on != 0;
+    k->loss = a->loss, k->pos_un = a->pos_unreduced, k->surf_dist = a->surf_norm_dist;
+    k->dx_dist = a->dx_dist, k->dy_dist = a->dy_dist, k->prob_un = a->prob_unreduced, k->ray_lse = a->ray_lse;
+    k->partial = (double*)a->workspace;
+    k->w_pos = a->w_pos, k->w_prob = a->w_prob, k->w_surf = a->w_surf, k->w_dx = a->w_dx, k->w_dy = a->w_dy;
+    k->g_loss_net = a->g_loss_net, k->g_pred_pos = a->g_pred_pos, k->g_logit = a->g_logit;
+    return LIDF_OK;
+}
+
+LIDF_API int lidf_stage1_loss_f32(const LidfLossArgs* args, lidf_stream_t stream) {
+    LossArgs k;
+    int rc = loss_args(args, &k);
+    if (rc) return rc;
+    if (k.R == 0) return LIDF_OK;
+    if (!k.loss || !k.pos_un || !k.surf_dist || !k.dx_dist || !k.dy_dist || !k.ray_lse || (k.P > 0 && !k.prob_un))
+        return LIDF_ERR_BAD_ARG;
+    if (!args->workspace || args->workspace_bytes < lidf_stage1_loss_workspace_bytes(k.R)) return LIDF_ERR_WORKSPACE;
+    CHECK_HIP(lidf_launch_stage1_loss(k, args->gt_surf_norm_img, args->pred_surf_norm_img, (hipStream_t)stream));
+    return LIDF_OK;
+}
+
+LIDF_API int lidf_stage1_loss_backward_f32(const LidfLossArgs* args, lidf_stream_t stream) {
+    LossArgs k;
+    int rc = loss_args(args, &k);
+    if (rc) return rc;
+    if (k.R == 0) return LIDF_OK;
+    if (!k.g_loss_net || !k.g_pred_pos || !k.ray_lse || (k.P > 0 && !k.g_logit)) return LIDF_ERR_BAD_ARG;
+    CHECK_HIP(lidf_launch_stage1_loss_backward(k, (hipStream_t)stream));
+    return LIDF_OK;
+}
+
 #include "lidf_api_pointnet_train.inc"
 #include "lidf_api_refine_train.inc"

@@ -363,6 +363,32 @@ struct CellLookup {
     int ready;          // the table already holds this voxel list
 };
 
+// Arguments of the stage-1 loss launches (lidf_loss.hip), filled by lidf_api.hip from LidfLossArgs.
+struct LossArgs {
+    long long R, P, hw;
+    int B, H, W;
+    const float* xyz;             // [B, H*W, 3] ground-truth frame
+    const int *ray_bid, *ray_flat, *pair_off;
+    const int* pix2ray;           // [B*H*W] ray of a sampled pixel, -1 elsewhere
+    const float* gt_pos;          // [R,3]
+    const long long* label;       // [P]
+    const long long* gt_maxid;    // [R]
+    const int* n_label;           // device count of labelled pairs
+    const float *pred_pos, *logit;
+    float pos_w, prob_w, surf_w, smooth_w;
+    int surf_on, smooth_on;       // whether the term enters loss_net
+    // forward
+    float* loss;                  // [8]
+    float *pos_un, *surf_dist, *dx_dist, *dy_dist;   // [R]
+    float* prob_un;               // [P]
+    float* ray_lse;               // [R,2]: max logit of the ray, log of its exponential sum
+    double* partial;              // [blocks, 9]
+    // backward
+    const float *w_pos, *w_prob, *w_surf, *w_dx, *w_dy;   // per-element weights, NULL = uniform means
+    const float* g_loss_net;      // device scalar
+    float *g_pred_pos, *g_logit;
+};
+
 // Arguments of one refine iteration's per-ray launch (lidf_refine.hip: lidf_refine_step_kernel).
 struct RefineStepArgs {
     const float* prev_pos;     // [R,3]

@@ -272,6 +272,15 @@ hipError_t lidf_launch_pnet_gather_segsum(const float* S, const int* perm, long 
                                           const int* first, long long V, long long n, float* partial, float* out,
                                           hipStream_t st);
 
+// ---- lidf_loss.hip
+hipError_t lidf_launch_pair_labels(const float* xyz, const int* ray_bid, const int* ray_flat, long long hw,
+                                   const int* pair_off, const int* pair_vox, const float* vbound, long long R,
+                                   long long P, float* gt_pos, long long* label, float* labelf, long long* maxid,
+                                   int* n_label, int* pix2ray, hipStream_t st);
+size_t lidf_stage1_loss_partial_bytes(long long R);
+hipError_t lidf_launch_stage1_loss(const LossArgs& a, float* gt_img, float* pred_img, hipStream_t st);
+hipError_t lidf_launch_stage1_loss_backward(const LossArgs& a, hipStream_t st);
+
 // ---- lidf_ief16.hip
 hipError_t lidf_launch_ief16(const Ief16Args& a, int cus, hipStream_t st);
 

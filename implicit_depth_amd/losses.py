@@ -1,0 +1,356 @@
+"""losses.py — ground-truth labels and the training loss of stage 1.
+
+Reference counterparts (paths relative to /root/reference/src):
+  compute_gt           <- LIDF.compute_gt                       models/pipeline.py:298-336
+  lidf_loss            <- LIDF.compute_loss, exp_type == 'train' models/pipeline.py:468-566
+  lidf_loss_composite  the same loss in plain torch ops (any dtype, any device): the A/B partner of
+                       lidf_loss and the route for CPU callers
+  LidfLossOptions      <- the loss.* keys of experiments/implicit_depth/default_config.yaml:97-107
+
+compute_gt and lidf_loss run in liblidf_hip.so (csrc/lidf_loss.hip): one launch for the labels, two for the
+loss, one for its backward; no ray x voxel mask and no image-sized normal map is built, and nothing here
+reads a size or a value back to the host (hard-negative mining reads the label count: its k depends on it).
+Pairs are RAY-MAJOR as everywhere in this package: pcl_label / gt_max_pair_id index that list
+(query.to_reference_order gives the reference's voxel-major order).
+"""
+import ctypes as C
+
+import torch
+import torch.nn.functional as F
+
+from . import _lib
+from .query import _as_i32, _f32, _i32
+
+LOSS_KEYS = ("pos_loss", "prob_loss", "surf_norm_loss", "smooth_loss", "loss_net", "acc", "err", "angle_err")
+
+
+class LidfLossOptions:
+    """loss.* of default_config.yaml:97-107 (train_refine_hardneg.yaml: hard_neg True, hard_neg_ratio 0.1)."""
+
+    def __init__(self, **kw):
+        self.hard_neg = False
+        self.hard_neg_ratio = None
+        self.pos_loss_type = "single"
+        self.pos_w = 100.0
+        self.prob_loss_type = "ray"
+        self.prob_w = 0.5
+        self.surf_norm_w = 10.0
+        self.surf_norm_epo = 0
+        self.smooth_w = 0
+        self.smooth_epo = 0
+        for k, v in kw.items():
+            if not hasattr(self, k):
+                raise TypeError("unknown option %s" % k)
+            setattr(self, k, v)
+
+
+def _check_types(opt):
+    if opt.pos_loss_type != "single":
+        raise NotImplementedError("pos_loss_type %s" % opt.pos_loss_type)
+    if opt.prob_loss_type != "ray":
+        raise NotImplementedError("prob_loss_type %s" % opt.prob_loss_type)
+    if opt.hard_neg and opt.hard_neg_ratio is None:
+        raise ValueError("hard_neg needs hard_neg_ratio")
+
+
+def _terms_on(opt, epoch):
+    """Whether the surface-normal / smoothness terms enter loss_net (models/pipeline.py:543-546)."""
+    return (opt.surf_norm_w > 0 and epoch >= opt.surf_norm_epo, opt.smooth_w > 0 and epoch >= opt.smooth_epo)
+
+
+def _ray_index(dd):
+    """(ray_bid, ray_flat) int32 of the sampled rays, from the int32 forms or the reference's int64 keys."""
+    bid = dd["ray_bid"] if "ray_bid" in dd else dd["miss_bid"]
+    flat = dd["ray_flat"] if "ray_flat" in dd else dd["miss_flat_img_id"]
+    return _as_i32(bid, "ray_bid").contiguous(), _as_i32(flat, "ray_flat").contiguous()
+
+
+def compute_gt(dd):
+    """LIDF.compute_gt (models/pipeline.py:298-336) on lidf_forward_train's data_dict (xyz_flat, the sampled rays,
+    the ray-major pair list, voxel_bound). Adds gt_pos [R,3], pcl_label [P] int64 (the reference's dtype),
+    pcl_label_float [P], gt_max_pair_id [R] int64 — the label-selected pair of every ray, scatter_max's choice of
+    :445: what lidf_query_train takes as max_pair_id while epoch < maxpool_label_epo — and n_label, the number of
+    labelled pairs as a 0-dim device tensor; pix2ray [bs*h*w] int32 (the ray of a sampled pixel, -1 elsewhere) is
+    kept for lidf_loss. valid_*_in_intersect (:312-335) are read nowhere in the reference and are not built."""
+    xyz = dd["xyz_flat"]
+    ray_bid, ray_flat = _ray_index(dd)
+    pair_off, pair_vox, vb = dd["pair_off"], dd["pair_vox"], dd["voxel_bound"]
+    _lib.require_cuda(xyz, ray_bid, ray_flat, pair_off, pair_vox, vb,
+                      names=["xyz_flat", "ray_bid", "ray_flat", "pair_off", "pair_vox", "voxel_bound"])
+    _f32(xyz, "xyz_flat"), _f32(vb, "voxel_bound"), _i32(pair_off, "pair_off"), _i32(pair_vox, "pair_vox")
+    bs, h, w = dd["bs"], dd["h"], dd["w"]
+    R, P, V = ray_bid.shape[0], pair_vox.shape[0], vb.shape[0]
+    if tuple(xyz.shape) != (bs, h * w, 3) or pair_off.shape[0] != R + 1 or tuple(vb.shape) != (V, 6):
+        raise RuntimeError("xyz_flat / pair_off / voxel_bound must be [bs,h*w,3] / [R+1] / [V,6]")
+    dev = xyz.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    i64 = dict(dtype=torch.int64, device=dev)
+    out = {
+        "gt_pos": torch.empty((R, 3), **f32), "pcl_label": torch.empty((P,), **i64),
+        "pcl_label_float": torch.empty((P,), **f32), "gt_max_pair_id": torch.empty((R,), **i64),
+        "pix2ray": torch.empty((bs * h * w,), dtype=torch.int32, device=dev),
+    }
+    n_label = torch.empty((1,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().lidf_pair_labels_f32(
+            _lib.ptr(xyz), bs, h, w, _lib.ptr(ray_bid), _lib.ptr(ray_flat), R, _lib.ptr(pair_off),
+            _lib.ptr(pair_vox), P, _lib.ptr(vb), V, _lib.ptr(out["gt_pos"]), _lib.ptr(out["pcl_label"]),
+            _lib.ptr(out["pcl_label_float"]), _lib.ptr(out["gt_max_pair_id"]), _lib.ptr(n_label),
+            _lib.ptr(out["pix2ray"]), _lib.current_stream(dev)))
+    out["n_label"] = n_label[0]
+    dd.update(out)
+    return dd
+
+
+def _loss_args(t, cfg):
+    """LidfLossArgs over the tensors `t` (a dict; absent / None entries stay NULL)."""
+    a = _lib.LidfLossArgs()
+    a.n_rays, a.n_pairs = t["gt_pos"].shape[0], t["pcl_label"].shape[0]
+    a.batch, a.height, a.width = cfg["bs"], cfg["h"], cfg["w"]
+    a.pos_w, a.prob_w = float(cfg["pos_w"]), float(cfg["prob_w"])
+    a.surf_norm_w, a.smooth_w = float(cfg["surf_norm_w"]), float(cfg["smooth_w"])
+    a.surf_norm_on, a.smooth_on = int(cfg["surf_on"]), int(cfg["smooth_on"])
+    for k, v in t.items():
+        if v is not None:
+            setattr(a, k, v.data_ptr())
+    return a
+
+
+def _topk_weights(v, k):
+    """(mean of the k largest entries of v, weights 1/k at them and 0 elsewhere): torch.topk as in
+    models/pipeline.py:475-490, 514-539."""
+    top, idx = torch.topk(v, k)
+    w = torch.zeros_like(v)
+    if k > 0:
+        w[idx] = 1.0 / k
+    return torch.mean(top), w
+
+
+class _Stage1LossFn(torch.autograd.Function):
+    """compute_loss of the training step as one autograd node over pred_pos and pred_prob_end
+    (lidf_stage1_loss_f32 / lidf_stage1_loss_backward_f32). Outputs: loss_net (differentiable) and the [8] vector
+    of loss_dict (detached: the other seven entries are metrics)."""
+
+    @staticmethod
+    def forward(ctx, pred_pos, pred_prob, cfg, maps, xyz, ray_bid, ray_flat, pair_off, pix2ray, gt_pos, pcl_label,
+                gt_max_pair_id, n_label):
+        dev = xyz.device
+        pp = pred_pos.detach().contiguous()
+        lg = pred_prob.detach().reshape(-1).contiguous()
+        R, P = gt_pos.shape[0], pcl_label.shape[0]
+        f32 = dict(dtype=torch.float32, device=dev)
+        L = _lib.lib()
+        wsb = L.lidf_stage1_loss_workspace_bytes(R)
+        n_label = n_label.reshape(1)
+        t = {"xyz": xyz, "ray_bid": ray_bid, "ray_flat": ray_flat, "pair_off": pair_off, "pix2ray": pix2ray,
+             "gt_pos": gt_pos, "pcl_label": pcl_label, "gt_max_pair_id": gt_max_pair_id, "n_label": n_label,
+             "pred_pos": pp, "pred_prob": lg}
+        fwd = {"loss": torch.empty((8,), **f32), "pos_unreduced": torch.empty((R,), **f32),
+               "surf_norm_dist": torch.empty((R,), **f32), "dx_dist": torch.empty((R,), **f32),
+               "dy_dist": torch.empty((R,), **f32), "prob_unreduced": torch.empty((P,), **f32),
+               "ray_lse": torch.empty((R, 2), **f32), "workspace": _lib.workspace(wsb, dev)}
+        if maps is not None:
+            fwd["gt_surf_norm_img"], fwd["pred_surf_norm_img"] = maps
+        a = _loss_args(dict(t, **fwd), cfg)
+        a.workspace_bytes = wsb
+        with torch.cuda.device(dev):
+            _lib.check(L.lidf_stage1_loss_f32(C.byref(a), _lib.current_stream(dev)))
+        loss = fwd["loss"]
+        weights = (None,) * 5
+        if cfg["hard_neg"]:
+            # hard-negative mining (models/pipeline.py:475-490, 514-539): the means over the top-k elements of the
+            # unreduced terms; the backward takes them as per-element weights
+            ratio = cfg["hard_neg_ratio"]
+            kr = int(R * ratio)
+            kl = int(int(n_label.item()) * ratio)   # (the one size read: k of the labelled pairs)
+            pos, w_pos = _topk_weights(fwd["pos_unreduced"], kr)
+            prob, w_prob = _topk_weights(fwd["prob_unreduced"], kl)
+            surf, w_surf = _topk_weights(fwd["surf_norm_dist"], kr)
+            sdx, w_dx = _topk_weights(fwd["dx_dist"], kr)
+            sdy, w_dy = _topk_weights(fwd["dy_dist"], kr)
+            smooth = sdx + sdy
+            net = cfg["pos_w"] * pos + cfg["prob_w"] * prob
+            if cfg["surf_on"]:
+                net = net + cfg["surf_norm_w"] * surf
+            if cfg["smooth_on"]:
+                net = net + cfg["smooth_w"] * smooth
+            loss = torch.cat((torch.stack((pos, prob, surf, smooth, net)), loss[5:]))
+            weights = (w_pos, w_prob, w_surf, w_dx, w_dy)
+        ctx.cfg = cfg
+        ctx.shapes = (tuple(pred_pos.shape), tuple(pred_prob.shape))
+        ctx.has_w = cfg["hard_neg"]
+        saved = [t[k] for k in ("xyz", "ray_bid", "ray_flat", "pair_off", "pix2ray", "gt_pos", "pcl_label",
+                                "gt_max_pair_id", "n_label", "pred_pos", "pred_prob")] + [fwd["ray_lse"]]
+        ctx.save_for_backward(*saved, *(weights if ctx.has_w else ()))
+        net = loss[4].clone()
+        ctx.mark_non_differentiable(loss)
+        return net, loss
+
+    @staticmethod
+    def backward(ctx, g_net, _g_loss):
+        s = ctx.saved_tensors
+        names = ("xyz", "ray_bid", "ray_flat", "pair_off", "pix2ray", "gt_pos", "pcl_label", "gt_max_pair_id",
+                 "n_label", "pred_pos", "pred_prob", "ray_lse")
+        t = dict(zip(names, s[:12]))
+        if ctx.has_w:
+            t.update(zip(("w_pos", "w_prob", "w_surf", "w_dx", "w_dy"), s[12:]))
+        dev = t["xyz"].device
+        R, P = t["gt_pos"].shape[0], t["pcl_label"].shape[0]
+        t["g_loss_net"] = g_net.detach().reshape(1).contiguous().float()
+        t["g_pred_pos"] = torch.empty((R, 3), dtype=torch.float32, device=dev)
+        t["g_logit"] = torch.empty((P,), dtype=torch.float32, device=dev)
+        a = _loss_args(t, ctx.cfg)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().lidf_stage1_loss_backward_f32(C.byref(a), _lib.current_stream(dev)))
+        return (t["g_pred_pos"].reshape(ctx.shapes[0]), t["g_logit"].reshape(ctx.shapes[1])) + (None,) * 11
+
+
+def _cfg(dd, opt, epoch):
+    surf_on, smooth_on = _terms_on(opt, epoch)
+    return {"bs": dd["bs"], "h": dd["h"], "w": dd["w"], "pos_w": float(opt.pos_w), "prob_w": float(opt.prob_w),
+            "surf_norm_w": float(opt.surf_norm_w), "smooth_w": float(opt.smooth_w), "surf_on": surf_on,
+            "smooth_on": smooth_on, "hard_neg": bool(opt.hard_neg),
+            "hard_neg_ratio": opt.hard_neg_ratio}
+
+
+def lidf_loss(dd, loss_opt=None, exp_type="train", epoch=0, normal_maps=False):
+    """LIDF.compute_loss for exp_type == 'train' (models/pipeline.py:468-566) on lidf_forward_train's data_dict
+    (compute_gt's entries + pred_pos [R,3] and pred_prob_end [P,1] of lidf_query_train): the reference's loss_dict
+    — pos_loss, prob_loss, surf_norm_loss, smooth_loss, loss_net, acc, err, angle_err — as 0-dim device tensors.
+    loss_net carries the graph (one autograd node whose inputs are pred_pos and pred_prob_end); the other seven
+    are detached. Nothing is read back to the host, except the label count under hard_neg.
+    normal_maps=True adds gt_surf_norm_img / pred_surf_norm_img [bs,3,h,w] to dd (visualisation only)."""
+    opt = loss_opt or LidfLossOptions()
+    if exp_type != "train":
+        raise NotImplementedError("lidf_loss covers exp_type 'train'; the evaluation statistics are "
+                                  "pipeline.eval_metrics")
+    _check_types(opt)
+    pred_pos, pred_prob = dd["pred_pos"], dd["pred_prob_end"]
+    _lib.require_cuda(pred_pos, pred_prob, dd["xyz_flat"], names=["pred_pos", "pred_prob_end", "xyz_flat"])
+    _f32(pred_pos, "pred_pos"), _f32(pred_prob, "pred_prob_end")
+    if "pix2ray" not in dd or "gt_pos" not in dd:
+        compute_gt(dd)
+    ray_bid, ray_flat = _ray_index(dd)
+    R, P = dd["gt_pos"].shape[0], dd["pcl_label"].shape[0]
+    if tuple(pred_pos.shape) != (R, 3) or pred_prob.numel() != P:
+        raise RuntimeError("pred_pos / pred_prob_end must be [R,3] / [P,1]")
+    # compute_gt's entries may come from an earlier call on a reused dict: the kernels index with them unchecked
+    xyz, pair_off, pix2ray = dd["xyz_flat"], dd["pair_off"], dd["pix2ray"]
+    gt = [dd[k] for k in ("gt_pos", "pcl_label", "gt_max_pair_id", "n_label")]
+    _lib.require_cuda(pair_off, pix2ray, ray_bid, ray_flat, *gt,
+                      names=["pair_off", "pix2ray", "ray_bid", "ray_flat", "gt_pos", "pcl_label", "gt_max_pair_id",
+                             "n_label"])
+    _f32(xyz, "xyz_flat"), _i32(pair_off, "pair_off"), _i32(pix2ray, "pix2ray"), _f32(gt[0], "gt_pos")
+    n_pix = dd["bs"] * dd["h"] * dd["w"]
+    if (tuple(xyz.shape) != (dd["bs"], dd["h"] * dd["w"], 3) or tuple(pair_off.shape) != (R + 1,)
+            or tuple(pix2ray.shape) != (n_pix,) or ray_bid.shape[0] != R or ray_flat.shape[0] != R
+            or tuple(gt[0].shape) != (R, 3) or tuple(gt[2].shape) != (R,)
+            or gt[1].dtype != torch.int64 or gt[2].dtype != torch.int64 or gt[3].dtype != torch.int32
+            or gt[3].numel() != 1):
+        raise RuntimeError("lidf_loss: xyz_flat / pair_off / pix2ray / ray index / compute_gt's entries do not "
+                           "belong to one frame batch and ray set: [bs,h*w,3] / [R+1] int32 / [bs*h*w] int32 / [R] "
+                           "/ gt_pos [R,3], pcl_label [P] and gt_max_pair_id [R] int64, n_label int32 — run "
+                           "compute_gt(dd) again")
+    if R == 0:
+        raise RuntimeError("lidf_loss: no ray (the reference returns before compute_loss, models/pipeline.py:686)")
+    maps = None
+    if normal_maps:
+        shape = (dd["bs"], 3, dd["h"], dd["w"])
+        maps = tuple(torch.empty(shape, dtype=torch.float32, device=pred_pos.device) for _ in range(2))
+        dd["gt_surf_norm_img"], dd["pred_surf_norm_img"] = maps
+    net, loss = _Stage1LossFn.apply(
+        pred_pos, pred_prob, _cfg(dd, opt, epoch), maps, dd["xyz_flat"].contiguous(), ray_bid, ray_flat,
+        dd["pair_off"], dd["pix2ray"], dd["gt_pos"], dd["pcl_label"], dd["gt_max_pair_id"], dd["n_label"])
+    out = {k: loss[i] for i, k in enumerate(LOSS_KEYS)}
+    out["loss_net"] = net
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
+# The same loss in plain torch ops
+# ------------------------------------------------------------------------------------------------
+def _first_argmax(src, index, n, fill):
+    """Per segment the lowest position of the largest value (scatter_max's index); `fill` for an empty segment
+    and for a segment in which no value compares equal to the maximum (NaN)."""
+    top = torch.full((n,), float("-inf"), dtype=src.dtype, device=src.device)
+    top = top.scatter_reduce(0, index, src, reduce="amax", include_self=True)
+    at = torch.arange(src.shape[0], device=src.device)
+    cand = torch.where((src == top[index]) & (src > float("-inf")), at, torch.full_like(at, fill))
+    return torch.full((n,), fill, dtype=torch.long, device=src.device).scatter_reduce(
+        0, index, cand, reduce="amin", include_self=True)
+
+
+def _neighbour_normals(xyz, table, pos, lin, x, y, h, w):
+    """Normals of the frame `xyz` [N,3] (sampled pixels replaced by `pos`) at the sampled pixels `lin`:
+    (unit normal, dx, dy) with dx = right - self, dy = below - self, constant 0 in the last column / row."""
+    n_pix = xyz.shape[0]
+
+    def point(q):
+        t = table[q]
+        return torch.where((t >= 0).unsqueeze(-1), pos[t.clamp(min=0)], xyz[q])
+    zero = torch.zeros((), dtype=pos.dtype, device=pos.device)
+    dx = torch.where((x < w - 1).unsqueeze(-1), point((lin + 1).clamp(max=n_pix - 1)) - pos, zero)
+    dy = torch.where((y < h - 1).unsqueeze(-1), point((lin + w).clamp(max=n_pix - 1)) - pos, zero)
+    n = torch.linalg.cross(dx, dy, dim=-1)
+    return n / (torch.linalg.vector_norm(n, dim=-1, keepdim=True) + 1e-8), dx, dy
+
+
+def lidf_loss_composite(dd, loss_opt=None, exp_type="train", epoch=0):
+    """lidf_loss written in differentiable torch ops, in the dtype of pred_pos, on any device: per-ray
+    log-softmax by scatter reductions, the normals by gathering each sampled pixel's right and lower neighbour.
+    Needs gt_pos and pcl_label in dd (compute_gt's, or a caller's own); every entry of the returned loss_dict
+    carries its graph. It takes many small launches where lidf_loss takes three."""
+    opt = loss_opt or LidfLossOptions()
+    if exp_type != "train":
+        raise NotImplementedError("lidf_loss_composite covers exp_type 'train'")
+    _check_types(opt)
+    pred_pos, logit = dd["pred_pos"], dd["pred_prob_end"].reshape(-1)
+    dt, dev = pred_pos.dtype, pred_pos.device
+    bs, h, w = dd["bs"], dd["h"], dd["w"]
+    gt_pos, label = dd["gt_pos"].to(dt), dd["pcl_label"].long()
+    ray = dd["pair_ray"].long()
+    bid = (dd["ray_bid"] if "ray_bid" in dd else dd["miss_bid"]).long()
+    flat = (dd["ray_flat"] if "ray_flat" in dd else dd["miss_flat_img_id"]).long()
+    R, P = pred_pos.shape[0], logit.shape[0]
+    topk_mean = lambda v: torch.mean(torch.topk(v, int(v.shape[0] * opt.hard_neg_ratio))[0])  # noqa: E731
+    reduce = topk_mean if opt.hard_neg else torch.mean
+    # position
+    pos_loss = reduce(torch.mean((pred_pos - gt_pos).abs(), -1)) if opt.hard_neg else \
+        torch.mean((pred_pos - gt_pos).abs())
+    # ray termination: -log_softmax over each ray's pairs at the labelled pairs
+    top = torch.full((R,), float("-inf"), dtype=dt, device=dev).scatter_reduce(
+        0, ray, logit.detach(), reduce="amax", include_self=True)
+    z = logit - top[ray]
+    lse = torch.log(torch.zeros((R,), dtype=dt, device=dev).index_add(0, ray, torch.exp(z)))
+    log_sm = z - lse[ray]
+    prob_loss = reduce(-log_sm[torch.nonzero(label, as_tuple=False).reshape(-1)])
+    # surface normals and smoothness at the sampled pixels
+    xyz = dd["xyz_flat"].reshape(-1, 3).to(dt)
+    lin = bid * (h * w) + flat
+    table = torch.full((bs * h * w,), -1, dtype=torch.long, device=dev)
+    table[lin] = torch.arange(R, device=dev)
+    x, y = flat % w, flat // w
+    n_gt, _, _ = _neighbour_normals(xyz, table, gt_pos, lin, x, y, h, w)
+    n_pred, dx, dy = _neighbour_normals(xyz, table, pred_pos, lin, x, y, h, w)
+    cos = F.cosine_similarity(n_pred, n_gt, dim=-1)
+    surf_norm_loss = reduce((1 - cos) / 2.0)
+    angle_err = torch.mean(torch.acos(torch.clamp(cos, min=-1, max=1))) / torch.pi * 180.0
+    smooth_loss = reduce(torch.sum(dx * dx, -1)) + reduce(torch.sum(dy * dy, -1))
+    loss_net = opt.pos_w * pos_loss + opt.prob_w * prob_loss
+    surf_on, smooth_on = _terms_on(opt, epoch)
+    if surf_on:
+        loss_net = loss_net + opt.surf_norm_w * surf_norm_loss
+    if smooth_on:
+        loss_net = loss_net + opt.smooth_w * smooth_loss
+    # metrics
+    with torch.no_grad():
+        sm = torch.exp(log_sm)
+        pred_label = _first_argmax(sm, ray, R, P)
+        gt_label = _first_argmax(label.to(dt), ray, R, P)
+        acc = torch.sum(torch.eq(pred_label, gt_label).to(dt)) / R
+        nonzero = (torch.sum(gt_pos.abs(), -1) != 0).to(dt)
+        l2 = torch.sqrt(torch.sum((pred_pos - gt_pos) ** 2, -1))
+        n = torch.sum(nonzero)
+        err = torch.where(n == 0, torch.zeros_like(n), torch.sum(l2 * nonzero) / n.clamp(min=1))
+    return {"pos_loss": pos_loss, "prob_loss": prob_loss, "surf_norm_loss": surf_norm_loss,
+            "smooth_loss": smooth_loss, "loss_net": loss_net, "acc": acc, "err": err, "angle_err": angle_err}

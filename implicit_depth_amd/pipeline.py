@@ -34,6 +34,9 @@ class LidfOptions:
         self.grid_res = 8
         self.xmin, self.xmax = (-1.0, -1.0, 0.0), (1.0, 1.0, 2.0)   # utils/constants.py:15-16
         self.valid_stride = None               # None = every valid point (valid_sample_num == -1)
+        # training (train_lidf.yaml): rays per image of the random window, label-selected pairs before this epoch
+        self.miss_sample_num = 20000
+        self.maxpool_label_epo = 6
         # stage 2 (test_refine.yaml)
         self.refine_forward_times = 2
         self.refine_offset_range = (-0.2, 0.2)
@@ -46,8 +49,9 @@ class LidfOptions:
             setattr(self, k, v)
 
 
-def prepare_data(batch, opt, pred_mask=None):
-    """LIDF.prepare_data, exp_type != 'train' (models/pipeline.py:91-133)."""
+def prepare_data(batch, opt, pred_mask=None, exp_type="test"):
+    """LIDF.prepare_data (models/pipeline.py:91-133). exp_type 'train': the batch's own valid_mask (or
+    1 - corrupt_mask), no pred_mask override (:126)."""
     rgb_img = batch["rgb"]
     bs, _, h, w = rgb_img.shape
     corrupt_mask = batch["corrupt_mask"].squeeze(1)
@@ -61,6 +65,8 @@ def prepare_data(batch, opt, pred_mask=None):
         "cx": batch["cx"].float(), "cy": batch["cy"].float(),
         "item_path": batch.get("item_path"),
     }
+    if exp_type == "train":
+        return dd
     if opt.mask_type == "pred":
         dd["pred_mask"] = pred_mask
         dd["valid_mask"] = 1 - pred_mask
@@ -108,7 +114,8 @@ def lidf_forward(batch, full_rgb_feat, pnet_model, prob_dec, offset_dec, opt=Non
     success False = one of the reference's early exits (no occupied voxel / no miss ray / no
     intersecting pair); data_dict then holds what was computed up to that point."""
     opt = opt or LidfOptions()
-    Q._refuse_autograd("pipeline.lidf_forward", "query.lidf_query_train (stage-1 training step)",
+    Q._refuse_autograd("pipeline.lidf_forward", "pipeline.lidf_forward_train (the stage-1 training step; its "
+                       "differentiable core is query.lidf_query_train)",
                        (("full_rgb_feat", full_rgb_feat),),
                        (("pnet_model", pnet_model), ("prob_dec", prob_dec), ("offset_dec", offset_dec)))
     _mark(marks, "start")
@@ -168,14 +175,71 @@ def lidf_forward(batch, full_rgb_feat, pnet_model, prob_dec, offset_dec, opt=Non
     return True, dd
 
 
+def lidf_forward_train(batch, full_rgb_feat, pnet_model, prob_dec, offset_dec, opt=None, loss_opt=None, epoch=0,
+                       valid_idx=None):
+    """LIDF.forward(batch, 'train', epoch) (models/pipeline.py:652-711) as one call: returns (success, data_dict,
+    loss_dict). prepare_data in the train flavour (the miss rays come from corrupt_mask), get_valid_points,
+    get_occ_vox_bound, get_miss_ray + the random window of opt.miss_sample_num rays per image (np.random, as the
+    reference draws it), compute_ray_aabb, compute_gt, the PointNet and the query under autograd
+    (query.lidf_query_train, pairs selected by the labels while epoch < opt.maxpool_label_epo) and
+    losses.lidf_loss. loss_dict['loss_net'].backward() reaches full_rgb_feat and every parameter of the three
+    modules. success False = one of the reference's three early exits (no occupied voxel / no miss ray / no
+    intersecting pair): loss_dict is then {} and data_dict holds what was computed up to that point. The DDP
+    success-flag handshake of :662-701 stays with the trainer."""
+    from .losses import compute_gt, lidf_loss
+    opt = opt or LidfOptions()
+    if opt.intersect_pos_type not in ("abs", "rel"):
+        raise NotImplementedError("intersect_pos_type %s" % opt.intersect_pos_type)
+    _lib.require_cuda(batch["rgb"], batch["xyz"], full_rgb_feat, names=["batch['rgb']", "batch['xyz']", "full_rgb_feat"])
+    dd = prepare_data(batch, opt, exp_type="train")
+    get_valid_points(dd, opt, valid_idx)
+    bs = dd["bs"]
+    if dd["valid_xyz"].shape[0] == 0:   # (no valid point at all: no occupied voxel)
+        return False, dd, {}
+    occ = Q.get_occ_vox_bound(dd["valid_xyz"].contiguous(), dd["valid_bid"].to(torch.int32).contiguous(),
+                              bs, opt.xmin, opt.xmax, opt.grid_res)
+    dd.update(occ)
+    V = occ["voxel_bound"].shape[0]
+    if V == 0:
+        return False, dd, {}
+    miss = Q.get_miss_ray(dd["corrupt_mask"], dd["fx"], dd["fy"], dd["cx"], dd["cy"])
+    dd.update(Q.sample_miss_rays(miss, bs, opt.miss_sample_num))
+    if dd["total_miss_sample_num"] == 0:
+        return False, dd, {}
+    vox_bid = occ["occ_vox_bid"].to(torch.int32).contiguous()
+    grid = dict(voxel_coord=occ["voxel_coord"], grid_dims=occ["grid_dims"], batch=bs) if V > 256 * bs else {}
+    pair_off, pair_ray, pair_vox, pair_t = Q.compute_ray_aabb(
+        dd["miss_ray_dir"], occ["voxel_bound"], dd["ray_bid"], vox_bid, **grid)
+    dd.update({"pair_off": pair_off, "pair_ray": pair_ray, "pair_vox": pair_vox, "pair_t": pair_t,
+               "voxel_bid": vox_bid})
+    if pair_ray.shape[0] == 0:
+        return False, dd, {}
+    compute_gt(dd)
+    valid_v_rgb = dd["valid_rgb"].index_select(0, occ["valid_v_pid"])
+    dd["pnet_inp"] = torch.cat((occ["valid_v_rel_coord"], valid_v_rgb), -1)
+    dd["occ_voxel_feat"] = pnet_model(dd["pnet_inp"], occ["revidx"], n_vox=V)
+    dd["full_rgb_feat"] = full_rgb_feat
+    vox_center = None
+    if opt.intersect_pos_type == "rel":
+        vb = occ["voxel_bound"]
+        vox_center = ((vb[:, :3] + vb[:, 3:]) / 2.0).contiguous()
+    dd.update(Q.lidf_query_train(
+        dd["miss_ray_dir"], dd["ray_pix"], dd["ray_bid"], pair_off, pair_ray, pair_vox, pair_t, full_rgb_feat,
+        dd["occ_voxel_feat"], prob_dec, offset_dec, multires=opt.multires, multires_views=opt.multires_views,
+        roi_inp_bbox=opt.roi_inp_bbox, offset_range=opt.offset_range, part_size=occ["part_size"],
+        vox_center=vox_center, pos_rel=opt.intersect_pos_type == "rel",
+        max_pair_id=dd["gt_max_pair_id"] if epoch < opt.maxpool_label_epo else None))
+    return True, dd, lidf_loss(dd, loss_opt, "train", epoch)
+
+
 def refine_forward(dd, pnet_model_refine, offset_dec_refine, opt=None, precision="f32", cell_lookup=True):
     """RefineNet.forward for evaluation (models/pipeline.py:1032-1041) on lidf_forward's data_dict:
     opt.refine_forward_times x get_pred_refine; adds pred_pos_refine and pred_depth_refine.
     cell_lookup: the end voxel of a ray through the cell table of get_occ_vox_bound's grid (the same ids as
     the reference's every-ray x every-voxel pcl_aabb, lidf_refine(grid=)); False tests every voxel."""
     opt = opt or LidfOptions()
-    Q._refuse_autograd("pipeline.refine_forward", "the modules on their own (the fused stage-2 call has "
-                       "no backward)", (("pred_pos", dd.get("pred_pos")),),
+    Q._refuse_autograd("pipeline.refine_forward", "query.lidf_refine_train (stage-2 training step)",
+                       (("pred_pos", dd.get("pred_pos")),),
                        (("pnet_model_refine", pnet_model_refine), ("offset_dec_refine", offset_dec_refine)))
     bs, h, w = dd["bs"], dd["h"], dd["w"]
     occ_rev = dd["revidx"].to(torch.int32).contiguous()

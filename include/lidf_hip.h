@@ -36,7 +36,7 @@ enum lidf_status {
 /* ABI version, bumped on any signature or struct-layout change and on added entry points. lidf_version() returns the value the
  * library was BUILT with; a binding compiled / written against this header must refuse a library that
  * answers anything else (implicit_depth_amd/_lib.py and csrc/lidf_torch_ext.cpp do, at load). */
-#define LIDF_ABI_VERSION 12
+#define LIDF_ABI_VERSION 13
 int lidf_version(void);
 /* Static string for a status code. */
 const char* lidf_strerror(int status);
@@ -925,6 +925,75 @@ int lidf_query_tail_backward_f32(const float* g_pair_pred_pos, const float* g_pr
                                  const float* ray_dir, int64_t n_rays, int64_t n_pairs,
                                  float offset_range0, float offset_range1, float part_size,
                                  float* d_pred_offset, lidf_stream_t stream);
+
+/* ---- Stage-1 training step: ground-truth labels and loss (ABI 13) -------------------------------
+ * lidf_pair_labels_f32 = LIDF.compute_gt (models/pipeline.py:298-336) on the compact ray-major pair
+ * list, one launch: gt_pos [R,3] = xyz[ray_bid, ray_flat] (xyz [B, h*w, 3], data_dict['xyz_flat']);
+ * pcl_label [P] i64 / pcl_label_float [P] = the inclusive box test of lidf_pcl_aabb_dense_f32 of the
+ * ray's gt_pos against the pair's voxel (the pairs of a ray lie in its own image: no batch test);
+ * gt_max_pair_id [R] i64 = scatter_max(pcl_label_float, ray) of :445 as a ray-major index (the first
+ * labelled pair of the ray, its first pair when none is labelled, n_pairs for a ray without pairs);
+ * n_label[0] = the number of labelled pairs, left on the device; pix2ray [B*h*w] i32 (optional) = the
+ * ray of every sampled pixel, -1 elsewhere — the table lidf_stage1_loss_f32 reads.
+ * valid_*_in_intersect of compute_gt (:312-335) are read nowhere in the reference and are not built. */
+int lidf_pair_labels_f32(const float* xyz, int32_t batch, int32_t height, int32_t width,
+                         const int32_t* ray_bid, const int32_t* ray_flat, int64_t n_rays,
+                         const int32_t* pair_off, const int32_t* pair_vox, int64_t n_pairs,
+                         const float* voxel_bound, int64_t n_vox, float* gt_pos, int64_t* pcl_label,
+                         float* pcl_label_float, int64_t* gt_max_pair_id, int32_t* n_label,
+                         int32_t* pix2ray, lidf_stream_t stream);
+
+/* The training part of LIDF.compute_loss (models/pipeline.py:468-566). Forward: the eight scalars of
+ * loss_dict in loss[8] = {pos_loss, prob_loss, surf_norm_loss, smooth_loss, loss_net, acc, err,
+ * angle_err} (means reduced in two stages with a fixed order; prob_loss is NaN when no pair is
+ * labelled, as torch.mean of an empty tensor), and the unreduced terms: pos_unreduced / surf_norm_dist /
+ * dx_dist / dy_dist [R], prob_unreduced [P] (-log_softmax at the labelled pairs, -inf elsewhere) — what
+ * hard-negative mining takes its top-k of. ray_lse [R,2] is kept for the backward. The surface normals
+ * are those of point_utils.get_surface_normal on the frame with the sampled pixels replaced by gt_pos /
+ * pred_pos, evaluated at the sampled pixels only; gt_surf_norm_img / pred_surf_norm_img [B,3,h,w] are
+ * written when non-NULL (visualisation). Backward: g_pred_pos [R,3] and g_logit [P] for the upstream
+ * gradient *g_loss_net of loss_net (a device scalar); w_* are per-element weights of the five means
+ * (1/k at the top-k elements, 0 elsewhere), NULL = the uniform means of the forward. A gather per ray:
+ * no float atomics, bit-identical from run to run.                                                    */
+typedef struct LidfLossArgs {
+    int64_t n_rays, n_pairs;
+    int32_t batch, height, width;
+    const float* xyz;               /* [B, h*w, 3] */
+    const int32_t* ray_bid;         /* [R] */
+    const int32_t* ray_flat;        /* [R] */
+    const int32_t* pair_off;        /* [R+1] */
+    const int32_t* pix2ray;         /* [B*h*w], lidf_pair_labels_f32 */
+    const float* gt_pos;            /* [R,3] */
+    const int64_t* pcl_label;       /* [P] */
+    const int64_t* gt_max_pair_id;  /* [R] */
+    const int32_t* n_label;         /* [1] */
+    const float* pred_pos;          /* [R,3] */
+    const float* pred_prob;         /* [P] logits */
+    float pos_w, prob_w, surf_norm_w, smooth_w;
+    int32_t surf_norm_on, smooth_on; /* the term enters loss_net (w > 0 and epoch >= its first epoch) */
+    float* loss;                    /* [8] */
+    float* pos_unreduced;           /* [R] */
+    float* surf_norm_dist;          /* [R] */
+    float* dx_dist;                 /* [R] */
+    float* dy_dist;                 /* [R] */
+    float* prob_unreduced;          /* [P] */
+    float* ray_lse;                 /* [R,2] */
+    float* gt_surf_norm_img;        /* [B,3,h,w] or NULL */
+    float* pred_surf_norm_img;      /* [B,3,h,w] or NULL */
+    void* workspace;                /* forward only */
+    size_t workspace_bytes;
+    const float* w_pos;             /* backward: [R] or NULL */
+    const float* w_prob;            /* [P] or NULL */
+    const float* w_surf;            /* [R] or NULL */
+    const float* w_dx;              /* [R] or NULL */
+    const float* w_dy;              /* [R] or NULL */
+    const float* g_loss_net;        /* [1] */
+    float* g_pred_pos;              /* [R,3] */
+    float* g_logit;                 /* [P] */
+} LidfLossArgs;
+size_t lidf_stage1_loss_workspace_bytes(int64_t n_rays);
+int lidf_stage1_loss_f32(const LidfLossArgs* args, lidf_stream_t stream);
+int lidf_stage1_loss_backward_f32(const LidfLossArgs* args, lidf_stream_t stream);
 
 #ifdef __cplusplus
 }
