@@ -8,7 +8,10 @@ Host-side mirror of the reference interface for this path (names follow the refe
         depth_metrics / lidf_query_train     <- models/pipeline.py:162-466, 577-627, 922-1041
   pipeline.lidf_forward / refine_forward     <- LIDF.forward / RefineNet.forward, eval flavour
   pipeline.lidf_forward_train                <- LIDF.forward, exp_type 'train' (one stage-1 training step)
+  pipeline.refine_forward_train / train_refine_step  <- RefineNet.forward, exp_type 'train' / the two forward
+                                                calls of trainers/train_refine.py:374-393 (one stage-2 training step)
   losses.compute_gt / lidf_loss              <- LIDF.compute_gt / compute_loss (train), models/pipeline.py:298-336, 468-566
+  losses.refine_loss                         <- RefineNet.compute_loss (train), models/pipeline.py:760-840
   torch_ext.ext()                            <- the pybind11 operator module (extensions/*/jit.py)
 All compute goes through csrc/liblidf_hip.so (C ABI in include/lidf_hip.h).
 """
@@ -16,9 +19,10 @@ from . import _lib  # noqa: F401
 from .decoders import (IEF, IMNet, Embedder, decoders_forward, decoders_forward_train,  # noqa: F401
                        get_embedder)
 from .pointnet import PointNet2Stage  # noqa: F401
-from .losses import LidfLossOptions, compute_gt, lidf_loss, lidf_loss_composite  # noqa: F401
-from .pipeline import LidfOptions, lidf_forward_train  # noqa: F401
+from .losses import (LidfLossOptions, compute_gt, lidf_loss, lidf_loss_composite, refine_loss,  # noqa: F401
+                     refine_loss_composite)
+from .pipeline import LidfOptions, lidf_forward_train, refine_forward_train, train_refine_step  # noqa: F401
 
 __all__ = ["IEF", "IMNet", "Embedder", "PointNet2Stage", "decoders_forward", "decoders_forward_train",
            "get_embedder", "LidfLossOptions", "LidfOptions", "compute_gt", "lidf_loss", "lidf_loss_composite",
-           "lidf_forward_train"]
+           "lidf_forward_train", "refine_loss", "refine_loss_composite", "refine_forward_train", "train_refine_step"]

@@ -15,7 +15,7 @@ LIDF_OK = 0
 # below follow that header's layouts; tests/test_host.py compares both with gcc's view of the header).
 # lib() refuses a liblidf_hip.so that answers another number — the library is git-ignored and travels
 # outside history, so a stale build must fail loudly, not be driven with wrong struct offsets.
-ABI = 13
+ABI = 14
 
 
 class LidfDecoder(C.Structure):
@@ -163,6 +163,23 @@ class LidfLossArgs(C.Structure):
     ]
 
 
+class LidfRefineLossArgs(C.Structure):
+    """struct LidfRefineLossArgs (include/lidf_hip.h)."""
+    _fields_ = [
+        ("n_rays", C.c_int64),
+        ("batch", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+        ("xyz", C.c_void_p), ("ray_bid", C.c_void_p), ("ray_flat", C.c_void_p), ("pix2ray", C.c_void_p),
+        ("gt_pos", C.c_void_p), ("pred_pos_refine", C.c_void_p),
+        ("pos_w", C.c_float), ("surf_norm_w", C.c_float), ("smooth_w", C.c_float),
+        ("surf_norm_on", C.c_int32), ("smooth_on", C.c_int32),
+        ("loss", C.c_void_p), ("pos_unreduced", C.c_void_p), ("surf_norm_dist", C.c_void_p),
+        ("dx_dist", C.c_void_p), ("dy_dist", C.c_void_p), ("pred_surf_norm_img", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+        ("w_pos", C.c_void_p), ("w_surf", C.c_void_p), ("w_dx", C.c_void_p), ("w_dy", C.c_void_p),
+        ("g_loss_net", C.c_void_p), ("g_pred_pos", C.c_void_p),
+    ]
+
+
 _P, _I64, _I, _SZ = C.c_void_p, C.c_int64, C.c_int, C.c_size_t
 
 # name -> (restype, argtypes); every symbol include/lidf_hip.h declares
@@ -286,6 +303,9 @@ SIGNATURES = {
     "lidf_stage1_loss_workspace_bytes": (_SZ, [_I64]),
     "lidf_stage1_loss_f32": (C.c_int, [C.POINTER(LidfLossArgs), _P]),
     "lidf_stage1_loss_backward_f32": (C.c_int, [C.POINTER(LidfLossArgs), _P]),
+    "lidf_refine_loss_workspace_bytes": (_SZ, [_I64]),
+    "lidf_refine_loss_f32": (C.c_int, [C.POINTER(LidfRefineLossArgs), _P]),
+    "lidf_refine_loss_backward_f32": (C.c_int, [C.POINTER(LidfRefineLossArgs), _P]),
 }
 
 _lib = None

@@ -3493,5 +3493,53 @@ LIDF_API int lidf_stage1_loss_backward_f32(const LidfLossArgs* args, lidf_stream
     return LIDF_OK;
 }
 
+// ---- Stage-2 training step: RefineNet's loss (lidf_loss.hip, the kernels without the pair terms) ----
+LIDF_API size_t lidf_refine_loss_workspace_bytes(int64_t n_rays) {
+    return n_rays > 0 ? lidf_stage1_loss_partial_bytes(n_rays) : 0;
+}
+
+static int refine_loss_args(const LidfRefineLossArgs* a, LossArgs* k) {
+    if (!a || a->n_rays < 0 || a->batch < 0 || a->height < 0 || a->width < 0) return LIDF_ERR_BAD_ARG;
+    if (a->n_rays > 0x7ffffffeLL || (long long)a->batch * a->height * a->width > 0x7ffffffeLL)
+        return LIDF_ERR_UNSUPPORTED;
+    if (a->n_rays > 0 && (!a->xyz || !a->ray_bid || !a->ray_flat || !a->pix2ray || !a->gt_pos ||
+                          !a->pred_pos_refine || (long long)a->batch * a->height * a->width == 0))
+        return LIDF_ERR_BAD_ARG;
+    memset(k, 0, sizeof(*k));
+    k->R = a->n_rays, k->hw = (long long)a->height * a->width;
+    k->B = a->batch, k->H = a->height, k->W = a->width;
+    k->xyz = a->xyz, k->ray_bid = a->ray_bid, k->ray_flat = a->ray_flat, k->pix2ray = a->pix2ray;
+    k->gt_pos = a->gt_pos, k->pred_pos = a->pred_pos_refine;
+    k->pos_w = a->pos_w, k->surf_w = a->surf_norm_w, k->smooth_w = a->smooth_w;
+    k->surf_on = a->surf_norm_on != 0, k->smooth_on = a->smooth_on != 0;
+    k->loss = a->loss, k->pos_un = a->pos_unreduced, k->surf_dist = a->surf_norm_dist;
+    k->dx_dist = a->dx_dist, k->dy_dist = a->dy_dist;
+    k->partial = (double*)a->workspace;
+    k->w_pos = a->w_pos, k->w_surf = a->w_surf, k->w_dx = a->w_dx, k->w_dy = a->w_dy;
+    k->g_loss_net = a->g_loss_net, k->g_pred_pos = a->g_pred_pos;
+    return LIDF_OK;
+}
+
+LIDF_API int lidf_refine_loss_f32(const LidfRefineLossArgs* args, lidf_stream_t stream) {
+    LossArgs k;
+    int rc = refine_loss_args(args, &k);
+    if (rc) return rc;
+    if (k.R == 0) return LIDF_OK;
+    if (!k.loss || !k.pos_un || !k.surf_dist || !k.dx_dist || !k.dy_dist) return LIDF_ERR_BAD_ARG;
+    if (!args->workspace || args->workspace_bytes < lidf_refine_loss_workspace_bytes(k.R)) return LIDF_ERR_WORKSPACE;
+    CHECK_HIP(lidf_launch_refine_loss(k, args->pred_surf_norm_img, (hipStream_t)stream));
+    return LIDF_OK;
+}
+
+LIDF_API int lidf_refine_loss_backward_f32(const LidfRefineLossArgs* args, lidf_stream_t stream) {
+    LossArgs k;
+    int rc = refine_loss_args(args, &k);
+    if (rc) return rc;
+    if (k.R == 0) return LIDF_OK;
+    if (!k.g_loss_net || !k.g_pred_pos) return LIDF_ERR_BAD_ARG;
+    CHECK_HIP(lidf_launch_refine_loss_backward(k, (hipStream_t)stream));
+    return LIDF_OK;
+}
+
 #include "lidf_api_pointnet_train.inc"
 #include "lidf_api_refine_train.inc"

@@ -363,7 +363,8 @@ struct CellLookup {
     int ready;          // the table already holds this voxel list
 };
 
-// Arguments of the stage-1 loss launches (lidf_loss.hip), filled by lidf_api.hip from LidfLossArgs.
+// Arguments of the loss launches (lidf_loss.hip), filled by lidf_api.hip from LidfLossArgs (stage 1) or
+// LidfRefineLossArgs (stage 2: pred_pos is pred_pos_refine, loss has six entries, the pair fields stay NULL).
 struct LossArgs {
     long long R, P, hw;
     int B, H, W;

@@ -280,6 +280,8 @@ hipError_t lidf_launch_pair_labels(const float* xyz, const int* ray_bid, const i
 size_t lidf_stage1_loss_partial_bytes(long long R);
 hipError_t lidf_launch_stage1_loss(const LossArgs& a, float* gt_img, float* pred_img, hipStream_t st);
 hipError_t lidf_launch_stage1_loss_backward(const LossArgs& a, hipStream_t st);
+hipError_t lidf_launch_refine_loss(const LossArgs& a, float* pred_img, hipStream_t st);
+hipError_t lidf_launch_refine_loss_backward(const LossArgs& a, hipStream_t st);
 
 // ---- lidf_ief16.hip
 hipError_t lidf_launch_ief16(const Ief16Args& a, int cus, hipStream_t st);

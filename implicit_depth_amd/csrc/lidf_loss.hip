@@ -1,12 +1,16 @@
-// lidf_loss.hip — the stage-1 training step's ground truth and loss (LIDF.compute_gt, models/pipeline.py:298-336,
-// and the training part of LIDF.compute_loss, :468-566) on the compact ray-major pair list:
+// lidf_loss.hip — the training steps' ground truth and losses (LIDF.compute_gt, models/pipeline.py:298-336, the
+// training part of LIDF.compute_loss, :468-566, and of RefineNet.compute_loss, :760-840) on the compact ray-major
+// pair list:
 //   lidf_pair_labels_kernel        gt_pos gather, per-pair inside test, label-selected pair of every ray, label count,
 //                                  pixel -> ray table
-//   lidf_stage1_loss_kernel        per ray: L1 position term, log-softmax terms of its labelled pairs, surface normal
+//   lidf_loss_kernel               per ray: L1 position term, log-softmax terms of its labelled pairs, surface normal
 //                                  and smoothness terms at its own pixel, the metrics; per-block partial sums
-//   lidf_stage1_loss_final_kernel  the partial sums in a fixed order -> the eight scalars of loss_dict
-//   lidf_stage1_loss_backward_kernel  per ray: d loss_net / d pred_pos (a gather over its own, its left and its
+//   lidf_loss_final_kernel         the partial sums in a fixed order -> the eight (stage 2: six) scalars of loss_dict
+//   lidf_loss_backward_kernel      per ray: d loss_net / d pred_pos (a gather over its own, its left and its
 //                                  upper pixel's normals) and d loss_net / d logits of its pairs (closed form)
+// The three loss kernels are templates on PAIRS: <true> is stage 1 (lidf_stage1_loss_*), <false> is stage 2
+// (lidf_refine_loss_*: pred_pos is pred_pos_refine, no ray-termination term and no acc, no pair list is read — a ray
+// without pairs is an ordinary ray — and loss_dict has six entries).
 // No V x R mask, no image-sized normal map (lidf_normal_map_kernel writes the two maps on request only), no float
 // atomics: every sum has a fixed order, so losses and gradients are bit-identical from run to run.
 #include "lidf_launch.h"
@@ -137,7 +141,8 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
-__global__ __launch_bounds__(LOSS_BLOCK) void lidf_stage1_loss_kernel(const LossArgs A) {
+template <bool PAIRS>
+__global__ __launch_bounds__(LOSS_BLOCK) void lidf_loss_kernel(const LossArgs A) {
     const long long r = (long long)blockIdx.x * LOSS_BLOCK + threadIdx.x;
     double v[NSUM];
 #pragma unroll
@@ -159,29 +164,31 @@ __global__ __launch_bounds__(LOSS_BLOCK) void lidf_stage1_loss_kernel(const Loss
         }
         // log-softmax over the ray's pairs, taken at its labelled pairs (:482-484); arg-max of the softmax with
         // lidf_ray_reduce_kernel's rule (first of equal values, P when nothing compares greater than -inf)
-        const int beg = A.pair_off[r], end = A.pair_off[r + 1];
-        float m = -INFINITY;
-        for (int i = beg; i < end; ++i) m = fmaxf(m, A.logit[i]);
-        float s = 0.f;
-        for (int i = beg; i < end; ++i) s += expf(A.logit[i] - m);
-        const float ls = logf(s);
-        float bv = -INFINITY, psum = 0.f;
-        int bi = 0x7fffffff;
-        for (int i = beg; i < end; ++i) {
-            const float z = A.logit[i] - m;
-            const float sm = expf(z) / s;
-            if (sm > bv) bv = sm, bi = i;
-            float l = -INFINITY;
-            if (A.label[i] != 0) {
-                l = -(z - ls);
-                psum += l;
+        if constexpr (PAIRS) {
+            const int beg = A.pair_off[r], end = A.pair_off[r + 1];
+            float m = -INFINITY;
+            for (int i = beg; i < end; ++i) m = fmaxf(m, A.logit[i]);
+            float s = 0.f;
+            for (int i = beg; i < end; ++i) s += expf(A.logit[i] - m);
+            const float ls = logf(s);
+            float bv = -INFINITY, psum = 0.f;
+            int bi = 0x7fffffff;
+            for (int i = beg; i < end; ++i) {
+                const float z = A.logit[i] - m;
+                const float sm = expf(z) / s;
+                if (sm > bv) bv = sm, bi = i;
+                float l = -INFINITY;
+                if (A.label[i] != 0) {
+                    l = -(z - ls);
+                    psum += l;
+                }
+                A.prob_un[i] = l;
             }
-            A.prob_un[i] = l;
+            A.ray_lse[2 * r] = m, A.ray_lse[2 * r + 1] = ls;
+            v[S_PROB] = psum;
+            const long long pred_label = (end <= beg || bi >= end) ? A.P : (long long)bi;
+            v[S_ACC] = pred_label == A.gt_maxid[r] ? 1.0 : 0.0;
         }
-        A.ray_lse[2 * r] = m, A.ray_lse[2 * r + 1] = ls;
-        v[S_PROB] = psum;
-        const long long pred_label = (end <= beg || bi >= end) ? A.P : (long long)bi;
-        v[S_ACC] = pred_label == A.gt_maxid[r] ? 1.0 : 0.0;
         // surface normal and smoothness terms at the ray's own pixel (:494-539)
         const int b = A.ray_bid[r], f = A.ray_flat[r];
         const int y = f / A.W, x = f - y * A.W;
@@ -215,8 +222,10 @@ __global__ __launch_bounds__(LOSS_BLOCK) void lidf_stage1_loss_kernel(const Loss
 }
 
 // Stage 2: wavefront k sums quantity k over the blocks (lane-strided, then a butterfly: a fixed order), thread 0
-// forms loss_dict = {pos_loss, prob_loss, surf_norm_loss, smooth_loss, loss_net, acc, err, angle_err} (:542-566).
-__global__ __launch_bounds__(64 * NSUM) void lidf_stage1_loss_final_kernel(const LossArgs A, int nblk) {
+// forms loss_dict = {pos_loss, prob_loss, surf_norm_loss, smooth_loss, loss_net, acc, err, angle_err} (:542-566);
+// stage 2: {pos_loss, surf_norm_loss, smooth_loss, loss_net, err, angle_err} (:823-840, :898-905).
+template <bool PAIRS>
+__global__ __launch_bounds__(64 * NSUM) void lidf_loss_final_kernel(const LossArgs A, int nblk) {
     __shared__ double tot[NSUM];
     const int k = threadIdx.x >> 6, ln = threadIdx.x & 63;
     double t = 0.0;
@@ -225,18 +234,28 @@ __global__ __launch_bounds__(64 * NSUM) void lidf_stage1_loss_final_kernel(const
     if (ln == 0) tot[k] = t;
     __syncthreads();
     if (threadIdx.x == 0) {
-        const double R = (double)A.R, L = (double)*A.n_label;
+        const double R = (double)A.R;
         const float pos = (float)(tot[S_POS] / (3.0 * R));
-        const float prob = (float)(tot[S_PROB] / L);   // L == 0: 0 / 0 = NaN, torch.mean of an empty tensor
         const float surf = (float)(tot[S_SURF] / R);
         const float smooth = (float)(tot[S_DX] / R) + (float)(tot[S_DY] / R);
-        float net = A.pos_w * pos + A.prob_w * prob;
-        if (A.surf_on) net += A.surf_w * surf;
-        if (A.smooth_on) net += A.smooth_w * smooth;
-        A.loss[0] = pos, A.loss[1] = prob, A.loss[2] = surf, A.loss[3] = smooth, A.loss[4] = net;
-        A.loss[5] = (float)(tot[S_ACC] / R);
-        A.loss[6] = tot[S_ELEM] == 0.0 ? 0.f : (float)(tot[S_ERR] / tot[S_ELEM]);
-        A.loss[7] = (float)(tot[S_ANGLE] / R) / 3.14159265358979323846f * 180.f;
+        const float err = tot[S_ELEM] == 0.0 ? 0.f : (float)(tot[S_ERR] / tot[S_ELEM]);
+        const float angle = (float)(tot[S_ANGLE] / R) / 3.14159265358979323846f * 180.f;
+        if constexpr (PAIRS) {
+            const double L = (double)*A.n_label;
+            const float prob = (float)(tot[S_PROB] / L);   // L == 0: 0 / 0 = NaN, torch.mean of an empty tensor
+            float net = A.pos_w * pos + A.prob_w * prob;
+            if (A.surf_on) net += A.surf_w * surf;
+            if (A.smooth_on) net += A.smooth_w * smooth;
+            A.loss[0] = pos, A.loss[1] = prob, A.loss[2] = surf, A.loss[3] = smooth, A.loss[4] = net;
+            A.loss[5] = (float)(tot[S_ACC] / R);
+            A.loss[6] = err;
+            A.loss[7] = angle;
+        } else {
+            float net = A.pos_w * pos;
+            if (A.surf_on) net += A.surf_w * surf;
+            if (A.smooth_on) net += A.smooth_w * smooth;
+            A.loss[0] = pos, A.loss[1] = surf, A.loss[2] = smooth, A.loss[3] = net, A.loss[4] = err, A.loss[5] = angle;
+        }
     }
 }
 
@@ -288,24 +307,27 @@ __device__ __forceinline__ void pix_weights(const LossArgs& A, long long rj, flo
     cdy = A.smooth_on ? up * A.smooth_w * (A.w_dy ? A.w_dy[rj] : invR) : 0.f;
 }
 
-__global__ __launch_bounds__(LOSS_BLOCK) void lidf_stage1_loss_backward_kernel(const LossArgs A) {
+template <bool PAIRS>
+__global__ __launch_bounds__(LOSS_BLOCK) void lidf_loss_backward_kernel(const LossArgs A) {
     const long long r = (long long)blockIdx.x * LOSS_BLOCK + threadIdx.x;
     if (r >= A.R) return;
     const float up = *A.g_loss_net;
     const float invR = 1.f / (float)A.R;
-    const int L = *A.n_label;
-    const float invL = L > 0 ? 1.f / (float)L : 0.f;   // (no labelled pair: the empty mean reaches no logit)
-    // logits: sum over the ray's labelled pairs j of w_j (softmax_i - [i == j])
-    const int beg = A.pair_off[r], end = A.pair_off[r + 1];
-    const float m = A.ray_lse[2 * r], ls = A.ray_lse[2 * r + 1];
-    float wsum = 0.f;
-    for (int i = beg; i < end; ++i)
-        if (A.label[i] != 0) wsum += A.w_prob ? A.w_prob[i] : invL;
-    const float kp = up * A.prob_w;
-    for (int i = beg; i < end; ++i) {
-        const float sm = expf((A.logit[i] - m) - ls);
-        const float wl = A.label[i] != 0 ? (A.w_prob ? A.w_prob[i] : invL) : 0.f;
-        A.g_logit[i] = kp * (wsum * sm - wl);
+    if constexpr (PAIRS) {
+        const int L = *A.n_label;
+        const float invL = L > 0 ? 1.f / (float)L : 0.f;   // (no labelled pair: the empty mean reaches no logit)
+        // logits: sum over the ray's labelled pairs j of w_j (softmax_i - [i == j])
+        const int beg = A.pair_off[r], end = A.pair_off[r + 1];
+        const float m = A.ray_lse[2 * r], ls = A.ray_lse[2 * r + 1];
+        float wsum = 0.f;
+        for (int i = beg; i < end; ++i)
+            if (A.label[i] != 0) wsum += A.w_prob ? A.w_prob[i] : invL;
+        const float kp = up * A.prob_w;
+        for (int i = beg; i < end; ++i) {
+            const float sm = expf((A.logit[i] - m) - ls);
+            const float wl = A.label[i] != 0 ? (A.w_prob ? A.w_prob[i] : invL) : 0.f;
+            A.g_logit[i] = kp * (wsum * sm - wl);
+        }
     }
     // position term: sign(pred - gt) / 3 per coordinate of the ray's mean
     const float kpos = up * A.pos_w * (A.w_pos ? A.w_pos[r] : invR) / 3.f;
@@ -387,8 +409,8 @@ extern "C" size_t lidf_stage1_loss_partial_bytes(long long R) {
 extern "C" hipError_t lidf_launch_stage1_loss(const LossArgs& a, float* gt_img, float* pred_img, hipStream_t st) {
     if (a.R <= 0) return hipSuccess;
     const int blocks = (int)((a.R + LOSS_BLOCK - 1) / LOSS_BLOCK);
-    hipLaunchKernelGGL(lidf_stage1_loss_kernel, dim3((unsigned)blocks), dim3(LOSS_BLOCK), 0, st, a);
-    hipLaunchKernelGGL(lidf_stage1_loss_final_kernel, dim3(1), dim3(64 * NSUM), 0, st, a, blocks);
+    hipLaunchKernelGGL(lidf_loss_kernel<true>, dim3((unsigned)blocks), dim3(LOSS_BLOCK), 0, st, a);
+    hipLaunchKernelGGL(lidf_loss_final_kernel<true>, dim3(1), dim3(64 * NSUM), 0, st, a, blocks);
     if (gt_img || pred_img) {
         const long long n = (long long)a.B * a.hw;
         hipLaunchKernelGGL(lidf_normal_map_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, gt_img,
@@ -399,7 +421,28 @@ extern "C" hipError_t lidf_launch_stage1_loss(const LossArgs& a, float* gt_img, 
 
 extern "C" hipError_t lidf_launch_stage1_loss_backward(const LossArgs& a, hipStream_t st) {
     if (a.R <= 0) return hipSuccess;
-    hipLaunchKernelGGL(lidf_stage1_loss_backward_kernel, dim3((unsigned)((a.R + LOSS_BLOCK - 1) / LOSS_BLOCK)),
+    hipLaunchKernelGGL(lidf_loss_backward_kernel<true>, dim3((unsigned)((a.R + LOSS_BLOCK - 1) / LOSS_BLOCK)),
+                       dim3(LOSS_BLOCK), 0, st, a);
+    return hipGetLastError();
+}
+
+// Stage 2 (RefineNet.compute_loss): a.pred_pos is pred_pos_refine; the pair fields of `a` are not read.
+extern "C" hipError_t lidf_launch_refine_loss(const LossArgs& a, float* pred_img, hipStream_t st) {
+    if (a.R <= 0) return hipSuccess;
+    const int blocks = (int)((a.R + LOSS_BLOCK - 1) / LOSS_BLOCK);
+    hipLaunchKernelGGL(lidf_loss_kernel<false>, dim3((unsigned)blocks), dim3(LOSS_BLOCK), 0, st, a);
+    hipLaunchKernelGGL(lidf_loss_final_kernel<false>, dim3(1), dim3(64 * NSUM), 0, st, a, blocks);
+    if (pred_img) {
+        const long long n = (long long)a.B * a.hw;
+        hipLaunchKernelGGL(lidf_normal_map_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a,
+                           (float*)nullptr, pred_img);
+    }
+    return hipGetLastError();
+}
+
+extern "C" hipError_t lidf_launch_refine_loss_backward(const LossArgs& a, hipStream_t st) {
+    if (a.R <= 0) return hipSuccess;
+    hipLaunchKernelGGL(lidf_loss_backward_kernel<false>, dim3((unsigned)((a.R + LOSS_BLOCK - 1) / LOSS_BLOCK)),
                        dim3(LOSS_BLOCK), 0, st, a);
     return hipGetLastError();
 }

@@ -1,10 +1,12 @@
-"""losses.py — ground-truth labels and the training loss of stage 1.
+"""losses.py — ground-truth labels and the training losses of stage 1 and stage 2.
 
 Reference counterparts (paths relative to /root/reference/src):
   compute_gt           <- LIDF.compute_gt                       models/pipeline.py:298-336
   lidf_loss            <- LIDF.compute_loss, exp_type == 'train' models/pipeline.py:468-566
   lidf_loss_composite  the same loss in plain torch ops (any dtype, any device): the A/B partner of
                        lidf_loss and the route for CPU callers
+  refine_loss          <- RefineNet.compute_loss, exp_type == 'train'  models/pipeline.py:760-840
+  refine_loss_composite  the same in plain torch ops
   LidfLossOptions      <- the loss.* keys of experiments/implicit_depth/default_config.yaml:97-107
 
 compute_gt and lidf_loss run in liblidf_hip.so (csrc/lidf_loss.hip): one launch for the labels, two for the
@@ -22,10 +24,14 @@ from . import _lib
 from .query import _as_i32, _f32, _i32
 
 LOSS_KEYS = ("pos_loss", "prob_loss", "surf_norm_loss", "smooth_loss", "loss_net", "acc", "err", "angle_err")
+REFINE_LOSS_KEYS = ("pos_loss", "surf_norm_loss", "smooth_loss", "loss_net", "err", "angle_err")
 
 
 class LidfLossOptions:
-    """loss.* of default_config.yaml:97-107 (train_refine_hardneg.yaml: hard_neg True, hard_neg_ratio 0.1)."""
+    """loss.* of default_config.yaml:97-107 (train_refine_hardneg.yaml: hard_neg True, hard_neg_ratio 0.1).
+    The defaults are stage 1's (train_lidf.yaml). Stage 2 reads the same keys (prob_w and prob_loss_type are not
+    used there) and ships other values: train_refine.yaml pos_w 100 / surf_norm_w 10, train_refine_hardneg.yaml
+    pos_w 20 / surf_norm_w 2 with hard_neg True and hard_neg_ratio 0.1."""
 
     def __init__(self, **kw):
         self.hard_neg = False
@@ -44,10 +50,10 @@ class LidfLossOptions:
             setattr(self, k, v)
 
 
-def _check_types(opt):
+def _check_types(opt, prob=True):
     if opt.pos_loss_type != "single":
         raise NotImplementedError("pos_loss_type %s" % opt.pos_loss_type)
-    if opt.prob_loss_type != "ray":
+    if prob and opt.prob_loss_type != "ray":
         raise NotImplementedError("prob_loss_type %s" % opt.prob_loss_type)
     if opt.hard_neg and opt.hard_neg_ratio is None:
         raise ValueError("hard_neg needs hard_neg_ratio")
@@ -295,35 +301,18 @@ def _neighbour_normals(xyz, table, pos, lin, x, y, h, w):
     return n / (torch.linalg.vector_norm(n, dim=-1, keepdim=True) + 1e-8), dx, dy
 
 
-def lidf_loss_composite(dd, loss_opt=None, exp_type="train", epoch=0):
-    """lidf_loss written in differentiable torch ops, in the dtype of pred_pos, on any device: per-ray
-    log-softmax by scatter reductions, the normals by gathering each sampled pixel's right and lower neighbour.
-    Needs gt_pos and pcl_label in dd (compute_gt's, or a caller's own); every entry of the returned loss_dict
-    carries its graph. It takes many small launches where lidf_loss takes three."""
-    opt = loss_opt or LidfLossOptions()
-    if exp_type != "train":
-        raise NotImplementedError("lidf_loss_composite covers exp_type 'train'")
-    _check_types(opt)
-    pred_pos, logit = dd["pred_pos"], dd["pred_prob_end"].reshape(-1)
+def _composite_terms(dd, pred_pos, gt_pos, opt):
+    """What the two composites share: (reduce, pos_loss, surf_norm_loss, smooth_loss, angle_err, err) of `pred_pos`
+    against `gt_pos` at the sampled pixels of dd."""
     dt, dev = pred_pos.dtype, pred_pos.device
     bs, h, w = dd["bs"], dd["h"], dd["w"]
-    gt_pos, label = dd["gt_pos"].to(dt), dd["pcl_label"].long()
-    ray = dd["pair_ray"].long()
     bid = (dd["ray_bid"] if "ray_bid" in dd else dd["miss_bid"]).long()
     flat = (dd["ray_flat"] if "ray_flat" in dd else dd["miss_flat_img_id"]).long()
-    R, P = pred_pos.shape[0], logit.shape[0]
+    R = pred_pos.shape[0]
     topk_mean = lambda v: torch.mean(torch.topk(v, int(v.shape[0] * opt.hard_neg_ratio))[0])  # noqa: E731
     reduce = topk_mean if opt.hard_neg else torch.mean
-    # position
     pos_loss = reduce(torch.mean((pred_pos - gt_pos).abs(), -1)) if opt.hard_neg else \
         torch.mean((pred_pos - gt_pos).abs())
-    # ray termination: -log_softmax over each ray's pairs at the labelled pairs
-    top = torch.full((R,), float("-inf"), dtype=dt, device=dev).scatter_reduce(
-        0, ray, logit.detach(), reduce="amax", include_self=True)
-    z = logit - top[ray]
-    lse = torch.log(torch.zeros((R,), dtype=dt, device=dev).index_add(0, ray, torch.exp(z)))
-    log_sm = z - lse[ray]
-    prob_loss = reduce(-log_sm[torch.nonzero(label, as_tuple=False).reshape(-1)])
     # surface normals and smoothness at the sampled pixels
     xyz = dd["xyz_flat"].reshape(-1, 3).to(dt)
     lin = bid * (h * w) + flat
@@ -336,21 +325,195 @@ def lidf_loss_composite(dd, loss_opt=None, exp_type="train", epoch=0):
     surf_norm_loss = reduce((1 - cos) / 2.0)
     angle_err = torch.mean(torch.acos(torch.clamp(cos, min=-1, max=1))) / torch.pi * 180.0
     smooth_loss = reduce(torch.sum(dx * dx, -1)) + reduce(torch.sum(dy * dy, -1))
+    with torch.no_grad():
+        nonzero = (torch.sum(gt_pos.abs(), -1) != 0).to(dt)
+        l2 = torch.sqrt(torch.sum((pred_pos - gt_pos) ** 2, -1))
+        n = torch.sum(nonzero)
+        err = torch.where(n == 0, torch.zeros_like(n), torch.sum(l2 * nonzero) / n.clamp(min=1))
+    return reduce, pos_loss, surf_norm_loss, smooth_loss, angle_err, err
+
+
+def lidf_loss_composite(dd, loss_opt=None, exp_type="train", epoch=0):
+    """lidf_loss written in differentiable torch ops, in the dtype of pred_pos, on any device: per-ray
+    log-softmax by scatter reductions, the normals by gathering each sampled pixel's right and lower neighbour.
+    Needs gt_pos and pcl_label in dd (compute_gt's, or a caller's own); every entry of the returned loss_dict
+    carries its graph. It takes many small launches where lidf_loss takes three."""
+    opt = loss_opt or LidfLossOptions()
+    if exp_type != "train":
+        raise NotImplementedError("lidf_loss_composite covers exp_type 'train'")
+    _check_types(opt)
+    pred_pos, logit = dd["pred_pos"], dd["pred_prob_end"].reshape(-1)
+    dt, dev = pred_pos.dtype, pred_pos.device
+    gt_pos, label = dd["gt_pos"].to(dt), dd["pcl_label"].long()
+    ray = dd["pair_ray"].long()
+    R, P = pred_pos.shape[0], logit.shape[0]
+    reduce, pos_loss, surf_norm_loss, smooth_loss, angle_err, err = _composite_terms(dd, pred_pos, gt_pos, opt)
+    # ray termination: -log_softmax over each ray's pairs at the labelled pairs
+    top = torch.full((R,), float("-inf"), dtype=dt, device=dev).scatter_reduce(
+        0, ray, logit.detach(), reduce="amax", include_self=True)
+    z = logit - top[ray]
+    lse = torch.log(torch.zeros((R,), dtype=dt, device=dev).index_add(0, ray, torch.exp(z)))
+    log_sm = z - lse[ray]
+    prob_loss = reduce(-log_sm[torch.nonzero(label, as_tuple=False).reshape(-1)])
     loss_net = opt.pos_w * pos_loss + opt.prob_w * prob_loss
     surf_on, smooth_on = _terms_on(opt, epoch)
     if surf_on:
         loss_net = loss_net + opt.surf_norm_w * surf_norm_loss
     if smooth_on:
         loss_net = loss_net + opt.smooth_w * smooth_loss
-    # metrics
     with torch.no_grad():
         sm = torch.exp(log_sm)
         pred_label = _first_argmax(sm, ray, R, P)
         gt_label = _first_argmax(label.to(dt), ray, R, P)
         acc = torch.sum(torch.eq(pred_label, gt_label).to(dt)) / R
-        nonzero = (torch.sum(gt_pos.abs(), -1) != 0).to(dt)
-        l2 = torch.sqrt(torch.sum((pred_pos - gt_pos) ** 2, -1))
-        n = torch.sum(nonzero)
-        err = torch.where(n == 0, torch.zeros_like(n), torch.sum(l2 * nonzero) / n.clamp(min=1))
     return {"pos_loss": pos_loss, "prob_loss": prob_loss, "surf_norm_loss": surf_norm_loss,
             "smooth_loss": smooth_loss, "loss_net": loss_net, "acc": acc, "err": err, "angle_err": angle_err}
+
+
+# ------------------------------------------------------------------------------------------------
+# Stage 2: the loss of the refinement network
+# ------------------------------------------------------------------------------------------------
+_REFINE_IN = ("xyz", "ray_bid", "ray_flat", "pix2ray", "gt_pos", "pred_pos_refine")
+
+
+def _refine_loss_args(t, cfg):
+    """LidfRefineLossArgs over the tensors `t` (a dict; absent / None entries stay NULL)."""
+    a = _lib.LidfRefineLossArgs()
+    a.n_rays = t["gt_pos"].shape[0]
+    a.batch, a.height, a.width = cfg["bs"], cfg["h"], cfg["w"]
+    a.pos_w, a.surf_norm_w, a.smooth_w = float(cfg["pos_w"]), float(cfg["surf_norm_w"]), float(cfg["smooth_w"])
+    a.surf_norm_on, a.smooth_on = int(cfg["surf_on"]), int(cfg["smooth_on"])
+    for k, v in t.items():
+        if v is not None:
+            setattr(a, k, v.data_ptr())
+    return a
+
+
+class _RefineLossFn(torch.autograd.Function):
+    """RefineNet.compute_loss of the training step as one autograd node over pred_pos_refine
+    (lidf_refine_loss_f32 / lidf_refine_loss_backward_f32). Outputs: loss_net (differentiable) and the [6] vector
+    of loss_dict (detached)."""
+
+    @staticmethod
+    def forward(ctx, pred_pos, cfg, img, xyz, ray_bid, ray_flat, pix2ray, gt_pos):
+        dev = xyz.device
+        pp = pred_pos.detach().contiguous()
+        R = gt_pos.shape[0]
+        f32 = dict(dtype=torch.float32, device=dev)
+        L = _lib.lib()
+        wsb = L.lidf_refine_loss_workspace_bytes(R)
+        t = dict(zip(_REFINE_IN, (xyz, ray_bid, ray_flat, pix2ray, gt_pos, pp)))
+        fwd = {"loss": torch.empty((6,), **f32), "pos_unreduced": torch.empty((R,), **f32),
+               "surf_norm_dist": torch.empty((R,), **f32), "dx_dist": torch.empty((R,), **f32),
+               "dy_dist": torch.empty((R,), **f32), "workspace": _lib.workspace(wsb, dev),
+               "pred_surf_norm_img": img}
+        a = _refine_loss_args(dict(t, **fwd), cfg)
+        a.workspace_bytes = wsb
+        with torch.cuda.device(dev):
+            _lib.check(L.lidf_refine_loss_f32(C.byref(a), _lib.current_stream(dev)))
+        loss = fwd["loss"]
+        weights = ()
+        if cfg["hard_neg"]:
+            # hard-negative mining (models/pipeline.py:767-770, 799-801, 818-821): k = int(R * ratio) is known on
+            # the host, so nothing is read back
+            k = int(R * cfg["hard_neg_ratio"])
+            pos, w_pos = _topk_weights(fwd["pos_unreduced"], k)
+            surf, w_surf = _topk_weights(fwd["surf_norm_dist"], k)
+            sdx, w_dx = _topk_weights(fwd["dx_dist"], k)
+            sdy, w_dy = _topk_weights(fwd["dy_dist"], k)
+            smooth = sdx + sdy
+            net = cfg["pos_w"] * pos
+            if cfg["surf_on"]:
+                net = net + cfg["surf_norm_w"] * surf
+            if cfg["smooth_on"]:
+                net = net + cfg["smooth_w"] * smooth
+            loss = torch.cat((torch.stack((pos, surf, smooth, net)), loss[4:]))
+            weights = (w_pos, w_surf, w_dx, w_dy)
+        ctx.cfg = cfg
+        ctx.shape = tuple(pred_pos.shape)
+        ctx.save_for_backward(*t.values(), *weights)
+        net = loss[3].clone()
+        ctx.mark_non_differentiable(loss)
+        return net, loss
+
+    @staticmethod
+    def backward(ctx, g_net, _g_loss):
+        s = ctx.saved_tensors
+        t = dict(zip(_REFINE_IN, s[:6]))
+        t.update(zip(("w_pos", "w_surf", "w_dx", "w_dy"), s[6:]))
+        dev = t["xyz"].device
+        t["g_loss_net"] = g_net.detach().reshape(1).contiguous().float()
+        t["g_pred_pos"] = torch.empty((t["gt_pos"].shape[0], 3), dtype=torch.float32, device=dev)
+        a = _refine_loss_args(t, ctx.cfg)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().lidf_refine_loss_backward_f32(C.byref(a), _lib.current_stream(dev)))
+        return (t["g_pred_pos"].reshape(ctx.shape),) + (None,) * 7
+
+
+def refine_loss(dd, loss_opt=None, exp_type="train", epoch=0, normal_maps=False):
+    """RefineNet.compute_loss for exp_type == 'train' (models/pipeline.py:760-840) on the data_dict of the stage-2
+    training step (pred_pos_refine [R,3], xyz_flat, the sampled rays): the reference's loss_dict — pos_loss,
+    surf_norm_loss, smooth_loss, loss_net, err, angle_err — as 0-dim device tensors. loss_net carries the graph (one
+    autograd node over pred_pos_refine: lidf_refine_loss_f32 and its backward, three launches in all); the other
+    five are detached. gt_pos and pix2ray are compute_gt's: it runs here when dd lacks them (it needs the pair list
+    then; the loss itself reads none — a ray without pairs is an ordinary ray). Nothing is read back to the host,
+    hard_neg included: its k = int(R * hard_neg_ratio) is known there.
+    loss_opt: LidfLossOptions; its defaults are train_refine.yaml's pos_w 100 / surf_norm_w 10, and
+    train_refine_hardneg.yaml is LidfLossOptions(hard_neg=True, hard_neg_ratio=0.1, pos_w=20.0, surf_norm_w=2.0).
+    normal_maps=True adds pred_surf_norm_img_refine [bs,3,h,w] to dd (:894, visualisation only)."""
+    opt = loss_opt or LidfLossOptions()
+    if exp_type != "train":
+        raise NotImplementedError("refine_loss covers exp_type 'train'; the evaluation statistics are "
+                                  "pipeline.eval_metrics")
+    _check_types(opt, prob=False)
+    pred = dd["pred_pos_refine"]
+    _lib.require_cuda(pred, dd["xyz_flat"], names=["pred_pos_refine", "xyz_flat"])
+    _f32(pred, "pred_pos_refine")
+    if "pix2ray" not in dd or "gt_pos" not in dd:
+        compute_gt(dd)
+    ray_bid, ray_flat = _ray_index(dd)
+    # compute_gt's entries may come from an earlier call on a reused dict: the kernels index with them unchecked
+    xyz, pix2ray, gt_pos = dd["xyz_flat"], dd["pix2ray"], dd["gt_pos"]
+    _lib.require_cuda(pix2ray, ray_bid, ray_flat, gt_pos, names=["pix2ray", "ray_bid", "ray_flat", "gt_pos"])
+    _f32(xyz, "xyz_flat"), _i32(pix2ray, "pix2ray"), _f32(gt_pos, "gt_pos")
+    bs, h, w = dd["bs"], dd["h"], dd["w"]
+    R = gt_pos.shape[0]
+    if (tuple(pred.shape) != (R, 3) or tuple(gt_pos.shape) != (R, 3) or tuple(xyz.shape) != (bs, h * w, 3)
+            or tuple(pix2ray.shape) != (bs * h * w,) or tuple(ray_bid.shape) != (R,)
+            or tuple(ray_flat.shape) != (R,)):
+        raise RuntimeError("refine_loss: pred_pos_refine / gt_pos / xyz_flat / pix2ray / ray index do not belong to "
+                           "one frame batch and ray set: [R,3] / [R,3] / [bs,h*w,3] / [bs*h*w] int32 / [R] — run "
+                           "compute_gt(dd) again")
+    if R == 0:
+        raise RuntimeError("refine_loss: no ray (the reference returns before stage 2, models/pipeline.py:686)")
+    img = None
+    if normal_maps:
+        img = torch.empty((bs, 3, h, w), dtype=torch.float32, device=pred.device)
+        dd["pred_surf_norm_img_refine"] = img
+    cfg = _cfg(dd, opt, epoch)
+    net, loss = _RefineLossFn.apply(pred, cfg, img, xyz.contiguous(), ray_bid, ray_flat, pix2ray.contiguous(),
+                                    gt_pos.contiguous())
+    out = {k: loss[i] for i, k in enumerate(REFINE_LOSS_KEYS)}
+    out["loss_net"] = net
+    return out
+
+
+def refine_loss_composite(dd, loss_opt=None, exp_type="train", epoch=0):
+    """refine_loss written in differentiable torch ops, in the dtype of pred_pos_refine, on any device (the A/B
+    partner of refine_loss and the route for CPU callers). Needs gt_pos in dd; every entry of the returned loss_dict
+    carries its graph."""
+    opt = loss_opt or LidfLossOptions()
+    if exp_type != "train":
+        raise NotImplementedError("refine_loss_composite covers exp_type 'train'")
+    _check_types(opt, prob=False)
+    pred = dd["pred_pos_refine"]
+    _, pos_loss, surf_norm_loss, smooth_loss, angle_err, err = _composite_terms(dd, pred, dd["gt_pos"].to(pred.dtype),
+                                                                                opt)
+    loss_net = opt.pos_w * pos_loss
+    surf_on, smooth_on = _terms_on(opt, epoch)
+    if surf_on:
+        loss_net = loss_net + opt.surf_norm_w * surf_norm_loss
+    if smooth_on:
+        loss_net = loss_net + opt.smooth_w * smooth_loss
+    return {"pos_loss": pos_loss, "surf_norm_loss": surf_norm_loss, "smooth_loss": smooth_loss,
+            "loss_net": loss_net, "err": err, "angle_err": angle_err}

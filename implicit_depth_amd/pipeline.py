@@ -7,6 +7,9 @@ Reference counterparts (paths relative to /root/reference/src, eval flavour `exp
                          (get_occ_vox_bound :162-201, get_miss_ray :203-269, compute_ray_aabb
                           :271-296, get_embedding :338-425, get_pred :427-466, depth map :593-596)
   refine_forward      <- RefineNet.forward          models/pipeline.py:1032-1041
+  lidf_forward_train  <- LIDF.forward, exp_type 'train'   models/pipeline.py:652-711
+  refine_forward_train <- RefineNet.forward, exp_type 'train'   models/pipeline.py:1032-1041
+  train_refine_step   <- the two forward calls of a stage-2 training iteration   trainers/train_refine.py:374-393
   eval_metrics        <- the bs == 1 statistics of LIDF.compute_loss   models/pipeline.py:577-627
 
 Every compute step is a call into liblidf_hip.so through implicit_depth_amd.query / .pointnet;
@@ -43,6 +46,9 @@ class LidfOptions:
         self.refine_use_all_pix = True
         self.refine_pnet_pos_type = "rel"
         self.refine_intersect_pos_type = "abs"
+        # stage-2 training (train_refine.yaml:66-67): the perturbation of the first iteration's input
+        self.refine_perturb = True
+        self.refine_perturb_prob = 0.8
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise TypeError("unknown option %s" % k)
@@ -175,6 +181,50 @@ def lidf_forward(batch, full_rgb_feat, pnet_model, prob_dec, offset_dec, opt=Non
     return True, dd
 
 
+def _train_geometry(batch, full_rgb_feat, opt, valid_idx):
+    """LIDF.forward(batch, 'train', epoch) up to and including compute_gt (models/pipeline.py:652-704): (success,
+    data_dict). success False = one of the reference's three early exits."""
+    from .losses import compute_gt
+    if opt.intersect_pos_type not in ("abs", "rel"):
+        raise NotImplementedError("intersect_pos_type %s" % opt.intersect_pos_type)
+    _lib.require_cuda(batch["rgb"], batch["xyz"], full_rgb_feat, names=["batch['rgb']", "batch['xyz']", "full_rgb_feat"])
+    dd = prepare_data(batch, opt, exp_type="train")
+    get_valid_points(dd, opt, valid_idx)
+    bs = dd["bs"]
+    if dd["valid_xyz"].shape[0] == 0:   # (no valid point at all: no occupied voxel)
+        return False, dd
+    occ = Q.get_occ_vox_bound(dd["valid_xyz"].contiguous(), dd["valid_bid"].to(torch.int32).contiguous(),
+                              bs, opt.xmin, opt.xmax, opt.grid_res)
+    dd.update(occ)
+    V = occ["voxel_bound"].shape[0]
+    if V == 0:
+        return False, dd
+    miss = Q.get_miss_ray(dd["corrupt_mask"], dd["fx"], dd["fy"], dd["cx"], dd["cy"])
+    dd.update(Q.sample_miss_rays(miss, bs, opt.miss_sample_num))
+    if dd["total_miss_sample_num"] == 0:
+        return False, dd
+    vox_bid = occ["occ_vox_bid"].to(torch.int32).contiguous()
+    grid = dict(voxel_coord=occ["voxel_coord"], grid_dims=occ["grid_dims"], batch=bs) if V > 256 * bs else {}
+    pair_off, pair_ray, pair_vox, pair_t = Q.compute_ray_aabb(
+        dd["miss_ray_dir"], occ["voxel_bound"], dd["ray_bid"], vox_bid, **grid)
+    dd.update({"pair_off": pair_off, "pair_ray": pair_ray, "pair_vox": pair_vox, "pair_t": pair_t,
+               "voxel_bid": vox_bid})
+    if pair_ray.shape[0] == 0:
+        return False, dd
+    compute_gt(dd)
+    valid_v_rgb = dd["valid_rgb"].index_select(0, occ["valid_v_pid"])
+    dd["pnet_inp"] = torch.cat((occ["valid_v_rel_coord"], valid_v_rgb), -1)
+    dd["full_rgb_feat"] = full_rgb_feat
+    return True, dd
+
+
+def _vox_center(dd, opt):
+    if opt.intersect_pos_type != "rel":
+        return None
+    vb = dd["voxel_bound"]
+    return ((vb[:, :3] + vb[:, 3:]) / 2.0).contiguous()
+
+
 def lidf_forward_train(batch, full_rgb_feat, pnet_model, prob_dec, offset_dec, opt=None, loss_opt=None, epoch=0,
                        valid_idx=None):
     """LIDF.forward(batch, 'train', epoch) (models/pipeline.py:652-711) as one call: returns (success, data_dict,
@@ -186,50 +236,86 @@ def lidf_forward_train(batch, full_rgb_feat, pnet_model, prob_dec, offset_dec, o
     modules. success False = one of the reference's three early exits (no occupied voxel / no miss ray / no
     intersecting pair): loss_dict is then {} and data_dict holds what was computed up to that point. The DDP
     success-flag handshake of :662-701 stays with the trainer."""
-    from .losses import compute_gt, lidf_loss
+    from .losses import lidf_loss
     opt = opt or LidfOptions()
-    if opt.intersect_pos_type not in ("abs", "rel"):
-        raise NotImplementedError("intersect_pos_type %s" % opt.intersect_pos_type)
-    _lib.require_cuda(batch["rgb"], batch["xyz"], full_rgb_feat, names=["batch['rgb']", "batch['xyz']", "full_rgb_feat"])
-    dd = prepare_data(batch, opt, exp_type="train")
-    get_valid_points(dd, opt, valid_idx)
-    bs = dd["bs"]
-    if dd["valid_xyz"].shape[0] == 0:   # (no valid point at all: no occupied voxel)
+    ok, dd = _train_geometry(batch, full_rgb_feat, opt, valid_idx)
+    if not ok:
         return False, dd, {}
-    occ = Q.get_occ_vox_bound(dd["valid_xyz"].contiguous(), dd["valid_bid"].to(torch.int32).contiguous(),
-                              bs, opt.xmin, opt.xmax, opt.grid_res)
-    dd.update(occ)
-    V = occ["voxel_bound"].shape[0]
-    if V == 0:
-        return False, dd, {}
-    miss = Q.get_miss_ray(dd["corrupt_mask"], dd["fx"], dd["fy"], dd["cx"], dd["cy"])
-    dd.update(Q.sample_miss_rays(miss, bs, opt.miss_sample_num))
-    if dd["total_miss_sample_num"] == 0:
-        return False, dd, {}
-    vox_bid = occ["occ_vox_bid"].to(torch.int32).contiguous()
-    grid = dict(voxel_coord=occ["voxel_coord"], grid_dims=occ["grid_dims"], batch=bs) if V > 256 * bs else {}
-    pair_off, pair_ray, pair_vox, pair_t = Q.compute_ray_aabb(
-        dd["miss_ray_dir"], occ["voxel_bound"], dd["ray_bid"], vox_bid, **grid)
-    dd.update({"pair_off": pair_off, "pair_ray": pair_ray, "pair_vox": pair_vox, "pair_t": pair_t,
-               "voxel_bid": vox_bid})
-    if pair_ray.shape[0] == 0:
-        return False, dd, {}
-    compute_gt(dd)
-    valid_v_rgb = dd["valid_rgb"].index_select(0, occ["valid_v_pid"])
-    dd["pnet_inp"] = torch.cat((occ["valid_v_rel_coord"], valid_v_rgb), -1)
-    dd["occ_voxel_feat"] = pnet_model(dd["pnet_inp"], occ["revidx"], n_vox=V)
-    dd["full_rgb_feat"] = full_rgb_feat
-    vox_center = None
-    if opt.intersect_pos_type == "rel":
-        vb = occ["voxel_bound"]
-        vox_center = ((vb[:, :3] + vb[:, 3:]) / 2.0).contiguous()
+    dd["occ_voxel_feat"] = pnet_model(dd["pnet_inp"], dd["revidx"], n_vox=dd["voxel_bound"].shape[0])
     dd.update(Q.lidf_query_train(
-        dd["miss_ray_dir"], dd["ray_pix"], dd["ray_bid"], pair_off, pair_ray, pair_vox, pair_t, full_rgb_feat,
+        dd["miss_ray_dir"], dd["ray_pix"], dd["ray_bid"], dd["pair_off"], dd["pair_ray"], dd["pair_vox"],
+        dd["pair_t"], full_rgb_feat,
         dd["occ_voxel_feat"], prob_dec, offset_dec, multires=opt.multires, multires_views=opt.multires_views,
-        roi_inp_bbox=opt.roi_inp_bbox, offset_range=opt.offset_range, part_size=occ["part_size"],
-        vox_center=vox_center, pos_rel=opt.intersect_pos_type == "rel",
+        roi_inp_bbox=opt.roi_inp_bbox, offset_range=opt.offset_range, part_size=dd["part_size"],
+        vox_center=_vox_center(dd, opt), pos_rel=opt.intersect_pos_type == "rel",
         max_pair_id=dd["gt_max_pair_id"] if epoch < opt.maxpool_label_epo else None))
     return True, dd, lidf_loss(dd, loss_opt, "train", epoch)
+
+
+def refine_forward_train(dd, pnet_model_refine, offset_dec_refine, opt=None, loss_opt=None, epoch=0):
+    """RefineNet.forward('train', epoch, data_dict) (models/pipeline.py:1032-1041) on the data_dict of the frozen
+    stage 1 (train_refine_step's, or lidf_forward_train's): returns (data_dict, loss_dict_refine).
+    opt.refine_forward_times x get_pred_refine under autograd (query.lidf_refine_train: one node, two library
+    calls), the perturbation of the first iteration drawn with the reference's own np.random calls — only when
+    opt.refine_perturb is set, as the reference's `and` short-circuits — then losses.refine_loss. Adds
+    pred_pos_refine [R,3], end_voxel_id [R] and refine_perturb_noise (the scalar drawn, None for none) to data_dict;
+    loss_dict_refine['loss_net'].backward() reaches every parameter of the two modules. The end voxels go through
+    the cell table when data_dict holds get_occ_vox_bound's grid."""
+    from .losses import refine_loss
+    opt = opt or LidfOptions()
+    noise = Q.refine_perturb_noise(opt.refine_perturb_prob) if opt.refine_perturb else None
+    valid_inp = dd["pnet_inp"]                     # cat(valid_v_rel_coord, valid_v_rgb), pipeline.py:1000
+    if opt.refine_pnet_pos_type == "abs":          # :1001-1003
+        valid_inp = torch.cat((dd["valid_xyz"].index_select(0, dd["valid_v_pid"]), dd["pnet_inp"][:, 3:]), -1)
+    pos, end_voxel = Q.lidf_refine_train(
+        dd["miss_ray_dir"], dd["ray_pix"], dd["ray_bid"], dd["ray_flat"], dd["pred_pos"], dd["max_pair_id"],
+        dd["pair_vox"], dd["voxel_bound"], dd["voxel_bid"], dd["rgb_img"], dd["full_rgb_feat"],
+        valid_inp.contiguous(), dd["revidx"].to(torch.int32).contiguous(), pnet_model_refine, offset_dec_refine,
+        forward_times=opt.refine_forward_times, multires=opt.multires, multires_views=opt.multires_views,
+        roi_inp_bbox=opt.roi_inp_bbox, offset_range=opt.refine_offset_range,
+        pos_rel=opt.refine_intersect_pos_type == "rel", pnet_pos_rel=opt.refine_pnet_pos_type == "rel",
+        perturb_noise=noise,
+        grid=dd if all(k in dd for k in ("voxel_coord", "grid_dims", "xmin", "part_size")) else None)
+    dd["pred_pos_refine"], dd["end_voxel_id"] = pos, end_voxel
+    dd["refine_perturb_noise"] = noise
+    return dd, refine_loss(dd, loss_opt, "train", epoch)
+
+
+def train_refine_step(batch, full_rgb_feat, pnet_model, prob_dec, offset_dec, pnet_model_refine, offset_dec_refine,
+                      opt=None, loss_opt=None, epoch=0, valid_idx=None):
+    """The two forward calls of a stage-2 training iteration (trainers/train_refine.py:374-393): the frozen
+    LIDF.forward(batch, 'train', epoch), then RefineNet.forward('train', epoch, data_dict). Returns (success,
+    data_dict, loss_dict, loss_dict_refine); loss_dict is stage 1's (the trainer logs its prob_loss and acc), and
+    loss_dict_refine['loss_net'].backward() is the step's backward. success False = one of stage 1's three early
+    exits: the result is then (False, data_dict, {}, {}).
+
+    Stage 1 is frozen (train_refine.py:71-73): it runs under torch.no_grad() whatever the requires_grad flags of
+    full_rgb_feat, pnet_model, prob_dec and offset_dec say, and never receives a gradient. It takes the train
+    flavour of the geometry (the corrupt_mask rays, the opt.miss_sample_num window, compute_gt) and then the
+    inference query (query.lidf_query) and losses.lidf_loss — nothing of it is differentiated. While
+    epoch < opt.maxpool_label_epo the pair of every ray is selected by the labels, as in the reference (not the
+    shipped stage-2 configuration: train_refine*.yaml set maxpool_label_epo 0; pass LidfOptions(maxpool_label_epo=0)).
+    loss_opt serves both losses, as the reference's one `loss` section does (train_refine.yaml: prob_w 0).
+    The DDP success-flag handshake and the optimiser stay with the trainer."""
+    from .losses import lidf_loss
+    opt = opt or LidfOptions()
+    with torch.no_grad():
+        ok, dd = _train_geometry(batch, full_rgb_feat.detach(), opt, valid_idx)
+        if not ok:
+            return False, dd, {}, {}
+        dd["occ_voxel_feat"] = pnet_model(dd["pnet_inp"], dd["revidx"], n_vox=dd["voxel_bound"].shape[0])
+        dd.update(Q.lidf_query(
+            dd["miss_ray_dir"], dd["ray_pix"], dd["ray_bid"], dd["pair_off"], dd["pair_ray"], dd["pair_vox"],
+            dd["pair_t"], dd["full_rgb_feat"], dd["occ_voxel_feat"], prob_dec, offset_dec, multires=opt.multires,
+            multires_views=opt.multires_views, roi_inp_bbox=opt.roi_inp_bbox, roi_out_bbox=opt.roi_out_bbox,
+            offset_range=opt.offset_range, part_size=dd["part_size"], vox_center=_vox_center(dd, opt),
+            pos_rel=opt.intersect_pos_type == "rel", want_rayfeat=False))
+        if epoch < opt.maxpool_label_epo:   # the label-selected pair of every ray (models/pipeline.py:444-454)
+            dd["max_pair_id"] = dd["gt_max_pair_id"]
+            dd["pred_pos"] = torch.cat((dd["pair_pred_pos"], dd["pair_pred_pos"].new_zeros((1, 3))), 0)[dd["max_pair_id"]]
+        loss_dict = lidf_loss(dd, loss_opt, "train", epoch)
+    dd, loss_dict_refine = refine_forward_train(dd, pnet_model_refine, offset_dec_refine, opt, loss_opt, epoch)
+    return True, dd, loss_dict, loss_dict_refine
 
 
 def refine_forward(dd, pnet_model_refine, offset_dec_refine, opt=None, precision="f32", cell_lookup=True):
@@ -238,7 +324,8 @@ def refine_forward(dd, pnet_model_refine, offset_dec_refine, opt=None, precision
     cell_lookup: the end voxel of a ray through the cell table of get_occ_vox_bound's grid (the same ids as
     the reference's every-ray x every-voxel pcl_aabb, lidf_refine(grid=)); False tests every voxel."""
     opt = opt or LidfOptions()
-    Q._refuse_autograd("pipeline.refine_forward", "query.lidf_refine_train (stage-2 training step)",
+    Q._refuse_autograd("pipeline.refine_forward", "pipeline.refine_forward_train (the stage-2 training step; its "
+                       "differentiable core is query.lidf_refine_train)",
                        (("pred_pos", dd.get("pred_pos")),),
                        (("pnet_model_refine", pnet_model_refine), ("offset_dec_refine", offset_dec_refine)))
     bs, h, w = dd["bs"], dd["h"], dd["w"]

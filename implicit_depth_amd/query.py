@@ -463,8 +463,8 @@ def lidf_refine(ray_dir, ray_pix, ray_bid, ray_flat, pred_pos, max_pair_id, pair
     testing every ray against every voxel (LidfRefineArgs.voxel_coord), O(R) instead of O(R V).
     Returns pred_pos_refine [R,3] and the last iteration's end_voxel_id [R] i32."""
     from .pointnet import pointnet_struct
-    _refuse_autograd("lidf_refine", "the modules on their own (PointNet2Stage, IEF and get_embedder are "
-                     "differentiable; the fused stage-2 call has no backward)",
+    _refuse_autograd("lidf_refine", "pipeline.refine_forward_train (the stage-2 training step; its differentiable "
+                     "core is lidf_refine_train)",
                      (("pred_pos", pred_pos), ("feat_grid", feat_grid), ("valid_inp", valid_inp),
                       ("rayfeat", rayfeat)), (("pnet_model", pnet_model), ("offset_dec", offset_dec)))
     ts = [ray_dir, ray_pix, ray_bid, ray_flat, pred_pos, max_pair_id, pair_vox, voxel_bound,

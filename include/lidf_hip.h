@@ -36,7 +36,7 @@ enum lidf_status {
 /* ABI version, bumped on any signature or struct-layout change and on added entry points. lidf_version() returns the value the
  * library was BUILT with; a binding compiled / written against this header must refuse a library that
  * answers anything else (implicit_depth_amd/_lib.py and csrc/lidf_torch_ext.cpp do, at load). */
-#define LIDF_ABI_VERSION 13
+#define LIDF_ABI_VERSION 14
 int lidf_version(void);
 /* Static string for a status code. */
 const char* lidf_strerror(int status);
@@ -994,6 +994,48 @@ typedef struct LidfLossArgs {
 size_t lidf_stage1_loss_workspace_bytes(int64_t n_rays);
 int lidf_stage1_loss_f32(const LidfLossArgs* args, lidf_stream_t stream);
 int lidf_stage1_loss_backward_f32(const LidfLossArgs* args, lidf_stream_t stream);
+
+/* ---- Stage-2 training step: the loss of the refinement network (ABI 14) --------------------------
+ * The training part of RefineNet.compute_loss (models/pipeline.py:760-840) on the sampled rays. It has
+ * no ray-termination term and no acc, and reads no pair list: a ray without pairs is an ordinary ray.
+ * Forward: loss[6] = {pos_loss, surf_norm_loss, smooth_loss, loss_net, err, angle_err} (the order of
+ * loss_dict, :898-905; loss_net = pos_w pos (+ surf_norm_w surf) (+ smooth_w smooth), the two gates as
+ * in LidfLossArgs) and the unreduced per-ray terms pos_unreduced / surf_norm_dist / dx_dist / dy_dist
+ * [R] for hard-negative mining. The normals are those of the frame xyz (the train flavour, :775-777)
+ * with the sampled pixels replaced by gt_pos / pred_pos_refine, at the sampled pixels only;
+ * pred_surf_norm_img [B,3,h,w] (data_dict['pred_surf_norm_img_refine'], :894) is written when non-NULL.
+ * Backward: g_pred_pos [R,3] for the device scalar *g_loss_net; w_pos / w_surf / w_dx / w_dy as in
+ * LidfLossArgs. The sums are those of the stage-1 loss (double partials per 256 rays, one final block
+ * in a fixed order, no float atomics): bit-identical from run to run.                                */
+typedef struct LidfRefineLossArgs {
+    int64_t n_rays;
+    int32_t batch, height, width;
+    const float* xyz;               /* [B, h*w, 3] */
+    const int32_t* ray_bid;         /* [R] */
+    const int32_t* ray_flat;        /* [R] */
+    const int32_t* pix2ray;         /* [B*h*w], lidf_pair_labels_f32 */
+    const float* gt_pos;            /* [R,3] */
+    const float* pred_pos_refine;   /* [R,3] */
+    float pos_w, surf_norm_w, smooth_w;
+    int32_t surf_norm_on, smooth_on;
+    float* loss;                    /* [6] */
+    float* pos_unreduced;           /* [R] */
+    float* surf_norm_dist;          /* [R] */
+    float* dx_dist;                 /* [R] */
+    float* dy_dist;                 /* [R] */
+    float* pred_surf_norm_img;      /* [B,3,h,w] or NULL */
+    void* workspace;                /* forward only */
+    size_t workspace_bytes;
+    const float* w_pos;             /* backward: [R] or NULL */
+    const float* w_surf;            /* [R] or NULL */
+    const float* w_dx;              /* [R] or NULL */
+    const float* w_dy;              /* [R] or NULL */
+    const float* g_loss_net;        /* [1] */
+    float* g_pred_pos;              /* [R,3] */
+} LidfRefineLossArgs;
+size_t lidf_refine_loss_workspace_bytes(int64_t n_rays);
+int lidf_refine_loss_f32(const LidfRefineLossArgs* args, lidf_stream_t stream);
+int lidf_refine_loss_backward_f32(const LidfRefineLossArgs* args, lidf_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,10 @@ In one process, on the 8 x 240 x 320 synthetic batch with the shipped window of 
 The two variants alternate inside the timed loop (device events around each, after a warm-up of both), so that
 clock state and other tenants of the machine hit both alike. Then the whole pipeline.lidf_forward_train step
 (forward + backward) is timed the same way. Launch counts come from torch's profiler on one extra step of each
-(kernel and memset records), taken after the timed loops. Prints one JSON line; --out writes it to a file too.
+(kernel and memset records), taken after the timed loops. The stage-2 leg ("stage2" in the result) does the same for
+losses.refine_loss against losses.refine_loss_composite on the pred_pos_refine of one pipeline.train_refine_step, and
+for that whole step (frozen stage 1 + RefineNet forward + backward). Prints one JSON line; --out writes it to a file
+too.
 """
 import argparse
 import json
@@ -130,6 +133,52 @@ def main():
         except Exception as e:   # the count is a by-product: a profiler problem must not lose the times
             return "not measured (%s)" % type(e).__name__
 
+    # ---- stage 2: RefineNet's loss fused against the composite, and the whole stage-2 step
+    from implicit_depth_amd import refine_loss, refine_loss_composite, train_refine_step
+    pnet_r = make_pointnet(orc.init_pointnet(4, 1.5), dev).train()
+    off_r = make_module("IEF", init_decoder_params("IEF", 334, 9, 5.0), 334, dev).train()
+    ropt, rlopt = LidfOptions(maxpool_label_epo=0), LidfLossOptions(prob_w=0.0)   # train_refine.yaml
+
+    def refine_step():
+        for m in (pnet_r, off_r):
+            for p in m.parameters():
+                p.grad = None
+        np.random.seed(77)
+        ok, d2, _, l2 = train_refine_step(batch, feat, *mods, pnet_r, off_r, opt=ropt, loss_opt=rlopt, epoch=0)
+        assert ok
+        l2["loss_net"].backward()
+        return d2, l2
+
+    dd2, _ = refine_step()
+    base2 = {k: dd2[k] for k in ("bs", "h", "w", "xyz_flat", "ray_bid", "ray_flat", "miss_bid", "miss_flat_img_id",
+                                 "gt_pos", "pix2ray")}
+    pos_r = dd2["pred_pos_refine"].detach().clone()
+
+    def stage2(fn):
+        def run():
+            d = dict(base2)
+            d["pred_pos_refine"] = pos_r.requires_grad_(True)
+            pos_r.grad = None
+            out = fn(d, rlopt, "train", 0)
+            out["loss_net"].backward()
+            return out, pos_r.grad
+        return run
+    fused2, composite2 = stage2(refine_loss), stage2(refine_loss_composite)
+    of2, g2f = fused2()
+    g2f = g2f.clone()
+    oc2, g2c = composite2()
+    same2 = {k: [float(of2[k]), float(oc2[k])] for k in of2}
+    t_fused2, t_comp2 = timed((fused2, composite2), args.reps)
+    (t_step2,) = timed((refine_step,), max(args.reps // 3, 5))
+    res2 = {
+        "what": "stage-2 training step: RefineNet's loss, fused (lidf_loss.hip) vs composite (torch ops)",
+        "rays": dd2["total_miss_sample_num"], "fused_loss_fwd_bwd": t_fused2, "composite_loss_fwd_bwd": t_comp2,
+        "whole_step_fwd_bwd": t_step2, "speedup_median": t_comp2["median_ms"] / t_fused2["median_ms"],
+        "launches": {"fused": launches(fused2), "composite": launches(composite2), "whole_step": launches(refine_step)},
+        "loss_dict_fused_vs_composite": same2,
+        "grad_rel_diff_pred_pos_refine": float((g2f - g2c).abs().max() / g2c.abs().max()),
+    }
+
     res = {
         "what": "stage-1 training step: ground truth + loss, fused (lidf_loss.hip) vs composite (dense pcl_aabb + torch ops)",
         "device": torch.cuda.get_device_name(0), "clock": "device events around each call, variants alternating",
@@ -138,6 +187,7 @@ def main():
         "speedup_median": t_comp["median_ms"] / t_fused["median_ms"],
         "launches": {"fused": launches(fused), "composite": launches(composite), "whole_step": launches(whole_step)},
         "loss_dict_fused_vs_composite": same, "grad_rel_diff_pred_pos_logit": grad_diff,
+        "stage2": res2,
     }
     line = json.dumps(res)
     print(line)
