@@ -209,6 +209,8 @@ SIGNATURES = {
     "lidf_miss_ray_workspace_bytes": (_SZ, [_I64]),
     "lidf_miss_ray_count": (C.c_int, [_P, _I, _I64, _P, _P, _SZ, _P]),
     "lidf_miss_ray_fill_f32": (C.c_int, [_P, _I, _P, _I, _I, _I, _P, _SZ, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "lidf_sample_valid_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "lidf_sample_valid_points": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "lidf_ray_aabb_dense_f32": (C.c_int, [_P, _P, _P, _P, _I64, _I64, _P, _P, _P]),
     "lidf_ray_aabb_count_f32": (C.c_int, [_P, _P, _P, _P, _I64, _I64, _P, _P]),
     "lidf_ray_aabb_fill_f32": (C.c_int, [_P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P, _P]),
@@ -398,7 +400,13 @@ def lib():
                 "of include/lidf_hip.h — rebuild it: `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(or implicit_depth_amd/csrc/build.py --force)" % (LIB_PATH, have, ABI))
         for name, (res, args) in SIGNATURES.items():
-            fn = getattr(handle, name)
+            try:
+                fn = getattr(handle, name)
+            except AttributeError:   # entry points added without an ABI bump (lidf_hip.h, next to the version)
+                raise RuntimeError(
+                    "%s answers ABI %d but lacks %s — it was built before that entry point was added; rebuild the "
+                    "library: `python -c 'import __graft_entry__ as g; g.build()'` (or implicit_depth_amd/csrc/"
+                    "build.py --force)" % (LIB_PATH, ABI, name)) from None
             fn.restype = res
             fn.argtypes = args
         _lib = handle

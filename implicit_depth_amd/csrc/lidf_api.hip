@@ -724,6 +724,28 @@ LIDF_API int lidf_miss_ray_fill_f32(const void* mask, int mask_dtype, const floa
     return LIDF_OK;
 }
 
+// ---- sample_valid_points (mask -> bs * sample_num valid points, block-sampled) -------------------
+LIDF_API size_t lidf_sample_valid_workspace_bytes(int batch, int height, int width) {
+    if (batch < 1 || height < 0 || width < 0) return 0;
+    return lidf_sample_valid_ws_bytes(batch, height, width);
+}
+
+LIDF_API int lidf_sample_valid_points(const void* mask, int mask_dtype, int batch, int height, int width,
+                                        int sample_num, const uint64_t* rng_state, int32_t* bid, int32_t* flat,
+                                        int64_t* idx, int32_t* valid_cnt, void* workspace, size_t workspace_bytes,
+                                        lidf_stream_t stream) {
+    if (batch < 1 || height < 8 || width < 8 || sample_num < 1) return LIDF_ERR_BAD_ARG;
+    if (height % 8 || width % 8) return LIDF_ERR_BAD_ARG;   // point_utils.py:81-82
+    if (mask_dtype < LIDF_MASK_F32 || mask_dtype > LIDF_MASK_I64) return LIDF_ERR_BAD_ARG;
+    if (!mask || !rng_state || !bid || !flat || !valid_cnt || !workspace) return LIDF_ERR_BAD_ARG;
+    if ((int64_t)batch * height * width > 0x7fffffffLL || batch > 65535) return LIDF_ERR_UNSUPPORTED;   // (grid.y)
+    if (workspace_bytes < lidf_sample_valid_ws_bytes(batch, height, width)) return LIDF_ERR_BAD_ARG;
+    CHECK_HIP(lidf_launch_sample_valid(mask, mask_dtype, batch, height, width, sample_num,
+                                       (const unsigned long long*)rng_state, bid, flat, (long long*)idx, valid_cnt,
+                                       workspace, (hipStream_t)stream));
+    return LIDF_OK;
+}
+
 static int check_box_args(const void* a, const void* b, const void* c, const void* d, int64_t n,
                           int64_t v) {
     if (n < 0 || v < 0) return LIDF_ERR_BAD_ARG;

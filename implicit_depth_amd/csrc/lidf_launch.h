@@ -283,6 +283,13 @@ hipError_t lidf_launch_stage1_loss_backward(const LossArgs& a, hipStream_t st);
 hipError_t lidf_launch_refine_loss(const LossArgs& a, float* pred_img, hipStream_t st);
 hipError_t lidf_launch_refine_loss_backward(const LossArgs& a, hipStream_t st);
 
+// ---- lidf_sample.hip
+size_t lidf_sample_valid_masks_bytes(int B, int H, int W);
+size_t lidf_sample_valid_ws_bytes(int B, int H, int W);
+hipError_t lidf_launch_sample_valid(const void* mask, int dtype, int B, int H, int W, int n,
+                                    const unsigned long long* rng, int* bid, int* flat, long long* idx,
+                                    int* valid_cnt, void* ws, hipStream_t st);
+
 // ---- lidf_ief16.hip
 hipError_t lidf_launch_ief16(const Ief16Args& a, int cus, hipStream_t st);
 

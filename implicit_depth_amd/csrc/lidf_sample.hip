@@ -1,0 +1,233 @@
+// lidf_sample.hip — the random block sampler of the valid points: utils/point_utils.py:79-125
+// sample_valid_points (what LIDF.get_valid_points keeps when grid.valid_sample_num != -1,
+// models/pipeline.py:137-160), on the device and without a size read.
+//
+// "Block order" is the reference's: 8x8 blocks in row-major order, pixels in row-major order inside a
+// block. One wave is one block: __ballot over the 64 pixels is the block's occupancy mask, its popcount
+// the block's number of valid pixels. Three small launches on the caller's stream:
+//   1  masks[blk] = ballot of block blk, the whole batch in one grid   (the only read of the mask: h*w elements
+//                                                                       per image)
+//   2  prefix[blk] = number of valid pixels in blocks < blk: one workgroup per image, chunks of SAMPLE_THREADS
+//      blocks with a carry; prefix[nblk] = valid_cnt
+//   3  slot i -> block-order rank -> pixel, one thread per slot: a binary search over prefix, then the k-th set bit
+//      of one mask
+// masks and prefix live in the caller's workspace (any block count; LDS does not grow with the image).
+// No compacted pixel list exists at any point. (All three as phases of ONE launch with one workgroup per image
+// was the first version: 73 us at 240 x 320, n = 10000 — ten slots per thread, each an 11-step dependent search —
+// against the launches below)
+//
+// Per image, cnt valid pixels, n = sample_num (semantics of point_utils.py:99-116):
+//   dense  (cnt >= n): step = cnt / n, inum = cnt / step; slot i takes interval j_i = perm(i), perm a keyed
+//          bijection of [0, inum), and rank j_i * step + off_i with off_i uniform in [0, step)
+//   sparse (0 < cnt < n): slots 0 .. cnt-1 are every valid point in block order; slot i >= cnt takes pool entry
+//          q = perm(i - cnt), perm a keyed bijection of [0, M), M = (ceil(n / cnt) - 1) * cnt, rank q mod cnt
+//   empty  (cnt == 0): (b, 0) in every slot, valid_cnt[b] = 0 (the reference's assertion; the callers that
+//          read sizes raise)
+// Randomness is counter-based and integer-only: Philox4x32-10 keyed by the 64-bit seed, counter words
+// (call counter lo, hi, image, slot | purpose); both come from device memory (rng_state), so a captured
+// graph draws fresh samples on every replay once the caller advances the counter. perm is a balanced
+// Feistel network of SAMPLE_ROUNDS rounds on 2 * ceil(bits / 2) bits with cycle walking: evaluating it at
+// 0 .. n-1 gives n distinct values in random order at O(1) per slot. Uniform integers are
+// (u32 * range) >> 32. tests/sampler_ref.py restates all of it in numpy, bit for bit.
+#include "lidf_launch.h"
+
+#define SAMPLE_THREADS 1024
+#define SAMPLE_WAVES (SAMPLE_THREADS / 64)
+#define SAMPLE_BLOCK_WAVES 4      // 8x8 blocks per workgroup of the ballot launch
+#define SAMPLE_SLOT_THREADS 256   // slots per workgroup of the sampling launch
+#define SAMPLE_ROUNDS 6
+#define SAMPLE_KEY_WORD 0x80000000u   // counter word 3 of the per-image key draws (slots are < 2^31)
+
+__device__ __forceinline__ bool sample_mask_nonzero(const void* mask, int dtype, long long i) {
+    switch (dtype) {   // as lidf_miss_ray_count: NaN != 0 is true
+        case 0: return ((const float*)mask)[i] != 0.f;
+        case 1: return ((const unsigned char*)mask)[i] != 0;
+        case 2: return ((const int*)mask)[i] != 0;
+        default: return ((const long long*)mask)[i] != 0;
+    }
+}
+
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0,
+                                              unsigned k1, unsigned out[4]) {
+    for (int r = 0; r < 10; ++r) {
+        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0;
+        c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1;
+        c3 = lo0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+__device__ __forceinline__ unsigned sample_mix(unsigned v) {
+    v ^= v >> 16; v *= 0x7FEB352Du;
+    v ^= v >> 15; v *= 0x846CA68Bu;
+    v ^= v >> 16;
+    return v;
+}
+
+// keyed bijection of [0, N): Feistel on 2h bits (2^(2h) < 4N for N > 1), walked until it lands below N
+__device__ __forceinline__ unsigned sample_perm(unsigned x, unsigned N, int h, const unsigned* key) {
+    const unsigned m = (1u << h) - 1u;
+    do {
+        unsigned L = x >> h, R = x & m;
+        for (int r = 0; r < SAMPLE_ROUNDS; ++r) {
+            const unsigned t = L ^ (sample_mix(R + key[r]) & m);
+            L = R;
+            R = t;
+        }
+        x = (L << h) | R;
+    } while (x >= N);
+    return x;
+}
+
+// position of the k-th (0-based) set bit of m; k < popcount(m)
+__device__ __forceinline__ int sample_select_bit(unsigned long long m, int k) {
+    int pos = 0;
+    for (int wd = 32; wd >= 1; wd >>= 1) {
+        const unsigned long long low = m & ((1ull << wd) - 1ull);
+        const int c = __popcll(low);
+        if (k >= c) {
+            k -= c;
+            pos += wd;
+            m >>= wd;
+        } else {
+            m = low;
+        }
+    }
+    return pos;
+}
+
+// 1: one wave, one 8x8 block; SAMPLE_BLOCK_WAVES blocks per workgroup, the whole batch in one grid
+__global__ __launch_bounds__(64 * SAMPLE_BLOCK_WAVES) void lidf_sample_blocks_kernel(
+    const void* __restrict__ mask, int dtype, int H, int W, unsigned long long* __restrict__ masks) {
+    const int b = blockIdx.y, lane = threadIdx.x & 63;
+    const int bw = W >> 3, nblk = (H >> 3) * bw;
+    const int blk = blockIdx.x * SAMPLE_BLOCK_WAVES + (threadIdx.x >> 6);
+    if (blk >= nblk) return;   // (uniform per wave)
+    const int by = blk / bw, bx = blk - by * bw;
+    const long long pix = (long long)b * H * W + (long long)(by * 8 + (lane >> 3)) * W + bx * 8 + (lane & 7);
+    const unsigned long long m = __ballot(sample_mask_nonzero(mask, dtype, pix));
+    if (lane == 0) masks[(size_t)b * nblk + blk] = m;
+}
+
+// 2: exclusive scan of the block counts of one image per workgroup, in chunks of SAMPLE_THREADS blocks
+__global__ __launch_bounds__(SAMPLE_THREADS) void lidf_sample_scan_kernel(
+    const unsigned long long* __restrict__ masks, int nblk, int* __restrict__ prefix, int* __restrict__ valid_cnt) {
+    __shared__ int s_wave[SAMPLE_WAVES];
+    __shared__ int s_carry;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned long long* mk = masks + (size_t)b * nblk;
+    int* pre = prefix + (size_t)b * (nblk + 1);
+    if (tid == 0) {
+        s_carry = 0;
+        pre[0] = 0;
+    }
+    __syncthreads();
+    for (int base = 0; base < nblk; base += SAMPLE_THREADS) {
+        const int blk = base + tid;
+        int inc = blk < nblk ? __popcll(mk[blk]) : 0;
+        for (int s = 1; s < 64; s <<= 1) {
+            const int o = __shfl_up(inc, s);
+            if (lane >= s) inc += o;
+        }
+        if (lane == 63) s_wave[wave] = inc;
+        __syncthreads();
+        int upto = s_carry;
+        for (int k = 0; k < wave; ++k) upto += s_wave[k];
+        upto += inc;
+        if (blk < nblk) pre[blk + 1] = upto;
+        __syncthreads();
+        if (tid == SAMPLE_THREADS - 1) s_carry = upto;
+        __syncthreads();
+    }
+    if (tid == 0) valid_cnt[b] = s_carry;
+}
+
+// 3: one thread, one slot
+__global__ __launch_bounds__(SAMPLE_SLOT_THREADS) void lidf_sample_slots_kernel(
+    int H, int W, int n, const unsigned long long* __restrict__ rng, int* __restrict__ bid, int* __restrict__ flat,
+    long long* __restrict__ idx, const unsigned long long* __restrict__ masks, const int* __restrict__ prefix) {
+    const int b = blockIdx.y, i = blockIdx.x * SAMPLE_SLOT_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const int bw = W >> 3, nblk = (H >> 3) * bw;
+    const unsigned long long* mk = masks + (size_t)b * nblk;
+    const int* pre = prefix + (size_t)b * (nblk + 1);
+    const int cnt = pre[nblk];
+    const long long s = (long long)b * n + i;
+    int f = 0;
+    if (cnt > 0) {
+        const unsigned long long seed = rng[0], ctr = rng[1];
+        const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+        const unsigned c0 = (unsigned)ctr, c1 = (unsigned)(ctr >> 32);
+        const bool dense = cnt >= n;
+        const unsigned step = dense ? (unsigned)(cnt / n) : 1u;
+        const unsigned N = dense ? (unsigned)cnt / step : (unsigned)((n + cnt - 1) / cnt - 1) * (unsigned)cnt;
+        const int bits = N > 1 ? 32 - __clz((int)(N - 1)) : 0;
+        const int h = (bits + 1) >> 1;
+        unsigned rank;
+        if (dense || i >= cnt) {
+            unsigned key[8];
+            philox4x32_10(c0, c1, (unsigned)b, SAMPLE_KEY_WORD, k0, k1, key);
+            philox4x32_10(c0, c1, (unsigned)b, SAMPLE_KEY_WORD + 1u, k0, k1, key + 4);
+            if (dense) {
+                const unsigned j = sample_perm((unsigned)i, N, h, key);
+                unsigned off = 0;
+                if (step > 1) {
+                    unsigned r[4];
+                    philox4x32_10(c0, c1, (unsigned)b, (unsigned)i, k0, k1, r);
+                    off = __umulhi(r[0], step);
+                }
+                rank = j * step + off;
+            } else {
+                rank = sample_perm((unsigned)(i - cnt), N, h, key) % (unsigned)cnt;
+            }
+        } else {
+            rank = (unsigned)i;
+        }
+        int lo = 0, hi = nblk;   // the block with prefix[blk] <= rank < prefix[blk + 1]
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if ((unsigned)pre[mid] <= rank) lo = mid; else hi = mid;
+        }
+        const int p = sample_select_bit(mk[lo], (int)rank - pre[lo]);
+        const int by = lo / bw, bx = lo - by * bw;
+        f = (by * 8 + (p >> 3)) * W + bx * 8 + (p & 7);
+    }
+    bid[s] = b;
+    flat[s] = f;
+    if (idx) {
+        idx[2 * s] = b;
+        idx[2 * s + 1] = f;
+    }
+}
+
+extern "C" size_t lidf_sample_valid_masks_bytes(int B, int H, int W) {
+    const size_t nblk = (size_t)(H / 8) * (size_t)(W / 8);
+    return ((size_t)B * nblk * 8 + 255) / 256 * 256;
+}
+
+extern "C" size_t lidf_sample_valid_ws_bytes(int B, int H, int W) {
+    const size_t nblk = (size_t)(H / 8) * (size_t)(W / 8);
+    return lidf_sample_valid_masks_bytes(B, H, W) + ((size_t)B * (nblk + 1) * 4 + 255) / 256 * 256;
+}
+
+extern "C" hipError_t lidf_launch_sample_valid(const void* mask, int dtype, int B, int H, int W, int n,
+                                               const unsigned long long* rng, int* bid, int* flat, long long* idx,
+                                               int* valid_cnt, void* ws, hipStream_t st) {
+    unsigned long long* masks = (unsigned long long*)ws;
+    int* prefix = (int*)((char*)ws + lidf_sample_valid_masks_bytes(B, H, W));
+    const int nblk = (H / 8) * (W / 8);
+    hipLaunchKernelGGL(lidf_sample_blocks_kernel, dim3((unsigned)((nblk + SAMPLE_BLOCK_WAVES - 1) / SAMPLE_BLOCK_WAVES),
+                                                       (unsigned)B),
+                       dim3(64 * SAMPLE_BLOCK_WAVES), 0, st, mask, dtype, H, W, masks);
+    hipLaunchKernelGGL(lidf_sample_scan_kernel, dim3((unsigned)B), dim3(SAMPLE_THREADS), 0, st, masks, nblk, prefix,
+                       valid_cnt);
+    hipLaunchKernelGGL(lidf_sample_slots_kernel, dim3((unsigned)((n + SAMPLE_SLOT_THREADS - 1) / SAMPLE_SLOT_THREADS),
+                                                      (unsigned)B),
+                       dim3(SAMPLE_SLOT_THREADS), 0, st, H, W, n, rng, bid, flat, idx, masks, prefix);
+    return hipGetLastError();
+}

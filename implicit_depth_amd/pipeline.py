@@ -37,6 +37,10 @@ class LidfOptions:
         self.grid_res = 8
         self.xmin, self.xmax = (-1.0, -1.0, 0.0), (1.0, 1.0, 2.0)   # utils/constants.py:15-16
         self.valid_stride = None               # None = every valid point (valid_sample_num == -1)
+        # grid.valid_sample_num (10000 in every shipped config): None or -1 = every valid point; n > 0 = the random
+        # block sample of n valid points per image (query.sample_valid_points) wherever no valid_idx is passed
+        self.valid_sample_num = None
+        self.sampler_state = None              # query.sampler_state(seed, device); None = the device's default state
         # training (train_lidf.yaml): rays per image of the random window, label-selected pairs before this epoch
         self.miss_sample_num = 20000
         self.maxpool_label_epo = 6
@@ -53,6 +57,19 @@ class LidfOptions:
             if not hasattr(self, k):
                 raise TypeError("unknown option %s" % k)
             setattr(self, k, v)
+        self.sample_num()
+
+    def sample_num(self):
+        """valid_sample_num as the sampler takes it: n > 0, or 0 for every valid point (None / -1)."""
+        n = self.valid_sample_num
+        if n is None or n == -1:
+            return 0
+        if int(n) != n or n < 1:
+            raise ValueError("valid_sample_num must be None, -1 (every valid point) or a positive count, not %r" % (n,))
+        if self.valid_stride and self.valid_stride > 1:
+            raise ValueError("valid_sample_num and valid_stride are two different selections of the valid points: "
+                             "set one of them")
+        return int(n)
 
 
 def prepare_data(batch, opt, pred_mask=None, exp_type="test"):
@@ -86,9 +103,13 @@ def prepare_data(batch, opt, pred_mask=None, exp_type="test"):
 
 def get_valid_points(dd, opt, valid_idx=None):
     """LIDF.get_valid_points (models/pipeline.py:135-160). valid_idx [Nv,2] (image, flat pixel)
-    may be supplied (the reference's random block sampler, utils/point_utils.py:79-120, is host
-    code upstream of the path); otherwise every valid pixel, optionally every opt.valid_stride-th."""
+    may be supplied and wins; otherwise opt.valid_sample_num > 0 draws the reference's random block sample
+    (utils/point_utils.py:79-125) on the device, query.sample_valid_points — an image without a valid pixel
+    raises RuntimeError, the reference's assertion; otherwise every valid pixel, optionally every
+    opt.valid_stride-th."""
     bs = dd["bs"]
+    if valid_idx is None and opt.sample_num():
+        valid_idx = Q.sample_valid_points(dd["valid_mask"], opt.sample_num(), state=opt.sampler_state)
     if valid_idx is None:
         nz = Q.nonzero_pixels(dd["valid_mask"])
         valid_bid, valid_flat = nz["bid"], nz["flat"]
@@ -383,7 +404,11 @@ class FrameRunner:
 
     result() gives the reference's data_dict keys as views of the capacity buffers (int32 index
     tensors; `reference_dtypes=True` adds the int64 forms). mask_type 'all' / 'pred', every valid
-    pixel or every opt.valid_stride-th; intersect_pos_type / refine_intersect_pos_type / refine_pnet_pos_type 'abs' or
+    pixel, every opt.valid_stride-th, or — opt.valid_sample_num = n > 0, the shipped configs' 10000 — the random
+    block sample of n valid pixels per image, drawn on the device at the head of the frame from `sampler_state`
+    (query.sampler_state; default: opt.sampler_state, else the device's default state) without a sync and
+    recorded into the graph, so every replay draws a fresh sample; result() raises on an image without a valid
+    pixel; intersect_pos_type / refine_intersect_pos_type / refine_pnet_pos_type 'abs' or
     'rel'; precision "f32"
     or "f16x3" (as lidf_query / lidf_refine).
     max_pairs bounds the pair list (default 32 per pixel: a ray crosses at most 25 cells of the 9^3
@@ -404,7 +429,7 @@ class FrameRunner:
 
     def __init__(self, bs, h, w, device, pnet_model, prob_dec, offset_dec, opt=None, pnet_model_refine=None,
                  offset_dec_refine=None, max_pairs=None, lds_voxels=None,
-                 precision="f32", guard_every=1, offsets="all", side_stream=None):
+                 precision="f32", guard_every=1, offsets="all", side_stream=None, sampler_state=None):
         import ctypes as C
         import math
         from .decoders import _check_supported
@@ -508,6 +533,22 @@ class FrameRunner:
         self.pack_blob = torch.empty((L.lidf_frame_pack_bytes(),), dtype=torch.uint8, device=dev)
         self.pack_guard = torch.zeros((L.lidf_frame_pack_guard_bytes(),), dtype=torch.uint8, device=dev)
         self.vidx, self.n_valid_idx = None, 0      # explicit valid points (load(valid_idx=))
+        # opt.valid_sample_num > 0: every frame starts with query.sample_valid_launch on the frame's valid mask,
+        # straight into vidx (no sync; part of the captured graph) unless load() was handed an explicit valid_idx
+        self.sample_n = opt.sample_num()
+        self._sample_now = bool(self.sample_n)
+        if self.sample_n:
+            if h % 8 or w % 8:
+                raise ValueError("valid_sample_num needs h = %d and w = %d to be multiples of the 8 x 8 block" % (h, w))
+            if self.sample_n > h * w:
+                raise ValueError("valid_sample_num = %d exceeds the %d pixels of an image" % (self.sample_n, h * w))
+            self.vidx = torch.empty((2, N), **i32)
+            self.sample_cnt = torch.ones((bs,), **i32)
+            self.sample_ws = Q.sample_valid_workspace(bs, h, w, dev)
+            st = sampler_state if sampler_state is not None else opt.sampler_state
+            self.sampler_state = Q.default_sampler_state(dev) if st is None else st
+            Q._check_sampler_state(self.sampler_state, dev)
+            self.n_valid_idx = bs * self.sample_n
         self.src = dict(self.inp)
         math.isfinite(self.part_size)
 
@@ -520,7 +561,9 @@ class FrameRunner:
         code upstream sampled them (LIDF.get_valid_points with grid.valid_sample_num != -1 keeps the
         output of utils/point_utils.py sample_valid_points) instead of every opt.valid_stride-th valid
         pixel; copied into the runner's static index buffers without a sync. A captured graph replays
-        the M it was captured with.
+        the M it was captured with. A runner with opt.valid_sample_num > 0 draws its own sample on the device
+        at the head of every frame; an explicit valid_idx replaces the draw for that frame (eager frames only:
+        a captured graph holds the sampler launch).
         copy=True (the default once a graph is captured: a graph replays fixed addresses) copies the
         tensors into the runner's static input buffers — device-to-device, no sync; copy=False passes
         the caller's own contiguous float32 tensors to the library as they lie (kept alive by the
@@ -558,6 +601,12 @@ class FrameRunner:
             torch.sub(1.0, self.src["miss_mask"], out=i["valid_mask"])
             self.src["valid_mask"] = i["valid_mask"]
         m = 0
+        if self.sample_n:
+            if valid_idx is not None and self.graph is not None:
+                raise RuntimeError("the captured graph draws its valid points itself (valid_sample_num = %d); it "
+                                   "cannot take an explicit valid_idx" % self.sample_n)
+            self._sample_now = valid_idx is None
+            m = self.bs * self.sample_n
         if valid_idx is not None:
             if valid_idx.dim() != 2 or valid_idx.shape[1] != 2:
                 raise RuntimeError("valid_idx must be [M,2] (image, flat pixel)")
@@ -596,6 +645,9 @@ class FrameRunner:
         pnet, prob, off, pnet_r, off_r = self.mods
         opt, b, i = self.opt, self.buf, self.src
         keep = []
+        if self._sample_now:   # ahead of the frame and of its side-stream fork, on the caller's stream
+            Q.sample_valid_launch(i["valid_mask"], self.sample_n, self.sampler_state, self.vidx[0], self.vidx[1],
+                                  None, self.sample_cnt, self.sample_ws)
         dp, do = _decoder_struct(prob, keep), _decoder_struct(off, keep)
         pn = pointnet_struct(pnet, keep)
         a = _lib.LidfFrameArgs()
@@ -723,6 +775,8 @@ class FrameRunner:
         if c["OVERFLOW"]:
             raise RuntimeError("FrameRunner: the frame has more than max_pairs = %d ray/voxel pairs; "
                                "construct the runner with a larger max_pairs" % self.max_pairs)
+        if self._sample_now:
+            Q.raise_on_empty_image(self.sample_cnt.tolist(), "FrameRunner (valid_sample_num = %d)" % self.sample_n)
         b, R, P, V, NV, NVS = self.buf, c["R"], c["P"], c["V"], c["NV"], c["NVS"]
         dd = {
             "bs": self.bs, "h": self.h, "w": self.w, "part_size": self.part_size,
@@ -768,7 +822,8 @@ class FramePipeline:
     S = 3 on one MI355X): S FrameRunners, each with its own buffers, packed-weight entries and HIP
     stream, take the batches in turn, so that one frame's low-occupancy stretches (PointNet chains, the
     per-voxel layers, scans, the partial last round of the matrix kernels) are filled by its neighbours'
-    kernels. Frames come back in submission order, each with its one size read.
+    kernels. Frames come back in submission order, each with its one size read. opt.valid_sample_num and
+    sampler_state are FrameRunner's (every lane samples from its own state).
 
         pipe = FramePipeline(3, bs, h, w, device, pnet, prob_dec, offset_dec, opt, pnet_refine, offset_refine)
         for batch in loader:
@@ -789,7 +844,17 @@ class FramePipeline:
         self.dev = torch.device(device)
         if streams > 1:
             kw.setdefault("side_stream", False)   # (the lanes fill each other's gaps: see FrameRunner)
-        self.runners = [FrameRunner(bs, h, w, device, *models, **kw) for _ in range(streams)]
+        # opt.valid_sample_num: every lane draws from a state of its own (the base state with the lane number added
+        # to the seed) — lanes run on different streams, and one shared counter would be advanced by all of them
+        opt = kw.get("opt") or (models[3] if len(models) > 3 else None)
+        states = [kw.pop("sampler_state", None)] * streams
+        if opt is not None and opt.sample_num() and streams > 1:
+            base = states[0] if states[0] is not None else opt.sampler_state
+            base = Q.default_sampler_state(self.dev) if base is None else base
+            states = [base.clone() for _ in range(streams)]
+            for k, st in enumerate(states):
+                st[0] += k
+        self.runners = [FrameRunner(bs, h, w, device, *models, sampler_state=states[k], **kw) for k in range(streams)]
         self.lanes = [torch.cuda.Stream(self.dev) for _ in range(streams)]
         self.with_metrics = with_metrics
         self.pending = []          # [(slot, metrics)] in submission order

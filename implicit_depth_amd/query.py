@@ -163,6 +163,108 @@ def sample_miss_rays(miss, bs, miss_sample_num):
     return out
 
 
+_SAMPLER_STATE = {}   # device index -> the default state of sample_valid_points on that device
+
+
+def sampler_state(seed, device, counter=0):
+    """The random state of sample_valid_points: an int64 [2] tensor (seed, call counter) on `device`, read by the
+    kernel as two unsigned 64-bit words. The same state gives the same sample; every call advances the counter
+    on the device (an enqueued add: no sync, recorded by a graph capture like any other launch)."""
+    words = [int(v) & (2 ** 64 - 1) for v in (seed, counter)]
+    return torch.tensor([v - 2 ** 64 if v >= 2 ** 63 else v for v in words], dtype=torch.int64, device=device)
+
+
+def default_sampler_state(device):
+    """The state sample_valid_points uses when none is passed: one per device, seeded from torch.initial_seed()
+    at its first use on that device."""
+    dev = torch.device(device)
+    key = dev.index if dev.index is not None else torch.cuda.current_device()
+    if key not in _SAMPLER_STATE:
+        _SAMPLER_STATE[key] = sampler_state(torch.initial_seed(), dev)
+    return _SAMPLER_STATE[key]
+
+
+def sample_valid_workspace(bs, h, w, device):
+    """The scratch buffer of one sample_valid_launch (block masks + their prefix sums)."""
+    return _lib.workspace(_lib.lib().lidf_sample_valid_workspace_bytes(bs, h, w), device)
+
+
+def sample_valid_launch(mask, sample_num, state, bid, flat, idx, valid_cnt, ws):
+    """lidf_sample_valid_points into the caller's buffers + the counter's increment, on the current stream: no
+    allocation, no size read (FrameRunner.enqueue records exactly this into its graph). mask [bs,h,w] contiguous;
+    bid / flat int32 [>= bs*sample_num], idx int64 [bs*sample_num,2] or None, valid_cnt int32 [bs]."""
+    bs, h, w = mask.shape
+    dev = mask.device
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().lidf_sample_valid_points(
+            _lib.ptr(mask), MASK_DTYPES[mask.dtype], bs, h, w, int(sample_num), _lib.ptr(state), _lib.ptr(bid),
+            _lib.ptr(flat), _lib.ptr(idx), _lib.ptr(valid_cnt), _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)))
+        state[1:].add_(1)
+
+
+def _check_sampler_state(state, dev):
+    if state.dtype != torch.int64 or state.shape != (2,) or state.device != dev or not state.is_contiguous():
+        raise RuntimeError("state must be a contiguous int64 [2] tensor (seed, counter) on the mask's device "
+                           "(query.sampler_state)")
+
+
+def raise_on_empty_image(valid_cnt, what):
+    """The reference's assertion (utils/point_utils.py:124), made legible: valid_cnt is the sampler's host-side
+    list of per-image valid-pixel counts."""
+    for b, c in enumerate(valid_cnt):
+        if c == 0:
+            raise RuntimeError("%s: image %d of the batch has no valid pixel to sample from" % (what, b))
+
+
+def sample_valid_points(valid_mask, sample_num, block_x=8, block_y=8, state=None, return_counts=False, check=True):
+    """utils/point_utils.py:79-125 sample_valid_points on the device (lidf_sample_valid_points, one launch): the
+    random block sample of exactly sample_num valid pixels per image that LIDF.get_valid_points keeps when
+    grid.valid_sample_num != -1. valid_mask [bs,h,w] (float, bool/uint8, int32 or int64; non-zero = valid, NaN
+    included), h and w multiples of 8. Returns int64 [bs*sample_num, 2] (image, flat pixel y*w+x) on the mask's
+    device; return_counts=True adds valid_cnt int32 [bs], the number of valid pixels of every image.
+
+    Images with at least sample_num valid pixels give sample_num distinct intervals of cnt // sample_num
+    consecutive valid pixels (8x8-block order) in random order, one uniformly drawn pixel of each; sparser images
+    give every valid pixel once, in block order, topped up with draws without replacement from ceil(n/cnt) - 1
+    further copies. The random stream is the library's own counter-based one (the reference mixes numpy's and
+    torch's generators; its draws are not reproduced): `state` is an int64 [2] device tensor (seed, counter) from
+    sampler_state(); the same state gives the same sample, and every call advances the counter on the device.
+    state=None uses one default state per device, seeded from torch.initial_seed() at its first use.
+
+    An image without a valid pixel is the reference's AssertionError; here the call raises RuntimeError naming the
+    image after reading the bs counts (the one host read of this function). check=False skips that read — nothing
+    then waits for the device; the slots of such an image hold (image, 0) and its valid_cnt is 0.
+    Block sizes other than 8 x 8 (one wave's ballot) raise ValueError."""
+    if block_x != 8 or block_y != 8:
+        raise ValueError("sample_valid_points is built for 8 x 8 blocks (block_x = %s, block_y = %s)"
+                         % (block_x, block_y))
+    if valid_mask.dim() == 4 and valid_mask.shape[1] == 1:
+        valid_mask = valid_mask[:, 0]
+    if valid_mask.dim() != 3:
+        raise RuntimeError("valid_mask must be [bs,h,w] or [bs,1,h,w]")
+    if valid_mask.dtype not in MASK_DTYPES:
+        raise RuntimeError("mask dtype %s is not supported" % valid_mask.dtype)
+    bs, h, w = valid_mask.shape
+    if h % 8 or w % 8 or h < 8 or w < 8:
+        raise ValueError("sample_valid_points: h = %d and w = %d must be multiples of the 8 x 8 block" % (h, w))
+    sample_num = int(sample_num)
+    if sample_num < 1 or bs < 1:
+        raise ValueError("sample_valid_points: sample_num and the batch must be >= 1")
+    mask = valid_mask.contiguous()
+    _lib.require_cuda(mask, names=["valid_mask"])
+    dev = mask.device
+    state = default_sampler_state(dev) if state is None else state
+    _check_sampler_state(state, dev)
+    idx = torch.empty((bs * sample_num, 2), dtype=torch.int64, device=dev)
+    i32 = torch.empty((2 * bs * sample_num + bs,), dtype=torch.int32, device=dev)
+    cnt = i32[2 * bs * sample_num:]
+    sample_valid_launch(mask, sample_num, state, i32[:bs * sample_num], i32[bs * sample_num:2 * bs * sample_num], idx,
+                        cnt, sample_valid_workspace(bs, h, w, dev))
+    if check:
+        raise_on_empty_image(cnt.tolist(), "sample_valid_points")
+    return (idx, cnt) if return_counts else idx
+
+
 def nonzero_pixels(mask):
     """torch.nonzero(mask.view(bs,-1)) of LIDF.get_valid_points (models/pipeline.py:144-146) with
     the same device compaction: {'bid', 'flat'} int64 [N]."""

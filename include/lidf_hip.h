@@ -35,7 +35,10 @@ enum lidf_status {
 
 /* ABI version, bumped on any signature or struct-layout change and on added entry points. lidf_version() returns the value the
  * library was BUILT with; a binding compiled / written against this header must refuse a library that
- * answers anything else (implicit_depth_amd/_lib.py and csrc/lidf_torch_ext.cpp do, at load). */
+ * answers anything else (implicit_depth_amd/_lib.py and csrc/lidf_torch_ext.cpp do, at load).
+ * lidf_sample_valid_workspace_bytes / lidf_sample_valid_points were added WITHOUT a bump: they are purely
+ * additive (no signature or struct layout changed), so the number stays 14; a binding that needs them looks the
+ * symbols up and asks for a rebuild when an ABI-14 library lacks them (implicit_depth_amd/_lib.py does). */
 #define LIDF_ABI_VERSION 14
 int lidf_version(void);
 /* Static string for a status code. */
@@ -245,6 +248,37 @@ int lidf_miss_ray_fill_f32(const void* mask, int mask_dtype, const float* intr, 
                            int32_t* ray_bid, int32_t* ray_flat, int32_t* ray_pix, float* ray_dir,
                            int64_t* miss_bid, int64_t* miss_flat_img_id, int64_t* miss_img_ind,
                            lidf_stream_t stream);
+
+/* ---- Valid-point sampler ---------------------------------------------------------------------
+ * Replaces utils/point_utils.py:79-125 sample_valid_points, the random block sampler LIDF.get_valid_points
+ * keeps when grid.valid_sample_num != -1 (models/pipeline.py:137-160; 10000 in every shipped config), with
+ * one launch on the caller's stream and no size read: exactly batch*sample_num points come out.
+ * mask: [batch,height,width] elements of mask_dtype (LIDF_MASK_*; NaN is non-zero); height and width are
+ * multiples of 8 (the reference's assertion) and batch*height*width < 2^31. "Block order" below: 8x8 blocks
+ * row-major, pixels row-major inside a block (point_utils.py:84-86). Per image b with cnt non-zero pixels,
+ * n = sample_num:
+ *   cnt >= n      step = cnt / n, inum = cnt / step: n distinct intervals out of [0, inum), uniformly and in
+ *                 random order; slot i holds the point of block-order rank j_i*step + off_i, off_i uniform in
+ *                 [0, step). Ranks >= inum*step are never drawn (as in the reference).
+ *   0 < cnt < n   slots 0 .. cnt-1 are every valid point in block order; the other n - cnt are drawn without
+ *                 replacement from (ceil(n/cnt) - 1) copies of the cnt points.
+ *   cnt == 0      (the reference dies on an assertion) every slot is (b, 0) and valid_cnt[b] = 0: the caller
+ *                 decides; the Python layers raise where they read sizes.
+ * Outputs: bid / flat int32 [batch*sample_num] (what LidfFrameArgs.valid_idx_bid / valid_idx_flat take), idx
+ * int64 [batch*sample_num, 2] (image, flat pixel: the reference's return value; may be NULL), valid_cnt int32
+ * [batch]. Randomness is counter-based (Philox4x32-10, integer arithmetic only): rng_state is DEVICE memory,
+ * uint64 [2] = (seed, call counter), read by the kernel, so a captured graph draws a fresh sample on every
+ * replay when the caller enqueues an increment of rng_state[1] behind the call; the same state gives the same
+ * sample. The reference's own stream (numpy + torch generators, mixed) is not reproduced.
+ * LIDF_ERR_BAD_ARG before any HIP call: batch < 1, sample_num < 1, height or width not a positive multiple of
+ * 8, unknown mask_dtype, a NULL pointer other than idx, workspace_bytes below
+ * lidf_sample_valid_workspace_bytes(batch, height, width).                                               */
+size_t lidf_sample_valid_workspace_bytes(int batch, int height, int width);
+int lidf_sample_valid_points(const void* mask, int mask_dtype, int batch, int height, int width,
+                             int sample_num, const uint64_t* rng_state /* device [2]: seed, counter */,
+                             int32_t* bid, int32_t* flat, int64_t* idx /* [batch*sample_num,2] or NULL */,
+                             int32_t* valid_cnt /* [batch] */, void* workspace, size_t workspace_bytes,
+                             lidf_stream_t stream);
 
 /* ---- Ray / voxel slab test ---------------------------------------------------------------
  * Dense drop-in for extensions/ray_aabb (ray_aabb_cuda_kernel.cu:10-126): mask [V,R] i32 and
@@ -534,8 +568,8 @@ typedef struct LidfFrameArgs {
     size_t workspace_bytes;
     /* optional: the valid points as an explicit list instead of every valid_stride-th valid pixel —
      * what LIDF.get_valid_points keeps when grid.valid_sample_num != -1 (models/pipeline.py:143-146:
-     * utils/point_utils.py sample_valid_points, a random block sampler that is host code upstream of
-     * the path). n_valid_idx > 0: point j is pixel valid_idx_flat[j] of image valid_idx_bid[j], in
+     * utils/point_utils.py sample_valid_points, a random block sampler: lidf_sample_valid_points above
+     * writes exactly these two buffers on the device). n_valid_idx > 0: point j is pixel valid_idx_flat[j] of image valid_idx_bid[j], in
      * this order (duplicates allowed, as the sampler produces them for sparse frames);
      * n_valid_idx <= batch*height*width (image / pixel indices outside the batch are clamped into it,
      * where the reference's index_select would raise); valid_mask is then only read by refine_use_all_pix == 0;
