@@ -21,7 +21,8 @@ Precision: by default every function computes on float32 CPU tensors, as above. 
 the decoders, roi_align_fast, scatter_softmax / scatter_max, query, pointnet2stage) follows the dtype and device of
 its inputs instead, so the same restatement evaluated on float64 (GPU) tensors is the high-precision reference of
 tests/test_f64_gpu.py. Discrete steps (ray_aabb / pcl_aabb, an arg-max given as max_pair_id) keep their float32
-definition. refine_step and lidf_forward are float32 CPU only (they go through numpy).
+definition. refine_step and lidf_forward stay on the CPU (they go through numpy); refine_step follows its inputs'
+dtype when the per-ray RoIAlign rows are given (ray_rgb, e.g. from roi_align_fast), lidf_forward is float32 only.
 """
 import math
 
@@ -539,24 +540,40 @@ def _scatter_max_rows(x, idx, n):
     return out.scatter_reduce(0, idx.view(-1, 1).expand_as(x), x, reduce="amax", include_self=True)
 
 
-def pointnet2stage(p, inp, vox, n_vox):
+def pointnet2stage(p, inp, vox, n_vox, trace=None):
+    """trace (tests only): a list that receives one dict per call — every ReLU pre-activation under its layer's
+    name (point_lin1..4 [n, .], vox_lin1 / vox_lin2 [n_vox, .]) and both pooling inputs with their voxel indices,
+    "pool1": (f2, vox) and "pool2": (f5, vox)."""
     lin = lambda x, k: F.linear(x, p[k + ".weight"], p[k + ".bias"])  # noqa: E731
-    f1 = F.relu(lin(inp, "point_lin1"))
-    f2 = F.relu(lin(f1, "point_lin2"))
-    g1 = F.relu(lin(_scatter_max_rows(f2, vox, n_vox), "vox_lin1"))
+    z1 = lin(inp, "point_lin1")
+    f1 = F.relu(z1)
+    z2 = lin(f1, "point_lin2")
+    f2 = F.relu(z2)
+    zv1 = lin(_scatter_max_rows(f2, vox, n_vox), "vox_lin1")
+    g1 = F.relu(zv1)
     f3 = torch.cat((g1[vox], f2), -1)
-    f4 = F.relu(lin(f3, "point_lin3"))
-    f5 = F.relu(lin(f4, "point_lin4"))
-    return F.relu(lin(_scatter_max_rows(f5, vox, n_vox), "vox_lin2"))
+    z3 = lin(f3, "point_lin3")
+    f4 = F.relu(z3)
+    z4 = lin(f4, "point_lin4")
+    f5 = F.relu(z4)
+    zv2 = lin(_scatter_max_rows(f5, vox, n_vox), "vox_lin2")
+    if trace is not None:
+        trace.append({"point_lin1": z1, "point_lin2": z2, "vox_lin1": zv1, "point_lin3": z3, "point_lin4": z4,
+                      "vox_lin2": zv2, "pool1": (f2, vox), "pool2": (f5, vox)})
+    return F.relu(zv2)
 
 
 def refine_step(pred_pos, ray_dir, ray_pix, ray_bid, ray_flat, max_pair_id, pair_vox, voxel_bound,
                 voxel_bid, rgb_img, feat_grid, valid_inp, valid_vox, pnet_p, off_p, off_kind="IEF",
                 n_iter=2, multires=8, multires_views=4, roi_inp_bbox=8, offset_range=(-0.2, 0.2),
-                pos_rel=False, pnet_pos_rel=True, ray_rgb=None, pnet_select=None):
+                pos_rel=False, pnet_pos_rel=True, ray_rgb=None, pnet_select=None, trace=None):
     """One get_pred_refine call. Returns (pred_pos_refine, end_voxel_id, occ_voxel_feat).
     pnet_select [R] bool: the mask_type 'all' / refine.use_all_pix False branch
-    (models/pipeline.py:987-996) — only the selected rays' predicted points join the PointNet."""
+    (models/pipeline.py:987-996) — only the selected rays' predicted points join the PointNet.
+    trace (tests only): a list that receives one dict per call — "pos": the position entering the iteration,
+    "end_voxel", "pnet": pointnet2stage's trace dict, "preacts": decoder_forward's preacts list.
+    The float tensors follow pred_pos' dtype (float64 with ray_rgb given: the RoIAlign here goes through numpy);
+    the inside test of the end voxel keeps its float32 definition."""
     R, P, V = ray_dir.shape[0], pair_vox.shape[0], voxel_bound.shape[0]
     h, w = rgb_img.shape[2], rgb_img.shape[3]
     # end voxel: arg-max pair's voxel (dummy row -> 0), raised to the largest containing voxel
@@ -582,10 +599,14 @@ def refine_step(pred_pos, ray_dir, ray_pix, ray_bid, ray_flat, max_pair_id, pair
     else:
         pn_inp = torch.cat((valid_inp, pred_inp), 0)
         pn_vox = torch.cat((valid_vox.long(), end_voxel), 0)
-    occ_voxel_feat = pointnet2stage(pnet_p, pn_inp, pn_vox, V)
+    tr = {"pos": pred_pos, "end_voxel": end_voxel, "pnet": [], "preacts": []} if trace is not None else None
+    occ_voxel_feat = pointnet2stage(pnet_p, pn_inp, pn_vox, V, trace=tr["pnet"] if tr else None)
     enter = (pred_pos - center) if pos_rel else pred_pos
     inp = torch.cat((occ_voxel_feat[end_voxel], ray_rgb, embed(enter, multires), e_dir), -1)
-    off = decoder_forward(off_p, inp, off_kind, n_iter)
+    off = decoder_forward(off_p, inp, off_kind, n_iter, preacts=tr["preacts"] if tr else None)
+    if tr:
+        tr["pnet"] = tr["pnet"][0]
+        trace.append(tr)
     scaled = off * (offset_range[1] - offset_range[0]) + offset_range[0]
     return pred_pos + scaled * ray_dir, end_voxel, occ_voxel_feat
 

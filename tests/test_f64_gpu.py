@@ -9,8 +9,8 @@ import gc
 import pytest
 import torch
 
-from util import (F64_K, assert_f64_close, inv_out_act, kink_rows, make_module, make_pointnet, oracle_grads, orc,
-                  run_query, tf32_off, to_dev)
+from util import (K_BIAS, assert_f64_close, inv_out_act, k_for as _k, kink_rows, make_module, make_pointnet,
+                  oracle_grads, orc, run_query, tf32_off, to_dev)
 
 pytestmark = pytest.mark.gpu
 
@@ -21,18 +21,6 @@ def _full_precision_references():
         yield
     gc.collect()
     torch.cuda.empty_cache()
-
-
-# Bias gradients are column sums of dZ over the rows. The training kernels sum them serially per lane over a
-# slice's rows (lidf_train.hip, asum / bs2 of the weight-gradient kernel) where torch's reference reduces with a
-# tree; on an MI355X that costs 2-4.3x the f32 reference's error (largest: off.linear_3.bias of the 614,400-pair
-# query-training step, 4.26 elementwise / 3.65 normwise; prob.linear_4.bias of the pair node at 320 rows, 4.16).
-# Weight gradients and every other tensor keep the shared F64_K.
-K_BIAS = 6.0
-
-
-def _k(name):
-    return K_BIAS if name.endswith(".bias") else F64_K
 
 
 def _dev(p, dev, dt):
