@@ -571,7 +571,8 @@ def refine_step(pred_pos, ray_dir, ray_pix, ray_bid, ray_flat, max_pair_id, pair
     pnet_select [R] bool: the mask_type 'all' / refine.use_all_pix False branch
     (models/pipeline.py:987-996) — only the selected rays' predicted points join the PointNet.
     trace (tests only): a list that receives one dict per call — "pos": the position entering the iteration,
-    "end_voxel", "pnet": pointnet2stage's trace dict, "preacts": decoder_forward's preacts list.
+    "end_voxel", "pnet": pointnet2stage's trace dict, "preacts": decoder_forward's preacts list, "rows": the
+    decoder's input rows [R, D].
     The float tensors follow pred_pos' dtype (float64 with ray_rgb given: the RoIAlign here goes through numpy);
     the inside test of the end voxel keeps its float32 definition."""
     R, P, V = ray_dir.shape[0], pair_vox.shape[0], voxel_bound.shape[0]
@@ -606,6 +607,7 @@ def refine_step(pred_pos, ray_dir, ray_pix, ray_bid, ray_flat, max_pair_id, pair
     off = decoder_forward(off_p, inp, off_kind, n_iter, preacts=tr["preacts"] if tr else None)
     if tr:
         tr["pnet"] = tr["pnet"][0]
+        tr["rows"] = inp
         trace.append(tr)
     scaled = off * (offset_range[1] - offset_range[0]) + offset_range[0]
     return pred_pos + scaled * ray_dir, end_voxel, occ_voxel_feat

@@ -64,11 +64,18 @@ def _gather_pool(x, vox, V):
     return torch.gather(torch.cat((x, x.new_zeros(1, x.shape[1])), 0), 0, arg)
 
 
-def pointnet_forward(p, inp, vox, V, pool=_gather_pool, spread=lambda g1, vox: g1[vox]):
-    """orc.pointnet2stage's operations in its order, with the two poolings (pool(x, vox, V) -> [V, F]) and the
-    voxel-to-point gather (spread(g1, vox) -> [n, 64]) replaceable: pointnet2stage_argrouted below, and the
-    deliberately wrong variants of tests/test_pointnet_ref.py."""
-    lin = lambda x, k: F.linear(x, p[k + ".weight"], p[k + ".bias"])  # noqa: E731
+def rowwise_linear(x, w, b):
+    """F.linear as one product-and-sum per output entry. A matrix product may round equal rows differently
+    depending on where in the batch they stand (a BLAS blocks the rows; seen in float64 on one CPU at a batch of
+    2 x 257); here a row's result depends on that row alone, so equal rows stay equal bit for bit."""
+    return (x.unsqueeze(1) * w.unsqueeze(0)).sum(-1) + b
+
+
+def pointnet_forward(p, inp, vox, V, pool=_gather_pool, spread=lambda g1, vox: g1[vox], linear=F.linear):
+    """orc.pointnet2stage's operations in its order, with the two poolings (pool(x, vox, V) -> [V, F]), the
+    voxel-to-point gather (spread(g1, vox) -> [n, 64]) and the linear map replaceable: pointnet2stage_argrouted
+    below, and the deliberately wrong variants of tests/test_pointnet_ref.py."""
+    lin = lambda x, k: linear(x, p[k + ".weight"], p[k + ".bias"])  # noqa: E731
     f1 = F.relu(lin(inp, "point_lin1"))
     f2 = F.relu(lin(f1, "point_lin2"))
     g1 = F.relu(lin(pool(f2, vox, V), "vox_lin1"))

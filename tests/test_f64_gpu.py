@@ -9,8 +9,8 @@ import gc
 import pytest
 import torch
 
-from util import (K_BIAS, assert_f64_close, inv_out_act, k_for as _k, kink_rows, make_module, make_pointnet,
-                  oracle_grads, orc, run_query, tf32_off, to_dev)
+from util import (K_BIAS, assert_f64_close, check_selection, inv_out_act, k_for as _k, kink_rows, make_module,
+                  make_pointnet, oracle_grads, orc, run_query, tf32_off, to_dev)
 
 pytestmark = pytest.mark.gpu
 
@@ -215,25 +215,6 @@ def _oracle_query_on(scene, dev, dt, max_pair_id, **kw):
                      _dev(scene["off_p"], dev, dt), fast_roi=True, max_pair_id=max_pair_id, **kw)
 
 
-def _check_selection(scene, got, r64, r32):
-    """The product's arg-max is a maximum of its ray's float64 logits, to within the rounding the f32 path
-    is allowed (k x the f32 oracle's largest logit error)."""
-    R = scene["R"]
-    pr = scene["pair_ray"].long().to(got["max_pair_id"].device)
-    l64 = r64["pred_prob_end"][:, 0]
-    tol = 4 * (r32["pred_prob_end"][:, 0].double() - l64).abs().max().item() + 2.0 ** -22
-    mx = torch.full((R,), -float("inf"), dtype=torch.float64, device=l64.device)
-    mx = mx.scatter_reduce(0, pr, l64, reduce="amax", include_self=True)
-    mid = got["max_pair_id"].long()
-    has = mid < scene["P"]
-    assert bool((mx[~has] == -float("inf")).all())                  # a ray without pairs selects the dummy row
-    chosen = l64[mid[has]]
-    assert (pr[mid[has]] == torch.arange(R, device=mid.device)[has]).all()
-    gap = (mx[has] - chosen).max().item()
-    print("arg-max: largest float64 logit gap of a selected pair %.3g (tolerance %.3g)" % (gap, tol))
-    assert gap <= tol, (gap, tol)
-
-
 def _check_query(scene, cuda, **kw):
     got = run_query(scene, cuda, **kw)
     mid = got["max_pair_id"].long()
@@ -243,7 +224,7 @@ def _check_query(scene, cuda, **kw):
         assert_f64_close(k + " logit", inv_out_act(got[k]), inv_out_act(r64[k]), inv_out_act(r32[k]))
     for k in ("pair_pred_pos", "pred_pos", "pred_prob_end_softmax"):
         assert_f64_close(k, got[k], r64[k], r32[k])
-    _check_selection(scene, got, r64, r32)
+    check_selection(scene, got, r64, r32)
 
 
 @pytest.mark.parametrize("ragged", [False, True])

@@ -92,15 +92,20 @@ def test_argrouted_equals_the_oracle_without_ties(n, V):
 
 def test_argrouted_puts_a_tied_gradient_on_the_lowest_row():
     """Every row twice (rows i and i + n): the values are the oracle's, the second copies get no gradient at all
-    and the first copies the whole of it — the oracle's amax autograd gives each half."""
+    and the first copies the whole of it — the oracle's amax autograd gives each half. The routing is taken with
+    ref.rowwise_linear, under which the two copies of a row are equal bit for bit on any CPU (a matrix product
+    does not promise that, and then there is no tie to route)."""
     c = ref.pointnet_case(257, 9)
     x, vx = _subset(c)
     n = x.shape[0]
     x2, v2 = torch.cat((x, x)), torch.cat((vx, vx))
-    out_a, ga = ref.pointnet_grads(ref.pointnet2stage_argrouted, c["p"], x2, v2, 9, c["w"], torch.float64)
+    rowwise = lambda p, inp, vox, V: ref.pointnet_forward(p, inp, vox, V, linear=ref.rowwise_linear)  # noqa: E731
+    out_a, _ = ref.pointnet_grads(ref.pointnet2stage_argrouted, c["p"], x2, v2, 9, c["w"], torch.float64)
+    out_r, ga = ref.pointnet_grads(rowwise, c["p"], x2, v2, 9, c["w"], torch.float64)
     out_o, go = ref.pointnet_grads(orc.pointnet2stage, c["p"], x2, v2, 9, c["w"], torch.float64)
     _, g1 = ref.pointnet_grads(orc.pointnet2stage, c["p"], x, vx, 9, c["w"], torch.float64)
     assert torch.equal(out_a, out_o)
+    assert (out_r - out_o).abs().max().item() <= 1e-12 * out_o.abs().max().item()
     assert not ga["inp"][n:].any() and ga["inp"][:n].any()
     assert (ga["inp"][:n] - g1["inp"]).abs().max().item() <= 1e-12 * g1["inp"].abs().max().item()
     assert go["inp"][n:].any()                                          # (the even split the product does not make)

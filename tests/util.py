@@ -169,6 +169,25 @@ def assert_f64_close(what, got, ref64, ref32, k=F64_K, floor_ulps=F64_FLOOR_ULPS
     return row
 
 
+def check_selection(scene, got, r64, r32):
+    """The product's arg-max is a maximum of its ray's float64 logits, to within the rounding the f32 path
+    is allowed (k x the f32 oracle's largest logit error)."""
+    R = scene["R"]
+    pr = scene["pair_ray"].long().to(got["max_pair_id"].device)
+    l64 = r64["pred_prob_end"][:, 0]
+    tol = 4 * (r32["pred_prob_end"][:, 0].double() - l64).abs().max().item() + 2.0 ** -22
+    mx = torch.full((R,), -float("inf"), dtype=torch.float64, device=l64.device)
+    mx = mx.scatter_reduce(0, pr, l64, reduce="amax", include_self=True)
+    mid = got["max_pair_id"].long()
+    has = mid < scene["P"]
+    assert bool((mx[~has] == -float("inf")).all())                  # a ray without pairs selects the dummy row
+    chosen = l64[mid[has]]
+    assert (pr[mid[has]] == torch.arange(R, device=mid.device)[has]).all()
+    gap = (mx[has] - chosen).max().item()
+    print("arg-max: largest float64 logit gap of a selected pair %.3g (tolerance %.3g)" % (gap, tol))
+    assert gap <= tol, (gap, tol)
+
+
 def decoder_preacts(p, x, kind, n_iter=2):
     """Every kink-bearing pre-activation of orc.decoder_forward(p, x, kind, n_iter), taken from the oracle itself
     (its preacts list): the three hidden layers of every pass, and the output clamp's argument (the IEF's running
