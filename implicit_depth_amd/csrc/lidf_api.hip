@@ -281,30 +281,59 @@ struct QueryWs {
         sel, box, total;
 };
 
+// Widths of the decoders' input rows: stage 1 [vox feat 128 | ROI 128 | embed(enter) | embed(leave) | embed(dir)],
+// stage 2 [vox feat 128 | ROI 128 | embed(pos) | embed(dir)].
+static inline int query_D(int L, int Lv) { return 256 + 2 * (3 + 6 * L) + 3 + 6 * Lv; }
+static inline int refine_D(int L, int Lv) { return 256 + 3 + 6 * L + 3 + 6 * Lv; }
+
+// What (L, Lv, precision) decide about a stage-1 query: the column maps and stream layouts of its three weight
+// streams. The packer, the workspace sizes and every entry point that launches the query read this one plan.
+// `mf` carries enter_c0 / leave_c0, which only the pack kernels read: lidf_make_layout takes L alone from a
+// fused map (lidf_l1_quads), lidf_make_layout_h takes nothing, and no launch passes a map to a kernel — so
+// the one map serves the pack side and the launch side.
+struct QueryPlan {
+    int L, Lv, E, Ed, D;
+    bool split;            // LIDF_PRECISION_F16X3
+    L1Map mf, mv, mr;      // per point (fused) | per voxel: vox feat + b1 (+ IEF constant) | per ray: ROI + embed(dir)
+    StreamLayout lf;       // per-point stream: f32 fused, or the split-f16 sections
+    StreamLayout lv, lr;   // f32 layer-1 streams of the two tables
+    StreamLayout lh;       // split only: rows_h layout of the per-ray table (it replaces lr)
+};
+static QueryPlan query_plan(int L, int Lv, int precision) {
+    QueryPlan p = {};
+    p.L = L; p.Lv = Lv;
+    p.E = 3 + 6 * L; p.Ed = 3 + 6 * Lv;
+    p.D = query_D(L, Lv);
+    p.split = precision == LIDF_PRECISION_F16X3;
+    p.mf.L = L;
+    p.mf.enter_c0 = 256;
+    p.mf.leave_c0 = 256 + p.E;
+    p.mv = rows_map(128, 0, 0, 0, 1);
+    p.mr = rows_map(128, 128, p.Ed, 256 + 2 * p.E, 0);
+    p.lf = p.split ? lidf_make_layout_h(2, p.mf) : lidf_make_layout(2, LIDF_MODE_FUSED, p.mf);
+    p.lv = lidf_make_layout(2, LIDF_MODE_L1ONLY, p.mv);
+    p.lr = lidf_make_layout(2, LIDF_MODE_L1ONLY, p.mr);
+    if (p.split) p.lh = lidf_make_layout_rows_h(2, p.mr.D, 1);
+    return p;
+}
+
 static QueryWs query_ws(int64_t R, int64_t V, int L, int Lv, int64_t grid_floats = 0) {
     QueryWs w;
-    L1Map mf = {};
-    mf.L = L;
-    const int Ed = 3 + 6 * Lv;
+    // the per-point and the per-ray slot serve either precision: sized for the larger stream
+    const QueryPlan f32 = query_plan(L, Lv, LIDF_PRECISION_F32), f16 = query_plan(L, Lv, LIDF_PRECISION_F16X3);
+    const size_t pts = (size_t)(f32.lf.total > f16.lf.total ? f32.lf.total : f16.lf.total) * 4;
+    const size_t ray = (size_t)(f32.lr.total > f16.lh.total ? f32.lr.total : f16.lh.total) * 4;
     size_t o = 0;
-    {
-        const size_t f32 = (size_t)lidf_make_layout(2, LIDF_MODE_FUSED, mf).total * 4;
-        const size_t f16 = (size_t)lidf_make_layout_h(2, mf).total * 4;
-        w.stream_pts = o; o += align_up(f32 > f16 ? f32 : f16, 256);
-    }
+    w.stream_pts = o; o += align_up(pts, 256);
     w.aux_pts = o;    o += align_up(2 * LIDF_AUX_FLOATS * 4, 256);
-    w.stream_vox = o; o += align_up((size_t)lidf_make_layout(2, LIDF_MODE_L1ONLY, rows_map(128, 0, 0, 0, 1)).total * 4, 256);
-    {
-        const size_t f32 = (size_t)lidf_make_layout(2, LIDF_MODE_L1ONLY, rows_map(128, 0, Ed, 0, 0)).total * 4;
-        const size_t f16 = (size_t)lidf_make_layout_rows_h(2, 128 + Ed, 1).total * 4;
-        w.stream_ray = o; o += align_up(f32 > f16 ? f32 : f16, 256);
-    }
+    w.stream_vox = o; o += align_up((size_t)f32.lv.total * 4, 256);
+    w.stream_ray = o; o += align_up(ray, 256);
     w.packed_end = o;
     w.counter = o;    o += 256;  // tile hand-out counter of the split-f16 kernel
     w.voxpart = o;    o += align_up((size_t)(V > 0 ? V : 1) * 512 * 4, 256);
     w.raypart = o;    o += align_up((size_t)(R > 0 ? R : 1) * 512 * 4, 256);
-    w.rayfeat = o;    o += align_up((size_t)(R > 0 ? R : 1) * (128 + Ed) * 4, 256);
-    // offsets_selected: the one-pair-per-ray list [ray | vox | t (2) | offset | position (3)]
+    w.rayfeat = o;    o += align_up((size_t)(R > 0 ? R : 1) * (128 + f32.Ed) * 4, 256);
+    // offsets_selected: the one-pair-per-ray list (sel_list)
     w.sel = o;        o += align_up((size_t)(R > 0 ? R : 1) * 32, 256);
     // optional box-sum image + the list of clamped-box rays (last)
     w.box = o;        o += grid_floats > 0 ? align_up((size_t)(grid_floats + R + 1) * 4, 256) : 0;
@@ -319,33 +348,23 @@ LIDF_API size_t lidf_query_workspace_bytes(int64_t n_rays, int64_t n_vox, int64_
 
 // The decoders' parameters re-ordered into the streams the query kernels consume: the per-point
 // stream (+ layer-4 operands), the per-voxel and the per-ray layer-1 streams.
-static int pack_query_weights(const LidfDecoder* prob, const LidfDecoder* off, int L, int Lv,
-                              int precision, char* dst, hipStream_t st) {
-    const int E = 3 + 6 * L, Ed = 3 + 6 * Lv;
-    const int D = 256 + 2 * E + Ed;
-    const QueryWs w = query_ws(1, 1, L, Lv);
+static int pack_query_weights(const LidfDecoder* prob, const LidfDecoder* off, const QueryPlan& p, char* dst,
+                              hipStream_t st) {
+    const QueryWs w = query_ws(1, 1, p.L, p.Lv);
     float* stream_pts = (float*)(dst + w.stream_pts);
     float* aux_pts = (float*)(dst + w.aux_pts);
     float* stream_vox = (float*)(dst + w.stream_vox);
     float* stream_ray = (float*)(dst + w.stream_ray);
-    NetW np = to_netw(prob, D), no = to_netw(off, D);
-    L1Map mf = {};
-    mf.L = L;
-    mf.enter_c0 = 256;
-    mf.leave_c0 = 256 + E;
-    const bool split = precision == LIDF_PRECISION_F16X3;
-    if (split)
-        CHECK_HIP(lidf_launch_pack_h(guarded(lidf_make_layout_h(2, mf)), np, no, mf, stream_pts, aux_pts, st));
+    NetW np = to_netw(prob, p.D), no = to_netw(off, p.D);
+    if (p.split)
+        CHECK_HIP(lidf_launch_pack_h(guarded(p.lf), np, no, p.mf, stream_pts, aux_pts, st));
     else
-        CHECK_HIP(pack_stream(lidf_make_layout(2, LIDF_MODE_FUSED, mf), np, no, mf, stream_pts, aux_pts, st));
-    L1Map mv = rows_map(128, 0, 0, 0, 1);  // voxel part carries b1 (+ IEF constant)
-    CHECK_HIP(pack_stream(lidf_make_layout(2, LIDF_MODE_L1ONLY, mv), np, no, mv, stream_vox, aux_pts, st));
-    L1Map mr = rows_map(128, 128, Ed, 256 + 2 * E, 0);  // rgb ROI columns + direction embedding
-    if (split)
-        CHECK_HIP(lidf_launch_pack_rows_h(guarded(lidf_make_layout_rows_h(2, mr.D, 1)), np, no, mr, stream_ray,
-                                          nullptr, st));
+        CHECK_HIP(pack_stream(p.lf, np, no, p.mf, stream_pts, aux_pts, st));
+    CHECK_HIP(pack_stream(p.lv, np, no, p.mv, stream_vox, aux_pts, st));
+    if (p.split)
+        CHECK_HIP(lidf_launch_pack_rows_h(guarded(p.lh), np, no, p.mr, stream_ray, nullptr, st));
     else
-        CHECK_HIP(pack_stream(lidf_make_layout(2, LIDF_MODE_L1ONLY, mr), np, no, mr, stream_ray, aux_pts, st));
+        CHECK_HIP(pack_stream(p.lr, np, no, p.mr, stream_ray, aux_pts, st));
     return LIDF_OK;
 }
 
@@ -374,7 +393,7 @@ LIDF_API int lidf_query_pack_f32(const LidfDecoder* prob, const LidfDecoder* off
     if (!packed || packed_bytes < query_ws(1, 1, multires, multires_views).packed_end)
         return LIDF_ERR_WORKSPACE;
     JobScope js;
-    if ((rc = pack_query_weights(prob, off, multires, multires_views, precision, (char*)packed,
+    if ((rc = pack_query_weights(prob, off, query_plan(multires, multires_views, precision), (char*)packed,
                                  (hipStream_t)stream)))
         return rc;
     CHECK_HIP(flush_jobs(js.jobs, (hipStream_t)stream));
@@ -383,8 +402,9 @@ LIDF_API int lidf_query_pack_f32(const LidfDecoder* prob, const LidfDecoder* off
 
 LIDF_API size_t lidf_pack_guard_bytes(void) { return align_up(sizeof(LidfPackGuardState), 64); }
 
-// the parameter buffers of one decoder as fingerprint segments (d_in = columns of linear_1)
-static int decoder_segs(const LidfDecoder* d, int d_in, const float** ptrs, long long* n, int k) {
+// the parameter buffers of one decoder as fingerprint segments (dcore = width of its input rows)
+static int decoder_segs(const LidfDecoder* d, int dcore, const float** ptrs, long long* n, int k) {
+    const int d_in = dcore + (d->is_ief ? 16 : 0);   // columns of linear_1
     const float* p[10] = {d->w1, d->b1, d->w2, d->b2, d->w3, d->b3, d->w4, d->b4, d->wenc, d->benc};
     const long long c[10] = {(long long)LIDF_H1 * d_in, LIDF_H1, (long long)LIDF_H2 * LIDF_H1, LIDF_H2,
                              (long long)LIDF_H3 * LIDF_H2, LIDF_H3, LIDF_H3, 1, 16, 16};
@@ -426,6 +446,17 @@ static int guard_fail(void* guard, size_t bytes, hipStream_t st, int rc) {
     return rc;
 }
 
+// The guarded pack of one module: the fingerprint launch over its parameter buffers, then `pack` under the guard
+// (its pack launches return at once when the fingerprint did not change).
+template <class Pack>
+static int guarded_pack(const float* const* ptrs, const long long* cnt, int k, unsigned long long salt,
+                        void* guard, hipStream_t st, Pack pack) {
+    CHECK_HIP(lidf_launch_fingerprint(ptrs, cnt, k, salt, (LidfPackGuardState*)guard, st));
+    GuardScope scope((const LidfPackGuardState*)guard);
+    const int rc = pack();
+    return rc ? guard_fail(guard, sizeof(LidfPackGuardState), st, rc) : LIDF_OK;
+}
+
 LIDF_API int lidf_query_pack_guarded_f32(const LidfDecoder* prob, const LidfDecoder* off, int multires,
                                            int multires_views, int precision, void* packed,
                                            size_t packed_bytes, void* guard, lidf_stream_t stream) {
@@ -434,22 +465,83 @@ LIDF_API int lidf_query_pack_guarded_f32(const LidfDecoder* prob, const LidfDeco
     if (!guard) return LIDF_ERR_BAD_ARG;
     if (!packed || packed_bytes < query_ws(1, 1, multires, multires_views).packed_end)
         return LIDF_ERR_WORKSPACE;
-    const int D = 256 + 2 * (3 + 6 * multires) + 3 + 6 * multires_views;
+    const int D = query_D(multires, multires_views);
     const float* ptrs[LIDF_FP_MAX_SEGS];
     long long cnt[LIDF_FP_MAX_SEGS];
-    int k = decoder_segs(prob, D + (prob->is_ief ? 16 : 0), ptrs, cnt, 0);
-    k = decoder_segs(off, D + (off->is_ief ? 16 : 0), ptrs, cnt, k);
-    const unsigned long long salt = query_salt(prob, off, multires, multires_views, precision);
-    CHECK_HIP(lidf_launch_fingerprint(ptrs, cnt, k, salt, (LidfPackGuardState*)guard,
-                                      (hipStream_t)stream));
-    GuardScope scope((const LidfPackGuardState*)guard);
-    JobScope js;
-    if ((rc = pack_query_weights(prob, off, multires, multires_views, precision, (char*)packed,
-                                 (hipStream_t)stream)))
-        return guard_fail(guard, sizeof(LidfPackGuardState), (hipStream_t)stream, rc);
-    if (flush_jobs(js.jobs, (hipStream_t)stream) != hipSuccess)
-        return guard_fail(guard, sizeof(LidfPackGuardState), (hipStream_t)stream, LIDF_ERR_HIP);
-    return LIDF_OK;
+    const int k = decoder_segs(off, D, ptrs, cnt, decoder_segs(prob, D, ptrs, cnt, 0));
+    return guarded_pack(ptrs, cnt, k, query_salt(prob, off, multires, multires_views, precision), guard,
+                        (hipStream_t)stream, [&] {
+                            return lidf_query_pack_f32(prob, off, multires, multires_views, precision, packed,
+                                                       packed_bytes, stream);
+                        });
+}
+
+// The arguments of one layer-1 table launch of the query, both nets ([n, 512]):
+//   per voxel  voxpart[v] = W1[:, 0:128] vox_feat[v] + b1 (+c),   per ray  raypart[r] = W1[:, rgb | dir] rayfeat[r]
+// pk: the packed weight streams (QueryWs prefix). The split-f16 query forms the per-ray table with the rows_h kernel.
+enum { L1_VOX, L1_RAY };
+static PointsArgs l1_table_args(const QueryPlan& p, int table, const float* X, int64_t n, const int* n_dev,
+                                float* out, const char* pk, const QueryWs& w) {
+    const bool vox = table == L1_VOX;
+    const L1Map& m = vox ? p.mv : p.mr;
+    const StreamLayout& l = vox ? p.lv : p.split ? p.lh : p.lr;
+    PointsArgs a = {};
+    a.stream = (const float*)(pk + (vox ? w.stream_vox : w.stream_ray));
+    a.aux = (const float*)(pk + w.aux_pts);
+    a.nets = 2; a.l1_quads = l.l1_quads; a.net_quads = l.net_quads;
+    a.n = n; a.n_dev = n_dev;
+    a.X = X; a.ldx = vox ? 128 : 128 + p.Ed;
+    a.D = m.D; a.KQ1 = m.KQ1; a.has_bias = m.add_bias;
+    a.out_base = out;
+    return a;
+}
+
+// The arguments of the per-point kernel that every caller sets alike: both nets of the stream over the P pairs and the
+// two tables in the workspace. The caller adds its nets' passes and outputs (fill_net_args) and what differs between
+// callers: n_dev, tile_counter, pair_pred_pos, the kept activations, a one-net launch (nets, part_ld, part_off).
+static PointsArgs points_args(const QueryPlan& p, const char* pk, char* ws, const QueryWs& w, int64_t P,
+                              const int* pair_ray, const int* pair_vox, const float* pair_t, const float* ray_dir,
+                              const float* vox_center, int pos_rel, float range0, float range1, float part_size) {
+    PointsArgs a = {};
+    a.stream = (const float*)(pk + w.stream_pts);
+    a.aux = (const float*)(pk + w.aux_pts);
+    a.nets = 2; a.l1_quads = p.lf.l1_quads; a.net_quads = p.lf.net_quads;
+    a.n = P;
+    a.pair_ray = pair_ray; a.pair_vox = pair_vox; a.pair_t = pair_t;
+    a.ray_dir = ray_dir;
+    a.voxpart = (const float*)(ws + w.voxpart); a.raypart = (const float*)(ws + w.raypart);
+    a.vox_center = vox_center; a.pos_rel = pos_rel; a.L = p.L;
+    a.r0 = range0;
+    a.rscale = range1 - range0;
+    a.sqrt3 = (float)1.7320508075688772;  // np.sqrt(3) rounded to f32 (pipeline.py:438)
+    a.part_size = part_size;
+    return a;
+}
+
+// offsets_selected: the one-pair-per-ray list [ray | vox | t (2) | offset | position (3)] x R in QueryWs.sel. The reduce
+// fills ray / vox / t with the selected pair of every ray, the offset net writes offset / position.
+struct SelList {
+    int *ray, *vox;
+    float *t, *off, *pos;
+};
+static SelList sel_list(char* sb, int64_t R) {
+    const size_t Rc = (size_t)R;
+    return {(int*)sb, (int*)(sb + Rc * 4), (float*)(sb + Rc * 8), (float*)(sb + Rc * 16), (float*)(sb + Rc * 20)};
+}
+// offset_dec on that list: the second net of the two-net stream and tables `base` launches, over R points
+// (static split: R / 32 wave-tiles). base's n_dev and kept activations are the caller's to replace.
+static PointsArgs offset_on_list(const PointsArgs& base, const QueryPlan& p, const LidfDecoder* off,
+                                 const SelList& s, int64_t R) {
+    PointsArgs ao = base;
+    ao.stream = base.stream + (size_t)p.lf.net_quads * 256; ao.aux = base.aux + LIDF_AUX_FLOATS;
+    ao.nets = 1; ao.part_ld = 512; ao.part_off = 256;
+    ao.n = R;
+    fill_net_args(ao, 0, off, s.off, 1);
+    ao.out[1] = nullptr;
+    ao.pair_ray = s.ray; ao.pair_vox = s.vox; ao.pair_t = s.t;
+    ao.pair_pred_pos = s.pos;
+    ao.tile_counter = nullptr;
+    return ao;
 }
 
 // dims (optional): device int32 {R, P, V} — the sync-free frame path. n_rays / n_pairs / n_vox of `q`
@@ -477,8 +569,6 @@ static int query_impl(const LidfQueryArgs* q, void* ev_points_begin, void* ev_po
         return rc;
     hipStream_t st = (hipStream_t)stream;
     const int L = q->multires, Lv = q->multires_views;
-    const int E = 3 + 6 * L, Ed = 3 + 6 * Lv;
-    const int D = 256 + 2 * E + Ed;
 
     if (q->offsets_selected && q->precision != LIDF_PRECISION_F32) return LIDF_ERR_UNSUPPORTED;
     if (R == 0) return LIDF_OK;  // nothing to write (pipeline.py:686-687 early exit)
@@ -502,60 +592,29 @@ static int query_impl(const LidfQueryArgs* q, void* ev_points_begin, void* ev_po
         // parameter version) or packed here, into the head of the workspace, for this call
         const char* pk = q->packed ? (const char*)q->packed : ws;
         if (!q->packed && phases != QP_ALL) return LIDF_ERR_BAD_ARG;
-        if (!q->packed &&
-            (rc = pack_query_weights(q->prob, q->off, L, Lv, q->precision, ws, st)))
-            return rc;
-        const float* stream_pts = (const float*)(pk + w.stream_pts);
-        const float* aux_pts = (const float*)(pk + w.aux_pts);
-        const float* stream_vox = (const float*)(pk + w.stream_vox);
-        const float* stream_ray = (const float*)(pk + w.stream_ray);
-        float* voxpart = (float*)(ws + w.voxpart);
-        float* raypart = (float*)(ws + w.raypart);
+        const QueryPlan p = query_plan(L, Lv, q->precision);
+        if (!q->packed && (rc = pack_query_weights(q->prob, q->off, p, ws, st))) return rc;
         float* rayfeat = q->rayfeat_out ? q->rayfeat_out : (float*)(ws + w.rayfeat);
         int cus;
         if ((rc = cu_count(&cus))) return rc;
-        L1Map mf = {};
-        mf.L = L;
-        const bool split = q->precision == LIDF_PRECISION_F16X3;
-        StreamLayout lf = split ? lidf_make_layout_h(2, mf) : lidf_make_layout(2, LIDF_MODE_FUSED, mf);
-        L1Map mv = rows_map(128, 0, 0, 0, 1);
-        StreamLayout lv = lidf_make_layout(2, LIDF_MODE_L1ONLY, mv);
-        L1Map mr = rows_map(128, 128, Ed, 256 + 2 * E, 0);
-        StreamLayout lr = lidf_make_layout(2, LIDF_MODE_L1ONLY, mr);
 
         // 2. per-ray features [ROI 2x2 of the feature map | embed(dir)]
         if (phases & QP_RAYFEAT)
             CHECK_HIP(lidf_launch_rayfeat_dev(q->feat_grid, use_box ? (float*)(ws + w.box) : nullptr,
                                               q->batch, q->height, q->width, q->ray_dir, q->ray_pix,
                                               q->ray_bid, R, dims, q->roi_inp_bbox / 2, Lv, rayfeat,
-                                              128 + Ed, st));
-        // 3. layer-1 partial products: per voxel  voxpart[v] = W1[:, 0:128] vox_feat[v] + b1 (+c),
-        //    per ray  raypart[r] = W1[:, rgb|dir] rayfeat[r]
+                                              128 + p.Ed, st));
+        // 3. layer-1 partial products: per voxel and per ray (l1_table_args)
         {
-            PointsArgs av = {};
-            av.stream = stream_vox; av.aux = aux_pts;
-            av.nets = 2; av.l1_quads = lv.l1_quads; av.net_quads = lv.net_quads;
-            av.n = V; av.X = q->vox_feat; av.ldx = 128;
-            av.n_dev = dims ? dims + 2 : nullptr;
-            av.D = mv.D; av.KQ1 = mv.KQ1; av.has_bias = 1;
-            av.out_base = voxpart;
-            const long long ntv = (V + 127) / 128;
-            PointsArgs a = {};
-            a.stream = stream_ray; a.aux = aux_pts;
-            a.nets = 2; a.l1_quads = lr.l1_quads; a.net_quads = lr.net_quads;
-            a.n = R; a.X = rayfeat; a.ldx = 128 + Ed;
-            a.n_dev = dims;
-            a.D = mr.D; a.KQ1 = mr.KQ1; a.has_bias = 0;
-            a.out_base = raypart;
-            long long nt = (R + 127) / 128;
-            if (extra_l1) { extra_l1->X = rayfeat; extra_l1->ldx = 128 + Ed; }
-            if (split) {
+            const PointsArgs av = l1_table_args(p, L1_VOX, q->vox_feat, V, dims ? dims + 2 : nullptr,
+                                                (float*)(ws + w.voxpart), pk, w);
+            const PointsArgs a = l1_table_args(p, L1_RAY, rayfeat, R, dims, (float*)(ws + w.raypart), pk, w);
+            const long long ntv = (V + 127) / 128, nt = (R + 127) / 128;
+            if (extra_l1) { extra_l1->X = rayfeat; extra_l1->ldx = 128 + p.Ed; }
+            if (p.split) {
                 if (phases & QP_MAIN)
                     CHECK_HIP(lidf_launch_points(LIDF_MODE_L1ONLY, av, (int)(ntv < 2 * cus ? ntv : 2 * cus), st));
                 // the per-ray partial products with the split-f16 rows kernel (layer 1 only)
-                StreamLayout lh = lidf_make_layout_rows_h(2, mr.D, 1);
-                a.l1_quads = lh.l1_quads; a.net_quads = lh.net_quads;
-                a.npass[0] = a.npass[1] = 0;
                 if (phases & QP_RAYTAB) CHECK_HIP(lidf_launch_rows_h(a, (int)(nt < cus ? nt : cus), st));
             } else {
                 // one launch over the (tile, net, half) items of the tables (an absent one: stream == NULL)
@@ -568,20 +627,11 @@ static int query_impl(const LidfQueryArgs* q, void* ev_points_begin, void* ev_po
         if (!(phases & QP_MAIN)) return LIDF_OK;
         // 4. per-point kernel
         {
-            PointsArgs a = {};
-            a.stream = stream_pts; a.aux = aux_pts;
-            a.nets = 2; a.l1_quads = lf.l1_quads; a.net_quads = lf.net_quads;
-            a.n = P;
+            PointsArgs a = points_args(p, pk, ws, w, P, q->pair_ray, q->pair_vox, q->pair_t, q->ray_dir,
+                                       q->vox_center, q->pos_rel, q->offset_range0, q->offset_range1, q->part_size);
             a.n_dev = dims ? dims + 1 : nullptr;
             fill_net_args(a, 0, q->prob, q->pred_prob, 0);
             fill_net_args(a, 1, q->off, q->pred_offset, 1);
-            a.pair_ray = q->pair_ray; a.pair_vox = q->pair_vox; a.pair_t = q->pair_t;
-            a.ray_dir = q->ray_dir; a.voxpart = voxpart; a.raypart = raypart;
-            a.vox_center = q->vox_center; a.pos_rel = q->pos_rel; a.L = L;
-            a.r0 = q->offset_range0;
-            a.rscale = q->offset_range1 - q->offset_range0;
-            a.sqrt3 = (float)1.7320508075688772;  // np.sqrt(3) rounded to f32 (pipeline.py:438)
-            a.part_size = q->part_size;
             a.pair_pred_pos = q->pair_pred_pos;
             a.tile_counter = (int*)(ws + w.counter);   // dynamic tile hand-out of both kernels
             // (the frame path zeroes the counter with its other scratch, in one launch up front)
@@ -591,7 +641,7 @@ static int query_impl(const LidfQueryArgs* q, void* ev_points_begin, void* ev_po
 #endif
             long long nt = (P + 127) / 128;
             if (ev_points_begin) CHECK_HIP(hipEventRecord((hipEvent_t)ev_points_begin, st));
-            if (split) {
+            if (p.split) {
                 CHECK_HIP(lidf_launch_points_h(a, cus, st));
             } else if (!q->offsets_selected) {
                 CHECK_HIP(lidf_launch_points(LIDF_MODE_FUSED, a, (int)(nt < cus ? nt : cus), st));
@@ -605,30 +655,17 @@ static int query_impl(const LidfQueryArgs* q, void* ev_points_begin, void* ev_po
                 ap.nets = 1; ap.part_ld = 512; ap.part_off = 0;
                 ap.out[1] = nullptr; ap.is_offset[0] = 0; ap.pair_pred_pos = nullptr;
                 CHECK_HIP(lidf_launch_points(LIDF_MODE_FUSED, ap, (int)(nt < cus ? nt : cus), st));
-                char* sb = ws + w.sel;
-                const size_t Rc = (size_t)R;
-                int* sel_ray = (int*)sb;
-                int* sel_vox = (int*)(sb + Rc * 4);
-                float* sel_t = (float*)(sb + Rc * 8);
-                float* off_sel = (float*)(sb + Rc * 16);
-                float* pos_sel = (float*)(sb + Rc * 20);
+                const SelList s = sel_list(ws + w.sel, R);
                 CHECK_HIP(lidf_launch_ray_reduce_dev(q->pred_prob, nullptr, q->pair_off, R, P, dims,
                                                      dims ? dims + 1 : nullptr, q->ray_bid, q->ray_flat,
                                                      (long long)q->height * q->width, q->pred_prob_softmax,
                                                      (long long*)q->max_pair_id, nullptr, nullptr, st, q->pair_vox,
-                                                     q->pair_t, sel_ray, sel_vox, sel_t));
-                PointsArgs ao = a;
-                ao.stream = stream_pts + (size_t)lf.net_quads * 256; ao.aux = aux_pts + LIDF_AUX_FLOATS;
-                ao.nets = 1; ao.part_ld = 512; ao.part_off = 256;
-                ao.n = R; ao.n_dev = dims;   // (dims[0] = R)
-                fill_net_args(ao, 0, q->off, off_sel, 1);
-                ao.out[1] = nullptr;
-                ao.pair_ray = sel_ray; ao.pair_vox = sel_vox; ao.pair_t = sel_t;
-                ao.pair_pred_pos = pos_sel;
-                ao.tile_counter = nullptr;   // (static split: R / 32 wave-tiles)
+                                                     q->pair_t, s.ray, s.vox, s.t));
+                PointsArgs ao = offset_on_list(a, p, q->off, s, R);
+                ao.n_dev = dims;   // (dims[0] = R)
                 const long long ntr = (R + 127) / 128;
                 CHECK_HIP(lidf_launch_points(LIDF_MODE_FUSED, ao, (int)(ntr < cus ? ntr : cus), st));
-                CHECK_HIP(lidf_launch_selected_finish((const long long*)q->max_pair_id, off_sel, pos_sel, R, P, dims,
+                CHECK_HIP(lidf_launch_selected_finish((const long long*)q->max_pair_id, s.off, s.pos, R, P, dims,
                                                       dims ? dims + 1 : nullptr, q->ray_bid, q->ray_flat,
                                                       (long long)q->height * q->width, q->pred_offset,
                                                       q->pair_pred_pos, q->pred_pos, q->depth, st));
@@ -1178,13 +1215,9 @@ LIDF_API int lidf_pointnet_pack_guarded_f32(const LidfPointNet* w, void* packed,
     if (!packed || packed_bytes < lidf_pointnet_pack_bytes()) return LIDF_ERR_WORKSPACE;
     const float* ptrs[12];
     long long cnt[12];
-    pnet_segs(w, ptrs, cnt, 0);
-    CHECK_HIP(lidf_launch_fingerprint(ptrs, cnt, 12, PNET_SALT, (LidfPackGuardState*)guard,
-                                      (hipStream_t)stream));
-    GuardScope scope((const LidfPackGuardState*)guard);
-    if ((rc = lidf_pointnet_pack_f32(w, packed, packed_bytes, stream)))
-        return guard_fail(guard, sizeof(LidfPackGuardState), (hipStream_t)stream, rc);
-    return LIDF_OK;
+    const int k = pnet_segs(w, ptrs, cnt, 0);
+    return guarded_pack(ptrs, cnt, k, PNET_SALT, guard, (hipStream_t)stream,
+                        [&] { return lidf_pointnet_pack_f32(w, packed, packed_bytes, stream); });
 }
 
 // ---- stage-2 refinement ----------------------------------------------------------------------
@@ -1200,6 +1233,12 @@ static int refine_ief_factorised(const LidfDecoder* off, int D, const float* vox
                                  void* const* ev_rows = nullptr, const float* rayfeat = nullptr, int Ed = 0,
                                  float* raypart = nullptr, bool make_raypart = false,
                                  bool voxpart_ready = false);
+// the counterpart of pointnet_pack_into for the stage-2 decoder: refine_ief_factorised in its pack-only form
+// (pack_mode 1: no rows, no tables, nothing launched but the packs)
+static int refine_pack_into(const LidfDecoder* off, int L, int Lv, char* dst, hipStream_t st) {
+    return refine_ief_factorised(off, refine_D(L, Lv), nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, dst, st, 1,
+                                 nullptr, nullptr, nullptr, nullptr, 3 + 6 * Lv, nullptr, false);
+}
 static RefineWs refine_ws(int64_t R, int64_t Nv, int64_t V, int D) {
     RefineWs w;
     size_t o = 0;
@@ -1238,8 +1277,8 @@ static int refine_impl(const LidfRefineArgs* q, lidf_stream_t stream, void* cons
         !q->voxel_bound || !q->voxel_bid || !q->rgb_img || !q->rayfeat || !q->pred_pos_out ||
         (P > 0 && !q->pair_vox) || (Nv > 0 && (!q->valid_inp || !q->valid_vox)))
         return LIDF_ERR_BAD_ARG;
-    const int E = 3 + 6 * q->multires, Ed = 3 + 6 * q->multires_views;
-    const int D = 256 + E + Ed;
+    const int Ed = 3 + 6 * q->multires_views;
+    const int D = refine_D(q->multires, q->multires_views);
     RefineWs w = refine_ws(R, Nv, V, D);
     if (!q->workspace || q->workspace_bytes < w.total) return LIDF_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
@@ -1458,14 +1497,13 @@ LIDF_API size_t lidf_frame_pack_guard_bytes(void) { return (size_t)LIDF_FP_GROUP
 static int frame_pack_guarded(const LidfFrameArgs* a, char* blob, char* guards, hipStream_t st) {
     const bool rf = a->refine_times > 0, split = a->precision == LIDF_PRECISION_F16X3;
     const int L = a->multires, Lv = a->multires_views;
-    const int D = 256 + 2 * (3 + 6 * L) + 3 + 6 * Lv, Dr = 256 + 3 + 6 * L + 3 + 6 * Lv;
+    const int D = query_D(L, Lv);
     const FramePackLay l = frame_pack_lay();
     const float* ptrs[LIDF_FP_MULTI_SEGS];
     long long cnt[LIDF_FP_MULTI_SEGS];
     int grp[LIDF_FP_MULTI_SEGS];
     unsigned long long salts[LIDF_FP_GROUPS] = {};
-    int k = decoder_segs(a->prob, D + (a->prob->is_ief ? 16 : 0), ptrs, cnt, 0);
-    k = decoder_segs(a->off, D + (a->off->is_ief ? 16 : 0), ptrs, cnt, k);
+    int k = decoder_segs(a->off, D, ptrs, cnt, decoder_segs(a->prob, D, ptrs, cnt, 0));
     for (int i = 0; i < k; ++i) grp[i] = 0;
     salts[0] = query_salt(a->prob, a->off, L, Lv, a->precision);
     int k0 = k, ngrp = 2;
@@ -1480,7 +1518,7 @@ static int frame_pack_guarded(const LidfFrameArgs* a, char* blob, char* guards, 
         ngrp = 3;
         if (!split) {   // (the split-f16 IEF of stage 2 packs its rows stream inside the call)
             k0 = k;
-            k = decoder_segs(a->off_refine, Dr + (a->off_refine->is_ief ? 16 : 0), ptrs, cnt, k);
+            k = decoder_segs(a->off_refine, refine_D(L, Lv), ptrs, cnt, k);
             for (int i = k0; i < k; ++i) grp[i] = 3;
             salts[3] = refine_salt(a->off_refine, L, Lv);
             ngrp = 4;
@@ -1492,7 +1530,7 @@ static int frame_pack_guarded(const LidfFrameArgs* a, char* blob, char* guards, 
     JobScope js;
     {
         GuardScope g((const LidfPackGuardState*)guards);
-        rc = pack_query_weights(a->prob, a->off, L, Lv, a->precision, blob + l.query, st);
+        rc = pack_query_weights(a->prob, a->off, query_plan(L, Lv, a->precision), blob + l.query, st);
     }
     if (!rc) {
         GuardScope g((const LidfPackGuardState*)(guards + FRAME_GUARD_STRIDE));
@@ -1504,9 +1542,7 @@ static int frame_pack_guarded(const LidfFrameArgs* a, char* blob, char* guards, 
     }
     if (!rc && rf && !split) {
         GuardScope g((const LidfPackGuardState*)(guards + 3 * FRAME_GUARD_STRIDE));
-        rc = refine_ief_factorised(a->off_refine, Dr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr,
-                                   blob + l.refine, st, 1, nullptr, nullptr, nullptr, nullptr, 3 + 6 * Lv,
-                                   nullptr, false);
+        rc = refine_pack_into(a->off_refine, L, Lv, blob + l.refine, st);
     }
     if (!rc && flush_jobs(js.jobs, st) != hipSuccess) rc = LIDF_ERR_HIP;
     return rc ? guard_fail(guards, gbytes, st, rc) : LIDF_OK;
@@ -1763,8 +1799,8 @@ static int frame_impl(const LidfFrameArgs* a_in, lidf_stream_t stream, ForkState
     if (!rf) return LIDF_OK;
 
     // 6. stage 2: refine_times x get_pred_refine on the device-resident state
-    const int E = 3 + 6 * a->multires, Ed = 3 + 6 * a->multires_views;
-    const int D = 256 + E + Ed;
+    const int Ed = 3 + 6 * a->multires_views;
+    const int D = refine_D(a->multires, a->multires_views);
     float* inp_embed = (float*)(ws + f.inp_embed);
     float* offv = (float*)(ws + f.off);
     float* vox_feat_r = (float*)(ws + f.vox_feat_r);
@@ -2303,7 +2339,7 @@ static int refine_ief_factorised(const LidfDecoder* off, int D, const float* vox
 
 LIDF_API size_t lidf_refine_pack_bytes(int32_t multires, int32_t multires_views) {
     if (multires < 0 || multires > 16 || multires_views < 0 || multires_views > 16) return 0;
-    return align_up(refine_fact_bytes(256 + 3 + 6 * multires + 3 + 6 * multires_views), 256);
+    return align_up(refine_fact_bytes(refine_D(multires, multires_views)), 256);
 }
 
 LIDF_API int lidf_refine_pack_f32(const LidfDecoder* off, int32_t multires, int32_t multires_views,
@@ -2314,12 +2350,8 @@ LIDF_API int lidf_refine_pack_f32(const LidfDecoder* off, int32_t multires, int3
     const size_t need = lidf_refine_pack_bytes(multires, multires_views);
     if (!need) return LIDF_ERR_UNSUPPORTED;
     if (!packed || packed_bytes < need) return LIDF_ERR_WORKSPACE;
-    const int D = 256 + 3 + 6 * multires + 3 + 6 * multires_views;
     JobScope js;
-    if ((rc = refine_ief_factorised(off, D, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr,
-                                    (char*)packed, (hipStream_t)stream, 1, nullptr, nullptr, nullptr, nullptr,
-                                    3 + 6 * multires_views, nullptr, false)))
-        return rc;
+    if ((rc = refine_pack_into(off, multires, multires_views, (char*)packed, (hipStream_t)stream))) return rc;
     CHECK_HIP(flush_jobs(js.jobs, (hipStream_t)stream));
     return LIDF_OK;
 }
@@ -2333,17 +2365,12 @@ LIDF_API int lidf_refine_pack_guarded_f32(const LidfDecoder* off, int32_t multir
     const size_t need = lidf_refine_pack_bytes(multires, multires_views);
     if (!need) return LIDF_ERR_UNSUPPORTED;
     if (!packed || packed_bytes < need) return LIDF_ERR_WORKSPACE;
-    const int D = 256 + 3 + 6 * multires + 3 + 6 * multires_views;
     const float* ptrs[LIDF_FP_MAX_SEGS];
     long long cnt[LIDF_FP_MAX_SEGS];
-    const int k = decoder_segs(off, D + (off->is_ief ? 16 : 0), ptrs, cnt, 0);
-    const unsigned long long salt = refine_salt(off, multires, multires_views);
-    CHECK_HIP(lidf_launch_fingerprint(ptrs, cnt, k, salt, (LidfPackGuardState*)guard,
-                                      (hipStream_t)stream));
-    GuardScope scope((const LidfPackGuardState*)guard);
-    if ((rc = lidf_refine_pack_f32(off, multires, multires_views, packed, packed_bytes, stream)))
-        return guard_fail(guard, sizeof(LidfPackGuardState), (hipStream_t)stream, rc);
-    return LIDF_OK;
+    const int k = decoder_segs(off, refine_D(multires, multires_views), ptrs, cnt, 0);
+    return guarded_pack(ptrs, cnt, k, refine_salt(off, multires, multires_views), guard, (hipStream_t)stream, [&] {
+        return lidf_refine_pack_f32(off, multires, multires_views, packed, packed_bytes, stream);
+    });
 }
 
 struct TrainWs {
@@ -2579,10 +2606,10 @@ LIDF_API int lidf_build_rows_f32(const int32_t* pair_ray, const int32_t* pair_vo
     if (!pair_ray || !pair_vox || !pair_t || !ray_dir || !vox_feat || !rayfeat || !rows)
         return LIDF_ERR_BAD_ARG;
     if (pos_rel && !vox_center) return LIDF_ERR_BAD_ARG;
-    const int E = 3 + 6 * multires, Ed = 3 + 6 * multires_views;
+    const int Ed = 3 + 6 * multires_views;
     CHECK_HIP(lidf_launch_build_rows(pair_ray, pair_vox, pair_t, ray_dir, vox_center, pos_rel,
                                      vox_feat, rayfeat, 128 + Ed, multires, Ed, n_pairs, rows,
-                                     256 + 2 * E + Ed, (hipStream_t)stream));
+                                     query_D(multires, multires_views), (hipStream_t)stream));
     return LIDF_OK;
 }
 
@@ -2598,7 +2625,7 @@ LIDF_API int lidf_rows_backward_f32(const float* d_rows, const int32_t* pair_off
     if (d_vox_feat && n_vox > 0) CHECK_HIP(hipMemsetAsync(d_vox_feat, 0, (size_t)n_vox * 128 * 4, st));
     if (n_rays == 0) return LIDF_OK;
     if (!pair_off || (n_pairs > 0 && (!d_rows || !pair_vox))) return LIDF_ERR_BAD_ARG;
-    CHECK_HIP(lidf_launch_rows_backward(d_rows, 256 + 2 * E + Ed, 2 * E, pair_off, pair_vox, n_rays,
+    CHECK_HIP(lidf_launch_rows_backward(d_rows, query_D(multires, multires_views), 2 * E, pair_off, pair_vox, n_rays,
                                         n_pairs, Ed, d_vox_feat, d_rayfeat, 128 + Ed, st));
     return LIDF_OK;
 }
@@ -2776,43 +2803,19 @@ LIDF_API int lidf_query_forward_train_f32(const LidfQueryTrainArgs* q, const Lid
     if (!workspace || workspace_bytes < w.total) return LIDF_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
-    if ((rc = pack_query_weights(q->dec, offset_dec, L, Lv, LIDF_PRECISION_F32, ws, st))) return rc;
-    const float* aux_pts = (const float*)(ws + w.aux_pts);
-    float* voxpart = (float*)(ws + w.voxpart);
-    float* raypart = (float*)(ws + w.raypart);
+    const QueryPlan p = query_plan(L, Lv, LIDF_PRECISION_F32);
+    if ((rc = pack_query_weights(q->dec, offset_dec, p, ws, st))) return rc;
     int cus;
     if ((rc = cu_count(&cus))) return rc;
-    const int E = 3 + 6 * L, Ed = 3 + 6 * Lv;
-    L1Map mf = {};
-    mf.L = L;
-    const StreamLayout lf = lidf_make_layout(2, LIDF_MODE_FUSED, mf);
-    const L1Map mv = rows_map(128, 0, 0, 0, 1);
-    const StreamLayout lv = lidf_make_layout(2, LIDF_MODE_L1ONLY, mv);
-    const L1Map mr = rows_map(128, 128, Ed, 256 + 2 * E, 0);
-    const StreamLayout lr = lidf_make_layout(2, LIDF_MODE_L1ONLY, mr);
-    {   // per-voxel and per-ray parts of layer 1, both nets: [V,512], [R,512]
-        PointsArgs av = {};
-        av.stream = (const float*)(ws + w.stream_vox); av.aux = aux_pts;
-        av.nets = 2; av.l1_quads = lv.l1_quads; av.net_quads = lv.net_quads;
-        av.n = V; av.X = q->vox_feat; av.ldx = 128;
-        av.D = mv.D; av.KQ1 = mv.KQ1; av.has_bias = 1; av.out_base = voxpart;
-        PointsArgs a = {};
-        a.stream = (const float*)(ws + w.stream_ray); a.aux = aux_pts;
-        a.nets = 2; a.l1_quads = lr.l1_quads; a.net_quads = lr.net_quads;
-        a.n = R; a.X = q->rayfeat; a.ldx = 128 + Ed;
-        a.D = mr.D; a.KQ1 = mr.KQ1; a.has_bias = 0; a.out_base = raypart;
-        CHECK_HIP(lidf_launch_l1only_pair(a, av, nullptr, cus, st));
-    }
-    PointsArgs a = {};
-    a.stream = (const float*)(ws + w.stream_pts); a.aux = aux_pts;
-    a.nets = 2; a.l1_quads = lf.l1_quads; a.net_quads = lf.net_quads;
-    a.n = P;
+    // per-voxel and per-ray parts of layer 1, both nets: [V,512], [R,512]
+    CHECK_HIP(lidf_launch_l1only_pair(
+        l1_table_args(p, L1_RAY, q->rayfeat, R, nullptr, (float*)(ws + w.raypart), ws, w),
+        l1_table_args(p, L1_VOX, q->vox_feat, V, nullptr, (float*)(ws + w.voxpart), ws, w), nullptr, cus, st));
+    // (pair_pred_pos stays NULL: the differentiable tail, lidf_query_tail_f32, forms it — no offset range here)
+    PointsArgs a = points_args(p, ws, ws, w, P, q->pair_ray, q->pair_vox, pair_t, ray_dir, vox_center, pos_rel,
+                               0.f, 0.f, 0.f);
     fill_net_args(a, 0, q->dec, out_prob, 0);
     fill_net_args(a, 1, offset_dec, out_off, 1);
-    a.pair_ray = q->pair_ray; a.pair_vox = q->pair_vox; a.pair_t = pair_t;
-    a.ray_dir = ray_dir; a.voxpart = voxpart; a.raypart = raypart;
-    a.vox_center = vox_center; a.pos_rel = pos_rel; a.L = L;
-    a.pair_pred_pos = nullptr;   // the differentiable tail (lidf_query_tail_f32) forms it
     const LidfDecoder* decs[2] = {q->dec, offset_dec};
     float* acts[2] = {act_prob, act_off};
     for (int i = 0; i < 2; ++i) {
@@ -2860,80 +2863,39 @@ LIDF_API int lidf_query_forward_train_selected_f32(const LidfQueryTrainArgs* q, 
     const QueryWs w = query_ws(R, V, L, Lv);
     if (!workspace || workspace_bytes < w.total) return LIDF_ERR_WORKSPACE;
     char* ws = (char*)workspace;
-    if ((rc = pack_query_weights(q->dec, offset_dec, L, Lv, LIDF_PRECISION_F32, ws, st))) return rc;
-    const float* aux_pts = (const float*)(ws + w.aux_pts);
-    const float* stream_pts = (const float*)(ws + w.stream_pts);
-    float* voxpart = (float*)(ws + w.voxpart);
-    float* raypart = (float*)(ws + w.raypart);
+    const QueryPlan p = query_plan(L, Lv, LIDF_PRECISION_F32);
+    if ((rc = pack_query_weights(q->dec, offset_dec, p, ws, st))) return rc;
     int cus;
     if ((rc = cu_count(&cus))) return rc;
-    const int E = 3 + 6 * L, Ed = 3 + 6 * Lv;
-    L1Map mf = {};
-    mf.L = L;
-    const StreamLayout lf = lidf_make_layout(2, LIDF_MODE_FUSED, mf);
-    const L1Map mv = rows_map(128, 0, 0, 0, 1);
-    const StreamLayout lv = lidf_make_layout(2, LIDF_MODE_L1ONLY, mv);
-    const L1Map mr = rows_map(128, 128, Ed, 256 + 2 * E, 0);
-    const StreamLayout lr = lidf_make_layout(2, LIDF_MODE_L1ONLY, mr);
-    {   // per-voxel and per-ray parts of layer 1, both nets: [V,512], [R,512]
-        PointsArgs av = {};
-        av.stream = (const float*)(ws + w.stream_vox); av.aux = aux_pts;
-        av.nets = 2; av.l1_quads = lv.l1_quads; av.net_quads = lv.net_quads;
-        av.n = V; av.X = q->vox_feat; av.ldx = 128;
-        av.D = mv.D; av.KQ1 = mv.KQ1; av.has_bias = 1; av.out_base = voxpart;
-        PointsArgs a = {};
-        a.stream = (const float*)(ws + w.stream_ray); a.aux = aux_pts;
-        a.nets = 2; a.l1_quads = lr.l1_quads; a.net_quads = lr.net_quads;
-        a.n = R; a.X = q->rayfeat; a.ldx = 128 + Ed;
-        a.D = mr.D; a.KQ1 = mr.KQ1; a.has_bias = 0; a.out_base = raypart;
-        CHECK_HIP(lidf_launch_l1only_pair(a, av, nullptr, cus, st));
-    }
-    PointsArgs a = {};
-    a.stream = stream_pts; a.aux = aux_pts;
-    a.nets = 1; a.l1_quads = lf.l1_quads; a.net_quads = lf.net_quads;
-    a.part_ld = 512; a.part_off = 0;
-    a.n = P;
+    // per-voxel and per-ray parts of layer 1, both nets: [V,512], [R,512]
+    CHECK_HIP(lidf_launch_l1only_pair(
+        l1_table_args(p, L1_RAY, q->rayfeat, R, nullptr, (float*)(ws + w.raypart), ws, w),
+        l1_table_args(p, L1_VOX, q->vox_feat, V, nullptr, (float*)(ws + w.voxpart), ws, w), nullptr, cus, st));
+    PointsArgs a = points_args(p, ws, ws, w, P, q->pair_ray, q->pair_vox, pair_t, ray_dir, vox_center, pos_rel,
+                               offset_range0, offset_range1, part_size);
+    a.nets = 1; a.part_ld = 512; a.part_off = 0;
     fill_net_args(a, 0, q->dec, out_prob, 0);
-    a.pair_ray = q->pair_ray; a.pair_vox = q->pair_vox; a.pair_t = pair_t;
-    a.ray_dir = ray_dir; a.voxpart = voxpart; a.raypart = raypart;
-    a.vox_center = vox_center; a.pos_rel = pos_rel; a.L = L;
-    a.r0 = offset_range0;
-    a.rscale = offset_range1 - offset_range0;
-    a.sqrt3 = (float)1.7320508075688772;
-    a.part_size = part_size;
     a.tr_passes[0] = act_prob + (size_t)(V + R) * LIDF_H1;
     a.tr_pre[0] = a.tr_passes[0] + qact_pass(P);
     a.tr_pass_floats = (long long)qact_pass(P);
     const long long nt = (P + 127) / 128;
     CHECK_HIP(lidf_launch_points(LIDF_MODE_FUSED, a, (int)(nt < cus ? nt : cus), st));
-    char* sb = ws + w.sel;
-    const size_t Rc = (size_t)R;
-    int* sel_ray = (int*)sb;
-    int* sel_vox = (int*)(sb + Rc * 4);
-    float* sel_t = (float*)(sb + Rc * 8);
-    float* off_sel = (float*)(sb + Rc * 16);
-    float* pos_sel = (float*)(sb + Rc * 20);
+    const SelList sl = sel_list(ws + w.sel, R);
     const bool given = max_pair_id_in != nullptr;
     CHECK_HIP(lidf_launch_ray_reduce_dev(out_prob, nullptr, q->pair_off, R, P, nullptr, nullptr, nullptr, nullptr, 0,
                                          softmax, (long long*)max_pair_id, nullptr, nullptr, st, q->pair_vox, pair_t,
-                                         given ? nullptr : sel_ray, sel_vox, sel_t));
+                                         given ? nullptr : sl.ray, sl.vox, sl.t));
     if (given)
-        CHECK_HIP(lidf_launch_sel_from_ids((const long long*)max_pair_id_in, q->pair_vox, pair_t, R, P, sel_ray, sel_vox,
-                                           sel_t, st));
+        CHECK_HIP(lidf_launch_sel_from_ids((const long long*)max_pair_id_in, q->pair_vox, pair_t, R, P, sl.ray, sl.vox,
+                                           sl.t, st));
     const int npo = offset_dec->is_ief ? offset_dec->n_iter : 1;
-    PointsArgs ao = a;
-    ao.stream = stream_pts + (size_t)lf.net_quads * 256; ao.aux = aux_pts + LIDF_AUX_FLOATS;
-    ao.part_off = 256;
-    ao.n = R;
-    fill_net_args(ao, 0, offset_dec, off_sel, 1);
-    ao.pair_ray = sel_ray; ao.pair_vox = sel_vox; ao.pair_t = sel_t;
-    ao.pair_pred_pos = pos_sel;
+    PointsArgs ao = offset_on_list(a, p, offset_dec, sl, R);
     ao.tr_passes[0] = act_off_rows + (size_t)(V + R) * LIDF_H1;
     ao.tr_pre[0] = ao.tr_passes[0] + (size_t)npo * qact_pass(R);
     ao.tr_pass_floats = (long long)qact_pass(R);
     const long long ntr = (R + 127) / 128;
     CHECK_HIP(lidf_launch_points(LIDF_MODE_FUSED, ao, (int)(ntr < cus ? ntr : cus), st));
-    CHECK_HIP(lidf_launch_selected_finish((const long long*)(given ? max_pair_id_in : max_pair_id), off_sel, pos_sel, R, P,
+    CHECK_HIP(lidf_launch_selected_finish((const long long*)(given ? max_pair_id_in : max_pair_id), sl.off, sl.pos, R, P,
                                           nullptr, nullptr, nullptr, nullptr, 0, pred_offset, pair_pred_pos, pred_pos,
                                           nullptr, st));
     return LIDF_OK;

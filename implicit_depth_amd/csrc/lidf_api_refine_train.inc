@@ -299,7 +299,7 @@ LIDF_API int lidf_refine_train_backward_f32(const LidfRefineArgs* q, int32_t for
         return LIDF_ERR_BAD_ARG;
     const int64_t R = q->n_rays, Nv = q->n_valid, V = q->n_vox, n = R + Nv;
     const int E = 3 + 6 * q->multires, Ed = 3 + 6 * q->multires_views;
-    const int D = 256 + E + Ed, ld1 = D + (dec->is_ief ? 16 : 0);
+    const int D = refine_D(q->multires, q->multires_views), ld1 = D + (dec->is_ief ? 16 : 0);
     const int npass = dec->is_ief ? dec->n_iter : 1;
     hipStream_t st = (hipStream_t)stream;
     // the gradients start at zero (also what an empty batch returns)

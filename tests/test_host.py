@@ -370,6 +370,27 @@ def test_c_abi_argument_errors_without_gpu():
     assert L.lidf_ray_features_workspace_bytes(1, 240, 320, 76800) >= 32 * 240 * 320 * 4
 
 
+def test_host_size_functions_keep_their_recorded_values():
+    """The size functions that make no HIP call (workspaces and pack blobs of the query, the training forward,
+    stage 2, the PointNet and the frame) against tests/golden/host_sizes.json: a list of {fn, args, bytes}
+    recorded from the library before the query's launch plan was unified. Callers size persistent blobs with
+    these, and the blobs' layouts are what the kernels read: a byte more or less is a layout change."""
+    import ctypes as C
+    import json
+    from implicit_depth_amd import _lib
+    L = _lib.lib()
+    recs = json.load(open(os.path.join(ROOT, "tests", "golden", "host_sizes.json")))
+    assert {r["fn"] for r in recs} == {
+        "lidf_query_workspace_bytes", "lidf_query_pack_bytes", "lidf_query_forward_train_workspace_bytes",
+        "lidf_refine_pack_bytes", "lidf_pointnet_pack_bytes", "lidf_frame_pack_bytes", "lidf_frame_pack_guard_bytes",
+        "lidf_frame_workspace_bytes"}
+    assert len(recs) == 20
+    for r in recs:
+        args = [(C.c_int32 * len(a))(*a) if isinstance(a, list) else a for a in r["args"]]   # (the frame's res[3])
+        assert getattr(L, r["fn"])(*args) == r["bytes"], (r["fn"], r["args"])
+    assert [r["bytes"] for r in recs if r["fn"] == "lidf_refine_pack_bytes" and r["args"] == [17, 0]] == [0]
+
+
 def test_generic_width_paths_have_no_cpu_route():
     """Widths other than the shipped ones run layer by layer on the device (generic.py): CPU tensors
     are refused there as everywhere, and the any-width entries check their arguments without a GPU."""
