@@ -12,6 +12,7 @@ Host-side mirror of the reference interface for this path (names follow the refe
                                                 calls of trainers/train_refine.py:374-393 (one stage-2 training step)
   losses.compute_gt / lidf_loss              <- LIDF.compute_gt / compute_loss (train), models/pipeline.py:298-336, 468-566
   losses.refine_loss                         <- RefineNet.compute_loss (train), models/pipeline.py:760-840
+  losses.topk_mean                           <- torch.topk + mean of hard-negative mining, :475-490, 767-770
   torch_ext.ext()                            <- the pybind11 operator module (extensions/*/jit.py)
 All compute goes through csrc/liblidf_hip.so (C ABI in include/lidf_hip.h).
 """
@@ -20,9 +21,9 @@ from .decoders import (IEF, IMNet, Embedder, decoders_forward, decoders_forward_
                        get_embedder)
 from .pointnet import PointNet2Stage  # noqa: F401
 from .losses import (LidfLossOptions, compute_gt, lidf_loss, lidf_loss_composite, refine_loss,  # noqa: F401
-                     refine_loss_composite)
+                     refine_loss_composite, topk_mean)
 from .pipeline import LidfOptions, lidf_forward_train, refine_forward_train, train_refine_step  # noqa: F401
 
 __all__ = ["IEF", "IMNet", "Embedder", "PointNet2Stage", "decoders_forward", "decoders_forward_train",
            "get_embedder", "LidfLossOptions", "LidfOptions", "compute_gt", "lidf_loss", "lidf_loss_composite",
-           "lidf_forward_train", "refine_loss", "refine_loss_composite", "refine_forward_train", "train_refine_step"]
+           "lidf_forward_train", "refine_loss", "refine_loss_composite", "topk_mean", "refine_forward_train", "train_refine_step"]

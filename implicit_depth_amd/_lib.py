@@ -180,6 +180,12 @@ class LidfRefineLossArgs(C.Structure):
     ]
 
 
+class LidfTopkJob(C.Structure):
+    """struct LidfTopkJob (include/lidf_hip.h)."""
+    _fields_ = [("values", C.c_void_p), ("n", C.c_int64), ("count", C.c_void_p), ("mean", C.c_void_p),
+                ("weights", C.c_void_p)]
+
+
 _P, _I64, _I, _SZ = C.c_void_p, C.c_int64, C.c_int, C.c_size_t
 
 # name -> (restype, argtypes); every symbol include/lidf_hip.h declares
@@ -308,6 +314,11 @@ SIGNATURES = {
     "lidf_refine_loss_workspace_bytes": (_SZ, [_I64]),
     "lidf_refine_loss_f32": (C.c_int, [C.POINTER(LidfRefineLossArgs), _P]),
     "lidf_refine_loss_backward_f32": (C.c_int, [C.POINTER(LidfRefineLossArgs), _P]),
+    "lidf_topk_mean_workspace_bytes": (_SZ, [_I, _I64]),
+    "lidf_topk_mean_f32": (C.c_int, [C.POINTER(LidfTopkJob), _I, C.c_double, _P, _SZ, _P]),
+    "lidf_stage1_hard_neg_f32": (C.c_int, [C.POINTER(LidfLossArgs), C.c_double, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "lidf_refine_hard_neg_f32": (C.c_int, [C.POINTER(LidfRefineLossArgs), C.c_double, _P, _P, _P, _P, _P, _SZ,
+                                           _P]),
 }
 
 _lib = None

@@ -3525,5 +3525,91 @@ LIDF_API int lidf_refine_loss_backward_f32(const LidfRefineLossArgs* args, lidf_
     return LIDF_OK;
 }
 
+// ---- Hard-negative mining: top-k means on the device (lidf_select.hip) ---------------------------
+LIDF_API size_t lidf_topk_mean_workspace_bytes(int n_jobs, int64_t n_max) {
+    return lidf_select_workspace_bytes(n_jobs, n_max);
+}
+
+// The checks every select call makes before any HIP call.
+static int select_check(const SelectJob* jobs, int n_jobs, double ratio, const void* workspace,
+                        size_t workspace_bytes) {
+    if (!jobs || n_jobs < 1 || n_jobs > LIDF_SELECT_MAX_JOBS || !(ratio >= 0.0 && ratio <= 1.0))
+        return LIDF_ERR_BAD_ARG;
+    long long n_max = 0;
+    for (int i = 0; i < n_jobs; ++i) {
+        const SelectJob& j = jobs[i];
+        if (j.n < 0 || (j.n > 0 && !j.values)) return LIDF_ERR_BAD_ARG;
+        if (((uintptr_t)j.values & 3) || ((uintptr_t)j.weights & 3) || ((uintptr_t)j.mean & 3) ||
+            ((uintptr_t)j.count & 3))
+            return LIDF_ERR_BAD_ARG;
+        if (j.n > 0x7ffffffeLL) return LIDF_ERR_UNSUPPORTED;
+        n_max = j.n > n_max ? j.n : n_max;
+    }
+    if ((uintptr_t)workspace & 7) return LIDF_ERR_BAD_ARG;
+    if (!workspace || workspace_bytes < lidf_select_workspace_bytes(n_jobs, n_max)) return LIDF_ERR_WORKSPACE;
+    return LIDF_OK;
+}
+
+LIDF_API int lidf_topk_mean_f32(const LidfTopkJob* jobs, int n_jobs, double ratio, void* workspace,
+                                size_t workspace_bytes, lidf_stream_t stream) {
+    if (!jobs || n_jobs < 1 || n_jobs > LIDF_SELECT_MAX_JOBS) return LIDF_ERR_BAD_ARG;
+    SelectJob s[LIDF_SELECT_MAX_JOBS];
+    for (int i = 0; i < n_jobs; ++i) {
+        if (!jobs[i].mean) return LIDF_ERR_BAD_ARG;
+        s[i].values = jobs[i].values, s[i].n = jobs[i].n, s[i].count = jobs[i].count;
+        s[i].mean = jobs[i].mean, s[i].weights = jobs[i].weights;
+    }
+    int rc = select_check(s, n_jobs, ratio, workspace, workspace_bytes);
+    if (rc) return rc;
+    SelectCompose c;
+    memset(&c, 0, sizeof(c));
+    CHECK_HIP(lidf_launch_select(s, n_jobs, ratio, c, workspace, (hipStream_t)stream));
+    return LIDF_OK;
+}
+
+// The jobs {pos, surf, dx, dy (, prob)} of one loss over the forward's unreduced terms.
+static int hard_neg_run(const LossArgs& k, bool pairs, double ratio, float* w_pos, float* w_prob, float* w_surf,
+                        float* w_dx, float* w_dy, void* workspace, size_t workspace_bytes, hipStream_t st) {
+    if (!k.loss || !k.pos_un || !k.surf_dist || !k.dx_dist || !k.dy_dist || (pairs && k.P > 0 && !k.prob_un) ||
+        (pairs && !k.n_label))
+        return LIDF_ERR_BAD_ARG;
+    SelectJob s[5] = {{k.pos_un, k.R, nullptr, nullptr, w_pos},
+                      {k.surf_dist, k.R, nullptr, nullptr, w_surf},
+                      {k.dx_dist, k.R, nullptr, nullptr, w_dx},
+                      {k.dy_dist, k.R, nullptr, nullptr, w_dy},
+                      {k.prob_un, k.P, k.n_label, nullptr, w_prob}};
+    const int n_jobs = pairs ? 5 : 4;
+    int rc = select_check(s, n_jobs, ratio, workspace, workspace_bytes);
+    if (rc) return rc;
+    SelectCompose c;
+    c.mode = pairs ? 1 : 2, c.loss = k.loss;
+    c.pos_w = k.pos_w, c.prob_w = k.prob_w, c.surf_w = k.surf_w, c.smooth_w = k.smooth_w;
+    c.surf_on = k.surf_on, c.smooth_on = k.smooth_on;
+    CHECK_HIP(lidf_launch_select(s, n_jobs, ratio, c, workspace, st));
+    return LIDF_OK;
+}
+
+LIDF_API int lidf_stage1_hard_neg_f32(const LidfLossArgs* args, double ratio, float* w_pos, float* w_prob,
+                                      float* w_surf, float* w_dx, float* w_dy, void* workspace,
+                                      size_t workspace_bytes, lidf_stream_t stream) {
+    LossArgs k;
+    int rc = loss_args(args, &k);
+    if (rc) return rc;
+    if (k.R == 0) return LIDF_OK;
+    return hard_neg_run(k, true, ratio, w_pos, w_prob, w_surf, w_dx, w_dy, workspace, workspace_bytes,
+                        (hipStream_t)stream);
+}
+
+LIDF_API int lidf_refine_hard_neg_f32(const LidfRefineLossArgs* args, double ratio, float* w_pos, float* w_surf,
+                                      float* w_dx, float* w_dy, void* workspace, size_t workspace_bytes,
+                                      lidf_stream_t stream) {
+    LossArgs k;
+    int rc = refine_loss_args(args, &k);
+    if (rc) return rc;
+    if (k.R == 0) return LIDF_OK;
+    return hard_neg_run(k, false, ratio, w_pos, nullptr, w_surf, w_dx, w_dy, workspace, workspace_bytes,
+                        (hipStream_t)stream);
+}
+
 #include "lidf_api_pointnet_train.inc"
 #include "lidf_api_refine_train.inc"

@@ -390,6 +390,24 @@ struct LossArgs {
     float *g_pred_pos, *g_logit;
 };
 
+// One top-k mean of lidf_select.hip (LidfTopkJob of the C ABI) and what its last kernel makes of the means.
+#define LIDF_SELECT_MAX_JOBS 8
+struct SelectJob {
+    const float* values;   // [n]
+    long long n;
+    const int* count;      // device count k is taken from, NULL = n
+    float* mean;           // device scalar, or NULL (the stage wrappers' dx / dy terms)
+    float* weights;        // [n] or NULL
+};
+// mode 1: stage 1, jobs {pos, surf, dx, dy, prob} -> loss[0..4] = {pos, prob, surf, dx + dy, net};
+// mode 2: stage 2, jobs {pos, surf, dx, dy} -> loss[0..3] = {pos, surf, dx + dy, net}; mode 0: the means alone
+struct SelectCompose {
+    int mode;
+    float* loss;
+    float pos_w, prob_w, surf_w, smooth_w;
+    int surf_on, smooth_on;
+};
+
 // Arguments of one refine iteration's per-ray launch (lidf_refine.hip: lidf_refine_step_kernel).
 struct RefineStepArgs {
     const float* prev_pos;     // [R,3]

@@ -283,6 +283,11 @@ hipError_t lidf_launch_stage1_loss_backward(const LossArgs& a, hipStream_t st);
 hipError_t lidf_launch_refine_loss(const LossArgs& a, float* pred_img, hipStream_t st);
 hipError_t lidf_launch_refine_loss_backward(const LossArgs& a, hipStream_t st);
 
+// ---- lidf_select.hip
+size_t lidf_select_workspace_bytes(int n_jobs, long long n_max);
+hipError_t lidf_launch_select(const SelectJob* jobs, int n_jobs, double ratio, const SelectCompose& c, void* ws,
+                              hipStream_t st);
+
 // ---- lidf_sample.hip
 size_t lidf_sample_valid_masks_bytes(int B, int H, int W);
 size_t lidf_sample_valid_ws_bytes(int B, int H, int W);

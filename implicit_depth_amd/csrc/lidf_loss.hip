@@ -13,6 +13,9 @@
 // without pairs is an ordinary ray — and loss_dict has six entries).
 // No V x R mask, no image-sized normal map (lidf_normal_map_kernel writes the two maps on request only), no float
 // atomics: every sum has a fixed order, so losses and gradients are bit-identical from run to run.
+// Hard-negative mining — the top-k means of the unreduced terms written here, and the w_* the backward reads — is
+// torch.topk on the host side by default and lidf_select.hip (lidf_stage1_hard_neg_f32 / lidf_refine_hard_neg_f32) on
+// request: that file rewrites loss[0..4] (stage 2: loss[0..3]) after lidf_loss_final_kernel.
 #include "lidf_launch.h"
 
 namespace {

@@ -11,7 +11,9 @@ Reference counterparts (paths relative to /root/reference/src):
 
 compute_gt and lidf_loss run in liblidf_hip.so (csrc/lidf_loss.hip): one launch for the labels, two for the
 loss, one for its backward; no ray x voxel mask and no image-sized normal map is built, and nothing here
-reads a size or a value back to the host (hard-negative mining reads the label count: its k depends on it).
+reads a size or a value back to the host (hard-negative mining by torch.topk, the default route, reads the label
+count: its k depends on it; LidfLossOptions.hard_neg_select = "device" takes the top-k means in csrc/lidf_select.hip
+and reads nothing). topk_mean is that select for a caller's own loss term.
 Pairs are RAY-MAJOR as everywhere in this package: pcl_label / gt_max_pair_id index that list
 (query.to_reference_order gives the reference's voxel-major order).
 """
@@ -31,11 +33,16 @@ class LidfLossOptions:
     """loss.* of default_config.yaml:97-107 (train_refine_hardneg.yaml: hard_neg True, hard_neg_ratio 0.1).
     The defaults are stage 1's (train_lidf.yaml). Stage 2 reads the same keys (prob_w and prob_loss_type are not
     used there) and ships other values: train_refine.yaml pos_w 100 / surf_norm_w 10, train_refine_hardneg.yaml
-    pos_w 20 / surf_norm_w 2 with hard_neg True and hard_neg_ratio 0.1."""
+    pos_w 20 / surf_norm_w 2 with hard_neg True and hard_neg_ratio 0.1.
+    hard_neg_select (no reference counterpart) is the route of hard-negative mining in lidf_loss / refine_loss:
+    "torch" (the default) is torch.topk per term, "device" is the radix select of csrc/lidf_select.hip — one launch
+    sequence for every term, no label count read back, and ties at the k-th value go to the lowest indices where
+    torch.topk leaves the choice open. The composites ignore it."""
 
     def __init__(self, **kw):
         self.hard_neg = False
         self.hard_neg_ratio = None
+        self.hard_neg_select = "torch"
         self.pos_loss_type = "single"
         self.pos_w = 100.0
         self.prob_loss_type = "ray"
@@ -57,6 +64,8 @@ def _check_types(opt, prob=True):
         raise NotImplementedError("prob_loss_type %s" % opt.prob_loss_type)
     if opt.hard_neg and opt.hard_neg_ratio is None:
         raise ValueError("hard_neg needs hard_neg_ratio")
+    if opt.hard_neg_select not in ("torch", "device"):
+        raise ValueError("hard_neg_select must be 'torch' or 'device', not %r" % (opt.hard_neg_select,))
 
 
 def _terms_on(opt, epoch):
@@ -132,6 +141,41 @@ def _topk_weights(v, k):
     return torch.mean(top), w
 
 
+def _ratio(ratio):
+    ratio = float(ratio)
+    if not 0.0 <= ratio <= 1.0:
+        raise ValueError("ratio must lie in [0, 1], not %r" % ratio)
+    return ratio
+
+
+def topk_mean(values, ratio, count=None):
+    """(mean of the k largest entries of `values`, weights [n]: float32(1 / k) at them and 0 elsewhere) by the radix
+    select of csrc/lidf_select.hip (lidf_topk_mean_f32). values: a float32 CUDA tensor, read flattened; k =
+    int(count * ratio) with count = n, or a 0-dim / [1] int32 device tensor that stays on the device (nothing is read
+    back; the call can be captured in a graph). torch.topk's order (NaN greatest, -0.0 == +0.0); ties at the k-th
+    value go to the lowest indices; k == 0 gives a NaN mean and zero weights. Not differentiable: the weights are
+    what a backward multiplies with."""
+    ratio = _ratio(ratio)
+    _lib.require_cuda(values, count, names=["values", "count"])
+    _f32(values, "values")
+    v = values.detach().reshape(-1)
+    if count is not None:
+        if count.dtype != torch.int32 or count.numel() != 1 or count.device != v.device:
+            raise RuntimeError("count must be one int32 on the device of values")
+        count = count.reshape(1)
+    dev, n = v.device, v.shape[0]
+    mean = torch.empty((), dtype=torch.float32, device=dev)
+    w = torch.empty((n,), dtype=torch.float32, device=dev)
+    L = _lib.lib()
+    wsb = L.lidf_topk_mean_workspace_bytes(1, n)
+    ws = _lib.workspace(wsb, dev)
+    job = _lib.LidfTopkJob(v.data_ptr() if n else None, n, None if count is None else count.data_ptr(),
+                           mean.data_ptr(), w.data_ptr() if n else None)
+    with torch.cuda.device(dev):
+        _lib.check(L.lidf_topk_mean_f32(C.byref(job), 1, ratio, _lib.ptr(ws), wsb, _lib.current_stream(dev)))
+    return mean, w
+
+
 class _Stage1LossFn(torch.autograd.Function):
     """compute_loss of the training step as one autograd node over pred_pos and pred_prob_end
     (lidf_stage1_loss_f32 / lidf_stage1_loss_backward_f32). Outputs: loss_net (differentiable) and the [8] vector
@@ -163,7 +207,17 @@ class _Stage1LossFn(torch.autograd.Function):
             _lib.check(L.lidf_stage1_loss_f32(C.byref(a), _lib.current_stream(dev)))
         loss = fwd["loss"]
         weights = (None,) * 5
-        if cfg["hard_neg"]:
+        if cfg["hard_neg"] and cfg["hard_neg_select"] == "device":
+            # the same means by the radix select of lidf_select.hip: one launch sequence for the five terms, k of the
+            # labelled pairs taken from n_label on the device, loss[0..4] rewritten in place
+            weights = tuple(torch.empty((n,), **f32) for n in (R, P, R, R, R))
+            hsb = L.lidf_topk_mean_workspace_bytes(5, max(R, P))
+            hws = _lib.workspace(hsb, dev)
+            with torch.cuda.device(dev):
+                _lib.check(L.lidf_stage1_hard_neg_f32(C.byref(a), _ratio(cfg["hard_neg_ratio"]),
+                                                      *(_lib.ptr(w) for w in weights), _lib.ptr(hws), hsb,
+                                                      _lib.current_stream(dev)))
+        elif cfg["hard_neg"]:
             # hard-negative mining (models/pipeline.py:475-490, 514-539): the means over the top-k elements of the
             # unreduced terms; the backward takes them as per-element weights
             ratio = cfg["hard_neg_ratio"]
@@ -216,7 +270,7 @@ def _cfg(dd, opt, epoch):
     return {"bs": dd["bs"], "h": dd["h"], "w": dd["w"], "pos_w": float(opt.pos_w), "prob_w": float(opt.prob_w),
             "surf_norm_w": float(opt.surf_norm_w), "smooth_w": float(opt.smooth_w), "surf_on": surf_on,
             "smooth_on": smooth_on, "hard_neg": bool(opt.hard_neg),
-            "hard_neg_ratio": opt.hard_neg_ratio}
+            "hard_neg_ratio": opt.hard_neg_ratio, "hard_neg_select": opt.hard_neg_select}
 
 
 def lidf_loss(dd, loss_opt=None, exp_type="train", epoch=0, normal_maps=False):
@@ -224,7 +278,9 @@ def lidf_loss(dd, loss_opt=None, exp_type="train", epoch=0, normal_maps=False):
     (compute_gt's entries + pred_pos [R,3] and pred_prob_end [P,1] of lidf_query_train): the reference's loss_dict
     — pos_loss, prob_loss, surf_norm_loss, smooth_loss, loss_net, acc, err, angle_err — as 0-dim device tensors.
     loss_net carries the graph (one autograd node whose inputs are pred_pos and pred_prob_end); the other seven
-    are detached. Nothing is read back to the host, except the label count under hard_neg.
+    are detached. Nothing is read back to the host, except the label count under hard_neg with the default
+    hard_neg_select "torch" (torch.topk per term; its k of the labelled pairs is a host number). With "device" the
+    five top-k means come from csrc/lidf_select.hip, which reads n_label on the device: nothing is read back.
     normal_maps=True adds gt_surf_norm_img / pred_surf_norm_img [bs,3,h,w] to dd (visualisation only)."""
     opt = loss_opt or LidfLossOptions()
     if exp_type != "train":
@@ -413,7 +469,16 @@ class _RefineLossFn(torch.autograd.Function):
             _lib.check(L.lidf_refine_loss_f32(C.byref(a), _lib.current_stream(dev)))
         loss = fwd["loss"]
         weights = ()
-        if cfg["hard_neg"]:
+        if cfg["hard_neg"] and cfg["hard_neg_select"] == "device":
+            # the same means by the radix select of lidf_select.hip, loss[0..3] rewritten in place
+            weights = tuple(torch.empty((R,), **f32) for _ in range(4))
+            hsb = L.lidf_topk_mean_workspace_bytes(4, R)
+            hws = _lib.workspace(hsb, dev)
+            with torch.cuda.device(dev):
+                _lib.check(L.lidf_refine_hard_neg_f32(C.byref(a), _ratio(cfg["hard_neg_ratio"]),
+                                                      *(_lib.ptr(w) for w in weights), _lib.ptr(hws), hsb,
+                                                      _lib.current_stream(dev)))
+        elif cfg["hard_neg"]:
             # hard-negative mining (models/pipeline.py:767-770, 799-801, 818-821): k = int(R * ratio) is known on
             # the host, so nothing is read back
             k = int(R * cfg["hard_neg_ratio"])
@@ -457,7 +522,9 @@ def refine_loss(dd, loss_opt=None, exp_type="train", epoch=0, normal_maps=False)
     autograd node over pred_pos_refine: lidf_refine_loss_f32 and its backward, three launches in all); the other
     five are detached. gt_pos and pix2ray are compute_gt's: it runs here when dd lacks them (it needs the pair list
     then; the loss itself reads none — a ray without pairs is an ordinary ray). Nothing is read back to the host,
-    hard_neg included: its k = int(R * hard_neg_ratio) is known there.
+    hard_neg included: its k = int(R * hard_neg_ratio) is known there. hard_neg_select "torch" (the default) takes
+    the four top-k means by torch.topk, "device" by csrc/lidf_select.hip in one launch sequence (ties at the k-th
+    value: the lowest indices).
     loss_opt: LidfLossOptions; its defaults are train_refine.yaml's pos_w 100 / surf_norm_w 10, and
     train_refine_hardneg.yaml is LidfLossOptions(hard_neg=True, hard_neg_ratio=0.1, pos_w=20.0, surf_norm_w=2.0).
     normal_maps=True adds pred_surf_norm_img_refine [bs,3,h,w] to dd (:894, visualisation only)."""

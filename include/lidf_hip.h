@@ -36,9 +36,11 @@ enum lidf_status {
 /* ABI version, bumped on any signature or struct-layout change and on added entry points. lidf_version() returns the value the
  * library was BUILT with; a binding compiled / written against this header must refuse a library that
  * answers anything else (implicit_depth_amd/_lib.py and csrc/lidf_torch_ext.cpp do, at load).
- * lidf_sample_valid_workspace_bytes / lidf_sample_valid_points were added WITHOUT a bump: they are purely
- * additive (no signature or struct layout changed), so the number stays 14; a binding that needs them looks the
- * symbols up and asks for a rebuild when an ABI-14 library lacks them (implicit_depth_amd/_lib.py does). */
+ * lidf_sample_valid_workspace_bytes / lidf_sample_valid_points, and after them lidf_topk_mean_workspace_bytes /
+ * lidf_topk_mean_f32 / lidf_stage1_hard_neg_f32 / lidf_refine_hard_neg_f32 with struct LidfTopkJob, were added
+ * WITHOUT a bump: they are purely additive (no signature or struct layout changed), so the number stays 14; a
+ * binding that needs them looks the symbols up and asks for a rebuild when an ABI-14 library lacks them
+ * (implicit_depth_amd/_lib.py does). */
 #define LIDF_ABI_VERSION 14
 int lidf_version(void);
 /* Static string for a status code. */
@@ -1070,6 +1072,48 @@ typedef struct LidfRefineLossArgs {
 size_t lidf_refine_loss_workspace_bytes(int64_t n_rays);
 int lidf_refine_loss_f32(const LidfRefineLossArgs* args, lidf_stream_t stream);
 int lidf_refine_loss_backward_f32(const LidfRefineLossArgs* args, lidf_stream_t stream);
+
+/* ---- Hard-negative mining on the device: the mean of the k largest values (added without a bump of
+ * ABI 14: purely additive) ---------------------------------------------------------------------------
+ * torch.topk + mean of models/pipeline.py:475-490, 514-539, 767-770 as a radix select (lidf_select.hip).
+ * One job: values[n] -> *mean = the mean of the k largest, weights[n] = (float)(1.0 / (double)k) at
+ * the selected elements and 0 elsewhere (what the loss backwards take as w_*).
+ *   order  torch.topk's: NaN is the greatest, then +inf ... -inf; -0.0 == +0.0, every NaN equals every NaN;
+ *   ties   at the k-th value the LOWEST INDICES win: the selected set is the first k elements sorted by
+ *          (value descending, index ascending);
+ *   k      (long long)((double)count * ratio), count = n or *count (a device int32, clamped to 0..n);
+ *          k == 0: *mean = NaN (0 / 0, torch.mean of an empty tensor), weights all 0; k == n is valid;
+ *   sum    in double in a fixed order, rounded once to float: bit-identical from run to run.
+ * Up to 8 jobs share one launch sequence (a memset and at most six launches), which depends on the
+ * number of jobs, their n and whether they ask for weights — never on the data; nothing is read back,
+ * so the call can be captured in a graph. `jobs` is host memory; values / weights need 4-byte alignment
+ * only. n == 0: NaN mean. Errors before any HIP call: LIDF_ERR_BAD_ARG for NULL jobs / values (n > 0) /
+ * mean, n_jobs outside 1..8, n < 0, ratio outside [0, 1] or NaN, misaligned values / weights / workspace;
+ * LIDF_ERR_UNSUPPORTED for n > 2^31 - 2; LIDF_ERR_WORKSPACE for a missing or too small workspace.       */
+typedef struct LidfTopkJob {
+    const float* values;    /* [n] */
+    int64_t n;
+    const int32_t* count;   /* device scalar, or NULL: k comes from n */
+    float* mean;            /* device scalar */
+    float* weights;         /* [n], or NULL: none are written */
+} LidfTopkJob;
+size_t lidf_topk_mean_workspace_bytes(int n_jobs, int64_t n_max);
+int lidf_topk_mean_f32(const LidfTopkJob* jobs, int n_jobs, double ratio, void* workspace,
+                       size_t workspace_bytes, lidf_stream_t stream);
+/* The top-k means of one loss, after its forward (same struct): the jobs are pos_unreduced,
+ * surf_norm_dist, dx_dist, dy_dist over [R] (count R) and, stage 1, prob_unreduced over [P] with the
+ * device count n_label (the unlabelled pairs hold -inf and k <= n_label: they are never taken). The
+ * last kernel overwrites loss[0..4] = {pos, prob, surf, smooth = dx + dy, net} (stage 2: loss[0..3] =
+ * {pos, surf, smooth, net}); net in float, in the order of the forward: pos_w pos + prob_w prob, then
+ * += surf_norm_w surf if on, then += smooth_w smooth if on. The other entries of loss stay. w_* [R] /
+ * [P] receive the weights (NULL: not written). Workspace: lidf_topk_mean_workspace_bytes(5 or 4,
+ * max(n_rays, n_pairs)).                                                                              */
+int lidf_stage1_hard_neg_f32(const LidfLossArgs* args, double ratio, float* w_pos, float* w_prob,
+                             float* w_surf, float* w_dx, float* w_dy, void* workspace,
+                             size_t workspace_bytes, lidf_stream_t stream);
+int lidf_refine_hard_neg_f32(const LidfRefineLossArgs* args, double ratio, float* w_pos, float* w_surf,
+                             float* w_dx, float* w_dy, void* workspace, size_t workspace_bytes,
+                             lidf_stream_t stream);
 
 #ifdef __cplusplus
 }
