@@ -1008,7 +1008,7 @@ __global__ void __launch_bounds__(256) lidf_ray_aabb_onepass_kernel(
         }
     }
     int tot;
-    const int ex = block_scan_256(n, s_tmp, tot);
+    const int ex = block_scan<256>(n, s_tmp, tot);
     if (threadIdx.x == 0) lb_store(status, bid, bid == 0 ? LIDF_LB_INC : LIDF_LB_AGG, (unsigned)tot);
     if (threadIdx.x < 64) {
         const unsigned long long pre = bid > 0 ? lb_exclusive(status, bid, lane) : 0ull;
@@ -1243,15 +1243,8 @@ extern "C" hipError_t lidf_launch_ray_aabb_grid(bool fill, const float* ray_dir,
 }
 
 // ------------------------------------------------------------------------------------------------
-// Point / voxel inside test — extensions/pcl_aabb/pcl_aabb_cuda_kernel.cu:23-44 (inclusive bounds).
+// Point / voxel inside test (inside_box, lidf_device.h).
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool inside_test(float x, float y, float z, const float* vb) {
-    if ((x < vb[0]) || (x > vb[3])) return false;
-    if ((y < vb[1]) || (y > vb[4])) return false;
-    if ((z < vb[2]) || (z > vb[5])) return false;
-    return true;
-}
-
 __global__ void lidf_pcl_aabb_dense_kernel(const float* __restrict__ pos,
                                            const float* __restrict__ vbound,
                                            const int* __restrict__ pcl_bid,
@@ -1264,7 +1257,7 @@ __global__ void lidf_pcl_aabb_dense_kernel(const float* __restrict__ pos,
     float vb[6];
 #pragma unroll
     for (int k = 0; k < 6; ++k) vb[k] = vbound[6 * v + k];
-    if (inside_test(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], vb)) mask[v * N + i] = 1;
+    if (inside_box(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], vb)) mask[v * N + i] = 1;
 }
 
 extern "C" hipError_t lidf_launch_pcl_aabb_dense(const float* pos, const float* vbound,
@@ -1302,7 +1295,7 @@ __global__ void lidf_pcl_aabb_last_kernel(const float* __restrict__ pos,
         __syncthreads();
         if (!live) continue;
         for (int j = 0; j < nv; ++j)
-            if (s_bid[j] == bid && inside_test(x, y, z, s_vb + 6 * j)) best = (int)(v0 + j);
+            if (s_bid[j] == bid && inside_box(x, y, z, s_vb + 6 * j)) best = (int)(v0 + j);
     }
     if (live) last[i] = best;
 }
@@ -1331,7 +1324,7 @@ __global__ void lidf_scan_sums_kernel(const int* __restrict__ in, long long n,
     for (int k = 0; k < 4; ++k)
         if (b0 + k < n) v += in[b0 + k];
     int total;
-    block_scan_256(v, s_tmp, total);
+    block_scan<256>(v, s_tmp, total);
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 
@@ -1343,7 +1336,7 @@ __global__ void lidf_scan_top_kernel(int* __restrict__ sums, long long nb) {
         const long long i = b + threadIdx.x;
         const int v = i < nb ? sums[i] : 0;
         int total;
-        const int ex = block_scan_256(v, s_tmp, total);
+        const int ex = block_scan<256>(v, s_tmp, total);
         if (i < nb) sums[i] = carry + ex;
         carry += total;
     }
@@ -1361,7 +1354,7 @@ __global__ void lidf_scan_final_kernel(const int* __restrict__ in, long long n,
         v += x[k];
     }
     int total;
-    int run = sums[blockIdx.x] + block_scan_256(v, s_tmp, total);
+    int run = sums[blockIdx.x] + block_scan<256>(v, s_tmp, total);
     if (blockIdx.x == 0 && threadIdx.x == 0) out[0] = 0;
     for (int k = 0; k < 4; ++k) {
         run += x[k];
@@ -1380,7 +1373,6 @@ __global__ void lidf_scan_final_kernel(const int* __restrict__ in, long long n,
 __global__ void __launch_bounds__(1024) lidf_scan_small_kernel(const int* __restrict__ in, int n,
                                                                int* __restrict__ out) {
     __shared__ int s_w[16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int carry = 0;
     for (int b = 0; b < n; b += 4096) {   // four consecutive entries per thread and round
         const int k = b + 4 * threadIdx.x;
@@ -1388,22 +1380,8 @@ __global__ void __launch_bounds__(1024) lidf_scan_small_kernel(const int* __rest
 #pragma unroll
         for (int j = 0; j < 4; ++j) c[j] = k + j < n ? in[k + j] : 0;
         const int mine = c[0] + c[1] + c[2] + c[3];
-        int inc = mine;
-#pragma unroll
-        for (int sft = 1; sft < 64; sft <<= 1) {
-            const int o = __shfl_up(inc, sft);
-            if (lane >= sft) inc += o;
-        }
-        __syncthreads();
-        if (lane == 63) s_w[wave] = inc;
-        __syncthreads();
-        int wpre = 0, tot = 0;
-        for (int w = 0; w < 16; ++w) {
-            const int t = s_w[w];
-            wpre += w < wave ? t : 0;
-            tot += t;
-        }
-        int run = carry + wpre + inc - mine;
+        int tot;
+        int run = carry + block_scan<1024>(mine, s_w, tot);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (k + j < n) out[k + j] = run;
@@ -1477,23 +1455,7 @@ __global__ void lidf_vox_cells_kernel(const int* __restrict__ cell_flag,
                                       int* __restrict__ vox_bid) {
     const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= ncell || !cell_flag[k]) return;
-    const int v = cell_rank[k];
-    int rem = (int)k;
-    const int cz = rem % g.r[2]; rem /= g.r[2];
-    const int cy = rem % g.r[1]; rem /= g.r[1];
-    const int cx = rem % g.r[0]; rem /= g.r[0];
-    occ[4 * v + 0] = rem;
-    if (vox_bid) vox_bid[v] = rem;   // the image index on its own ([V] i32: what the box tests take)
-    occ[4 * v + 1] = cx;
-    occ[4 * v + 2] = cy;
-    occ[4 * v + 3] = cz;
-    const int c[3] = {cx, cy, cz};
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float lo = g.xmin[a] + (float)c[a] * g.crop;  // pipeline.py:186
-        vbound[6 * v + a] = lo;
-        vbound[6 * v + 3 + a] = lo + g.crop;               // :187
-    }
+    vox_row_write((int)k, cell_rank[k], g, occ, vbound, vox_bid, nullptr);
 }
 
 __global__ void lidf_vox_points_kernel(const float* __restrict__ xyz,
@@ -1637,8 +1599,7 @@ __global__ void __launch_bounds__(1024) lidf_depth_metrics_kernel(
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int i = 0; i < METRIC_SUMS; ++i) {
-        double v = acc[i];
-        for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+        const double v = wave_sum(acc[i]);
         if (lane == 0) red[i][wave] = v;
     }
     __syncthreads();
@@ -1714,15 +1675,6 @@ extern "C" hipError_t lidf_launch_depth_metrics(const float* pred, const float* 
 // ------------------------------------------------------------------------------------------------
 #define MISS_ITEMS 1024
 
-__device__ __forceinline__ bool mask_nonzero(const void* mask, int dtype, long long i) {
-    switch (dtype) {
-        case 0: return ((const float*)mask)[i] != 0.f;
-        case 1: return ((const unsigned char*)mask)[i] != 0;
-        case 2: return ((const int*)mask)[i] != 0;
-        default: return ((const long long*)mask)[i] != 0;
-    }
-}
-
 __global__ void lidf_miss_count_kernel(const void* __restrict__ mask, int dtype, long long n,
                                        int* __restrict__ block_cnt) {
     __shared__ int s_tmp[4];
@@ -1731,7 +1683,7 @@ __global__ void lidf_miss_count_kernel(const void* __restrict__ mask, int dtype,
     for (int k = 0; k < 4; ++k)
         if (b0 + k < n && mask_nonzero(mask, dtype, b0 + k)) ++v;
     int total;
-    block_scan_256(v, s_tmp, total);
+    block_scan<256>(v, s_tmp, total);
     if (threadIdx.x == 0) block_cnt[blockIdx.x] = total;
 }
 
@@ -1756,7 +1708,7 @@ __global__ void lidf_miss_fill_kernel(const void* __restrict__ mask, int dtype, 
         v += f[k] ? 1 : 0;
     }
     int total;
-    int j = block_off[blockIdx.x] + block_scan_256(v, s_tmp, total);
+    int j = block_off[blockIdx.x] + block_scan<256>(v, s_tmp, total);
     const long long hw = (long long)H * W;
     for (int k = 0; k < 4; ++k) {
         if (!f[k]) continue;
@@ -1845,13 +1797,10 @@ __device__ __forceinline__ unsigned long long fp_mix(unsigned long long x) {
 
 #define FP_WORDS 4096   // per workgroup: 256 threads x 16 words, four loads in flight per thread
 
-__global__ void __launch_bounds__(256) lidf_fingerprint_kernel(FpSegs s, unsigned long long salt,
-                                                               LidfPackGuardState* g) {
-    int seg = 0;
-    for (int k = 1; k < LIDF_FP_MAX_SEGS; ++k) seg += (k < s.nseg && blockIdx.x >= s.blk0[k]) ? 1 : 0;
-    const unsigned n = s.n[seg], base = s.base[seg];
-    const unsigned* __restrict__ p = s.p[seg];
-    const unsigned w0 = (blockIdx.x - s.blk0[seg]) * FP_WORDS;
+// One workgroup's slab: FP_WORDS words of segment p (n words, the first one word `base` of the concatenation)
+// from word w0 on, hashed and summed over the workgroup. Thread 0 holds the sum; `part`: 4 words of LDS.
+__device__ __forceinline__ unsigned long long fp_slab_sum(const unsigned* __restrict__ p, unsigned n, unsigned base,
+                                                          unsigned w0, unsigned long long* part) {
     unsigned long long acc = 0;
 #pragma unroll
     for (int r = 0; r < FP_WORDS / 1024; ++r) {
@@ -1867,29 +1816,37 @@ __global__ void __launch_bounds__(256) lidf_fingerprint_kernel(FpSegs s, unsigne
             if (i < n) acc += fp_mix(((unsigned long long)(base + i) << 32) | w[j]);
         }
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned lo = __shfl_xor((unsigned)acc, o), hi = __shfl_xor((unsigned)(acc >> 32), o);
-        acc += ((unsigned long long)hi << 32) | lo;
-    }
-    __shared__ unsigned long long part[4];
-    __shared__ bool last;
+    acc = wave_sum(acc);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
     __syncthreads();
-    if (threadIdx.x == 0) {
-        // (the returned value orders the ticket behind the sum without a release fence = an L2 write-back)
-        const unsigned long long was = atomicAdd(&g->acc, part[0] + part[1] + part[2] + part[3]);
-        asm volatile("" ::"v"(was));
-        last = atomicAdd(&g->ticket, 1u) == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (last && threadIdx.x == 0) {
-        const unsigned long long h = atomicAdd(&g->acc, 0ull) + salt;
-        g->dirty = (!g->valid || g->hash != h) ? 1 : 0;
-        g->hash = h;
-        g->valid = 1;
-        g->acc = 0;
-        g->ticket = 0;
-    }
+    return part[0] + part[1] + part[2] + part[3];
+}
+
+// Thread 0 adds the workgroup's sum to the guard's accumulator and takes a ticket; the last of the guard's
+// `nblocks` workgroups leaves the verdict and re-arms the accumulator.
+__device__ __forceinline__ void fp_commit(LidfPackGuardState* g, unsigned long long sum, unsigned long long salt,
+                                          unsigned nblocks) {
+    if (threadIdx.x != 0) return;
+    // (the returned value orders the ticket behind the sum without a release fence = an L2 write-back)
+    const unsigned long long was = atomicAdd(&g->acc, sum);
+    asm volatile("" ::"v"(was));
+    if (atomicAdd(&g->ticket, 1u) != nblocks - 1) return;
+    const unsigned long long h = atomicAdd(&g->acc, 0ull) + salt;
+    g->dirty = (!g->valid || g->hash != h) ? 1 : 0;
+    g->hash = h;
+    g->valid = 1;
+    g->acc = 0;
+    g->ticket = 0;
+}
+
+__global__ void __launch_bounds__(256) lidf_fingerprint_kernel(FpSegs s, unsigned long long salt,
+                                                               LidfPackGuardState* g) {
+    __shared__ unsigned long long part[4];
+    int seg = 0;
+    for (int k = 1; k < LIDF_FP_MAX_SEGS; ++k) seg += (k < s.nseg && blockIdx.x >= s.blk0[k]) ? 1 : 0;
+    const unsigned long long sum =
+        fp_slab_sum(s.p[seg], s.n[seg], s.base[seg], (blockIdx.x - s.blk0[seg]) * FP_WORDS, part);
+    fp_commit(g, sum, salt, gridDim.x);
 }
 
 extern "C" hipError_t lidf_launch_fingerprint(const float* const* ptrs, const long long* floats,
@@ -1930,50 +1887,13 @@ struct FpSegsM {
 
 __global__ void __launch_bounds__(256) lidf_fingerprint_multi_kernel(FpSegsM s, LidfPackGuardState* guards,
                                                                      int guard_stride) {
+    __shared__ unsigned long long part[4];
     int seg = 0;
     for (int k = 1; k < LIDF_FP_MULTI_SEGS; ++k) seg += (k < s.nseg && blockIdx.x >= s.blk0[k]) ? 1 : 0;
-    const unsigned n = s.n[seg], base = s.base[seg];
     const int grp = s.grp[seg];
-    LidfPackGuardState* g = (LidfPackGuardState*)((char*)guards + (size_t)grp * guard_stride);
-    const unsigned* __restrict__ p = s.p[seg];
-    const unsigned w0 = (blockIdx.x - s.blk0[seg]) * FP_WORDS;
-    unsigned long long acc = 0;
-#pragma unroll
-    for (int r = 0; r < FP_WORDS / 1024; ++r) {
-        unsigned w[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const unsigned i = w0 + (4 * r + j) * 256 + threadIdx.x;
-            w[j] = i < n ? p[i] : 0u;
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const unsigned i = w0 + (4 * r + j) * 256 + threadIdx.x;
-            if (i < n) acc += fp_mix(((unsigned long long)(base + i) << 32) | w[j]);
-        }
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned lo = __shfl_xor((unsigned)acc, o), hi = __shfl_xor((unsigned)(acc >> 32), o);
-        acc += ((unsigned long long)hi << 32) | lo;
-    }
-    __shared__ unsigned long long part[4];
-    __shared__ bool last;
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned long long was = atomicAdd(&g->acc, part[0] + part[1] + part[2] + part[3]);
-        asm volatile("" ::"v"(was));
-        last = atomicAdd(&g->ticket, 1u) == s.gblocks[grp] - 1;
-    }
-    __syncthreads();
-    if (last && threadIdx.x == 0) {
-        const unsigned long long h = atomicAdd(&g->acc, 0ull) + s.salt[grp];
-        g->dirty = (!g->valid || g->hash != h) ? 1 : 0;
-        g->hash = h;
-        g->valid = 1;
-        g->acc = 0;
-        g->ticket = 0;
-    }
+    const unsigned long long sum =
+        fp_slab_sum(s.p[seg], s.n[seg], s.base[seg], (blockIdx.x - s.blk0[seg]) * FP_WORDS, part);
+    fp_commit((LidfPackGuardState*)((char*)guards + (size_t)grp * guard_stride), sum, s.salt[grp], s.gblocks[grp]);
 }
 
 // segments sorted by group (grp ascending, every group non-empty); guards: ngrp states guard_stride bytes apart

@@ -532,24 +532,87 @@ __device__ __forceinline__ float pe_value(float q, int k) {
 
 
 #ifdef __HIPCC__
-__device__ __forceinline__ int block_scan_256(int v, int* s_tmp, int& total) {
-    // inclusive scan of one value per thread over 256 threads; returns exclusive prefix
+// Sum over the wavefront, every lane receives it (butterfly, xor 32 down to 1: the order is part of the result
+// of the floating-point instantiations).
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// Exclusive prefix of one value per thread over a workgroup of NT threads (256 or 1024), in thread order, and
+// the workgroup's total. T: int or unsigned; sh: NT / 64 words of LDS. Barrier contract: EVERY thread of the
+// workgroup calls it, and it contains two barriers — one between the store and the loads of `sh` (it also orders
+// whatever the caller wrote to LDS before the call), one after the loads, so `sh` is free again on return and
+// a loop may call it round after round with nothing but registers carried over.
+template <int NT, typename T>
+__device__ __forceinline__ T block_scan(T v, T* sh, T& total) {
+    static_assert(NT == 256 || NT == 1024, "block_scan: 256 or 1024 threads");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
+    T inc = v;
 #pragma unroll
     for (int s = 1; s < 64; s <<= 1) {
-        const int o = __shfl_up(inc, s);
+        const T o = __shfl_up(inc, s);
         if (lane >= s) inc += o;
     }
-    if (lane == 63) s_tmp[wave] = inc;
+    if (lane == 63) sh[wave] = inc;
     __syncthreads();
-    int wpre = 0;
-    for (int w = 0; w < wave; ++w) wpre += s_tmp[w];
-    total = s_tmp[0] + s_tmp[1] + s_tmp[2] + s_tmp[3];
+    T wpre = 0, tot = 0;
+    for (int w = 0; w < NT / 64; ++w) {
+        const T t = sh[w];
+        wpre += w < wave ? t : 0;
+        tot += t;
+    }
     __syncthreads();
+    total = tot;
     return wpre + inc - v;
 }
 
+// mask element types as torch.nonzero accepts them: 0 f32, 1 u8 / bool, 2 i32, else i64. NaN counts as non-zero.
+__device__ __forceinline__ bool mask_nonzero(const void* mask, int dtype, long long i) {
+    switch (dtype) {
+        case 0: return ((const float*)mask)[i] != 0.f;
+        case 1: return ((const unsigned char*)mask)[i] != 0;
+        case 2: return ((const int*)mask)[i] != 0;
+        default: return ((const long long*)mask)[i] != 0;
+    }
+}
+
+// Point / voxel inside test — extensions/pcl_aabb/pcl_aabb_cuda_kernel.cu:23-44, in its order: inclusive bounds,
+// and a NaN coordinate fails no comparison, so it is inside.
+__device__ __forceinline__ bool inside_box(float x, float y, float z, const float* vb) {
+    if ((x < vb[0]) || (x > vb[3])) return false;
+    if ((y < vb[1]) || (y > vb[4])) return false;
+    if ((z < vb[2]) || (z > vb[5])) return false;
+    return true;
+}
+
+// Occupied cell k (key ((b * rx + cx) * ry + cy) * rz + cz) -> row v of the voxel tables: occ_bid_coord [V,4],
+// voxel_bound [V,6] (LIDF.get_occ_vox_bound, models/pipeline.py:162-201) and, where asked for, the image index on
+// its own ([V] i32: what the box tests take) and the voxel centre.
+__device__ __forceinline__ void vox_row_write(int k, int v, const GridSpec& g, int* __restrict__ occ,
+                                              float* __restrict__ vbound, int* __restrict__ vox_bid,
+                                              float* __restrict__ vox_center) {
+    int rem = k;
+    const int cz = rem % g.r[2]; rem /= g.r[2];
+    const int cy = rem % g.r[1]; rem /= g.r[1];
+    const int cx = rem % g.r[0]; rem /= g.r[0];
+    occ[4 * v + 0] = rem;
+    if (vox_bid) vox_bid[v] = rem;
+    occ[4 * v + 1] = cx;
+    occ[4 * v + 2] = cy;
+    occ[4 * v + 3] = cz;
+    const int c[3] = {cx, cy, cz};
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float lo = g.xmin[a] + (float)c[a] * g.crop;  // pipeline.py:186
+        vbound[6 * v + a] = lo;
+        vbound[6 * v + 3 + a] = lo + g.crop;               // :187
+        // intersect_pos_type 'rel': the voxel centre (bound_min + bound_max) / 2 (pipeline.py:355-360)
+        if (vox_center) vox_center[3 * v + a] = (lo + (lo + g.crop)) / 2.f;
+    }
+}
 #endif  // __HIPCC__
 
 #ifdef __HIPCC__
@@ -570,14 +633,6 @@ __device__ __forceinline__ void lb_store(unsigned long long* st, long long i, un
                                          unsigned long long v) {
     __hip_atomic_store(st + i, (flag << 62) | v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ __forceinline__ unsigned long long lb_wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned lo = __shfl_xor((unsigned)v, o), hi = __shfl_xor((unsigned)(v >> 32), o);
-        v += ((unsigned long long)hi << 32) | lo;
-    }
-    return v;
-}
 // exclusive prefix of workgroup `bid`; every lane of ONE wavefront calls it and receives the result
 __device__ __forceinline__ unsigned long long lb_exclusive(const unsigned long long* st, long long bid,
                                                            int lane) {
@@ -593,7 +648,7 @@ __device__ __forceinline__ unsigned long long lb_exclusive(const unsigned long l
         }
         const unsigned long long inc = __ballot((w >> 62) == LIDF_LB_INC);
         const int first = inc ? __builtin_ctzll(inc) : 64;
-        run += lb_wave_sum(lane <= first ? (w & LIDF_LB_MASK) : 0ull);
+        run += wave_sum(lane <= first ? (w & LIDF_LB_MASK) : 0ull);
         if (inc) break;
     }
     return run;

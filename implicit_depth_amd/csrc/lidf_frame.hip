@@ -99,7 +99,7 @@ __global__ void __launch_bounds__(256) lidf_frame_head_kernel(FrameHeadArgs a) {
                                    a.valid_xyz, a.valid_rgb, a.cell_flag, a.pt_key);
         }
         int tot;
-        const int ex = block_scan_256(ok ? 1 : 0, s_tmp, tot);
+        const int ex = block_scan<256>(ok ? 1 : 0, s_tmp, tot);
         if (threadIdx.x == 0) lb_store(a.stL, bid, bid == 0 ? LIDF_LB_INC : LIDF_LB_AGG, (unsigned)tot);
         if (threadIdx.x < 64) {
             const unsigned long long pre = bid > 0 ? lb_exclusive(a.stL, bid, lane) : 0ull;
@@ -128,8 +128,8 @@ __global__ void __launch_bounds__(256) lidf_frame_head_kernel(FrameHeadArgs a) {
         nm += fm[k] ? 1 : 0;
     }
     int tv, tm;
-    const int ev = block_scan_256(nv, s_tmp, tv);
-    const int em = block_scan_256(nm, s_tmp, tm);
+    const int ev = block_scan<256>(nv, s_tmp, tv);
+    const int em = block_scan<256>(nm, s_tmp, tm);
     const unsigned long long own = ((unsigned long long)tv << 31) | (unsigned long long)tm;
     if (threadIdx.x == 0) lb_store(a.stA, bid, bid == 0 ? LIDF_LB_INC : LIDF_LB_AGG, own);
     if (threadIdx.x < 64) {
@@ -182,7 +182,7 @@ __global__ void __launch_bounds__(256) lidf_frame_head_kernel(FrameHeadArgs a) {
     }
     int cg = 0, tg = 0;
     if (!list_mode) {   // rank of the in-grid points among the selected valid points
-        const int eg = block_scan_256(ng, s_tmp, tg);
+        const int eg = block_scan<256>(ng, s_tmp, tg);
         if (threadIdx.x == 0) lb_store(a.stB, bid, bid == 0 ? LIDF_LB_INC : LIDF_LB_AGG, (unsigned)tg);
         if (threadIdx.x < 64) {
             const unsigned long long pre = bid > 0 ? lb_exclusive(a.stB, bid, lane) : 0ull;
@@ -223,51 +223,17 @@ __global__ void __launch_bounds__(1024) lidf_frame_cells_kernel(const int* __res
                                                                  int* __restrict__ vox_start) {
     __shared__ int s_w[16];
     const long long cpi = (long long)g.r[0] * g.r[1] * g.r[2];   // cells per image
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int carry = 0;
     for (long long b = 0; b < ncell; b += 1024) {
         const long long k = b + threadIdx.x;
         const int f = (k < ncell && cell_flag[k] != 0) ? 1 : 0;
-        int inc = f;
-#pragma unroll
-        for (int s = 1; s < 64; s <<= 1) {
-            const int o = __shfl_up(inc, s);
-            if (lane >= s) inc += o;
-        }
-        __syncthreads();
-        if (lane == 63) s_w[wave] = inc;
-        __syncthreads();
-        int wpre = 0, total = 0;
-        for (int w = 0; w < 16; ++w) {
-            const int t = s_w[w];
-            wpre += w < wave ? t : 0;
-            total += t;
-        }
-        const int v = carry + wpre + inc - f;
+        int total;
+        const int v = carry + block_scan<1024>(f, s_w, total);
         if (k < ncell) {
             // the voxels are in cell order, image-major: image i owns voxels [vox_start[i], vox_start[i + 1])
             if (vox_start && k % cpi == 0) vox_start[k / cpi] = v;
             cell_rank[k] = f ? v : -1;   // cell -> voxel table (-1: not occupied)
-            if (f) {
-                int rem = (int)k;
-                const int cz = rem % g.r[2]; rem /= g.r[2];
-                const int cy = rem % g.r[1]; rem /= g.r[1];
-                const int cx = rem % g.r[0]; rem /= g.r[0];
-                occ[4 * v + 0] = rem;
-                vox_bid[v] = rem;   // the image index on its own ([V] i32: what the box tests take)
-                occ[4 * v + 1] = cx;
-                occ[4 * v + 2] = cy;
-                occ[4 * v + 3] = cz;
-                const int c[3] = {cx, cy, cz};
-#pragma unroll
-                for (int a = 0; a < 3; ++a) {
-                    const float lo = g.xmin[a] + (float)c[a] * g.crop;  // pipeline.py:186
-                    vbound[6 * v + a] = lo;
-                    vbound[6 * v + 3 + a] = lo + g.crop;               // :187
-                    // intersect_pos_type 'rel': the voxel centre (bound_min + bound_max) / 2 (pipeline.py:355-360)
-                    if (vox_center) vox_center[3 * v + a] = (lo + (lo + g.crop)) / 2.f;
-                }
-            }
+            if (f) vox_row_write((int)k, v, g, occ, vbound, vox_bid, vox_center);
         }
         carry += total;
     }

@@ -24,15 +24,6 @@ constexpr int LOSS_BLOCK = 256;
 constexpr int NSUM = 9;
 enum { S_POS, S_PROB, S_SURF, S_DX, S_DY, S_ACC, S_ERR, S_ELEM, S_ANGLE };
 
-// the comparisons of lidf_pcl_aabb_dense_kernel (extensions/pcl_aabb/pcl_aabb_cuda_kernel.cu:23-44), in its order:
-// inclusive bounds, and a NaN coordinate fails no comparison, so it is inside
-__device__ __forceinline__ bool label_inside(float x, float y, float z, const float* vb) {
-    if ((x < vb[0]) || (x > vb[3])) return false;
-    if ((y < vb[1]) || (y > vb[4])) return false;
-    if ((z < vb[2]) || (z > vb[5])) return false;
-    return true;
-}
-
 // G lanes per ray (a wavefront takes 64 / G rays): a geometry-derived frame has a handful of pairs per ray.
 template <int G>
 __global__ void lidf_pair_labels_kernel(const float* __restrict__ xyz, const int* __restrict__ ray_bid,
@@ -60,7 +51,7 @@ __global__ void lidf_pair_labels_kernel(const float* __restrict__ xyz, const int
             const float* src = vbound + 6 * (size_t)pair_vox[i];
 #pragma unroll
             for (int k = 0; k < 6; ++k) vb[k] = src[k];
-            const bool in = label_inside(x, y, z, vb);
+            const bool in = inside_box(x, y, z, vb);
             label[i] = in ? 1 : 0;
             labelf[i] = in ? 1.f : 0.f;
             if (in) {
@@ -136,12 +127,6 @@ __device__ __forceinline__ float cosine(const float* a, const float* b, float& n
         c += (a[k] / na) * bh[k];
     }
     return c;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s);
-    return v;
 }
 
 template <bool PAIRS>

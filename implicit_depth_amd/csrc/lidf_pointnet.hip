@@ -568,28 +568,14 @@ __global__ void __launch_bounds__(256) lidf_group_count_kernel(const int* __rest
 __global__ void __launch_bounds__(1024) lidf_group_scan_kernel(int* __restrict__ counts, int V,
                                                                int* __restrict__ cursor) {
     __shared__ int s_w[16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int carry = 0;
     for (int b = 0; b < V; b += 1024) {
         const int k = b + threadIdx.x;
         const int c = k < V ? counts[k] : 0;
-        int inc = c;
-#pragma unroll
-        for (int sft = 1; sft < 64; sft <<= 1) {
-            const int o = __shfl_up(inc, sft);
-            if (lane >= sft) inc += o;
-        }
-        __syncthreads();
-        if (lane == 63) s_w[wave] = inc;
-        __syncthreads();
-        int wpre = 0, total = 0;
-        for (int w = 0; w < 16; ++w) {
-            const int t = s_w[w];
-            wpre += w < wave ? t : 0;
-            total += t;
-        }
+        int total;
+        const int ex = block_scan<1024>(c, s_w, total);
         if (k < V) {
-            cursor[k] = carry + wpre + inc - c;
+            cursor[k] = carry + ex;
             counts[k] = 0;   // (ready for the next call)
         }
         carry += total;

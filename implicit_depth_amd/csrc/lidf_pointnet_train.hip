@@ -267,7 +267,6 @@ __global__ void __launch_bounds__(1024) lidf_pnet_tables_kernel(const int* __res
                                                                 const int* __restrict__ n_perm, int ch,
                                                                 int* __restrict__ vstart, int* __restrict__ first) {
     __shared__ int s_w[16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int total = *n_perm;
     int carry = 0;
     for (int b = 0; b < V; b += 1024) {
@@ -279,22 +278,9 @@ __global__ void __launch_bounds__(1024) lidf_pnet_tables_kernel(const int* __res
             vstart[v] = beg;
             c = (end - beg + ch - 1) / ch;
         }
-        int inc = c;
-#pragma unroll
-        for (int sft = 1; sft < 64; sft <<= 1) {
-            const int o = __shfl_up(inc, sft);
-            if (lane >= sft) inc += o;
-        }
-        __syncthreads();
-        if (lane == 63) s_w[wave] = inc;
-        __syncthreads();
-        int wpre = 0, tot = 0;
-        for (int w = 0; w < 16; ++w) {
-            const int t = s_w[w];
-            wpre += w < wave ? t : 0;
-            tot += t;
-        }
-        if (v < V) first[v] = carry + wpre + inc - c;
+        int tot;
+        const int ex = block_scan<1024>(c, s_w, tot);
+        if (v < V) first[v] = carry + ex;
         carry += tot;
     }
     if (threadIdx.x == 0) {

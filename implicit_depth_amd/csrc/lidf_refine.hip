@@ -2,14 +2,6 @@
 // (RefineNet.get_pred_refine, models/pipeline.py:922-1030), built with -ffp-contract=off.
 #include "lidf_launch.h"
 
-// inside test of extensions/pcl_aabb/pcl_aabb_cuda_kernel.cu:23-44 (inclusive bounds)
-__device__ __forceinline__ bool inside_box(float x, float y, float z, const float* vb) {
-    if ((x < vb[0]) || (x > vb[3])) return false;
-    if ((y < vb[1]) || (y > vb[4])) return false;
-    if ((z < vb[2]) || (z > vb[5])) return false;
-    return true;
-}
-
 // One thread per ray:
 //   end_voxel = max( voxel of the arg-max pair (0 for a ray without pairs: the dummy row,
 //                    pipeline.py:941-943), largest occupied voxel of the same image containing

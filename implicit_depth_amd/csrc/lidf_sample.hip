@@ -38,15 +38,6 @@
 #define SAMPLE_ROUNDS 6
 #define SAMPLE_KEY_WORD 0x80000000u   // counter word 3 of the per-image key draws (slots are < 2^31)
 
-__device__ __forceinline__ bool sample_mask_nonzero(const void* mask, int dtype, long long i) {
-    switch (dtype) {   // as lidf_miss_ray_count: NaN != 0 is true
-        case 0: return ((const float*)mask)[i] != 0.f;
-        case 1: return ((const unsigned char*)mask)[i] != 0;
-        case 2: return ((const int*)mask)[i] != 0;
-        default: return ((const long long*)mask)[i] != 0;
-    }
-}
-
 __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0,
                                               unsigned k1, unsigned out[4]) {
     for (int r = 0; r < 10; ++r) {
@@ -110,7 +101,7 @@ __global__ __launch_bounds__(64 * SAMPLE_BLOCK_WAVES) void lidf_sample_blocks_ke
     if (blk >= nblk) return;   // (uniform per wave)
     const int by = blk / bw, bx = blk - by * bw;
     const long long pix = (long long)b * H * W + (long long)(by * 8 + (lane >> 3)) * W + bx * 8 + (lane & 7);
-    const unsigned long long m = __ballot(sample_mask_nonzero(mask, dtype, pix));
+    const unsigned long long m = __ballot(mask_nonzero(mask, dtype, pix));
     if (lane == 0) masks[(size_t)b * nblk + blk] = m;
 }
 
@@ -118,33 +109,20 @@ __global__ __launch_bounds__(64 * SAMPLE_BLOCK_WAVES) void lidf_sample_blocks_ke
 __global__ __launch_bounds__(SAMPLE_THREADS) void lidf_sample_scan_kernel(
     const unsigned long long* __restrict__ masks, int nblk, int* __restrict__ prefix, int* __restrict__ valid_cnt) {
     __shared__ int s_wave[SAMPLE_WAVES];
-    __shared__ int s_carry;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const unsigned long long* mk = masks + (size_t)b * nblk;
     int* pre = prefix + (size_t)b * (nblk + 1);
-    if (tid == 0) {
-        s_carry = 0;
-        pre[0] = 0;
-    }
-    __syncthreads();
+    if (tid == 0) pre[0] = 0;
+    int carry = 0;
     for (int base = 0; base < nblk; base += SAMPLE_THREADS) {
         const int blk = base + tid;
-        int inc = blk < nblk ? __popcll(mk[blk]) : 0;
-        for (int s = 1; s < 64; s <<= 1) {
-            const int o = __shfl_up(inc, s);
-            if (lane >= s) inc += o;
-        }
-        if (lane == 63) s_wave[wave] = inc;
-        __syncthreads();
-        int upto = s_carry;
-        for (int k = 0; k < wave; ++k) upto += s_wave[k];
-        upto += inc;
-        if (blk < nblk) pre[blk + 1] = upto;
-        __syncthreads();
-        if (tid == SAMPLE_THREADS - 1) s_carry = upto;
-        __syncthreads();
+        const int c = blk < nblk ? __popcll(mk[blk]) : 0;
+        int tot;
+        const int ex = block_scan<SAMPLE_THREADS>(c, s_wave, tot);
+        if (blk < nblk) pre[blk + 1] = carry + ex + c;
+        carry += tot;
     }
-    if (tid == 0) valid_cnt[b] = s_carry;
+    if (tid == 0) valid_cnt[b] = carry;
 }
 
 // 3: one thread, one slot

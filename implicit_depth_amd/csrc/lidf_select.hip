@@ -90,29 +90,6 @@ __device__ __forceinline__ void sel_load(const SelJob& j, long long q, float* v,
     }
 }
 
-// Exclusive prefix of c over the workgroup's threads in thread order, and the workgroup's total. sh: 4 words.
-__device__ __forceinline__ unsigned sel_scan(unsigned c, unsigned* sh, unsigned& total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    unsigned inc = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned o = __shfl_up(inc, d);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63) sh[wv] = inc;
-    __syncthreads();
-    unsigned base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < SEL_BLOCK / 64; ++w) {
-        const unsigned s = sh[w];
-        base += w < wv ? s : 0u;
-        tot += s;
-    }
-    __syncthreads();   // (sh is free again)
-    total = tot;
-    return base + inc - c;
-}
-
 // The bin that holds the k-th largest element of a finished histogram (1 <= k <= its total) and how many are still
 // to take inside it. Thread t owns bins NB-1 - (t*PER .. t*PER+PER-1), the highest first. sh: 6 words.
 struct SelPick {
@@ -131,7 +108,7 @@ __device__ __forceinline__ SelPick sel_pick(const unsigned* __restrict__ hist, u
     }
     if (t == 0) sh[4] = 0u, sh[5] = 1u;
     unsigned total;
-    unsigned cum = sel_scan(s, sh, total);   // (its first barrier also orders the two stores above)
+    unsigned cum = block_scan<SEL_BLOCK>(s, sh, total);   // (its first barrier also orders the two stores above)
     if (cum < k && k <= cum + s) {
 #pragma unroll
         for (int i = 0; i < PER; ++i) {
@@ -200,15 +177,9 @@ __global__ __launch_bounds__(SEL_BLOCK) void lidf_select_hist_kernel(const SelJo
     }
 }
 
-__device__ __forceinline__ double sel_wave_sum(double v) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s);
-    return v;
-}
-
 // The workgroup's sum in a fixed order: wavefront butterflies, then the four wavefronts in order (thread 0 holds it).
 __device__ __forceinline__ double sel_block_sum(double v, double* dsh) {
-    const double t = sel_wave_sum(v);
+    const double t = wave_sum(v);
     if ((threadIdx.x & 63) == 0) dsh[threadIdx.x >> 6] = t;
     __syncthreads();
     double r = 0.0;
@@ -243,7 +214,7 @@ __global__ __launch_bounds__(SEL_BLOCK) void lidf_select_partial_kernel(const Se
         }
     }
     unsigned eq_total;
-    sel_scan(eq, sh, eq_total);
+    block_scan<SEL_BLOCK>(eq, sh, eq_total);
     const double sum = sel_block_sum(acc, dsh);
     if (threadIdx.x == 0) j.tie_cnt[blockIdx.x] = eq_total, j.partial[blockIdx.x] = sum;
 }
@@ -264,7 +235,7 @@ __global__ __launch_bounds__(SEL_BLOCK) void lidf_select_final_kernel(const SelJ
                 const int s = base + threadIdx.x;
                 const unsigned c = s < j.nslab ? j.tie_cnt[s] : 0u;
                 unsigned tot;
-                const unsigned exc = sel_scan(c, sh, tot);
+                const unsigned exc = block_scan<SEL_BLOCK>(c, sh, tot);
                 if (s < j.nslab) j.tie_pre[s] = carry + exc;
                 carry += tot;
             }
@@ -324,7 +295,7 @@ __global__ __launch_bounds__(SEL_BLOCK) void lidf_select_weights_kernel(const Se
         }
         if (ranked) {   // (the same in every thread of the workgroup)
             unsigned tot;
-            unsigned r = run + sel_scan(c, sh, tot);
+            unsigned r = run + block_scan<SEL_BLOCK>(c, sh, tot);
 #pragma unroll
             for (int i = 0; i < 4; ++i)
                 if (eq[i]) {

@@ -618,12 +618,6 @@ extern "C" hipError_t lidf_launch_out_act(const float* pre, long long n, int use
 // Column sums: per-workgroup partial vectors, summed in a fixed order by lidf_colsum_reduce_kernel
 // (deterministic).
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-
 __global__ void __launch_bounds__(256) lidf_l4_backward_kernel(
     const float* __restrict__ goff, const float* __restrict__ h3, const float* __restrict__ w4,
     float slope, long long n, long long rows_per_wg, float* __restrict__ dz3,

@@ -143,7 +143,9 @@ def test_pcl_aabb(cuda, N, V):
     assert (last == exp).all()
 
 
-@pytest.mark.parametrize("n", [0, 1, 1023, 1024, 1025, 300000])
+@pytest.mark.parametrize("n", [0, 1, 1023, 1024, 1025, 300000,
+                               4095, 4096, 4097,    # a round of the one-workgroup form: 1024 threads x 4 entries
+                               32768, 32769])       # the last one-workgroup length, the first three-launch length
 def test_exclusive_scan(cuda, n):
     from implicit_depth_amd import _lib
     g = torch.Generator().manual_seed(n)

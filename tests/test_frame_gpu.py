@@ -48,20 +48,41 @@ def _compare(dd, ref):
         assert torch.equal(dd[k].long(), ref[k].long()), k
 
 
+def _occupy_checkerboard(batch):
+    """Moves the valid points so that every second cell of every image's 9^3 grid (even coordinate sum, 365 cells) is
+    occupied: the j-th valid pixel of an image lies in chosen cell j % 365. Returns the number of voxels."""
+    k = torch.arange(729)
+    cells = k[(k // 81 + (k // 9) % 9 + k % 9) % 2 == 0]
+    B, _, h, w = batch["xyz_corrupt"].shape
+    valid = (batch["depth_corrupt"] != 0).reshape(B, h * w)
+    assert int(valid.sum(1).min()) >= cells.numel()
+    cell = cells[(torch.cumsum(valid.long(), 1) - 1) % cells.numel()]
+    c = torch.stack((cell // 81, (cell // 9) % 9, cell % 9), 1).float()            # [B, 3, h w]
+    pts = torch.tensor([-1.125, -1.125, -0.125]).reshape(1, 3, 1) + (c + 0.5) * 0.25   # the cells' centres
+    batch["xyz_corrupt"] = (pts * valid.unsqueeze(1).float()).reshape(B, 3, h, w).contiguous()
+    return B * cells.numel()
+
+
 @pytest.mark.parametrize("shape,stride,use_all_pix,graph", [((1, 240, 320), 6, True, True),
                                                             ((1, 240, 320), None, True, False),
                                                             ((2, 48, 64), None, False, True),
                                                             ((4, 60, 80), 3, True, True),
                                                             ((4, 240, 320), 6, True, True),
-                                                            ((4, 240, 320), None, True, False)])
+                                                            ((4, 240, 320), None, True, False),
+                                                            ((3, 30, 40, "checkerboard"), None, True, False)])
 def test_frame_equals_stepwise_path(cuda, shape, stride, use_all_pix, graph):
+    """The "checkerboard" case holds V = 3 * 365 = 1095 voxels, so the one-workgroup scan of the per-voxel point
+    counts (the grouping in front of PointNet) takes a second round; P / R = 6.82 keeps the per-ray softmax on its
+    8-lane form on both paths (with every cell occupied each ray has 9 to 18 pairs, and the stepwise path, which
+    knows P on the host, switches to the 64-lane form: another order of the same sum)."""
     from implicit_depth_amd import pipeline as pl
     from implicit_depth_amd.synthetic import synthetic_batch
-    B, h, w = shape
+    B, h, w = shape[:3]
     models = _models(cuda)
     opt = pl.LidfOptions(valid_stride=stride, refine_use_all_pix=use_all_pix)
     runner = pl.FrameRunner(B, h, w, cuda, models[0], models[1], models[2], opt, models[3], models[4])
     batch, feat = synthetic_batch(B, h, w, seed=77)
+    V = _occupy_checkerboard(batch) if len(shape) > 3 else None
     batch, feat = _dev(batch, cuda), feat.to(cuda)
     with torch.no_grad():
         runner.load(batch, feat)
@@ -75,6 +96,7 @@ def test_frame_equals_stepwise_path(cuda, shape, stride, use_all_pix, graph):
     assert (c["R"], c["P"], c["V"]) == (ref["miss_ray_dir"].shape[0], ref["pair_ray"].shape[0],
                                         ref["voxel_bound"].shape[0])
     assert c["NV"] == ref["revidx"].shape[0] and c["NPN"] == c["NV"] + c["R"] and c["OVERFLOW"] == 0
+    assert V is None or c["V"] == V
     _compare(dd, ref)
     # a second, different batch through the same runner (and the same graph): nothing stale
     batch2, feat2 = synthetic_batch(B, h, w, seed=78, hole_frac=1.3)
