@@ -513,6 +513,13 @@ extern "C" hipError_t lidf_launch_zero_segments(float* const* ptrs, const long l
 // ------------------------------------------------------------------------------------------------
 // G lanes per ray: 64 (a wavefront) for long candidate lists, 8 for short ones (a geometry-derived
 // frame has 3-4 pairs per ray: a wavefront per ray would idle 60 of its lanes).
+// Both widths sum a ray's exponentials in ONE order, so that the same list gives the same bits whichever
+// width the launcher picks (the frame path, with its counts on the device, always takes 8 lanes; the
+// stepwise path takes 64 on a dense list): 64 slots, slot j adding e[j], e[j + 64], ... in ascending
+// order from 0.f, then a butterfly over the slots with strides 32, 16, 8, 4, 2, 1. At 64 lanes a lane
+// is a slot; at 8 lanes lane l holds slots l + 8 q and combines them itself before the shuffles. The
+// fast paths (one pair per lane at most) are that order with zeros in the missing slots. Max and
+// arg-max do not depend on the order.
 template <int G>
 __device__ __forceinline__ float group_max(float v) {
 #pragma unroll
@@ -594,7 +601,26 @@ __global__ void lidf_ray_reduce_kernel(const float* __restrict__ prob,
             for (int i = beg[u] + lane; i < end[u]; i += G) m = fmaxf(m, prob[i]);
             m = group_max<G>(m);
             float s = 0.f;
-            for (int i = beg[u] + lane; i < end[u]; i += G) s += expf(prob[i] - m);
+            if constexpr (G == 8) {
+                // the canonical order at 8 lanes: lane l holds slots l + 8 q in a[q]; their in-lane
+                // combination q ^ 4, q ^ 2, q ^ 1 is the butterfly's strides 32, 16, 8
+                float a[8];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) a[q] = 0.f;
+                for (int i0 = beg[u] + lane; i0 < end[u]; i0 += 64) {
+#pragma unroll
+                    for (int q = 0; q < 8; ++q)
+                        if (i0 + 8 * q < end[u]) a[q] += expf(prob[i0 + 8 * q] - m);
+                }
+#pragma unroll
+                for (int h = 4; h >= 1; h >>= 1) {
+#pragma unroll
+                    for (int q = 0; q < h; ++q) a[q] += a[q + h];
+                }
+                s = a[0];
+            } else {
+                for (int i = beg[u] + lane; i < end[u]; i += G) s += expf(prob[i] - m);
+            }
             s = group_sum<G>(s);
             for (int i = beg[u] + lane; i < end[u]; i += G) {
                 const float v = expf(prob[i] - m) / s;

@@ -48,11 +48,9 @@ def _compare(dd, ref):
         assert torch.equal(dd[k].long(), ref[k].long()), k
 
 
-def _occupy_checkerboard(batch):
-    """Moves the valid points so that every second cell of every image's 9^3 grid (even coordinate sum, 365 cells) is
-    occupied: the j-th valid pixel of an image lies in chosen cell j % 365. Returns the number of voxels."""
-    k = torch.arange(729)
-    cells = k[(k // 81 + (k // 9) % 9 + k % 9) % 2 == 0]
+def _occupy(batch, cells):
+    """Moves the valid points so that the cells `cells` (indices into the 9^3 grid) of every image are occupied: the
+    j-th valid pixel of an image lies in chosen cell j % len(cells). Returns the number of voxels."""
     B, _, h, w = batch["xyz_corrupt"].shape
     valid = (batch["depth_corrupt"] != 0).reshape(B, h * w)
     assert int(valid.sum(1).min()) >= cells.numel()
@@ -63,18 +61,36 @@ def _occupy_checkerboard(batch):
     return B * cells.numel()
 
 
+def _occupy_checkerboard(batch):
+    """Every second cell of every image's 9^3 grid (even coordinate sum, 365 cells)."""
+    k = torch.arange(729)
+    return _occupy(batch, k[(k // 81 + (k // 9) % 9 + k % 9) % 2 == 0])
+
+
+def _occupy_all(batch):
+    """Every cell of every image's 9^3 grid: each ray crosses 9 to 18 voxels."""
+    return _occupy(batch, torch.arange(729))
+
+
+OCCUPY = {"checkerboard": _occupy_checkerboard, "dense": _occupy_all}
+# the smallest 4:3 image whose valid pixels (about 90 % of them) number 729 in each of the two images: 741 and 735
+DENSE_SHAPE = (2, 25, 33, "dense")
+
+
 @pytest.mark.parametrize("shape,stride,use_all_pix,graph", [((1, 240, 320), 6, True, True),
                                                             ((1, 240, 320), None, True, False),
                                                             ((2, 48, 64), None, False, True),
                                                             ((4, 60, 80), 3, True, True),
                                                             ((4, 240, 320), 6, True, True),
                                                             ((4, 240, 320), None, True, False),
-                                                            ((3, 30, 40, "checkerboard"), None, True, False)])
+                                                            ((3, 30, 40, "checkerboard"), None, True, False),
+                                                            (DENSE_SHAPE, None, True, False)])
 def test_frame_equals_stepwise_path(cuda, shape, stride, use_all_pix, graph):
     """The "checkerboard" case holds V = 3 * 365 = 1095 voxels, so the one-workgroup scan of the per-voxel point
-    counts (the grouping in front of PointNet) takes a second round; P / R = 6.82 keeps the per-ray softmax on its
-    8-lane form on both paths (with every cell occupied each ray has 9 to 18 pairs, and the stepwise path, which
-    knows P on the host, switches to the 64-lane form: another order of the same sum)."""
+    counts (the grouping in front of PointNet) takes a second round. The "dense" case occupies every cell: each ray
+    has 9 to 18 pairs, P / R > 8, so the stepwise path, which knows P on the host, runs the per-ray softmax at 64
+    lanes per ray while the frame path runs it at 8. Both widths sum in one order (lidf_ray_reduce_kernel), so
+    the two paths stay bit-equal there too."""
     from implicit_depth_amd import pipeline as pl
     from implicit_depth_amd.synthetic import synthetic_batch
     B, h, w = shape[:3]
@@ -82,7 +98,7 @@ def test_frame_equals_stepwise_path(cuda, shape, stride, use_all_pix, graph):
     opt = pl.LidfOptions(valid_stride=stride, refine_use_all_pix=use_all_pix)
     runner = pl.FrameRunner(B, h, w, cuda, models[0], models[1], models[2], opt, models[3], models[4])
     batch, feat = synthetic_batch(B, h, w, seed=77)
-    V = _occupy_checkerboard(batch) if len(shape) > 3 else None
+    V = OCCUPY[shape[3]](batch) if len(shape) > 3 else None
     batch, feat = _dev(batch, cuda), feat.to(cuda)
     with torch.no_grad():
         runner.load(batch, feat)
@@ -97,6 +113,7 @@ def test_frame_equals_stepwise_path(cuda, shape, stride, use_all_pix, graph):
                                         ref["voxel_bound"].shape[0])
     assert c["NV"] == ref["revidx"].shape[0] and c["NPN"] == c["NV"] + c["R"] and c["OVERFLOW"] == 0
     assert V is None or c["V"] == V
+    assert shape[3:] != ("dense",) or c["P"] > 8 * c["R"]
     _compare(dd, ref)
     # a second, different batch through the same runner (and the same graph): nothing stale
     batch2, feat2 = synthetic_batch(B, h, w, seed=78, hole_frac=1.3)
@@ -265,18 +282,23 @@ def test_frame_position_types(cuda, pos, rpos, rpnet):
         assert not torch.equal(ref0["pred_offset"], ref["pred_offset"])
 
 
-@pytest.mark.parametrize("shape,graph", [((1, 240, 320), True), ((3, 37, 53), False)])
+@pytest.mark.parametrize("shape,graph", [((1, 240, 320), True), ((3, 37, 53), False), (DENSE_SHAPE, False)])
 def test_frame_offsets_for_selected_pairs_only(cuda, shape, graph):
     """offsets='selected' (opt-in): offset_dec on the arg-max pair of every ray only. Everything the reference
     reads downstream of get_pred (pred_prob_end, softmax, max_pair_id, pred_pos — models/pipeline.py:453-454 —,
     depth, stage 2, the statistics) is bit-identical to the default; pred_offset / pair_pred_pos agree at the
-    selected pairs; frame and stepwise paths agree with each other in this mode too."""
+    selected pairs; frame and stepwise paths agree with each other in this mode too. The "dense" case (every cell
+    occupied, every valid point kept: more than 8 pairs per ray) sends long rays through the selected-pair list that
+    lidf_ray_reduce_kernel writes and lidf_selected_finish_kernel reads, at 8 lanes on the frame path and 64 on the
+    stepwise one."""
     from implicit_depth_amd import pipeline as pl
     from implicit_depth_amd.synthetic import synthetic_batch
-    B, h, w = shape
+    B, h, w = shape[:3]
+    dense = shape[3:] == ("dense",)
     models = _models(cuda)
-    opt = pl.LidfOptions(valid_stride=3)
+    opt = pl.LidfOptions(valid_stride=None if dense else 3)
     batch, feat = synthetic_batch(B, h, w, seed=83)
+    V = OCCUPY[shape[3]](batch) if len(shape) > 3 else None
     batch, feat = _dev(batch, cuda), feat.to(cuda)
     full = pl.FrameRunner(B, h, w, cuda, *models[:3], opt, models[3], models[4])
     sel = pl.FrameRunner(B, h, w, cuda, *models[:3], opt, models[3], models[4], offsets="selected")
@@ -289,6 +311,7 @@ def test_frame_offsets_for_selected_pairs_only(cuda, shape, graph):
     ok, a = full.result()
     ok2, b = sel.result()
     assert ok and ok2 and a["counts"] == b["counts"]
+    assert not dense or (a["counts"]["V"] == V and a["counts"]["P"] > 8 * a["counts"]["R"])
     for k in ("pred_prob_end", "pred_prob_end_softmax", "pred_pos", "pred_depth", "pred_pos_refine",
               "pred_depth_refine", "occ_voxel_feat", "rayfeat"):
         assert torch.equal(a[k], b[k]), k
@@ -310,8 +333,9 @@ def test_frame_offsets_for_selected_pairs_only(cuda, shape, graph):
         ok3, c = pl.lidf_forward(batch, feat, models[0], models[1], models[2], opt, offsets="selected")
         pl.refine_forward(c, models[3], models[4], opt)
     assert ok3
-    for k in ("pred_prob_end", "pred_pos", "pred_depth", "pred_pos_refine"):
+    for k in ("pred_prob_end", "pred_prob_end_softmax", "pred_pos", "pred_depth", "pred_pos_refine"):
         assert torch.equal(b[k], c[k]), k
+    assert torch.equal(b["max_pair_id"].long(), c["max_pair_id"].long())
     assert torch.equal(b["pred_offset"][m], c["pred_offset"][m])
 
 
