@@ -10,8 +10,11 @@ Host-side mirror of the reference interface for this path (names follow the refe
   pipeline.lidf_forward_train                <- LIDF.forward, exp_type 'train' (one stage-1 training step)
   pipeline.refine_forward_train / train_refine_step  <- RefineNet.forward, exp_type 'train' / the two forward
                                                 calls of trainers/train_refine.py:374-393 (one stage-2 training step)
-  losses.compute_gt / lidf_loss              <- LIDF.compute_gt / compute_loss (train), models/pipeline.py:298-336, 468-566
-  losses.refine_loss                         <- RefineNet.compute_loss (train), models/pipeline.py:760-840
+  losses.compute_gt / lidf_loss              <- LIDF.compute_gt / compute_loss ('train', 'valid', 'test'),
+                                                models/pipeline.py:298-336, 468-650
+  losses.refine_loss                         <- RefineNet.compute_loss ('train', 'valid', 'test'), models/pipeline.py:760-919
+  pipeline.eval_loss / FrameRunner.loss_dict <- loss_dict of LIDF.forward / RefineNet.forward for 'valid' / 'test'
+                                                (what trainers' validate() / test() read)
   losses.topk_mean                           <- torch.topk + mean of hard-negative mining, :475-490, 767-770
   torch_ext.ext()                            <- the pybind11 operator module (extensions/*/jit.py)
 All compute goes through csrc/liblidf_hip.so (C ABI in include/lidf_hip.h).
@@ -22,8 +25,10 @@ from .decoders import (IEF, IMNet, Embedder, decoders_forward, decoders_forward_
 from .pointnet import PointNet2Stage  # noqa: F401
 from .losses import (LidfLossOptions, compute_gt, lidf_loss, lidf_loss_composite, refine_loss,  # noqa: F401
                      refine_loss_composite, topk_mean)
-from .pipeline import LidfOptions, lidf_forward_train, refine_forward_train, train_refine_step  # noqa: F401
+from .pipeline import (LidfOptions, eval_loss, lidf_forward_train, refine_forward_train,  # noqa: F401
+                       train_refine_step)
 
 __all__ = ["IEF", "IMNet", "Embedder", "PointNet2Stage", "decoders_forward", "decoders_forward_train",
            "get_embedder", "LidfLossOptions", "LidfOptions", "compute_gt", "lidf_loss", "lidf_loss_composite",
-           "lidf_forward_train", "refine_loss", "refine_loss_composite", "topk_mean", "refine_forward_train", "train_refine_step"]
+           "lidf_forward_train", "refine_loss", "refine_loss_composite", "topk_mean", "refine_forward_train", "train_refine_step",
+           "eval_loss"]

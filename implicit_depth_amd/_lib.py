@@ -180,6 +180,23 @@ class LidfRefineLossArgs(C.Structure):
     ]
 
 
+class LidfEvalLossArgs(C.Structure):
+    """struct LidfEvalLossArgs (include/lidf_hip.h)."""
+    _fields_ = [
+        ("n_rays", C.c_int64), ("n_pairs", C.c_int64),
+        ("batch", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("resize_metrics", C.c_int32),
+        ("xyz_base", C.c_void_p), ("xyz_gt", C.c_void_p), ("seg_mask", C.c_void_p), ("seg_dtype", C.c_int32),
+        ("ray_bid", C.c_void_p), ("ray_flat", C.c_void_p), ("pair_off", C.c_void_p), ("pix2ray", C.c_void_p),
+        ("gt_pos", C.c_void_p), ("pcl_label", C.c_void_p), ("gt_max_pair_id", C.c_void_p), ("n_label", C.c_void_p),
+        ("pred_pos", C.c_void_p), ("pred_prob", C.c_void_p),
+        ("pos_w", C.c_float), ("prob_w", C.c_float), ("surf_norm_w", C.c_float), ("smooth_w", C.c_float),
+        ("surf_norm_on", C.c_int32), ("smooth_on", C.c_int32),
+        ("loss", C.c_void_p), ("pos_unreduced", C.c_void_p), ("surf_norm_dist", C.c_void_p),
+        ("dx_dist", C.c_void_p), ("dy_dist", C.c_void_p), ("prob_unreduced", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
 class LidfTopkJob(C.Structure):
     """struct LidfTopkJob (include/lidf_hip.h)."""
     _fields_ = [("values", C.c_void_p), ("n", C.c_int64), ("count", C.c_void_p), ("mean", C.c_void_p),
@@ -319,6 +336,12 @@ SIGNATURES = {
     "lidf_stage1_hard_neg_f32": (C.c_int, [C.POINTER(LidfLossArgs), C.c_double, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "lidf_refine_hard_neg_f32": (C.c_int, [C.POINTER(LidfRefineLossArgs), C.c_double, _P, _P, _P, _P, _P, _SZ,
                                            _P]),
+    "lidf_stage1_eval_loss_workspace_bytes": (_SZ, [_I64, _I64]),
+    "lidf_refine_eval_loss_workspace_bytes": (_SZ, [_I64, _I64]),
+    "lidf_stage1_eval_loss_f32": (C.c_int, [C.POINTER(LidfEvalLossArgs), _P]),
+    "lidf_refine_eval_loss_f32": (C.c_int, [C.POINTER(LidfEvalLossArgs), _P]),
+    "lidf_stage1_eval_hard_neg_f32": (C.c_int, [C.POINTER(LidfEvalLossArgs), C.c_double, _P, _SZ, _P]),
+    "lidf_refine_eval_hard_neg_f32": (C.c_int, [C.POINTER(LidfEvalLossArgs), C.c_double, _P, _SZ, _P]),
 }
 
 _lib = None

@@ -3611,5 +3611,110 @@ LIDF_API int lidf_refine_hard_neg_f32(const LidfRefineLossArgs* args, double rat
                         (hipStream_t)stream);
 }
 
+// ---- The evaluation flavour of the two losses (lidf_loss.hip: <.., EVAL = true>) ----------------------
+// Workspace: the double partial sums | the depth-metrics workspace | its ten outputs (64 bytes) | the two depth
+// images of the bs == 1 branch.
+static const int EVAL_DST_H = 144, EVAL_DST_W = 256;   // cv2.resize(..., (256, 144)), models/pipeline.py:582
+
+static size_t eval_loss_ws_bytes(int64_t n_rays, int64_t resize_pixels) {
+    if (n_rays <= 0) return 0;
+    size_t n = lidf_eval_loss_partial_bytes(n_rays);
+    if (resize_pixels > 0) n += lidf_depth_metrics_ws_bytes() + 64 + 2 * (size_t)resize_pixels * sizeof(float);
+    return n;
+}
+LIDF_API size_t lidf_stage1_eval_loss_workspace_bytes(int64_t n_rays, int64_t resize_pixels) {
+    return eval_loss_ws_bytes(n_rays, resize_pixels);
+}
+LIDF_API size_t lidf_refine_eval_loss_workspace_bytes(int64_t n_rays, int64_t resize_pixels) {
+    return eval_loss_ws_bytes(n_rays, resize_pixels);
+}
+
+static int eval_loss_args(const LidfEvalLossArgs* a, bool pairs, LossArgs* k) {
+    if (!a || a->n_rays < 0 || a->batch < 0 || a->height < 0 || a->width < 0 || (pairs && a->n_pairs < 0))
+        return LIDF_ERR_BAD_ARG;
+    const long long npix = (long long)a->batch * a->height * a->width;
+    if (a->n_rays > 0x7ffffffeLL || (pairs && a->n_pairs > 0x7ffffffeLL) || npix > 0x7ffffffeLL)
+        return LIDF_ERR_UNSUPPORTED;
+    if (a->n_rays > 0 && (!a->xyz_base || !a->ray_bid || !a->ray_flat || !a->pix2ray || !a->gt_pos || !a->pred_pos ||
+                          npix == 0))
+        return LIDF_ERR_BAD_ARG;
+    if (pairs && a->n_rays > 0 && (!a->pair_off || !a->gt_max_pair_id || !a->n_label)) return LIDF_ERR_BAD_ARG;
+    if (pairs && a->n_pairs > 0 && (!a->pcl_label || !a->pred_prob)) return LIDF_ERR_BAD_ARG;
+    if (a->n_rays > 0 && a->resize_metrics &&
+        (a->batch != 1 || !a->xyz_gt || a->seg_dtype < 0 || a->seg_dtype > 2 || (a->seg_dtype != 0 && !a->seg_mask)))
+        return LIDF_ERR_BAD_ARG;
+    memset(k, 0, sizeof(*k));
+    k->R = a->n_rays, k->P = pairs ? a->n_pairs : 0, k->hw = (long long)a->height * a->width;
+    k->B = a->batch, k->H = a->height, k->W = a->width;
+    k->xyz = a->xyz_base, k->ray_bid = a->ray_bid, k->ray_flat = a->ray_flat, k->pix2ray = a->pix2ray;
+    k->gt_pos = a->gt_pos, k->pred_pos = a->pred_pos;
+    k->pos_w = a->pos_w, k->surf_w = a->surf_norm_w, k->smooth_w = a->smooth_w;
+    k->surf_on = a->surf_norm_on != 0, k->smooth_on = a->smooth_on != 0;
+    k->loss = a->loss, k->pos_un = a->pos_unreduced, k->surf_dist = a->surf_norm_dist;
+    k->dx_dist = a->dx_dist, k->dy_dist = a->dy_dist;
+    if (pairs) {
+        k->pair_off = a->pair_off, k->label = (const long long*)a->pcl_label;
+        k->gt_maxid = (const long long*)a->gt_max_pair_id, k->n_label = a->n_label;
+        k->logit = a->pred_prob, k->prob_w = a->prob_w, k->prob_un = a->prob_unreduced;
+    }
+    return LIDF_OK;
+}
+
+static int eval_loss_run(const LidfEvalLossArgs* args, bool pairs, hipStream_t st) {
+    LossArgs k;
+    int rc = eval_loss_args(args, pairs, &k);
+    if (rc) return rc;
+    if (k.R == 0) return LIDF_OK;
+    if (!k.loss) return LIDF_ERR_BAD_ARG;
+    // (the kernel stores the three per-ray vectors of the normals under one test)
+    if ((k.surf_dist || k.dx_dist || k.dy_dist) && !(k.surf_dist && k.dx_dist && k.dy_dist)) return LIDF_ERR_BAD_ARG;
+    const long long rpix = args->resize_metrics ? k.hw : 0;
+    if ((uintptr_t)args->workspace & 7) return LIDF_ERR_BAD_ARG;
+    if (!args->workspace || args->workspace_bytes < eval_loss_ws_bytes(k.R, rpix)) return LIDF_ERR_WORKSPACE;
+    char* ws = (char*)args->workspace;
+    k.partial = (double*)ws;
+    if (rpix > 0) {
+        char* mws = ws + lidf_eval_loss_partial_bytes(k.R);
+        float* mout = (float*)(mws + lidf_depth_metrics_ws_bytes());
+        float* pred_img = mout + 16;
+        float* gt_img = pred_img + rpix;
+        CHECK_HIP(hipMemsetAsync(mws, 0, lidf_depth_metrics_ws_bytes(), st));
+        CHECK_HIP(lidf_launch_eval_depth_images(k, args->xyz_gt, pred_img, gt_img, st));
+        CHECK_HIP(lidf_launch_depth_metrics(pred_img, gt_img, args->seg_mask, args->seg_mask ? args->seg_dtype : 0,
+                                            k.H, k.W, EVAL_DST_H, EVAL_DST_W, mout, mws, st));
+        k.metrics = mout;
+    }
+    CHECK_HIP(lidf_launch_eval_loss(k, pairs ? 1 : 0, st));
+    return LIDF_OK;
+}
+
+LIDF_API int lidf_stage1_eval_loss_f32(const LidfEvalLossArgs* args, lidf_stream_t stream) {
+    return eval_loss_run(args, true, (hipStream_t)stream);
+}
+
+LIDF_API int lidf_refine_eval_loss_f32(const LidfEvalLossArgs* args, lidf_stream_t stream) {
+    return eval_loss_run(args, false, (hipStream_t)stream);
+}
+
+LIDF_API int lidf_stage1_eval_hard_neg_f32(const LidfEvalLossArgs* args, double ratio, void* workspace,
+                                           size_t workspace_bytes, lidf_stream_t stream) {
+    LossArgs k;
+    int rc = eval_loss_args(args, true, &k);
+    if (rc) return rc;
+    if (k.R == 0) return LIDF_OK;
+    return hard_neg_run(k, true, ratio, nullptr, nullptr, nullptr, nullptr, nullptr, workspace, workspace_bytes,
+                        (hipStream_t)stream);
+}
+
+LIDF_API int lidf_refine_eval_hard_neg_f32(const LidfEvalLossArgs* args, double ratio, void* workspace,
+                                           size_t workspace_bytes, lidf_stream_t stream) {
+    LossArgs k;
+    int rc = eval_loss_args(args, false, &k);
+    if (rc) return rc;
+    if (k.R == 0) return LIDF_OK;
+    return hard_neg_run(k, false, ratio, nullptr, nullptr, nullptr, nullptr, nullptr, workspace, workspace_bytes,
+                        (hipStream_t)stream);
+}
+
 #include "lidf_api_pointnet_train.inc"
 #include "lidf_api_refine_train.inc"

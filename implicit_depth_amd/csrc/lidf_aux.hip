@@ -1605,20 +1605,7 @@ __global__ void __launch_bounds__(1024) lidf_depth_metrics_kernel(
             float g = gv[k];
             if (isnan(g) || isinf(g)) g = 0.f;
             if (!(g > 0.f) || !mv[k]) continue;
-            const float p = pv[k];
-            // same f32 operations as the torch expressions (pipeline.py:612-623)
-            const float thresh = fmaxf(g / p, p / g);
-            const float d = g - p;
-            const float lg = logf(fminf(fmaxf(g, 1e-6f), 1e6f)), lp = logf(fminf(fmaxf(p, 1e-6f), 1e6f));
-            acc[0] += thresh < 1.05f ? 1.0 : 0.0;
-            acc[1] += thresh < 1.10f ? 1.0 : 0.0;
-            acc[2] += thresh < 1.25f ? 1.0 : 0.0;
-            acc[3] += (double)(d * d);
-            acc[4] += (double)((lg - lp) * (lg - lp));
-            acc[5] += (double)fabsf(lg - lp);
-            acc[6] += (double)(fabsf(d) / g);
-            acc[7] += (double)fabsf(d);
-            acc[8] += (double)(d * d / g);
+            depth_metric_terms(g, pv[k], acc);
             acc[9] += 1.0;
         }
     }
@@ -1661,15 +1648,7 @@ __global__ void __launch_bounds__(1024) lidf_depth_metrics_kernel(
         double s[METRIC_SUMS];
         for (int i = 0; i < METRIC_SUMS; ++i) s[i] = red[i][0];
         const double c = s[9];  // 0 valid pixels: torch's mean of an empty tensor is NaN, so is 0/0
-        out[0] = (float)(s[0] / c);
-        out[1] = (float)(s[1] / c);
-        out[2] = (float)(s[2] / c);
-        out[3] = (float)sqrt(s[3] / c);
-        out[4] = (float)sqrt(s[4] / c);
-        out[5] = (float)(s[5] / c);
-        out[6] = (float)(s[6] / c);
-        out[7] = (float)(s[7] / c);
-        out[8] = (float)(s[8] / c);
+        depth_metric_stats(s, c, out);
         out[9] = (float)c;
         *ticket = 0;   // the workspace is left as it was found
     }

@@ -388,6 +388,9 @@ struct LossArgs {
     const float *w_pos, *w_prob, *w_surf, *w_dx, *w_dy;   // per-element weights, NULL = uniform means
     const float* g_loss_net;      // device scalar
     float *g_pred_pos, *g_logit;
+    // evaluation flavour (LidfEvalLossArgs): xyz is the base cloud xyz_corrupt_flat, loss has 17 (stage 2: 15)
+    // entries, the unreduced vectors may be NULL (written for hard-negative mining only), ray_lse is not written
+    const float* metrics;         // [9] statistics of the resized frame (bs == 1), NULL = taken over the rays
 };
 
 // One top-k mean of lidf_select.hip (LidfTopkJob of the C ABI) and what its last kernel makes of the means.
@@ -577,6 +580,37 @@ __device__ __forceinline__ bool mask_nonzero(const void* mask, int dtype, long l
         case 2: return ((const int*)mask)[i] != 0;
         default: return ((const long long*)mask)[i] != 0;
     }
+}
+
+// One element's terms of the nine ClearGrasp statistics (models/pipeline.py:605-618), in the f32 operations of the
+// torch expressions (safe_log10 of the reference is the natural logarithm, :607), added to acc[0..8] = {a1, a2, a3
+// counts, (g - p)^2, log difference squared, |log difference|, |g - p| / g, |g - p|, (g - p)^2 / g}. g: ground truth,
+// p: prediction. Shared by lidf_depth_metrics_kernel (the resized image) and the evaluation loss (the rays).
+__device__ __forceinline__ void depth_metric_terms(float g, float p, double* acc) {
+    const float thresh = fmaxf(g / p, p / g);
+    const float d = g - p;
+    const float lg = logf(fminf(fmaxf(g, 1e-6f), 1e6f)), lp = logf(fminf(fmaxf(p, 1e-6f), 1e6f));
+    acc[0] += thresh < 1.05f ? 1.0 : 0.0;
+    acc[1] += thresh < 1.10f ? 1.0 : 0.0;
+    acc[2] += thresh < 1.25f ? 1.0 : 0.0;
+    acc[3] += (double)(d * d);
+    acc[4] += (double)((lg - lp) * (lg - lp));
+    acc[5] += (double)fabsf(lg - lp);
+    acc[6] += (double)(fabsf(d) / g);
+    acc[7] += (double)fabsf(d);
+    acc[8] += (double)(d * d / g);
+}
+// The nine statistics from those sums s[0..8] over c elements; c == 0: 0 / 0 = NaN, torch.mean of an empty tensor.
+__device__ __forceinline__ void depth_metric_stats(const double* s, double c, float* out) {
+    out[0] = (float)(s[0] / c);
+    out[1] = (float)(s[1] / c);
+    out[2] = (float)(s[2] / c);
+    out[3] = (float)sqrt(s[3] / c);
+    out[4] = (float)sqrt(s[4] / c);
+    out[5] = (float)(s[5] / c);
+    out[6] = (float)(s[6] / c);
+    out[7] = (float)(s[7] / c);
+    out[8] = (float)(s[8] / c);
 }
 
 // Point / voxel inside test — extensions/pcl_aabb/pcl_aabb_cuda_kernel.cu:23-44, in its order: inclusive bounds,

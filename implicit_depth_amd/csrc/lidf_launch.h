@@ -282,6 +282,10 @@ hipError_t lidf_launch_stage1_loss(const LossArgs& a, float* gt_img, float* pred
 hipError_t lidf_launch_stage1_loss_backward(const LossArgs& a, hipStream_t st);
 hipError_t lidf_launch_refine_loss(const LossArgs& a, float* pred_img, hipStream_t st);
 hipError_t lidf_launch_refine_loss_backward(const LossArgs& a, hipStream_t st);
+size_t lidf_eval_loss_partial_bytes(long long R);
+hipError_t lidf_launch_eval_loss(const LossArgs& a, int pairs, hipStream_t st);
+hipError_t lidf_launch_eval_depth_images(const LossArgs& a, const float* xyz_gt, float* pred_img, float* gt_img,
+                                         hipStream_t st);
 
 // ---- lidf_select.hip
 size_t lidf_select_workspace_bytes(int n_jobs, long long n_max);

@@ -6,6 +6,9 @@
 //   lidf_loss_kernel               per ray: L1 position term, log-softmax terms of its labelled pairs, surface normal
 //                                  and smoothness terms at its own pixel, the metrics; per-block partial sums
 //   lidf_loss_final_kernel         the partial sums in a fixed order -> the eight (stage 2: six) scalars of loss_dict
+//   <.., EVAL = true> of the two    the evaluation flavour ('valid' / 'test', :571-650, :843-919): xyz_corrupt_flat as
+//                                  the base cloud, no stored terms unless asked for, the nine ClearGrasp statistics
+//                                  -> 17 (stage 2: 15) scalars; lidf_eval_depth_images_kernel feeds the bs == 1 branch
 //   lidf_loss_backward_kernel      per ray: d loss_net / d pred_pos (a gather over its own, its left and its
 //                                  upper pixel's normals) and d loss_net / d logits of its pairs (closed form)
 // The three loss kernels are templates on PAIRS: <true> is stage 1 (lidf_stage1_loss_*), <false> is stage 2
@@ -23,6 +26,7 @@ namespace {
 constexpr int LOSS_BLOCK = 256;
 constexpr int NSUM = 9;
 enum { S_POS, S_PROB, S_SURF, S_DX, S_DY, S_ACC, S_ERR, S_ELEM, S_ANGLE };
+constexpr int NMET = 9;   // evaluation flavour: depth_metric_terms' sums follow the NSUM sums of the training flavour
 
 // G lanes per ray (a wavefront takes 64 / G rays): a geometry-derived frame has a handful of pairs per ray.
 template <int G>
@@ -129,26 +133,34 @@ __device__ __forceinline__ float cosine(const float* a, const float* b, float& n
     return c;
 }
 
-template <bool PAIRS>
+// EVAL: the exp_type != 'train' flavour (:571-618, :843-889). A.xyz is then xyz_corrupt_flat (:497), the unreduced
+// terms are stored only where their pointer is set (hard-negative mining), ray_lse is not stored (no backward), and
+// the terms of the nine statistics over the rays with nonzero ground truth (the bs != 1 branch: pred = pred_pos z,
+// gt = gt_pos z) join the partial sums.
+template <bool PAIRS, bool EVAL>
 __global__ __launch_bounds__(LOSS_BLOCK) void lidf_loss_kernel(const LossArgs A) {
+    constexpr int NS = EVAL ? NSUM + NMET : NSUM;
     const long long r = (long long)blockIdx.x * LOSS_BLOCK + threadIdx.x;
-    double v[NSUM];
+    double v[NS];
 #pragma unroll
-    for (int k = 0; k < NSUM; ++k) v[k] = 0.0;
+    for (int k = 0; k < NS; ++k) v[k] = 0.0;
     if (r < A.R) {
         // position term and the L2 error over rays whose ground truth is not the zero-depth point (:560-566)
         float g[3], d[3];
+        float pz = 0.f;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             g[k] = A.gt_pos[3 * r + k];
-            d[k] = A.pred_pos[3 * r + k] - g[k];
+            pz = A.pred_pos[3 * r + k];   // (after the loop: the predicted depth)
+            d[k] = pz - g[k];
         }
         const float l1 = fabsf(d[0]) + fabsf(d[1]) + fabsf(d[2]);
-        A.pos_un[r] = l1 / 3.f;
+        if (!EVAL || A.pos_un) A.pos_un[r] = l1 / 3.f;
         v[S_POS] = l1;
         if (fabsf(g[0]) + fabsf(g[1]) + fabsf(g[2]) != 0.f) {
             v[S_ERR] = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
             v[S_ELEM] = 1.0;
+            if constexpr (EVAL) depth_metric_terms(g[2], pz, v + NSUM);
         }
         // log-softmax over the ray's pairs, taken at its labelled pairs (:482-484); arg-max of the softmax with
         // lidf_ray_reduce_kernel's rule (first of equal values, P when nothing compares greater than -inf)
@@ -170,9 +182,9 @@ __global__ __launch_bounds__(LOSS_BLOCK) void lidf_loss_kernel(const LossArgs A)
                     l = -(z - ls);
                     psum += l;
                 }
-                A.prob_un[i] = l;
+                if (!EVAL || A.prob_un) A.prob_un[i] = l;
             }
-            A.ray_lse[2 * r] = m, A.ray_lse[2 * r + 1] = ls;
+            if constexpr (!EVAL) A.ray_lse[2 * r] = m, A.ray_lse[2 * r + 1] = ls;
             v[S_PROB] = psum;
             const long long pred_label = (end <= beg || bi >= end) ? A.P : (long long)bi;
             v[S_ACC] = pred_label == A.gt_maxid[r] ? 1.0 : 0.0;
@@ -189,37 +201,44 @@ __global__ __launch_bounds__(LOSS_BLOCK) void lidf_loss_kernel(const LossArgs A)
         const float cc = c < -1.f ? -1.f : (c > 1.f ? 1.f : c);   // (a NaN stays a NaN, as in torch.clamp)
         const float dxd = np.dx[0] * np.dx[0] + np.dx[1] * np.dx[1] + np.dx[2] * np.dx[2];
         const float dyd = np.dy[0] * np.dy[0] + np.dy[1] * np.dy[1] + np.dy[2] * np.dy[2];
-        A.surf_dist[r] = dist, A.dx_dist[r] = dxd, A.dy_dist[r] = dyd;
+        if (!EVAL || A.surf_dist) A.surf_dist[r] = dist, A.dx_dist[r] = dxd, A.dy_dist[r] = dyd;
         v[S_SURF] = dist, v[S_DX] = dxd, v[S_DY] = dyd, v[S_ANGLE] = acosf(cc);
     }
     // stage 1 of the means: the block's sums (wavefront butterflies, then the four wavefronts in order)
-    __shared__ double part[LOSS_BLOCK / 64][NSUM];
+    __shared__ double part[LOSS_BLOCK / 64][NS];
     const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
 #pragma unroll
-    for (int k = 0; k < NSUM; ++k) {
+    for (int k = 0; k < NS; ++k) {
         const double t = wave_sum(v[k]);
         if (ln == 0) part[wv][k] = t;
     }
     __syncthreads();
-    if (threadIdx.x < NSUM) {
+    if (threadIdx.x < NS) {
         double t = 0.0;
 #pragma unroll
         for (int i = 0; i < LOSS_BLOCK / 64; ++i) t += part[i][threadIdx.x];
-        A.partial[(size_t)blockIdx.x * NSUM + threadIdx.x] = t;
+        A.partial[(size_t)blockIdx.x * NS + threadIdx.x] = t;
     }
 }
 
 // Stage 2: wavefront k sums quantity k over the blocks (lane-strided, then a butterfly: a fixed order), thread 0
 // forms loss_dict = {pos_loss, prob_loss, surf_norm_loss, smooth_loss, loss_net, acc, err, angle_err} (:542-566);
 // stage 2: {pos_loss, surf_norm_loss, smooth_loss, loss_net, err, angle_err} (:823-840, :898-905).
-template <bool PAIRS>
+// EVAL: every wavefront takes a second quantity, and the nine statistics follow in loss_dict's order (:639-649,
+// :906-917) — from the rays' sums, or copied from A.metrics (the resized frame of the bs == 1 branch).
+template <bool PAIRS, bool EVAL>
 __global__ __launch_bounds__(64 * NSUM) void lidf_loss_final_kernel(const LossArgs A, int nblk) {
-    __shared__ double tot[NSUM];
-    const int k = threadIdx.x >> 6, ln = threadIdx.x & 63;
-    double t = 0.0;
-    for (int i = ln; i < nblk; i += 64) t += A.partial[(size_t)i * NSUM + k];
-    t = wave_sum(t);
-    if (ln == 0) tot[k] = t;
+    constexpr int NS = EVAL ? NSUM + NMET : NSUM;
+    __shared__ double tot[NS];
+    const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
+    auto total = [&](int k) {
+        double t = 0.0;
+        for (int i = ln; i < nblk; i += 64) t += A.partial[(size_t)i * NS + k];
+        t = wave_sum(t);
+        if (ln == 0) tot[k] = t;
+    };
+    total(wv);
+    if constexpr (EVAL) total(wv + NSUM);
     __syncthreads();
     if (threadIdx.x == 0) {
         const double R = (double)A.R;
@@ -244,7 +263,27 @@ __global__ __launch_bounds__(64 * NSUM) void lidf_loss_final_kernel(const LossAr
             if (A.smooth_on) net += A.smooth_w * smooth;
             A.loss[0] = pos, A.loss[1] = surf, A.loss[2] = smooth, A.loss[3] = net, A.loss[4] = err, A.loss[5] = angle;
         }
+        if constexpr (EVAL) {
+            float* out = A.loss + (PAIRS ? 8 : 6);
+            if (A.metrics) {
+#pragma unroll
+                for (int i = 0; i < NMET; ++i) out[i] = A.metrics[i];
+            } else {
+                depth_metric_stats(tot + NSUM, tot[S_ELEM], out);
+            }
+        }
     }
+}
+
+// The bs == 1 branch's two depth images (:579-597), which lidf_depth_metrics_kernel resizes: z of the ground-truth
+// frame, and z of the base cloud with the queried pixels replaced by pred_pos.
+__global__ void lidf_eval_depth_images_kernel(const LossArgs A, const float* __restrict__ xyz_gt,
+                                              float* __restrict__ pred_img, float* __restrict__ gt_img) {
+    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= A.hw) return;
+    const int t = A.pix2ray[q];
+    pred_img[q] = t >= 0 ? A.pred_pos[3 * (size_t)t + 2] : A.xyz[3 * (size_t)q + 2];
+    gt_img[q] = xyz_gt[3 * (size_t)q + 2];
 }
 
 // d loss_net / d (dx, dy) of the sampled pixel (y, x) of ray rj, through its normal's cosine term (weight cs on
@@ -397,13 +436,40 @@ extern "C" size_t lidf_stage1_loss_partial_bytes(long long R) {
 extern "C" hipError_t lidf_launch_stage1_loss(const LossArgs& a, float* gt_img, float* pred_img, hipStream_t st) {
     if (a.R <= 0) return hipSuccess;
     const int blocks = (int)((a.R + LOSS_BLOCK - 1) / LOSS_BLOCK);
-    hipLaunchKernelGGL(lidf_loss_kernel<true>, dim3((unsigned)blocks), dim3(LOSS_BLOCK), 0, st, a);
-    hipLaunchKernelGGL(lidf_loss_final_kernel<true>, dim3(1), dim3(64 * NSUM), 0, st, a, blocks);
+    hipLaunchKernelGGL((lidf_loss_kernel<true, false>), dim3((unsigned)blocks), dim3(LOSS_BLOCK), 0, st, a);
+    hipLaunchKernelGGL((lidf_loss_final_kernel<true, false>), dim3(1), dim3(64 * NSUM), 0, st, a, blocks);
     if (gt_img || pred_img) {
         const long long n = (long long)a.B * a.hw;
         hipLaunchKernelGGL(lidf_normal_map_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, gt_img,
                            pred_img);
     }
+    return hipGetLastError();
+}
+
+// The evaluation flavour of either stage (pairs: stage 1), two launches.
+extern "C" size_t lidf_eval_loss_partial_bytes(long long R) {
+    const long long blocks = R > 0 ? (R + LOSS_BLOCK - 1) / LOSS_BLOCK : 0;
+    return (size_t)blocks * (NSUM + NMET) * sizeof(double);
+}
+
+extern "C" hipError_t lidf_launch_eval_loss(const LossArgs& a, int pairs, hipStream_t st) {
+    if (a.R <= 0) return hipSuccess;
+    const int blocks = (int)((a.R + LOSS_BLOCK - 1) / LOSS_BLOCK);
+    if (pairs) {
+        hipLaunchKernelGGL((lidf_loss_kernel<true, true>), dim3((unsigned)blocks), dim3(LOSS_BLOCK), 0, st, a);
+        hipLaunchKernelGGL((lidf_loss_final_kernel<true, true>), dim3(1), dim3(64 * NSUM), 0, st, a, blocks);
+    } else {
+        hipLaunchKernelGGL((lidf_loss_kernel<false, true>), dim3((unsigned)blocks), dim3(LOSS_BLOCK), 0, st, a);
+        hipLaunchKernelGGL((lidf_loss_final_kernel<false, true>), dim3(1), dim3(64 * NSUM), 0, st, a, blocks);
+    }
+    return hipGetLastError();
+}
+
+extern "C" hipError_t lidf_launch_eval_depth_images(const LossArgs& a, const float* xyz_gt, float* pred_img,
+                                                    float* gt_img, hipStream_t st) {
+    if (a.hw <= 0) return hipSuccess;
+    hipLaunchKernelGGL(lidf_eval_depth_images_kernel, dim3((unsigned)((a.hw + 255) / 256)), dim3(256), 0, st, a, xyz_gt,
+                       pred_img, gt_img);
     return hipGetLastError();
 }
 
@@ -418,8 +484,8 @@ extern "C" hipError_t lidf_launch_stage1_loss_backward(const LossArgs& a, hipStr
 extern "C" hipError_t lidf_launch_refine_loss(const LossArgs& a, float* pred_img, hipStream_t st) {
     if (a.R <= 0) return hipSuccess;
     const int blocks = (int)((a.R + LOSS_BLOCK - 1) / LOSS_BLOCK);
-    hipLaunchKernelGGL(lidf_loss_kernel<false>, dim3((unsigned)blocks), dim3(LOSS_BLOCK), 0, st, a);
-    hipLaunchKernelGGL(lidf_loss_final_kernel<false>, dim3(1), dim3(64 * NSUM), 0, st, a, blocks);
+    hipLaunchKernelGGL((lidf_loss_kernel<false, false>), dim3((unsigned)blocks), dim3(LOSS_BLOCK), 0, st, a);
+    hipLaunchKernelGGL((lidf_loss_final_kernel<false, false>), dim3(1), dim3(64 * NSUM), 0, st, a, blocks);
     if (pred_img) {
         const long long n = (long long)a.B * a.hw;
         hipLaunchKernelGGL(lidf_normal_map_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a,

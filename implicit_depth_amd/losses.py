@@ -1,11 +1,13 @@
-"""losses.py — ground-truth labels and the training losses of stage 1 and stage 2.
+"""losses.py — ground-truth labels and the losses of stage 1 and stage 2, training and evaluation flavour.
 
 Reference counterparts (paths relative to /root/reference/src):
   compute_gt           <- LIDF.compute_gt                       models/pipeline.py:298-336
-  lidf_loss            <- LIDF.compute_loss, exp_type == 'train' models/pipeline.py:468-566
+  lidf_loss            <- LIDF.compute_loss                     models/pipeline.py:468-650: exp_type 'train' (:468-566,
+                       differentiable) and 'valid' / 'test' (the evaluation flavour: xyz_corrupt_flat as the base
+                       cloud of the normals, the nine ClearGrasp statistics, no backward)
   lidf_loss_composite  the same loss in plain torch ops (any dtype, any device): the A/B partner of
                        lidf_loss and the route for CPU callers
-  refine_loss          <- RefineNet.compute_loss, exp_type == 'train'  models/pipeline.py:760-840
+  refine_loss          <- RefineNet.compute_loss                models/pipeline.py:760-919, the same three flavours
   refine_loss_composite  the same in plain torch ops
   LidfLossOptions      <- the loss.* keys of experiments/implicit_depth/default_config.yaml:97-107
 
@@ -27,6 +29,11 @@ from .query import _as_i32, _f32, _i32
 
 LOSS_KEYS = ("pos_loss", "prob_loss", "surf_norm_loss", "smooth_loss", "loss_net", "acc", "err", "angle_err")
 REFINE_LOSS_KEYS = ("pos_loss", "surf_norm_loss", "smooth_loss", "loss_net", "err", "angle_err")
+# what exp_type 'valid' / 'test' appends (models/pipeline.py:639-649, 906-917)
+EVAL_METRIC_KEYS = ("a1", "a2", "a3", "rmse", "rmse_log", "log10", "abs_rel", "mae", "sq_rel")
+EVAL_LOSS_KEYS = LOSS_KEYS + EVAL_METRIC_KEYS
+REFINE_EVAL_LOSS_KEYS = REFINE_LOSS_KEYS + EVAL_METRIC_KEYS
+EXP_TYPES = ("train", "valid", "test")
 
 
 class LidfLossOptions:
@@ -141,6 +148,45 @@ def _topk_weights(v, k):
     return torch.mean(top), w
 
 
+def _stage1_topk(fwd, loss, n_label, R, cfg):
+    """Hard-negative mining of stage 1 by torch.topk (models/pipeline.py:475-490, 514-539): the means over the top-k
+    elements of the unreduced terms. Returns (loss with its first five entries replaced, the five weight vectors a
+    backward takes)."""
+    ratio = cfg["hard_neg_ratio"]
+    kr = int(R * ratio)
+    kl = int(int(n_label.item()) * ratio)   # (the one size read: k of the labelled pairs)
+    pos, w_pos = _topk_weights(fwd["pos_unreduced"], kr)
+    prob, w_prob = _topk_weights(fwd["prob_unreduced"], kl)
+    surf, w_surf = _topk_weights(fwd["surf_norm_dist"], kr)
+    sdx, w_dx = _topk_weights(fwd["dx_dist"], kr)
+    sdy, w_dy = _topk_weights(fwd["dy_dist"], kr)
+    smooth = sdx + sdy
+    net = cfg["pos_w"] * pos + cfg["prob_w"] * prob
+    if cfg["surf_on"]:
+        net = net + cfg["surf_norm_w"] * surf
+    if cfg["smooth_on"]:
+        net = net + cfg["smooth_w"] * smooth
+    return torch.cat((torch.stack((pos, prob, surf, smooth, net)), loss[5:])), (w_pos, w_prob, w_surf, w_dx, w_dy)
+
+
+def _refine_topk(fwd, loss, R, cfg):
+    """Hard-negative mining of stage 2 by torch.topk (models/pipeline.py:767-770, 799-801, 818-821): k = int(R *
+    ratio) is known on the host, so nothing is read back. Returns (loss with its first four entries replaced, the
+    four weight vectors)."""
+    k = int(R * cfg["hard_neg_ratio"])
+    pos, w_pos = _topk_weights(fwd["pos_unreduced"], k)
+    surf, w_surf = _topk_weights(fwd["surf_norm_dist"], k)
+    sdx, w_dx = _topk_weights(fwd["dx_dist"], k)
+    sdy, w_dy = _topk_weights(fwd["dy_dist"], k)
+    smooth = sdx + sdy
+    net = cfg["pos_w"] * pos
+    if cfg["surf_on"]:
+        net = net + cfg["surf_norm_w"] * surf
+    if cfg["smooth_on"]:
+        net = net + cfg["smooth_w"] * smooth
+    return torch.cat((torch.stack((pos, surf, smooth, net)), loss[4:])), (w_pos, w_surf, w_dx, w_dy)
+
+
 def _ratio(ratio):
     ratio = float(ratio)
     if not 0.0 <= ratio <= 1.0:
@@ -218,24 +264,8 @@ class _Stage1LossFn(torch.autograd.Function):
                                                       *(_lib.ptr(w) for w in weights), _lib.ptr(hws), hsb,
                                                       _lib.current_stream(dev)))
         elif cfg["hard_neg"]:
-            # hard-negative mining (models/pipeline.py:475-490, 514-539): the means over the top-k elements of the
-            # unreduced terms; the backward takes them as per-element weights
-            ratio = cfg["hard_neg_ratio"]
-            kr = int(R * ratio)
-            kl = int(int(n_label.item()) * ratio)   # (the one size read: k of the labelled pairs)
-            pos, w_pos = _topk_weights(fwd["pos_unreduced"], kr)
-            prob, w_prob = _topk_weights(fwd["prob_unreduced"], kl)
-            surf, w_surf = _topk_weights(fwd["surf_norm_dist"], kr)
-            sdx, w_dx = _topk_weights(fwd["dx_dist"], kr)
-            sdy, w_dy = _topk_weights(fwd["dy_dist"], kr)
-            smooth = sdx + sdy
-            net = cfg["pos_w"] * pos + cfg["prob_w"] * prob
-            if cfg["surf_on"]:
-                net = net + cfg["surf_norm_w"] * surf
-            if cfg["smooth_on"]:
-                net = net + cfg["smooth_w"] * smooth
-            loss = torch.cat((torch.stack((pos, prob, surf, smooth, net)), loss[5:]))
-            weights = (w_pos, w_prob, w_surf, w_dx, w_dy)
+            # the top-k means by torch.topk; the backward takes them as per-element weights
+            loss, weights = _stage1_topk(fwd, loss, n_label, R, cfg)
         ctx.cfg = cfg
         ctx.shapes = (tuple(pred_pos.shape), tuple(pred_prob.shape))
         ctx.has_w = cfg["hard_neg"]
@@ -273,6 +303,71 @@ def _cfg(dd, opt, epoch):
             "hard_neg_ratio": opt.hard_neg_ratio, "hard_neg_select": opt.hard_neg_select}
 
 
+def _eval_loss(dd, opt, epoch, pairs, t):
+    """The evaluation flavour (exp_type 'valid' / 'test', models/pipeline.py:468-650, 760-919) of either stage over
+    the checked tensors `t` (LidfEvalLossArgs' names): lidf_stage1_eval_loss_f32 / lidf_refine_eval_loss_f32, two
+    launches (bs == 1, the resized-frame statistics: a memset and four). Forward only: every entry is detached, no
+    autograd node is made, and the unreduced [R] / [P] terms are allocated under hard_neg alone. Nothing is read
+    back, except the label count of stage 1 under hard_neg with hard_neg_select "torch"."""
+    from .query import _seg_mask_arg
+    who = "lidf_loss" if pairs else "refine_loss"
+    bs, h, w = dd["bs"], dd["h"], dd["w"]
+    base, xyz = dd["xyz_corrupt_flat"], dd["xyz_flat"]
+    _lib.require_cuda(base, names=["xyz_corrupt_flat"])
+    _f32(base, "xyz_corrupt_flat")
+    if tuple(base.shape) != (bs, h * w, 3) or base.device != xyz.device:
+        raise RuntimeError("%s: xyz_corrupt_flat must be [bs,h*w,3] on the device of xyz_flat" % who)
+    dev = xyz.device
+    R, P = t["gt_pos"].shape[0], (t["pcl_label"].shape[0] if pairs else 0)
+    cfg = _cfg(dd, opt, epoch)
+    resize = bs == 1   # (the reference's branch, models/pipeline.py:572, 844)
+    t = dict(t, xyz_base=base)
+    seg_dtype = 0
+    if resize:
+        if "corrupt_mask" not in dd:
+            raise RuntimeError("%s: at bs == 1 the statistics are masked by dd['corrupt_mask'] "
+                               "(models/pipeline.py:587-590), which dd lacks" % who)
+        mask = dd["corrupt_mask"]
+        if mask.numel() != h * w:
+            raise RuntimeError("%s: corrupt_mask must hold bs*h*w elements" % who)
+        t["xyz_gt"] = xyz
+        t["seg_mask"], seg_dtype = _seg_mask_arg(mask.reshape(h, w))
+    f32 = dict(dtype=torch.float32, device=dev)
+    out = {"loss": torch.empty((len(EVAL_LOSS_KEYS if pairs else REFINE_EVAL_LOSS_KEYS),), **f32)}
+    if cfg["hard_neg"]:
+        out.update({k: torch.empty((R,), **f32) for k in ("pos_unreduced", "surf_norm_dist", "dx_dist", "dy_dist")})
+        if pairs:
+            out["prob_unreduced"] = torch.empty((P,), **f32)
+    L = _lib.lib()
+    size_fn, loss_fn, hard_fn = (
+        (L.lidf_stage1_eval_loss_workspace_bytes, L.lidf_stage1_eval_loss_f32, L.lidf_stage1_eval_hard_neg_f32)
+        if pairs else
+        (L.lidf_refine_eval_loss_workspace_bytes, L.lidf_refine_eval_loss_f32, L.lidf_refine_eval_hard_neg_f32))
+    wsb = size_fn(R, h * w if resize else 0)
+    ws = _lib.workspace(wsb, dev)
+    a = _lib.LidfEvalLossArgs()
+    a.n_rays, a.n_pairs = R, P
+    a.batch, a.height, a.width, a.resize_metrics, a.seg_dtype = bs, h, w, int(resize), seg_dtype
+    a.pos_w, a.prob_w = cfg["pos_w"], cfg["prob_w"]
+    a.surf_norm_w, a.smooth_w = cfg["surf_norm_w"], cfg["smooth_w"]
+    a.surf_norm_on, a.smooth_on = int(cfg["surf_on"]), int(cfg["smooth_on"])
+    for k, v in dict(t, **out).items():
+        if v is not None:
+            setattr(a, k, v.data_ptr())
+    a.workspace, a.workspace_bytes = ws.data_ptr(), wsb
+    with torch.no_grad(), torch.cuda.device(dev):
+        _lib.check(loss_fn(C.byref(a), _lib.current_stream(dev)))
+        loss = out["loss"]
+        if cfg["hard_neg"] and cfg["hard_neg_select"] == "device":
+            hsb = L.lidf_topk_mean_workspace_bytes(5 if pairs else 4, max(R, P))
+            hws = _lib.workspace(hsb, dev)
+            _lib.check(hard_fn(C.byref(a), _ratio(cfg["hard_neg_ratio"]), _lib.ptr(hws), hsb,
+                               _lib.current_stream(dev)))
+        elif cfg["hard_neg"]:
+            loss = _stage1_topk(out, loss, t["n_label"], R, cfg)[0] if pairs else _refine_topk(out, loss, R, cfg)[0]
+    return {k: loss[i] for i, k in enumerate(EVAL_LOSS_KEYS if pairs else REFINE_EVAL_LOSS_KEYS)}
+
+
 def lidf_loss(dd, loss_opt=None, exp_type="train", epoch=0, normal_maps=False):
     """LIDF.compute_loss for exp_type == 'train' (models/pipeline.py:468-566) on lidf_forward_train's data_dict
     (compute_gt's entries + pred_pos [R,3] and pred_prob_end [P,1] of lidf_query_train): the reference's loss_dict
@@ -281,11 +376,18 @@ def lidf_loss(dd, loss_opt=None, exp_type="train", epoch=0, normal_maps=False):
     are detached. Nothing is read back to the host, except the label count under hard_neg with the default
     hard_neg_select "torch" (torch.topk per term; its k of the labelled pairs is a host number). With "device" the
     five top-k means come from csrc/lidf_select.hip, which reads n_label on the device: nothing is read back.
-    normal_maps=True adds gt_surf_norm_img / pred_surf_norm_img [bs,3,h,w] to dd (visualisation only)."""
+    normal_maps=True adds gt_surf_norm_img / pred_surf_norm_img [bs,3,h,w] to dd (visualisation only).
+
+    exp_type 'valid' / 'test' (:468-650) is the evaluation flavour, what a trainer's validate() / test() reads: the
+    same dict followed by a1, a2, a3, rmse, rmse_log, log10, abs_rel, mae, sq_rel (EVAL_LOSS_KEYS), every entry —
+    loss_net included — detached, no autograd node. The surface-normal and smoothness terms are taken on
+    dd['xyz_corrupt_flat'] with the queried pixels replaced (:497); the nine statistics over the rays with a nonzero
+    gt_pos when dd['bs'] != 1, over the 144 x 256 resize of the frame masked by gt > 0 and dd['corrupt_mask'] when
+    dd['bs'] == 1 (bit-equal to pipeline.eval_metrics on the same depth image). A dict without xyz_corrupt_flat (the
+    training step's own) has no evaluation flavour: NotImplementedError. hard_neg applies as in training, by
+    either hard_neg_select route; without it no [R] / [P] term buffer is allocated."""
     opt = loss_opt or LidfLossOptions()
-    if exp_type != "train":
-        raise NotImplementedError("lidf_loss covers exp_type 'train'; the evaluation statistics are "
-                                  "pipeline.eval_metrics")
+    _base_cloud(dd, exp_type, "lidf_loss")
     _check_types(opt)
     pred_pos, pred_prob = dd["pred_pos"], dd["pred_prob_end"]
     _lib.require_cuda(pred_pos, pred_prob, dd["xyz_flat"], names=["pred_pos", "pred_prob_end", "xyz_flat"])
@@ -315,6 +417,13 @@ def lidf_loss(dd, loss_opt=None, exp_type="train", epoch=0, normal_maps=False):
                            "compute_gt(dd) again")
     if R == 0:
         raise RuntimeError("lidf_loss: no ray (the reference returns before compute_loss, models/pipeline.py:686)")
+    if exp_type != "train":
+        if normal_maps:
+            raise NotImplementedError("lidf_loss: normal_maps is the training flavour's")
+        t = {"ray_bid": ray_bid, "ray_flat": ray_flat, "pair_off": pair_off, "pix2ray": pix2ray, "gt_pos": gt[0],
+             "pcl_label": gt[1], "gt_max_pair_id": gt[2], "n_label": gt[3].reshape(1),
+             "pred_pos": pred_pos.detach().contiguous(), "pred_prob": pred_prob.detach().reshape(-1).contiguous()}
+        return _eval_loss(dd, opt, epoch, True, t)
     maps = None
     if normal_maps:
         shape = (dd["bs"], 3, dd["h"], dd["w"])
@@ -357,9 +466,65 @@ def _neighbour_normals(xyz, table, pos, lin, x, y, h, w):
     return n / (torch.linalg.vector_norm(n, dim=-1, keepdim=True) + 1e-8), dx, dy
 
 
-def _composite_terms(dd, pred_pos, gt_pos, opt):
+def _resize_nearest_index(src, dst, device):
+    """Source index of every destination index of cv2.resize(..., interpolation=INTER_NEAREST):
+    min(floor(index * (1 / (dst / src))), src - 1), the factor in double (lidf_depth_metrics_kernel's rule)."""
+    at = torch.arange(dst, dtype=torch.float64, device=device) * (1.0 / (dst / src))
+    return torch.floor(at).long().clamp(max=src - 1)
+
+
+def _composite_statistics(dd, pred_pos, gt_pos, eval_size=(144, 256)):
+    """The nine statistics of exp_type 'valid' / 'test' (models/pipeline.py:571-618) in torch ops, in the dtype of
+    pred_pos: {a1 .. sq_rel}. The selection is a boolean mask (a size read on a GPU)."""
+    dt, dev = pred_pos.dtype, pred_pos.device
+    bs, h, w = dd["bs"], dd["h"], dd["w"]
+    with torch.no_grad():
+        if bs != 1:
+            keep = torch.sum(gt_pos.abs(), -1) != 0
+            pred, gt = pred_pos[:, 2][keep], gt_pos[:, 2][keep]
+        else:
+            bid = (dd["ray_bid"] if "ray_bid" in dd else dd["miss_bid"]).long()
+            flat = (dd["ray_flat"] if "ray_flat" in dd else dd["miss_flat_img_id"]).long()
+            sy, sx = _resize_nearest_index(h, eval_size[0], dev), _resize_nearest_index(w, eval_size[1], dev)
+            gt = dd["xyz_flat"].to(dt).reshape(bs, h, w, 3)[0, :, :, 2][sy][:, sx]
+            gt = torch.where(torch.isfinite(gt), gt, torch.zeros_like(gt))
+            seg = dd["corrupt_mask"].reshape(h, w)
+            # (the reference's astype(np.uint8), :588: truncation toward zero, modulo 256)
+            seg = (seg.long() & 255) != 0 if seg.is_floating_point() else seg != 0
+            mask = (gt > 0) & seg[sy][:, sx]
+            frame = dd["xyz_corrupt_flat"].to(dt).clone()
+            frame[bid, flat] = pred_pos.detach()
+            pred = frame.reshape(bs, h, w, 3)[0, :, :, 2][sy][:, sx]
+            gt, pred = gt[mask], pred[mask]
+        safe_log = lambda v: torch.log(torch.clamp(v, 1e-6, 1e6))  # noqa: E731  (safe_log10 is this too, :607)
+        thresh = torch.max(gt / pred, pred / gt)
+        d = gt - pred
+        ld = safe_log(gt) - safe_log(pred)
+        return {"a1": (thresh < 1.05).to(dt).mean(), "a2": (thresh < 1.10).to(dt).mean(),
+                "a3": (thresh < 1.25).to(dt).mean(), "rmse": (d ** 2).mean().sqrt(),
+                "rmse_log": (ld ** 2).mean().sqrt(), "log10": ld.abs().mean(), "abs_rel": (d.abs() / gt).mean(),
+                "mae": d.abs().mean(), "sq_rel": (d ** 2 / gt).mean()}
+
+
+def _base_cloud(dd, exp_type, who):
+    """The key of the cloud the queried pixels are replaced in for the normals: xyz_flat for 'train',
+    xyz_corrupt_flat for 'valid' / 'test' (models/pipeline.py:493-498, 775-780). A dict that holds the training
+    step's entries alone has no evaluation flavour: NotImplementedError, before any tensor is looked at."""
+    if exp_type not in EXP_TYPES:
+        raise ValueError("exp_type must be one of %s, not %r" % (EXP_TYPES, exp_type))
+    if exp_type == "train":
+        return "xyz_flat"
+    if "xyz_corrupt_flat" not in dd:
+        raise NotImplementedError(
+            "%s: exp_type %r takes its surface normals and smoothness on dd['xyz_corrupt_flat'] "
+            "(models/pipeline.py:497, 779), which this dict lacks — with xyz_flat alone only 'train' is defined; "
+            "the nine statistics on their own are pipeline.eval_metrics" % (who, exp_type))
+    return "xyz_corrupt_flat"
+
+
+def _composite_terms(dd, pred_pos, gt_pos, opt, base="xyz_flat"):
     """What the two composites share: (reduce, pos_loss, surf_norm_loss, smooth_loss, angle_err, err) of `pred_pos`
-    against `gt_pos` at the sampled pixels of dd."""
+    against `gt_pos` at the sampled pixels of dd; dd[base] is the cloud the sampled pixels are replaced in."""
     dt, dev = pred_pos.dtype, pred_pos.device
     bs, h, w = dd["bs"], dd["h"], dd["w"]
     bid = (dd["ray_bid"] if "ray_bid" in dd else dd["miss_bid"]).long()
@@ -370,7 +535,7 @@ def _composite_terms(dd, pred_pos, gt_pos, opt):
     pos_loss = reduce(torch.mean((pred_pos - gt_pos).abs(), -1)) if opt.hard_neg else \
         torch.mean((pred_pos - gt_pos).abs())
     # surface normals and smoothness at the sampled pixels
-    xyz = dd["xyz_flat"].reshape(-1, 3).to(dt)
+    xyz = dd[base].reshape(-1, 3).to(dt)
     lin = bid * (h * w) + flat
     table = torch.full((bs * h * w,), -1, dtype=torch.long, device=dev)
     table[lin] = torch.arange(R, device=dev)
@@ -393,17 +558,18 @@ def lidf_loss_composite(dd, loss_opt=None, exp_type="train", epoch=0):
     """lidf_loss written in differentiable torch ops, in the dtype of pred_pos, on any device: per-ray
     log-softmax by scatter reductions, the normals by gathering each sampled pixel's right and lower neighbour.
     Needs gt_pos and pcl_label in dd (compute_gt's, or a caller's own); every entry of the returned loss_dict
-    carries its graph. It takes many small launches where lidf_loss takes three."""
+    carries its graph. It takes many small launches where lidf_loss takes three.
+    exp_type 'valid' / 'test': the evaluation flavour (dd['xyz_corrupt_flat'] as the base cloud; the nine statistics
+    appended, and dd['corrupt_mask'] read, as lidf_loss describes); its entries are detached."""
     opt = loss_opt or LidfLossOptions()
-    if exp_type != "train":
-        raise NotImplementedError("lidf_loss_composite covers exp_type 'train'")
+    base = _base_cloud(dd, exp_type, "lidf_loss_composite")
     _check_types(opt)
     pred_pos, logit = dd["pred_pos"], dd["pred_prob_end"].reshape(-1)
     dt, dev = pred_pos.dtype, pred_pos.device
     gt_pos, label = dd["gt_pos"].to(dt), dd["pcl_label"].long()
     ray = dd["pair_ray"].long()
     R, P = pred_pos.shape[0], logit.shape[0]
-    reduce, pos_loss, surf_norm_loss, smooth_loss, angle_err, err = _composite_terms(dd, pred_pos, gt_pos, opt)
+    reduce, pos_loss, surf_norm_loss, smooth_loss, angle_err, err = _composite_terms(dd, pred_pos, gt_pos, opt, base)
     # ray termination: -log_softmax over each ray's pairs at the labelled pairs
     top = torch.full((R,), float("-inf"), dtype=dt, device=dev).scatter_reduce(
         0, ray, logit.detach(), reduce="amax", include_self=True)
@@ -422,8 +588,12 @@ def lidf_loss_composite(dd, loss_opt=None, exp_type="train", epoch=0):
         pred_label = _first_argmax(sm, ray, R, P)
         gt_label = _first_argmax(label.to(dt), ray, R, P)
         acc = torch.sum(torch.eq(pred_label, gt_label).to(dt)) / R
-    return {"pos_loss": pos_loss, "prob_loss": prob_loss, "surf_norm_loss": surf_norm_loss,
-            "smooth_loss": smooth_loss, "loss_net": loss_net, "acc": acc, "err": err, "angle_err": angle_err}
+    out = {"pos_loss": pos_loss, "prob_loss": prob_loss, "surf_norm_loss": surf_norm_loss,
+           "smooth_loss": smooth_loss, "loss_net": loss_net, "acc": acc, "err": err, "angle_err": angle_err}
+    if exp_type != "train":
+        out = {k: v.detach() for k, v in out.items()}
+        out.update(_composite_statistics(dd, pred_pos.detach(), gt_pos))
+    return out
 
 
 # ------------------------------------------------------------------------------------------------
@@ -479,21 +649,7 @@ class _RefineLossFn(torch.autograd.Function):
                                                       *(_lib.ptr(w) for w in weights), _lib.ptr(hws), hsb,
                                                       _lib.current_stream(dev)))
         elif cfg["hard_neg"]:
-            # hard-negative mining (models/pipeline.py:767-770, 799-801, 818-821): k = int(R * ratio) is known on
-            # the host, so nothing is read back
-            k = int(R * cfg["hard_neg_ratio"])
-            pos, w_pos = _topk_weights(fwd["pos_unreduced"], k)
-            surf, w_surf = _topk_weights(fwd["surf_norm_dist"], k)
-            sdx, w_dx = _topk_weights(fwd["dx_dist"], k)
-            sdy, w_dy = _topk_weights(fwd["dy_dist"], k)
-            smooth = sdx + sdy
-            net = cfg["pos_w"] * pos
-            if cfg["surf_on"]:
-                net = net + cfg["surf_norm_w"] * surf
-            if cfg["smooth_on"]:
-                net = net + cfg["smooth_w"] * smooth
-            loss = torch.cat((torch.stack((pos, surf, smooth, net)), loss[4:]))
-            weights = (w_pos, w_surf, w_dx, w_dy)
+            loss, weights = _refine_topk(fwd, loss, R, cfg)
         ctx.cfg = cfg
         ctx.shape = tuple(pred_pos.shape)
         ctx.save_for_backward(*t.values(), *weights)
@@ -527,11 +683,11 @@ def refine_loss(dd, loss_opt=None, exp_type="train", epoch=0, normal_maps=False)
     value: the lowest indices).
     loss_opt: LidfLossOptions; its defaults are train_refine.yaml's pos_w 100 / surf_norm_w 10, and
     train_refine_hardneg.yaml is LidfLossOptions(hard_neg=True, hard_neg_ratio=0.1, pos_w=20.0, surf_norm_w=2.0).
-    normal_maps=True adds pred_surf_norm_img_refine [bs,3,h,w] to dd (:894, visualisation only)."""
+    normal_maps=True adds pred_surf_norm_img_refine [bs,3,h,w] to dd (:894, visualisation only).
+    exp_type 'valid' / 'test' (:760-919): the evaluation flavour as in lidf_loss — REFINE_EVAL_LOSS_KEYS, detached,
+    dd['xyz_corrupt_flat'] as the base cloud, the nine statistics by dd['bs'] == 1 or not."""
     opt = loss_opt or LidfLossOptions()
-    if exp_type != "train":
-        raise NotImplementedError("refine_loss covers exp_type 'train'; the evaluation statistics are "
-                                  "pipeline.eval_metrics")
+    _base_cloud(dd, exp_type, "refine_loss")
     _check_types(opt, prob=False)
     pred = dd["pred_pos_refine"]
     _lib.require_cuda(pred, dd["xyz_flat"], names=["pred_pos_refine", "xyz_flat"])
@@ -553,6 +709,12 @@ def refine_loss(dd, loss_opt=None, exp_type="train", epoch=0, normal_maps=False)
                            "compute_gt(dd) again")
     if R == 0:
         raise RuntimeError("refine_loss: no ray (the reference returns before stage 2, models/pipeline.py:686)")
+    if exp_type != "train":
+        if normal_maps:
+            raise NotImplementedError("refine_loss: normal_maps is the training flavour's")
+        t = {"ray_bid": ray_bid, "ray_flat": ray_flat, "pix2ray": pix2ray, "gt_pos": gt_pos,
+             "pred_pos": pred.detach().contiguous()}
+        return _eval_loss(dd, opt, epoch, False, t)
     img = None
     if normal_maps:
         img = torch.empty((bs, 3, h, w), dtype=torch.float32, device=pred.device)
@@ -568,19 +730,22 @@ def refine_loss(dd, loss_opt=None, exp_type="train", epoch=0, normal_maps=False)
 def refine_loss_composite(dd, loss_opt=None, exp_type="train", epoch=0):
     """refine_loss written in differentiable torch ops, in the dtype of pred_pos_refine, on any device (the A/B
     partner of refine_loss and the route for CPU callers). Needs gt_pos in dd; every entry of the returned loss_dict
-    carries its graph."""
+    carries its graph. exp_type 'valid' / 'test': the evaluation flavour, as lidf_loss_composite's."""
     opt = loss_opt or LidfLossOptions()
-    if exp_type != "train":
-        raise NotImplementedError("refine_loss_composite covers exp_type 'train'")
+    base = _base_cloud(dd, exp_type, "refine_loss_composite")
     _check_types(opt, prob=False)
     pred = dd["pred_pos_refine"]
-    _, pos_loss, surf_norm_loss, smooth_loss, angle_err, err = _composite_terms(dd, pred, dd["gt_pos"].to(pred.dtype),
-                                                                                opt)
+    gt_pos = dd["gt_pos"].to(pred.dtype)
+    _, pos_loss, surf_norm_loss, smooth_loss, angle_err, err = _composite_terms(dd, pred, gt_pos, opt, base)
     loss_net = opt.pos_w * pos_loss
     surf_on, smooth_on = _terms_on(opt, epoch)
     if surf_on:
         loss_net = loss_net + opt.surf_norm_w * surf_norm_loss
     if smooth_on:
         loss_net = loss_net + opt.smooth_w * smooth_loss
-    return {"pos_loss": pos_loss, "surf_norm_loss": surf_norm_loss, "smooth_loss": smooth_loss,
-            "loss_net": loss_net, "err": err, "angle_err": angle_err}
+    out = {"pos_loss": pos_loss, "surf_norm_loss": surf_norm_loss, "smooth_loss": smooth_loss,
+           "loss_net": loss_net, "err": err, "angle_err": angle_err}
+    if exp_type != "train":
+        out = {k: v.detach() for k, v in out.items()}
+        out.update(_composite_statistics(dd, pred.detach(), gt_pos))
+    return out

@@ -383,6 +383,19 @@ def eval_metrics(dd, key="pred_depth", frame=0):
     return Q.depth_metrics(dd[key][frame].contiguous(), gt, dd["corrupt_mask"][frame])
 
 
+def eval_loss(dd, loss_opt=None, exp_type="valid", epoch=0, stage=1):
+    """loss_dict of LIDF.forward(batch, 'valid' | 'test', epoch) (stage=1, models/pipeline.py:704-710) or of
+    RefineNet.forward (stage=2, :1032-1041) on the data_dict of lidf_forward / refine_forward: compute_gt where its
+    entries are missing, then losses.lidf_loss / losses.refine_loss in the evaluation flavour — the number a
+    trainer's validate() picks its best checkpoint by. Every entry is a detached 0-dim device tensor."""
+    from .losses import lidf_loss, refine_loss
+    if stage not in (1, 2):
+        raise ValueError("stage must be 1 or 2, not %r" % (stage,))
+    if exp_type not in ("valid", "test"):
+        raise ValueError("eval_loss is the evaluation flavour: exp_type 'valid' or 'test', not %r" % (exp_type,))
+    return (lidf_loss if stage == 1 else refine_loss)(dd, loss_opt, exp_type, epoch)
+
+
 # ------------------------------------------------------------------------------------------------
 # The same evaluation path as ONE library call per batch, without a host round trip
 # ------------------------------------------------------------------------------------------------
@@ -808,6 +821,22 @@ class FrameRunner:
             dd["end_voxel_id"] = b["end_voxel_id"][:R]
             dd["pred_depth_refine"] = b["pred_depth_refine"]
         return ok, dd
+
+    def loss_dict(self, batch, loss_opt=None, exp_type="valid", epoch=0):
+        """What a trainer's validate() / test() reads after a frame: eval_loss on result()'s data_dict plus what it
+        lacks — xyz_flat, xyz_corrupt_flat and corrupt_mask of `batch`. Returns (success, loss_dict of stage 1,
+        loss_dict of stage 2 — {} without refinement); success False (an early exit of the frame): two empty dicts.
+        It reads the frame's counts as result() does and touches neither the frame call, its graph nor its
+        workspace."""
+        ok, dd = self.result()
+        if not ok:
+            return False, {}, {}
+        bs = self.bs
+        dd["xyz_flat"] = batch["xyz"].permute(0, 2, 3, 1).contiguous().reshape(bs, -1, 3)
+        dd["xyz_corrupt_flat"] = batch["xyz_corrupt"].permute(0, 2, 3, 1).contiguous().reshape(bs, -1, 3)
+        dd["corrupt_mask"] = batch["corrupt_mask"].reshape(bs, self.h, self.w)
+        loss1 = eval_loss(dd, loss_opt, exp_type, epoch, stage=1)
+        return True, loss1, (eval_loss(dd, loss_opt, exp_type, epoch, stage=2) if self.refine else {})
 
     def metrics(self, batch, key=None, frame=0):
         """The nine ClearGrasp statistics (models/pipeline.py:577-627) of frame `frame` on the device:

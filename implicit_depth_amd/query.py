@@ -791,6 +791,25 @@ METRIC_NAMES = ("a1", "a2", "a3", "rmse", "rmse_log", "log10", "abs_rel", "mae",
 _METRICS_WS = {}   # (device index, stream) -> zeroed workspace of lidf_depth_metrics_f32
 
 
+def _seg_mask_arg(seg_mask):
+    """(mask, seg_dtype) as lidf_depth_metrics_f32 takes a segmentation mask: (None, 0) for none; the reference's
+    float corrupt_mask is read as it lies (seg_dtype 2: cast per pixel as its astype(np.uint8),
+    models/pipeline.py:588); bool / uint8 masks byte-wise (1); other integer types are converted."""
+    if seg_mask is None:
+        return None, 0
+    if seg_mask.dtype == torch.float32:
+        seg_dtype = 2
+    elif seg_mask.dtype in (torch.bool, torch.uint8):
+        seg_dtype = 1
+        if seg_mask.dtype == torch.bool:
+            seg_mask = seg_mask.view(torch.uint8)
+    else:
+        seg_mask, seg_dtype = seg_mask.to(torch.uint8), 1
+    seg_mask = seg_mask.contiguous()
+    _lib.require_cuda(seg_mask, names=["seg_mask"])
+    return seg_mask, seg_dtype
+
+
 def depth_metrics(pred_depth, gt_depth, seg_mask=None, out_size=(144, 256)):
     """The evaluation statistics of LIDF.compute_loss (models/pipeline.py:577-627, the bs == 1
     branch) on the device: cv2.resize(..., (256, 144), INTER_NEAREST) of the predicted depth, the
@@ -803,22 +822,9 @@ def depth_metrics(pred_depth, gt_depth, seg_mask=None, out_size=(144, 256)):
     if pred_depth.dim() != 2 or pred_depth.shape != gt_depth.shape:
         raise RuntimeError("pred_depth and gt_depth must be [h,w] tensors of the same shape")
     h, w = pred_depth.shape
-    seg_dtype = 0
-    if seg_mask is not None:
-        if seg_mask.shape != pred_depth.shape:
-            raise RuntimeError("seg_mask must have the shape of the depth maps")
-        # the reference's float corrupt_mask is read as it lies (cast per pixel as its astype(np.uint8),
-        # models/pipeline.py:588); bool / uint8 masks byte-wise; other integer types are converted
-        if seg_mask.dtype == torch.float32:
-            seg_dtype = 2
-        elif seg_mask.dtype in (torch.bool, torch.uint8):
-            seg_dtype = 1
-            if seg_mask.dtype == torch.bool:
-                seg_mask = seg_mask.view(torch.uint8)
-        else:
-            seg_mask, seg_dtype = seg_mask.to(torch.uint8), 1
-        seg_mask = seg_mask.contiguous()
-        _lib.require_cuda(seg_mask, names=["seg_mask"])
+    if seg_mask is not None and seg_mask.shape != pred_depth.shape:
+        raise RuntimeError("seg_mask must have the shape of the depth maps")
+    seg_mask, seg_dtype = _seg_mask_arg(seg_mask)
     dh, dw = (h, w) if out_size is None else out_size
     dev = pred_depth.device
     out = torch.empty((10,), dtype=torch.float32, device=dev)

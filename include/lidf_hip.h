@@ -37,7 +37,9 @@ enum lidf_status {
  * library was BUILT with; a binding compiled / written against this header must refuse a library that
  * answers anything else (implicit_depth_amd/_lib.py and csrc/lidf_torch_ext.cpp do, at load).
  * lidf_sample_valid_workspace_bytes / lidf_sample_valid_points, and after them lidf_topk_mean_workspace_bytes /
- * lidf_topk_mean_f32 / lidf_stage1_hard_neg_f32 / lidf_refine_hard_neg_f32 with struct LidfTopkJob, were added
+ * lidf_topk_mean_f32 / lidf_stage1_hard_neg_f32 / lidf_refine_hard_neg_f32 with struct LidfTopkJob, and after
+ * those the evaluation losses (struct LidfEvalLossArgs, lidf_stage1_eval_loss_f32 / lidf_refine_eval_loss_f32, their
+ * workspace-size functions and lidf_stage1_eval_hard_neg_f32 / lidf_refine_eval_hard_neg_f32), were added
  * WITHOUT a bump: they are purely additive (no signature or struct layout changed), so the number stays 14; a
  * binding that needs them looks the symbols up and asks for a rebuild when an ABI-14 library lacks them
  * (implicit_depth_amd/_lib.py does). */
@@ -1114,6 +1116,72 @@ int lidf_stage1_hard_neg_f32(const LidfLossArgs* args, double ratio, float* w_po
 int lidf_refine_hard_neg_f32(const LidfRefineLossArgs* args, double ratio, float* w_pos, float* w_surf,
                              float* w_dx, float* w_dy, void* workspace, size_t workspace_bytes,
                              lidf_stream_t stream);
+
+/* ---- The evaluation flavour of the two losses: exp_type 'valid' / 'test' (added without a bump of ABI 14:
+ * purely additive) -----------------------------------------------------------------------------------
+ * LIDF.compute_loss / RefineNet.compute_loss for exp_type != 'train' (models/pipeline.py:468-650, 760-919),
+ * forward only. It differs from the training flavour in three ways:
+ *   base cloud   the surface-normal and smoothness terms are taken on xyz_base = xyz_corrupt_flat with the
+ *                queried pixels replaced by gt_pos / pred_pos (:493-498, :775-780); the ground truth is
+ *                gt_pos of lidf_pair_labels_f32 (taken from xyz_flat) as before;
+ *   statistics   a1, a2, a3, rmse, rmse_log, log10 (the natural logarithm, as :607), abs_rel, mae, sq_rel
+ *                follow the training flavour's scalars: loss[17] = {pos_loss, prob_loss, surf_norm_loss,
+ *                smooth_loss, loss_net, acc, err, angle_err, a1 .. sq_rel} for stage 1, loss[15] =
+ *                {pos_loss, surf_norm_loss, smooth_loss, loss_net, err, angle_err, a1 .. sq_rel} for stage 2
+ *                (the key order of loss_dict, :628-649, :898-917). resize_metrics == 0 (the reference's
+ *                bs != 1): over the rays whose gt_pos is not the zero point, pred = pred_pos z, gt = gt_pos
+ *                z. resize_metrics != 0 (bs == 1; batch must be 1): lidf_depth_metrics_f32's statistics of
+ *                the 144 x 256 nearest-neighbour resize of the frame — gt = z of xyz_gt (xyz_flat), pred =
+ *                z of xyz_base with the queried pixels replaced, valid = gt > 0 and seg_mask (seg_dtype as
+ *                lidf_depth_metrics_f32: 0 none, 1 uint8 / bool, 2 float32) — bit-equal to that call on the
+ *                same images. No selected element: NaN (torch.mean of an empty tensor); err stays 0 (:563);
+ *   no backward  pos_unreduced / surf_norm_dist / dx_dist / dy_dist [R] and prob_unreduced [P] are written
+ *                where non-NULL only — the three per-ray vectors of the normals all or none — and serve
+ *                lidf_*_eval_hard_neg_f32 alone.
+ * Stage 2 (lidf_refine_eval_loss_f32) reads pred_pos as pred_pos_refine and none of n_pairs, pair_off,
+ * pcl_label, gt_max_pair_id, n_label, pred_prob, prob_w, prob_unreduced. Two launches (resize_metrics: a
+ * memset and four), double partial sums in a fixed order, no float atomics: bit-identical from run to run.
+ * Workspace: lidf_*_eval_loss_workspace_bytes(n_rays, resize_metrics ? height * width : 0), 8-byte aligned.
+ * lidf_*_eval_hard_neg_f32 are lidf_*_hard_neg_f32 on this struct after its forward (every unreduced
+ * vector must then have been written): loss[0..4] (stage 2: loss[0..3]) are rewritten, no weights are
+ * produced. Workspace: lidf_topk_mean_workspace_bytes(5 or 4, max(n_rays, n_pairs)).                    */
+typedef struct LidfEvalLossArgs {
+    int64_t n_rays, n_pairs;
+    int32_t batch, height, width;
+    int32_t resize_metrics;         /* 0: statistics over the rays; else over the resized frame (batch 1) */
+    const float* xyz_base;          /* [B, h*w, 3] xyz_corrupt_flat */
+    const float* xyz_gt;            /* [B, h*w, 3] xyz_flat: read under resize_metrics only */
+    const void* seg_mask;           /* [h, w] corrupt_mask of the frame, or NULL: resize_metrics only */
+    int32_t seg_dtype;
+    const int32_t* ray_bid;         /* [R] */
+    const int32_t* ray_flat;        /* [R] */
+    const int32_t* pair_off;        /* [R+1] */
+    const int32_t* pix2ray;         /* [B*h*w], lidf_pair_labels_f32 */
+    const float* gt_pos;            /* [R,3] */
+    const int64_t* pcl_label;       /* [P] */
+    const int64_t* gt_max_pair_id;  /* [R] */
+    const int32_t* n_label;         /* [1] */
+    const float* pred_pos;          /* [R,3] (stage 2: pred_pos_refine) */
+    const float* pred_prob;         /* [P] logits */
+    float pos_w, prob_w, surf_norm_w, smooth_w;
+    int32_t surf_norm_on, smooth_on;
+    float* loss;                    /* [17] (stage 2: [15]) */
+    float* pos_unreduced;           /* [R] or NULL */
+    float* surf_norm_dist;          /* [R] or NULL */
+    float* dx_dist;                 /* [R] or NULL */
+    float* dy_dist;                 /* [R] or NULL */
+    float* prob_unreduced;          /* [P] or NULL */
+    void* workspace;
+    size_t workspace_bytes;
+} LidfEvalLossArgs;
+size_t lidf_stage1_eval_loss_workspace_bytes(int64_t n_rays, int64_t resize_pixels);
+size_t lidf_refine_eval_loss_workspace_bytes(int64_t n_rays, int64_t resize_pixels);
+int lidf_stage1_eval_loss_f32(const LidfEvalLossArgs* args, lidf_stream_t stream);
+int lidf_refine_eval_loss_f32(const LidfEvalLossArgs* args, lidf_stream_t stream);
+int lidf_stage1_eval_hard_neg_f32(const LidfEvalLossArgs* args, double ratio, void* workspace,
+                                  size_t workspace_bytes, lidf_stream_t stream);
+int lidf_refine_eval_hard_neg_f32(const LidfEvalLossArgs* args, double ratio, void* workspace,
+                                  size_t workspace_bytes, lidf_stream_t stream);
 
 #ifdef __cplusplus
 }
