@@ -234,6 +234,9 @@ SIGNATURES = {
     "lidf_miss_ray_fill_f32": (C.c_int, [_P, _I, _P, _I, _I, _I, _P, _SZ, _P, _P, _P, _P, _P, _P, _P, _P]),
     "lidf_sample_valid_workspace_bytes": (_SZ, [_I, _I, _I]),
     "lidf_sample_valid_points": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "lidf_miss_window_workspace_bytes": (_SZ, [_I, _I64]),
+    "lidf_miss_ray_window_f32": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                           _SZ, _P]),
     "lidf_ray_aabb_dense_f32": (C.c_int, [_P, _P, _P, _P, _I64, _I64, _P, _P, _P]),
     "lidf_ray_aabb_count_f32": (C.c_int, [_P, _P, _P, _P, _I64, _I64, _P, _P]),
     "lidf_ray_aabb_fill_f32": (C.c_int, [_P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P, _P]),

@@ -783,6 +783,51 @@ LIDF_API int lidf_sample_valid_points(const void* mask, int mask_dtype, int batc
     return LIDF_OK;
 }
 
+// ---- the random window of the miss rays (mask -> at most bs * miss_sample_num rays) -------------------------------
+struct MissWindowWs {
+    size_t block_cnt, block_off, img_off, total;
+};
+static MissWindowWs miss_window_ws(int batch, int64_t n) {
+    const size_t nb = (size_t)((n + MISS_ITEMS - 1) / MISS_ITEMS);
+    MissWindowWs w;
+    size_t o = 0;
+    w.block_cnt = o; o += align_up((nb + 1) * 4, 256);
+    w.block_off = o; o += align_up((nb + 1) * 4, 256);
+    w.img_off = o;   o += align_up(((size_t)batch + 1) * 4, 256);
+    w.total = o;
+    return w;
+}
+
+LIDF_API size_t lidf_miss_window_workspace_bytes(int batch, int64_t n_pixels) {
+    if (batch < 1 || n_pixels < 0) return 0;
+    return miss_window_ws(batch, n_pixels).total;
+}
+
+LIDF_API int lidf_miss_ray_window_f32(const void* mask, int mask_dtype, const float* intr, int batch, int height,
+                                        int width, int miss_sample_num, const uint64_t* rng_state,
+                                        const int32_t* starts, int32_t* ray_bid, int32_t* ray_flat, int32_t* ray_pix,
+                                        float* ray_dir, int64_t* miss_bid, int64_t* miss_flat_img_id,
+                                        int64_t* miss_img_ind, int32_t* window, int32_t* n_rays, void* workspace,
+                                        size_t workspace_bytes, lidf_stream_t stream) {
+    if (batch < 1 || height < 1 || width < 1 || miss_sample_num < 1) return LIDF_ERR_BAD_ARG;
+    if (mask_dtype < LIDF_MASK_F32 || mask_dtype > LIDF_MASK_I64) return LIDF_ERR_BAD_ARG;
+    if (!mask || !window || !n_rays || !workspace) return LIDF_ERR_BAD_ARG;
+    if (!rng_state && !starts) return LIDF_ERR_BAD_ARG;
+    if (ray_dir && !intr) return LIDF_ERR_BAD_ARG;
+    const int64_t n = (int64_t)batch * height * width;
+    if (n > 0x7ffffbffLL) return LIDF_ERR_UNSUPPORTED;                                   // (as lidf_miss_ray_count)
+    if ((int64_t)batch * miss_sample_num > 0x7fffffffLL) return LIDF_ERR_UNSUPPORTED;   // rows of the outputs
+    const MissWindowWs w = miss_window_ws(batch, n);
+    if (workspace_bytes < w.total) return LIDF_ERR_WORKSPACE;
+    char* ws = (char*)workspace;
+    CHECK_HIP(lidf_launch_miss_window(mask, mask_dtype, intr, batch, height, width, miss_sample_num,
+                                      (const unsigned long long*)rng_state, starts, (int*)(ws + w.block_cnt),
+                                      (int*)(ws + w.block_off), (int*)(ws + w.img_off), ray_bid, ray_flat, ray_pix,
+                                      ray_dir, (long long*)miss_bid, (long long*)miss_flat_img_id,
+                                      (long long*)miss_img_ind, window, n_rays, (hipStream_t)stream));
+    return LIDF_OK;
+}
+
 static int check_box_args(const void* a, const void* b, const void* c, const void* d, int64_t n,
                           int64_t v) {
     if (n < 0 || v < 0) return LIDF_ERR_BAD_ARG;

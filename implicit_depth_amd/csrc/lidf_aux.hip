@@ -1678,8 +1678,6 @@ extern "C" hipError_t lidf_launch_depth_metrics(const float* pred, const float* 
 // mask element types as torch.nonzero accepts them: f32 (the reference's corrupt_mask / pred_mask
 // are float tensors, datasets/cleargrasp_dataset.py:114), u8/bool, i32, i64. NaN counts as non-zero.
 // ------------------------------------------------------------------------------------------------
-#define MISS_ITEMS 1024
-
 __global__ void lidf_miss_count_kernel(const void* __restrict__ mask, int dtype, long long n,
                                        int* __restrict__ block_cnt) {
     __shared__ int s_tmp[4];
@@ -1718,44 +1716,28 @@ __global__ void lidf_miss_fill_kernel(const void* __restrict__ mask, int dtype, 
     for (int k = 0; k < 4; ++k) {
         if (!f[k]) continue;
         const long long i = b0 + k;
-        const int b = (int)(i / hw);
-        const int rem = (int)(i % hw);
-        const int y = rem / W, x = rem % W;
-        if (ray_bid) ray_bid[j] = b;
-        if (ray_flat) ray_flat[j] = rem;
-        if (ray_pix) {
-            ray_pix[2 * j] = x;
-            ray_pix[2 * j + 1] = y;
-        }
-        if (bid64) bid64[j] = b;
-        if (flat64) flat64[j] = rem;
-        if (pix64) {
-            pix64[2 * j] = x;
-            pix64[2 * j + 1] = y;
-        }
-        if (ray_dir) {  // pipeline.py:215-219, as lidf_ray_dirs_kernel
-            const float fx = intr[4 * b], fy = intr[4 * b + 1], cx = intr[4 * b + 2],
-                        cy = intr[4 * b + 3];
-            const float vx = (float)x - cx;
-            const float vy = ((float)y - cy) * fx / fy;
-            const float vz = fx;
-            const float nrm = sqrtf(vx * vx + vy * vy + vz * vz);
-            ray_dir[3 * j] = vx / nrm;
-            ray_dir[3 * j + 1] = vy / nrm;
-            ray_dir[3 * j + 2] = vz / nrm;
-        }
+        miss_ray_write(j, (int)(i / hw), (int)(i % hw), W, intr, ray_bid, ray_flat, ray_pix, ray_dir, bid64, flat64,
+                       pix64);
         ++j;
     }
+}
+
+// pass 1 alone: block_cnt[blk] = non-zero pixels of block blk (lidf_sample.hip scans them itself)
+extern "C" hipError_t lidf_launch_miss_block_count(const void* mask, int dtype, long long n, int* block_cnt,
+                                                   hipStream_t st) {
+    const long long nb = (n + MISS_ITEMS - 1) / MISS_ITEMS;
+    if (nb <= 0) return hipSuccess;
+    hipLaunchKernelGGL(lidf_miss_count_kernel, dim3((unsigned)nb), dim3(256), 0, st, mask, dtype, n, block_cnt);
+    return hipGetLastError();
 }
 
 extern "C" hipError_t lidf_launch_miss_count(const void* mask, int dtype, long long n,
                                              int* block_cnt, int* block_off, int* sums,
                                              int* n_rays, hipStream_t st) {
     const long long nb = (n + MISS_ITEMS - 1) / MISS_ITEMS;
-    if (nb > 0)
-        hipLaunchKernelGGL(lidf_miss_count_kernel, dim3((unsigned)nb), dim3(256), 0, st, mask, dtype,
-                           n, block_cnt);
-    hipError_t e = lidf_launch_scan(block_cnt, nb, block_off, sums, st);
+    hipError_t e = lidf_launch_miss_block_count(mask, dtype, n, block_cnt, st);
+    if (e != hipSuccess) return e;
+    e = lidf_launch_scan(block_cnt, nb, block_off, sums, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(lidf_miss_total_kernel, dim3(1), dim3(64), 0, st, block_off, nb, n_rays);
     return hipGetLastError();

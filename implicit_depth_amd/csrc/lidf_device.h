@@ -582,6 +582,43 @@ __device__ __forceinline__ bool mask_nonzero(const void* mask, int dtype, long l
     }
 }
 
+// Pixels per workgroup of the mask compaction (lidf_aux.hip: get_miss_ray; lidf_sample.hip: its random window):
+// four consecutive pixels per thread, 256 threads.
+#define MISS_ITEMS 1024
+
+// Row j of the miss-ray outputs for pixel rem = y * W + x of image b (models/pipeline.py:215-230): the int32 forms
+// the query kernels take, the reference's int64 forms and the unit ray direction (as lidf_ray_dirs_kernel, formed
+// for the selected pixel only). Every output may be NULL; ray_dir needs intr [B,4] = (fx, fy, cx, cy).
+__device__ __forceinline__ void miss_ray_write(long long j, int b, int rem, int W, const float* __restrict__ intr,
+                                               int* __restrict__ ray_bid, int* __restrict__ ray_flat,
+                                               int* __restrict__ ray_pix, float* __restrict__ ray_dir,
+                                               long long* __restrict__ bid64, long long* __restrict__ flat64,
+                                               long long* __restrict__ pix64) {
+    const int y = rem / W, x = rem % W;
+    if (ray_bid) ray_bid[j] = b;
+    if (ray_flat) ray_flat[j] = rem;
+    if (ray_pix) {
+        ray_pix[2 * j] = x;
+        ray_pix[2 * j + 1] = y;
+    }
+    if (bid64) bid64[j] = b;
+    if (flat64) flat64[j] = rem;
+    if (pix64) {
+        pix64[2 * j] = x;
+        pix64[2 * j + 1] = y;
+    }
+    if (ray_dir) {  // pipeline.py:215-219
+        const float fx = intr[4 * b], fy = intr[4 * b + 1], cx = intr[4 * b + 2], cy = intr[4 * b + 3];
+        const float vx = (float)x - cx;
+        const float vy = ((float)y - cy) * fx / fy;
+        const float vz = fx;
+        const float nrm = sqrtf(vx * vx + vy * vy + vz * vz);
+        ray_dir[3 * j] = vx / nrm;
+        ray_dir[3 * j + 1] = vy / nrm;
+        ray_dir[3 * j + 2] = vz / nrm;
+    }
+}
+
 // One element's terms of the nine ClearGrasp statistics (models/pipeline.py:605-618), in the f32 operations of the
 // torch expressions (safe_log10 of the reference is the natural logarithm, :607), added to acc[0..8] = {a1, a2, a3
 // counts, (g - p)^2, log difference squared, |log difference|, |g - p| / g, |g - p|, (g - p)^2 / g}. g: ground truth,

@@ -101,6 +101,7 @@ hipError_t lidf_launch_vox_points(const float* xyz, const int* pt_key, const int
 size_t lidf_depth_metrics_ws_bytes(void);
 hipError_t lidf_launch_depth_metrics(const float* pred, const float* gt, const void* seg, int seg_dtype, int src_h,
                                      int src_w, int dst_h, int dst_w, float* out, void* ws, hipStream_t st);
+hipError_t lidf_launch_miss_block_count(const void* mask, int dtype, long long n, int* block_cnt, hipStream_t st);
 hipError_t lidf_launch_miss_count(const void* mask, int dtype, long long n, int* block_cnt, int* block_off, int* sums,
                                   int* n_rays, hipStream_t st);
 hipError_t lidf_launch_miss_fill(const void* mask, int dtype, long long n, const int* block_off, const float* intr,
@@ -298,6 +299,11 @@ size_t lidf_sample_valid_ws_bytes(int B, int H, int W);
 hipError_t lidf_launch_sample_valid(const void* mask, int dtype, int B, int H, int W, int n,
                                     const unsigned long long* rng, int* bid, int* flat, long long* idx,
                                     int* valid_cnt, void* ws, hipStream_t st);
+hipError_t lidf_launch_miss_window(const void* mask, int dtype, const float* intr, int B, int H, int W, int n,
+                                   const unsigned long long* rng, const int* starts, int* block_cnt, int* block_off,
+                                   int* img_off, int* ray_bid, int* ray_flat, int* ray_pix, float* ray_dir,
+                                   long long* bid64, long long* flat64, long long* pix64, int* window, int* n_rays,
+                                   hipStream_t st);
 
 // ---- lidf_ief16.hip
 hipError_t lidf_launch_ief16(const Ief16Args& a, int cus, hipStream_t st);

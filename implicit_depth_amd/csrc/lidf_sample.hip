@@ -29,6 +29,8 @@
 // Feistel network of SAMPLE_ROUNDS rounds on 2 * ceil(bits / 2) bits with cycle walking: evaluating it at
 // 0 .. n-1 gives n distinct values in random order at O(1) per slot. Uniform integers are
 // (u32 * range) >> 32. tests/sampler_ref.py restates all of it in numpy, bit for bit.
+// The second half of the file is the other random draw of the training front end, the window of the miss rays
+// (lidf_miss_ray_window_f32), on the same Philox and the same state.
 #include "lidf_launch.h"
 
 #define SAMPLE_THREADS 1024
@@ -207,5 +209,134 @@ extern "C" hipError_t lidf_launch_sample_valid(const void* mask, int dtype, int 
     hipLaunchKernelGGL(lidf_sample_slots_kernel, dim3((unsigned)((n + SAMPLE_SLOT_THREADS - 1) / SAMPLE_SLOT_THREADS),
                                                       (unsigned)B),
                        dim3(SAMPLE_SLOT_THREADS), 0, st, H, W, n, rng, bid, flat, idx, masks, prefix);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// The random window of the miss rays: LIDF.get_miss_ray, models/pipeline.py:232-254 (what training keeps of the
+// corrupt pixels when grid.miss_sample_num != -1), without compacting the pixels outside the windows and without a
+// size read. Image b has cnt_b non-zero pixels, T = sum cnt_b, n = miss_sample_num:
+//   sampling = B * n < T (strict, :232); sampling and cnt_b > n: the ranks [s_b, s_b + n) of the image's non-zero
+//   pixels in ascending pixel order, s_b uniform in [0, cnt_b - n]; every other image keeps all cnt_b (s_b = 0).
+// s_b = __umulhi(r[0], cnt_b - n + 1), r the Philox block of counter words (call counter lo, hi, b,
+// SAMPLE_KEY_WORD + 2) — a domain the valid sampler above never draws from, so both share one state —, or
+// clamp(starts[b], 0, cnt_b - n) when the caller passes starts. Three launches on the caller's stream:
+//   1  block_cnt[blk] = non-zero pixels of every block of MISS_ITEMS pixels (lidf_miss_count_kernel, lidf_aux.hip)
+//   2  ONE workgroup: block_off = exclusive scan of block_cnt; img_off[b] = non-zero pixels before image b, one wave
+//      per image boundary: the offset of the boundary's block plus the pixels of the partial block in front of it
+//      (h * w is no multiple of MISS_ITEMS in general); then one thread per image: the window (cnt, s, len, dst),
+//      dst the exclusive scan of len, and n_rays = (sum len, T)
+//   3  the fill pass of get_miss_ray with one more test: a non-zero pixel of global rank j is rank j - img_off[b] of
+//      its image and is written — at dst_b + rank - s_b, so in (image, pixel) order without an atomic — only if that
+//      lies in [s_b, s_b + len_b). No list of all T pixels exists at any point; rows >= sum len are not written.
+// tests/miss_window_ref.py restates the selection in numpy, bit for bit.
+__global__ __launch_bounds__(SAMPLE_THREADS) void lidf_miss_window_kernel(
+    const void* __restrict__ mask, int dtype, int B, long long hw, int n, const unsigned long long* __restrict__ rng,
+    const int* __restrict__ starts, const int* __restrict__ block_cnt, long long nb, int* block_off, int* img_off,
+    int* __restrict__ window, int* __restrict__ n_rays) {
+    __shared__ int s_wave[SAMPLE_WAVES];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int T = 0;
+    for (long long base = 0; base < nb; base += SAMPLE_THREADS) {
+        const long long blk = base + tid;
+        const int c = blk < nb ? block_cnt[blk] : 0;
+        int tot;
+        const int ex = block_scan<SAMPLE_THREADS>(c, s_wave, tot);
+        if (blk < nb) block_off[blk] = T + ex;
+        T += tot;
+    }
+    __syncthreads();   // (block_off is read below by other threads of this workgroup)
+    for (int b = wave; b <= B; b += SAMPLE_WAVES) {
+        const long long p = (long long)b * hw, blk = p / MISS_ITEMS;
+        int v = 0;
+        for (long long i = blk * MISS_ITEMS + lane; i < p; i += 64) v += mask_nonzero(mask, dtype, i) ? 1 : 0;
+        v = wave_sum(v);
+        if (lane == 0) img_off[b] = (blk < nb ? block_off[blk] : T) + v;
+    }
+    __syncthreads();   // (img_off likewise)
+    const bool sampling = (long long)B * n < (long long)T;
+    unsigned k0 = 0, k1 = 0, c0 = 0, c1 = 0;
+    if (!starts) {
+        const unsigned long long seed = rng[0], ctr = rng[1];
+        k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+        c0 = (unsigned)ctr, c1 = (unsigned)(ctr >> 32);
+    }
+    int run = 0;
+    for (int base = 0; base < B; base += SAMPLE_THREADS) {
+        const int b = base + tid;
+        int cnt = 0, s = 0, len = 0;
+        if (b < B) {
+            cnt = img_off[b + 1] - img_off[b];
+            len = cnt;
+            if (sampling && cnt > n) {
+                len = n;
+                if (starts) {
+                    s = min(max(starts[b], 0), cnt - n);
+                } else {
+                    unsigned r[4];
+                    philox4x32_10(c0, c1, (unsigned)b, SAMPLE_KEY_WORD + 2u, k0, k1, r);
+                    s = (int)__umulhi(r[0], (unsigned)(cnt - n + 1));
+                }
+            }
+        }
+        int tot;
+        const int dst = run + block_scan<SAMPLE_THREADS>(len, s_wave, tot);
+        if (b < B) {
+            window[4 * b] = cnt;
+            window[4 * b + 1] = s;
+            window[4 * b + 2] = len;
+            window[4 * b + 3] = dst;
+        }
+        run += tot;
+    }
+    if (tid == 0) {
+        n_rays[0] = run;
+        n_rays[1] = T;
+    }
+}
+
+__global__ __launch_bounds__(256) void lidf_miss_window_fill_kernel(
+    const void* __restrict__ mask, int dtype, long long npix, const int* __restrict__ block_off,
+    const int* __restrict__ img_off, const int* __restrict__ window, const float* __restrict__ intr, int H, int W,
+    int* __restrict__ ray_bid, int* __restrict__ ray_flat, int* __restrict__ ray_pix, float* __restrict__ ray_dir,
+    long long* __restrict__ bid64, long long* __restrict__ flat64, long long* __restrict__ pix64) {
+    __shared__ int s_tmp[4];
+    const long long b0 = (long long)blockIdx.x * MISS_ITEMS + threadIdx.x * 4;
+    bool f[4];
+    int v = 0;
+    for (int k = 0; k < 4; ++k) {
+        f[k] = b0 + k < npix && mask_nonzero(mask, dtype, b0 + k);
+        v += f[k] ? 1 : 0;
+    }
+    int total;
+    int j = block_off[blockIdx.x] + block_scan<256>(v, s_tmp, total);
+    const long long hw = (long long)H * W;
+    for (int k = 0; k < 4; ++k) {
+        if (!f[k]) continue;
+        const long long i = b0 + k;
+        const int b = (int)(i / hw);
+        const int rank = j - img_off[b];
+        const int s = window[4 * b + 1], len = window[4 * b + 2];
+        if (rank >= s && rank - s < len)
+            miss_ray_write((long long)window[4 * b + 3] + (rank - s), b, (int)(i % hw), W, intr, ray_bid, ray_flat,
+                           ray_pix, ray_dir, bid64, flat64, pix64);
+        ++j;
+    }
+}
+
+extern "C" hipError_t lidf_launch_miss_window(const void* mask, int dtype, const float* intr, int B, int H, int W,
+                                              int n, const unsigned long long* rng, const int* starts, int* block_cnt,
+                                              int* block_off, int* img_off, int* ray_bid, int* ray_flat, int* ray_pix,
+                                              float* ray_dir, long long* bid64, long long* flat64, long long* pix64,
+                                              int* window, int* n_rays, hipStream_t st) {
+    const long long hw = (long long)H * W, npix = (long long)B * hw;
+    const long long nb = (npix + MISS_ITEMS - 1) / MISS_ITEMS;
+    hipError_t e = lidf_launch_miss_block_count(mask, dtype, npix, block_cnt, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(lidf_miss_window_kernel, dim3(1), dim3(SAMPLE_THREADS), 0, st, mask, dtype, B, hw, n, rng,
+                       starts, (const int*)block_cnt, nb, block_off, img_off, window, n_rays);
+    hipLaunchKernelGGL(lidf_miss_window_fill_kernel, dim3((unsigned)nb), dim3(256), 0, st, mask, dtype, npix,
+                       (const int*)block_off, (const int*)img_off, (const int*)window, intr, H, W, ray_bid, ray_flat,
+                       ray_pix, ray_dir, bid64, flat64, pix64);
     return hipGetLastError();
 }

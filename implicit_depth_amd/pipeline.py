@@ -43,6 +43,11 @@ class LidfOptions:
         self.sampler_state = None              # query.sampler_state(seed, device); None = the device's default state
         # training (train_lidf.yaml): rays per image of the random window, label-selected pairs before this epoch
         self.miss_sample_num = 20000
+        # who draws that window: 'numpy' = get_miss_ray + sample_miss_rays (np.random.choice per image, the reference's
+        # own call); 'device' = query.sample_miss_window (one library call, starts drawn from sampler_state). miss_starts:
+        # device int32 [bs], the window starts of the 'device' route instead of a draw (None = draw)
+        self.miss_sample = "numpy"
+        self.miss_starts = None
         self.maxpool_label_epo = 6
         # stage 2 (test_refine.yaml)
         self.refine_forward_times = 2
@@ -58,6 +63,13 @@ class LidfOptions:
                 raise TypeError("unknown option %s" % k)
             setattr(self, k, v)
         self.sample_num()
+        self.miss_route()
+
+    def miss_route(self):
+        """miss_sample, checked: 'numpy' or 'device'."""
+        if self.miss_sample not in ("numpy", "device"):
+            raise ValueError("miss_sample must be 'numpy' or 'device', not %r" % (self.miss_sample,))
+        return self.miss_sample
 
     def sample_num(self):
         """valid_sample_num as the sampler takes it: n > 0, or 0 for every valid point (None / -1)."""
@@ -220,8 +232,12 @@ def _train_geometry(batch, full_rgb_feat, opt, valid_idx):
     V = occ["voxel_bound"].shape[0]
     if V == 0:
         return False, dd
-    miss = Q.get_miss_ray(dd["corrupt_mask"], dd["fx"], dd["fy"], dd["cx"], dd["cy"])
-    dd.update(Q.sample_miss_rays(miss, bs, opt.miss_sample_num))
+    if opt.miss_route() == "device" and opt.miss_sample_num != -1:
+        dd.update(Q.sample_miss_window(dd["corrupt_mask"], dd["fx"], dd["fy"], dd["cx"], dd["cy"], opt.miss_sample_num,
+                                       state=opt.sampler_state, starts=opt.miss_starts))
+    else:
+        miss = Q.get_miss_ray(dd["corrupt_mask"], dd["fx"], dd["fy"], dd["cx"], dd["cy"])
+        dd.update(Q.sample_miss_rays(miss, bs, opt.miss_sample_num))
     if dd["total_miss_sample_num"] == 0:
         return False, dd
     vox_bid = occ["occ_vox_bid"].to(torch.int32).contiguous()
@@ -251,7 +267,8 @@ def lidf_forward_train(batch, full_rgb_feat, pnet_model, prob_dec, offset_dec, o
     """LIDF.forward(batch, 'train', epoch) (models/pipeline.py:652-711) as one call: returns (success, data_dict,
     loss_dict). prepare_data in the train flavour (the miss rays come from corrupt_mask), get_valid_points,
     get_occ_vox_bound, get_miss_ray + the random window of opt.miss_sample_num rays per image (np.random, as the
-    reference draws it), compute_ray_aabb, compute_gt, the PointNet and the query under autograd
+    reference draws it; opt.miss_sample = 'device': query.sample_miss_window, drawn on the device from opt.sampler_state
+    or taken from opt.miss_starts, with the windows in data_dict['miss_window']), compute_ray_aabb, compute_gt, the PointNet and the query under autograd
     (query.lidf_query_train, pairs selected by the labels while epoch < opt.maxpool_label_epo) and
     losses.lidf_loss. loss_dict['loss_net'].backward() reaches full_rgb_feat and every parameter of the three
     modules. success False = one of the reference's three early exits (no occupied voxel / no miss ray / no

@@ -131,7 +131,8 @@ def get_miss_ray(mask, fx, fy, cx, cy):
     miss_ray_dir [R,3] f32, miss_img_ind [R,2] i64 (x, y), total_miss_sample_num, plus the int32
     forms the query kernels take: ray_bid, ray_flat [R], ray_pix [R,2]. R == 0 is the reference's
     'no miss ray' early exit (pipeline.py:676, :686-687). The train-only random window of
-    pipeline.py:232-254 is a slice [start:start+miss_sample_num] of these outputs per image."""
+    pipeline.py:232-254 is a slice [start:start+miss_sample_num] of these outputs per image (sample_miss_rays), or
+    sample_miss_window, which writes the windows alone."""
     intr = torch.stack((fx.float(), fy.float(), cx.float(), cy.float()), 1).contiguous()
     return _compact_mask(mask, intr)
 
@@ -263,6 +264,101 @@ def sample_valid_points(valid_mask, sample_num, block_x=8, block_y=8, state=None
     if check:
         raise_on_empty_image(cnt.tolist(), "sample_valid_points")
     return (idx, cnt) if return_counts else idx
+
+
+MISS_WINDOW_KEYS = ("ray_bid", "ray_flat", "ray_pix", "miss_ray_dir", "miss_bid", "miss_flat_img_id", "miss_img_ind")
+
+
+def miss_window_workspace(bs, h, w, device):
+    """The scratch buffer of one sample_miss_window_launch (block counts, their offsets, the image offsets)."""
+    return _lib.workspace(_lib.lib().lidf_miss_window_workspace_bytes(bs, bs * h * w), device)
+
+
+def miss_window_buffers(bs, miss_sample_num, device, ray_dir=True):
+    """Buffers of one sample_miss_window_launch: get_miss_ray's seven arrays with a capacity of bs * miss_sample_num
+    rows (no window can hold more), 'miss_window' int32 [bs,4] and 'n_rays' int32 [2]."""
+    cap = bs * int(miss_sample_num)
+    i32 = dict(dtype=torch.int32, device=device)
+    i64 = dict(dtype=torch.int64, device=device)
+    out = {"ray_bid": torch.empty((cap,), **i32), "ray_flat": torch.empty((cap,), **i32),
+           "ray_pix": torch.empty((cap, 2), **i32), "miss_bid": torch.empty((cap,), **i64),
+           "miss_flat_img_id": torch.empty((cap,), **i64), "miss_img_ind": torch.empty((cap, 2), **i64),
+           "miss_window": torch.empty((bs, 4), **i32), "n_rays": torch.empty((2,), **i32)}
+    if ray_dir:
+        out["miss_ray_dir"] = torch.empty((cap, 3), dtype=torch.float32, device=device)
+    return out
+
+
+def sample_miss_window_launch(mask, intr, miss_sample_num, state, starts, out, ws):
+    """lidf_miss_ray_window_f32 into the caller's buffers + the counter's increment, on the current stream: no
+    allocation, no read — the counterpart of sample_valid_launch, usable under torch.cuda.graph. mask [bs,h,w]
+    contiguous; intr [bs,4] f32 (fx, fy, cx, cy) or None; state int64 [2] (sampler_state) or None when starts
+    (int32 [bs]) gives the window starts; out: miss_window_buffers' dict (any of the seven arrays may be missing);
+    rows >= n_rays[0] of the arrays are left as they were."""
+    bs, h, w = mask.shape
+    dev = mask.device
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().lidf_miss_ray_window_f32(
+            _lib.ptr(mask), MASK_DTYPES[mask.dtype], _lib.ptr(intr), bs, h, w, int(miss_sample_num), _lib.ptr(state),
+            _lib.ptr(starts), _lib.ptr(out.get("ray_bid")), _lib.ptr(out.get("ray_flat")), _lib.ptr(out.get("ray_pix")),
+            _lib.ptr(out.get("miss_ray_dir")), _lib.ptr(out.get("miss_bid")), _lib.ptr(out.get("miss_flat_img_id")),
+            _lib.ptr(out.get("miss_img_ind")), _lib.ptr(out["miss_window"]), _lib.ptr(out["n_rays"]), _lib.ptr(ws),
+            ws.numel(), _lib.current_stream(dev)))
+        if state is not None:
+            state[1:].add_(1)
+
+
+def sample_miss_window(mask, fx, fy, cx, cy, miss_sample_num, state=None, starts=None):
+    """get_miss_ray + the train-only random window of LIDF.get_miss_ray (models/pipeline.py:232-254) as one library
+    call (lidf_miss_ray_window_f32): per image a contiguous window of miss_sample_num of its non-zero pixels at a
+    random start when the batch holds more than bs * miss_sample_num of them and the image more than
+    miss_sample_num, every non-zero pixel otherwise. Only the rays inside the windows are written, and the one host
+    read is the pair (R_out, T).
+
+    Returns get_miss_ray's dict (same keys and dtypes, R_out rows, total_miss_sample_num = R_out) plus 'miss_window',
+    the int32 [bs,4] device tensor (cnt_b, start_b, len_b, first output row of image b), and 'miss_total' = T, the
+    number of non-zero pixels of the whole mask. miss_sample_num == -1 is plain get_miss_ray, as for
+    sample_miss_rays.
+
+    The starts are drawn on the device from `state` (query.sampler_state; None = the device's default state — the one
+    sample_valid_points uses, from another counter domain), which every call advances. `starts` (int32 [bs] on the
+    mask's device) gives them instead, clamped to [0, cnt_b - miss_sample_num]: how a run of the reference's
+    np.random.choice draws is reproduced; the state is then neither read nor advanced."""
+    miss_sample_num = int(miss_sample_num)
+    if miss_sample_num == -1:
+        return get_miss_ray(mask, fx, fy, cx, cy)
+    if miss_sample_num < 1:
+        raise ValueError("sample_miss_window: miss_sample_num must be -1 (every ray) or >= 1")
+    if mask.dim() == 4 and mask.shape[1] == 1:
+        mask = mask[:, 0]
+    if mask.dim() != 3:
+        raise RuntimeError("mask must be [bs,h,w] or [bs,1,h,w]")
+    if mask.dtype not in MASK_DTYPES:
+        raise RuntimeError("mask dtype %s is not supported" % mask.dtype)
+    bs, h, w = mask.shape
+    if bs < 1 or h < 1 or w < 1:
+        raise ValueError("sample_miss_window: the batch, h and w must be >= 1")
+    mask = mask.contiguous()
+    intr = torch.stack((fx.float(), fy.float(), cx.float(), cy.float()), 1).contiguous()
+    dev = mask.device
+    if starts is not None:
+        if starts.dtype != torch.int32 or tuple(starts.shape) != (bs,) or starts.device != dev:
+            raise RuntimeError("starts must be an int32 [bs] tensor on the mask's device")
+        state = None
+    elif state is not None:
+        _check_sampler_state(state, dev)
+    _lib.require_cuda(mask, intr, starts, names=["mask", "intrinsics", "starts"])
+    if intr.shape[0] != bs:
+        raise RuntimeError("fx/fy/cx/cy must have one entry per image")
+    if starts is None and state is None:
+        state = default_sampler_state(dev)
+    buf = miss_window_buffers(bs, miss_sample_num, dev)
+    sample_miss_window_launch(mask, intr, miss_sample_num, state, starts, buf, miss_window_workspace(bs, h, w, dev))
+    R, T = buf.pop("n_rays").tolist()   # the one host read
+    out = {k: (v[:R] if k in MISS_WINDOW_KEYS else v) for k, v in buf.items()}
+    out["total_miss_sample_num"] = R
+    out["miss_total"] = T
+    return out
 
 
 def nonzero_pixels(mask):

@@ -39,7 +39,8 @@ enum lidf_status {
  * lidf_sample_valid_workspace_bytes / lidf_sample_valid_points, and after them lidf_topk_mean_workspace_bytes /
  * lidf_topk_mean_f32 / lidf_stage1_hard_neg_f32 / lidf_refine_hard_neg_f32 with struct LidfTopkJob, and after
  * those the evaluation losses (struct LidfEvalLossArgs, lidf_stage1_eval_loss_f32 / lidf_refine_eval_loss_f32, their
- * workspace-size functions and lidf_stage1_eval_hard_neg_f32 / lidf_refine_eval_hard_neg_f32), were added
+ * workspace-size functions and lidf_stage1_eval_hard_neg_f32 / lidf_refine_eval_hard_neg_f32), and after those
+ * lidf_miss_window_workspace_bytes / lidf_miss_ray_window_f32, were added
  * WITHOUT a bump: they are purely additive (no signature or struct layout changed), so the number stays 14; a
  * binding that needs them looks the symbols up and asks for a rebuild when an ABI-14 library lacks them
  * (implicit_depth_amd/_lib.py does). */
@@ -231,7 +232,7 @@ int lidf_ray_dirs_f32(const float* intr, int batch, int height, int width, float
 
 /* ---- Miss-ray selection -------------------------------------------------------------------
  * Replaces LIDF.get_miss_ray (models/pipeline.py:203-269), eval flavour (the train-only random
- * window of :232-254 is the caller's slice of the outputs): miss_idx = nonzero(mask.view(bs,-1))
+ * window of :232-254 is the caller's slice of the outputs, or lidf_miss_ray_window_f32 below): miss_idx = nonzero(mask.view(bs,-1))
  * in (image, pixel) order, then per selected pixel the image index, the flat pixel index y*w+x,
  * the unit ray direction (pipeline.py:215-219) and the integer pixel (x, y).
  * mask: [batch*height*width] elements of mask_dtype (the reference passes float masks; NaN is
@@ -283,6 +284,42 @@ int lidf_sample_valid_points(const void* mask, int mask_dtype, int batch, int he
                              int32_t* bid, int32_t* flat, int64_t* idx /* [batch*sample_num,2] or NULL */,
                              int32_t* valid_cnt /* [batch] */, void* workspace, size_t workspace_bytes,
                              lidf_stream_t stream);
+
+/* ---- Miss-ray window --------------------------------------------------------------------------
+ * Replaces the train-only random window of LIDF.get_miss_ray (models/pipeline.py:232-254; grid.miss_sample_num,
+ * 20000 in every shipped training config) together with the compaction in front of it: one call on the caller's
+ * stream, no size read, and only the rays inside the windows are ever written.
+ * mask: [batch,height,width] elements of mask_dtype (LIDF_MASK_*; NaN is non-zero, -0.0 is zero), any
+ * height, width >= 1, batch >= 1, batch*height*width limited as in lidf_miss_ray_count. n = miss_sample_num >= 1.
+ * Image b has cnt_b non-zero pixels, T = sum of cnt_b:
+ *   sampling = (batch * n < T), in 64-bit, strict as in the reference (:232)
+ *   sampling and cnt_b > n   the image keeps the ranks [s_b, s_b + n) of its own non-zero pixels in ascending
+ *                            pixel order, s_b uniform in [0, cnt_b - n]
+ *   otherwise                the image keeps all cnt_b (s_b = 0) — every image when sampling is false
+ * The outputs are the kept rays of image 0, 1, ... one behind the other: R_out = sum of len_b <= batch * n in both
+ * branches, so batch * n rows is the capacity of every output and no size has to be known to allocate.
+ * Draw: Philox4x32-10 (the sampler's), key (seed lo, seed hi), counter words (call counter lo, call counter hi, b,
+ * 0x80000000 + 2) — a domain lidf_sample_valid_points never draws from, so the two calls can share one state without
+ * sharing a stream of numbers — and s_b = (r[0] * (cnt_b - n + 1)) >> 32 (relative bias <= range / 2^32: 1.8e-5 at
+ * 76,800 pixels). rng_state: DEVICE memory, uint64 [2] = (seed, call counter), as for lidf_sample_valid_points; the
+ * caller enqueues the counter's increment behind the call.
+ * starts: optional DEVICE int32 [batch]; where a window is drawn s_b = clamp(starts[b], 0, cnt_b - n), elsewhere it
+ * is ignored; rng_state may then be NULL. This is how a run of the reference (numpy's generator) is reproduced.
+ * Outputs: the arrays of lidf_miss_ray_fill_f32 with a capacity of batch * n rows, any of them NULL; rows >= R_out
+ * are NOT written; ray_dir is the same expression as there (bit-equal rows). window int32 [batch,4] =
+ * (cnt_b, s_b, len_b, dst_b), dst_b the exclusive scan of len_b; n_rays int32 [2] = (R_out, T).
+ * Before any HIP call: LIDF_ERR_BAD_ARG for batch < 1, height < 1, width < 1, miss_sample_num < 1, an unknown
+ * mask_dtype, a NULL mask / window / n_rays / workspace, rng_state and starts both NULL, ray_dir without intr;
+ * LIDF_ERR_UNSUPPORTED for batch*height*width beyond lidf_miss_ray_count's limit or batch * miss_sample_num >= 2^31;
+ * LIDF_ERR_WORKSPACE for workspace_bytes below lidf_miss_window_workspace_bytes(batch, batch*height*width).  */
+size_t lidf_miss_window_workspace_bytes(int batch, int64_t n_pixels);
+int lidf_miss_ray_window_f32(const void* mask, int mask_dtype, const float* intr, int batch, int height, int width,
+                             int miss_sample_num, const uint64_t* rng_state /* device [2] or NULL */,
+                             const int32_t* starts /* device [batch] or NULL */,
+                             int32_t* ray_bid, int32_t* ray_flat, int32_t* ray_pix, float* ray_dir,
+                             int64_t* miss_bid, int64_t* miss_flat_img_id, int64_t* miss_img_ind,
+                             int32_t* window /* [batch,4] */, int32_t* n_rays /* [2] */,
+                             void* workspace, size_t workspace_bytes, lidf_stream_t stream);
 
 /* ---- Ray / voxel slab test ---------------------------------------------------------------
  * Dense drop-in for extensions/ray_aabb (ray_aabb_cuda_kernel.cu:10-126): mask [V,R] i32 and
