@@ -1634,9 +1634,12 @@ __global__ void __launch_bounds__(1024) lidf_depth_metrics_kernel(
     // (every partial is requested by a thread of its own — one memory round trip —, then added in
     // workgroup order)
     __shared__ double s_part[METRIC_MAX_WGS * METRIC_SUMS];
-    if (threadIdx.x < gridDim.x * METRIC_SUMS)
+    if (threadIdx.x < gridDim.x * METRIC_SUMS) {
         s_part[threadIdx.x] = __longlong_as_double((long long)__hip_atomic_load(
             partial + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        // (and cleared: with the ticket below the whole workspace is zero again when the call ends)
+        __hip_atomic_store(partial + threadIdx.x, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     __syncthreads();
     if (threadIdx.x < METRIC_SUMS) {
         double sum = 0.0;
@@ -1650,7 +1653,7 @@ __global__ void __launch_bounds__(1024) lidf_depth_metrics_kernel(
         const double c = s[9];  // 0 valid pixels: torch's mean of an empty tensor is NaN, so is 0/0
         depth_metric_stats(s, c, out);
         out[9] = (float)c;
-        *ticket = 0;   // the workspace is left as it was found
+        *ticket = 0;   // the workspace is left as it was found: all zero
     }
 }
 

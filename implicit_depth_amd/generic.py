@@ -72,7 +72,7 @@ def decoder_chain(mod, x, k, w1_col0=0, voxpart=None, vox_idx=None, raypart=None
     state = packed if packed is not None else {}
     ws = state.get("ws")
     if ws is None:
-        ws = state["ws"] = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=dev)
+        ws = state["ws"] = _lib.workspace(wsb, dev)
         state["ready"] = 0
     keep = []
     dec = _decoder_struct(mod, keep)
@@ -124,7 +124,7 @@ def linear_hip(x, weight, bias=None, act=0, slope=0.0, addrows=None, addidx=None
         out = torch.empty((n, nout), dtype=torch.float32, device=x.device)
     L = _lib.lib()
     wsb = L.lidf_linear_workspace_bytes(k)
-    ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=x.device)
+    ws = _lib.workspace(wsb, x.device)
     if n == 0:
         return out
     if addrows2 is not None:
@@ -413,7 +413,7 @@ class _LinearFn(torch.autograd.Function):
             db = torch.zeros((nout,), dtype=torch.float32, device=g.device) if has_bias else None
             xc = x if x.stride(1) == 1 else x.contiguous()
             wsb = L.lidf_wgrad_workspace_bytes()
-            ws = torch.empty((wsb,), dtype=torch.uint8, device=g.device)
+            ws = _lib.workspace(wsb, g.device)
             if n:
                 with torch.cuda.device(g.device):
                     _lib.check(L.lidf_wgrad_f32(_lib.ptr(g), g.stride(0), nout, _lib.ptr(xc), xc.stride(0) if n > 1 else k,

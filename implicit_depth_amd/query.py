@@ -813,7 +813,8 @@ def _cell_lookup(grid, V, B, dev, voxel_bound=None):
         raise RuntimeError("grid['grid_dims'] / grid['xmin'] must hold three entries")
     return {"coord": coord, "res": (C.c_int32 * 3)(*res), "xmin": (C.c_float * 3)(*xmin),
             "part": float(grid["part_size"]),
-            "table": torch.empty((B * res[0] * res[1] * res[2],), dtype=torch.int32, device=dev)}
+            # (per-call scratch the library fills itself: through the one allocation point, as the workspaces)
+            "table": _lib.workspace(4 * B * res[0] * res[1] * res[2], dev).view(torch.int32)}
 
 
 def _validate_grid(grid, voxel_bound):

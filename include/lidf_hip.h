@@ -750,7 +750,7 @@ int lidf_roi_align_f32(const float* feat_grid, int32_t batch, int32_t channels, 
  * — no .cpu() round trip. dst == src gives the plain masked statistics. 0 valid pixels: NaN, as
  * torch's mean of an empty tensor.
  * workspace: lidf_depth_metrics_workspace_bytes() bytes, ZERO-FILLED ONCE by the caller; a call leaves
- * it as it found it, so one buffer serves every later call of the same stream (the statistics image is
+ * it as it found it (all zero), so one buffer serves every later call of the same stream (the image is
  * summed by several workgroups, the one that arrives last adds their partial sums in a fixed order:
  * run-to-run identical). (ABI 7)                                                                 */
 size_t lidf_depth_metrics_workspace_bytes(void);
