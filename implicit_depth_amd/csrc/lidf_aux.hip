@@ -796,7 +796,7 @@ __global__ void lidf_ray_dirs_kernel(const float* __restrict__ intr, int B, int 
     const float vx = (float)x - cx;
     const float vy = ((float)y - cy) * fx / fy;
     const float vz = fx;
-    const float nrm = sqrtf(vx * vx + vy * vy + vz * vz);
+    const float nrm = ray_norm(vx, vy, vz);
     dir[3 * i] = vx / nrm;
     dir[3 * i + 1] = vy / nrm;
     dir[3 * i + 2] = vz / nrm;
@@ -1068,7 +1068,9 @@ __global__ void __launch_bounds__(256) lidf_ray_aabb_onepass_kernel(
             pair_vox[p] = v;
             *(f32x2*)(pair_t + 2 * p) = f32x2{t0, t1};
         }
-    } else {   // more hits than the LDS list holds (cannot happen on a 9^3 grid: <= 25 cells per ray)
+    } else {   // more hits than the LDS list holds. Not on the default 9^3 grid (<= 25 cells per ray); finer or
+               // longer grids get here: at full occupancy 17^3 (grid_res 16) gives rays of up to 38 hits, a
+               // 3 x 3 x 41 box rays of up to 44 (tests/test_grids_gpu.py runs both)
         int m = 0;
         for (long long v = 0; v < V; ++v) {
             if (vox_bid[v] != rb) continue;

@@ -589,6 +589,14 @@ __device__ __forceinline__ bool mask_nonzero(const void* mask, int dtype, long l
 // Row j of the miss-ray outputs for pixel rem = y * W + x of image b (models/pipeline.py:215-230): the int32 forms
 // the query kernels take, the reference's int64 forms and the unit ray direction (as lidf_ray_dirs_kernel, formed
 // for the selected pixel only). Every output may be NULL; ray_dir needs intr [B,4] = (fx, fy, cx, cy).
+// Length of a pixel's ray (x - cx, (y - cy) fx / fy, fx), pipeline.py:219, as the reference's torch.norm forms it:
+// x^2, then one fused multiply-add per further component. That reproduces the reference's own rays
+// (tests/golden g3 / g6) bit for bit; the unfused sum of three squares is one unit in the last place off on some
+// pixels, which is enough to move a ray across a cell corner it grazes (another pair list than the reference's).
+__device__ __forceinline__ float ray_norm(float vx, float vy, float vz) {
+    return sqrtf(fmaf(vz, vz, fmaf(vy, vy, vx * vx)));
+}
+
 __device__ __forceinline__ void miss_ray_write(long long j, int b, int rem, int W, const float* __restrict__ intr,
                                                int* __restrict__ ray_bid, int* __restrict__ ray_flat,
                                                int* __restrict__ ray_pix, float* __restrict__ ray_dir,
@@ -612,7 +620,7 @@ __device__ __forceinline__ void miss_ray_write(long long j, int b, int rem, int 
         const float vx = (float)x - cx;
         const float vy = ((float)y - cy) * fx / fy;
         const float vz = fx;
-        const float nrm = sqrtf(vx * vx + vy * vy + vz * vz);
+        const float nrm = ray_norm(vx, vy, vz);
         ray_dir[3 * j] = vx / nrm;
         ray_dir[3 * j + 1] = vy / nrm;
         ray_dir[3 * j + 2] = vz / nrm;

@@ -173,7 +173,7 @@ __global__ void __launch_bounds__(256) lidf_frame_head_kernel(FrameHeadArgs a) {
             const float vx = (float)x - cx;            // pipeline.py:215-219, as lidf_ray_dirs_kernel
             const float vy = ((float)y - cy) * fx / fy;
             const float vz = fx;
-            const float nrm = sqrtf(vx * vx + vy * vy + vz * vz);
+            const float nrm = ray_norm(vx, vy, vz);
             a.ray_dir[3 * im] = vx / nrm;
             a.ray_dir[3 * im + 1] = vy / nrm;
             a.ray_dir[3 * im + 2] = vz / nrm;

@@ -441,8 +441,11 @@ class FrameRunner:
     pixel; intersect_pos_type / refine_intersect_pos_type / refine_pnet_pos_type 'abs' or
     'rel'; precision "f32"
     or "f16x3" (as lidf_query / lidf_refine).
-    max_pairs bounds the pair list (default 32 per pixel: a ray crosses at most 25 cells of the 9^3
-    grid); a frame with more pairs raises in result().
+    max_pairs bounds the pair list (default 32 per pixel: a ray crosses at most 25 cells of the default 9^3
+    grid); a frame with more pairs raises in result(). The default is a statement about the default grid: with
+    opt.grid_res / xmin / xmax single rays exceed 32 pairs (at full occupancy up to 38 on 17^3, grid_res 16, and
+    up to 44 in a 3 x 3 x 41 box — the kernel handles such rays), while the mean per pixel, which is what the
+    capacity bounds, stays below (25.2 and 8.8 there); pass max_pairs for a finer grid that is densely occupied.
     offsets="selected" (opt-in; see query.lidf_query): the offset decoder runs on the arg-max pair of every ray
     only — pred_pos, the depth maps, stage 2 and the statistics are bit-identical, pred_offset / pair_pred_pos
     are meaningful at the selected pairs only (other rows: NaN, or a previous frame's selected values).

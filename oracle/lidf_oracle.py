@@ -614,12 +614,14 @@ def refine_step(pred_pos, ray_dir, ray_pix, ray_bid, ray_flat, max_pair_id, pair
 
 
 def lidf_forward(batch, full_rgb_feat, pnet_p, prob_p, off_p, valid_stride=None, multires=8,
-                 multires_views=4, offset_range=(0.0, 1.0), fast_roi=True):
+                 multires_views=4, offset_range=(0.0, 1.0), fast_roi=True, xmin=(-1.0, -1.0, 0.0),
+                 xmax=(1.0, 1.0, 2.0), grid_res=8):
     """LIDF.forward, exp_type 'test', mask_type 'all' (models/pipeline.py:652-717) as a chain of the
     restatements above: prepare_data (:91-133), get_valid_points with every valid pixel (:135-160;
     optionally every valid_stride-th), get_occ_vox_bound, get_miss_ray, compute_ray_aabb,
     PointNet2Stage, get_embedding + get_pred, and the depth map of compute_loss (:593-596).
-    Returns (success, dict)."""
+    xmin / xmax / grid_res: the voxel grid (utils/constants.py:15-16 and grid.res, the defaults), handed to
+    occupied_voxels as they are. Returns (success, dict)."""
     rgb = batch["rgb"]
     bs, _, h, w = rgb.shape
     dd = {"bs": bs, "h": h, "w": w}
@@ -632,7 +634,7 @@ def lidf_forward(batch, full_rgb_feat, pnet_p, prob_p, off_p, valid_stride=None,
     vb_, vf_ = valid_idx[:, 0], valid_idx[:, 1]
     valid_xyz = xyz_corrupt_flat[vb_, vf_]
     valid_rgb = rgb.permute(0, 2, 3, 1).contiguous().reshape(bs, -1, 3)[vb_, vf_]
-    occ = occupied_voxels(valid_xyz, vb_)
+    occ = occupied_voxels(valid_xyz, vb_, xmin, xmax, grid_res)
     dd.update(occ)
     dd.update({"valid_mask": valid_mask, "valid_xyz": valid_xyz, "valid_rgb": valid_rgb, "valid_bid": vb_})
     V = occ["voxel_bound"].shape[0]

@@ -45,8 +45,8 @@ def test_eval_chain_vs_oracle(cuda, shape, use_all_pix, precision):
     assert (dd["pair_off"].cpu().long() == ref["pair_off"]).all()
     assert (dd["pair_ray"].cpu().long() == ref["pair_ray"]).all()
     assert (dd["pair_vox"].cpu().long() == ref["pair_vox"]).all()
-    # the HIP rays differ from the oracle's by <= 1 ulp (normalisation), so t_enter/t_leave are
-    # compared with a tolerance here; bit-exactness on identical rays is test_boxes_gpu / g3
+    # (the HIP rays once differed from the oracle's by <= 1 ulp, hence the tolerances here; they are bit-equal
+    # since ray_norm in lidf_device.h: test_miss_ray_gpu.py and test_grids_gpu.py hold rays and t values exactly)
     assert (dd["pair_t"].cpu() - ref["pair_t"]).abs().max().item() <= 2e-6
     P, R = ref["pair_ray"].shape[0], ref["miss_ray_dir"].shape[0]
     cnt = ref["pair_off"][1:] - ref["pair_off"][:-1]

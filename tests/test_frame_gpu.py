@@ -50,15 +50,10 @@ def _compare(dd, ref):
 
 def _occupy(batch, cells):
     """Moves the valid points so that the cells `cells` (indices into the 9^3 grid) of every image are occupied: the
-    j-th valid pixel of an image lies in chosen cell j % len(cells). Returns the number of voxels."""
-    B, _, h, w = batch["xyz_corrupt"].shape
-    valid = (batch["depth_corrupt"] != 0).reshape(B, h * w)
-    assert int(valid.sum(1).min()) >= cells.numel()
-    cell = cells[(torch.cumsum(valid.long(), 1) - 1) % cells.numel()]
-    c = torch.stack((cell // 81, (cell // 9) % 9, cell % 9), 1).float()            # [B, 3, h w]
-    pts = torch.tensor([-1.125, -1.125, -0.125]).reshape(1, 3, 1) + (c + 0.5) * 0.25   # the cells' centres
-    batch["xyz_corrupt"] = (pts * valid.unsqueeze(1).float()).reshape(B, 3, h, w).contiguous()
-    return B * cells.numel()
+    j-th valid pixel of an image lies in chosen cell j % len(cells). Returns the number of voxels. (grids.occupy on
+    the shipped grid: the same points, tests/test_grids.py::test_occupy_on_the_default_grid_is_test_frame_gpus.)"""
+    import grids
+    return grids.occupy(batch, cells, grids.BY_NAME["default"])
 
 
 def _occupy_checkerboard(batch):

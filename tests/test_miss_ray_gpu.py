@@ -93,3 +93,35 @@ def test_train_window_matches_reference(cuda):
     ref = {k: g["t_" + k] for k in ("miss_bid", "miss_flat_img_id", "miss_ray_dir", "miss_img_ind")}
     _check(sub, ref, ref["miss_bid"].shape[0])
     assert sample_miss_rays(res, mask.shape[0], -1) is res          # miss_sample_num == -1: all rays
+
+
+def test_ray_directions_are_the_references_bit_for_bit(cuda):
+    """The unit rays of get_miss_ray and ray_dirs against the reference's own (g3 / g6 fixtures) and against the
+    oracle, exactly: the kernels form the length of a ray as the reference's torch.norm does (x^2, then one fused
+    multiply-add per further component). With the unfused sum 192 of g3's 768 rays were one unit in the last place
+    off — within the 2e-7 the tests above allow, yet enough to give a ray that grazes a cell corner another pair
+    list than the reference's on a finer grid (tests/test_grids_gpu.py, the 17^3 frame)."""
+    from implicit_depth_amd.query import get_miss_ray, ray_dirs
+    g3, g6 = np.load(os.path.join(GOLD, "g3_pipeline.npz")), np.load(os.path.join(GOLD, "g6_miss_ray.npz"))
+    h, w = [int(v) for v in g3["hw"]]
+    intr = torch.from_numpy(g3["intr"]).to(cuda)
+    res = get_miss_ray(torch.ones((2, 1, h, w), device=cuda), intr[:, 0], intr[:, 1], intr[:, 2], intr[:, 3])
+    assert (res["miss_ray_dir"].cpu().numpy() == g3["miss_ray_dir"]).all()
+    for key in ("a", "b", "c", "t"):
+        intr = torch.from_numpy(g6[key + "_intr"]).to(cuda)
+        res = get_miss_ray(torch.from_numpy(g6[key + "_mask"]).to(cuda), intr[:, 0], intr[:, 1], intr[:, 2], intr[:, 3])
+        sel = slice(None)
+        if key == "t":   # the fixture holds the train-time window of these rays
+            np.random.seed(int(g6["t_seed"]))
+            idx = torch.stack((res["miss_bid"], res["miss_flat_img_id"]), 1).cpu()
+            sel = orc.sample_miss_window(idx, g6["t_mask"].shape[0], int(g6["t_miss_sample_num"])).numpy()
+        assert (res["miss_ray_dir"].cpu().numpy()[sel] == g6[key + "_miss_ray_dir"]).all(), key
+    # image sizes and intrinsics where the two sums differ (fx != fy, principal point off the centre too)
+    for (B, h, w), skew in (((1, 66, 88), 1.0), ((2, 16, 24), 1.0), ((3, 48, 64), 1.04), ((2, 25, 33), 0.97)):
+        fx = torch.full((B,), 0.9 * w) + 0.37 * torch.arange(B)
+        fy = fx * skew
+        cx = torch.full((B,), w / 2 - 0.5) + 0.3 * (skew != 1.0)
+        cy = torch.full((B,), h / 2 - 0.5)
+        ref, _ = orc.ray_dirs(fx, fy, cx, cy, h, w)
+        got = ray_dirs(fx.to(cuda), fy.to(cuda), cx.to(cuda), cy.to(cuda), h, w)
+        assert torch.equal(got.cpu().reshape(B, h, w, 3), ref), (B, h, w)

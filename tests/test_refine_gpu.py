@@ -232,45 +232,55 @@ def test_refine_packed_weights_follow_parameter_updates(cuda):
     assert (f1.cpu() - ref).abs().max().item() <= 2e-5 and (f1 - f0).abs().max().item() > 1e-5
 
 
-@pytest.mark.parametrize("frames,occupancy", [(1, 0.1), (3, 0.4), (2, 1.0)])
-def test_refine_end_voxel_through_the_cell_table(cuda, frames, occupancy):
-    """LidfRefineArgs.voxel_coord / lidf_refine(grid=): the end voxel of a ray looked up in the cell table of
-    get_occ_vox_bound's grid instead of testing every ray against every voxel (the reference's pcl_aabb +
-    scatter max, models/pipeline.py:939-944). Same ids and — the rest of the iteration being the same kernels —
-    bit-identical positions, on points inside cells, exactly on cell faces / edges / corners (inclusive bounds:
-    the larger voxel wins), outside the grid, far away, +-inf and NaN (a NaN coordinate fails no comparison of
-    the reference's predicate: "inside" every voxel of its image), rays without a pair, random arg-max pairs."""
+def check_end_voxel_lookup(cuda, frames, occupancy, grid=None, neighbours=False):
+    """The body of test_refine_end_voxel_through_the_cell_table on any grid (`grid`: an entry of tests/grids.py;
+    None = the shipped 9^3 grid). neighbours=True also queries the torch.nextafter neighbours of the stored bounds,
+    on both sides (they take the place of some of the random interior points)."""
+    import grids
     from implicit_depth_amd.query import get_occ_vox_bound, lidf_refine
+    grid = grid or grids.BY_NAME["default"]
     g = torch.Generator().manual_seed(100 + frames)
     h, w = 24, 32
     # occupied cells: random valid points (occupancy 1.0: a point in every cell)
-    res, part = 9, 0.25
-    lo = torch.tensor([-1.125, -1.125, -0.125])
-    ncell = frames * res ** 3
+    lo, part, dims = grids.widened(*grid[1:])
+    dims_t = torch.tensor(dims)
+    n = dims[0] * dims[1] * dims[2]
+    ncell = frames * n
     cells = torch.nonzero(torch.rand(ncell, generator=g) < occupancy)[:, 0]
     if cells.numel() == 0:
         cells = torch.tensor([5])
-    cb, cr = cells // res ** 3, cells % res ** 3
-    cxyz = torch.stack((cr // 81, (cr // 9) % 9, cr % 9), 1).float()
+    cb, cr = cells // n, cells % n
+    cxyz = grids.cell_coords(cr, dims).float()
     pts = lo + (cxyz + 0.2 + 0.6 * torch.rand(cells.numel(), 3, generator=g)) * part
-    occ = get_occ_vox_bound(pts.to(cuda), cb.int().to(cuda), frames, res=8)
+    occ = get_occ_vox_bound(pts.to(cuda), cb.int().to(cuda), frames, *grid[1:])
     vb, vbid = occ["voxel_bound"], occ["occ_vox_bid"].int().contiguous()
     V = vb.shape[0]
-    assert V == cells.numel() and tuple(occ["grid_dims"]) == (9, 9, 9)
+    assert V == cells.numel() and tuple(occ["grid_dims"]) == dims
     # query points
     R = 6000
     bid = torch.randint(0, frames, (R,), generator=g)
-    pos = lo + torch.rand(R, 3, generator=g) * (res * part)
+    pos = lo + torch.rand(R, 3, generator=g) * (dims_t.float() * part)
     k = R // 6
-    face = torch.randint(0, res + 1, (k, 3), generator=g).float()
+    face = (torch.randint(0, max(dims) + 1, (k, 3), generator=g) % (dims_t + 1)).float()
     pos[:k] = lo + face * part                                            # cell corners
-    pos[k:2 * k, 0] = (lo + torch.randint(0, res + 1, (k, 3), generator=g).float() * part)[:, 0]   # on x faces
+    face = (torch.randint(0, max(dims) + 1, (k, 3), generator=g) % (dims_t + 1)).float()
+    pos[k:2 * k, 0] = (lo + face * part)[:, 0]                            # on x faces
     pos[2 * k:3 * k] = vb.cpu()[torch.randint(0, V, (k,), generator=g)][:, [0, 4, 2]]   # stored bounds themselves
     pos[3 * k:3 * k + 50] = lo - 0.3                                       # outside, near
     pos[3 * k + 50:3 * k + 100] = 1e6
     pos[3 * k + 100:3 * k + 120, 1] = float("nan")
     pos[3 * k + 120:3 * k + 130, 2] = float("inf")
     pos[3 * k + 130:3 * k + 140, 0] = -float("inf")
+    if neighbours:   # one unit in the last place off the stored bounds, every coordinate on a side of its own
+        g2 = torch.Generator().manual_seed(7 + frames)
+        stored = vb.cpu()[torch.randint(0, V, (2 * k,), generator=g2)]
+        pick = torch.randint(0, 2, (2 * k, 3), generator=g2)
+        on = torch.where(pick == 0, stored[:, :3], stored[:, 3:])
+        side = torch.randint(0, 3, (2 * k, 3), generator=g2)
+        inf = torch.tensor(float("inf"))
+        pos[4 * k:6 * k] = torch.where(side == 0, torch.nextafter(on, -inf),
+                                       torch.where(side == 1, on, torch.nextafter(on, inf)))
+        bid[4 * k:6 * k] = vbid.cpu()[torch.randint(0, V, (2 * k,), generator=g2)].long()
     P = 4000
     pair_vox = torch.randint(0, V, (P,), generator=g).int()
     mid = torch.randint(0, P + 1, (R,), generator=g)                       # P = a ray without pairs
@@ -302,3 +312,15 @@ def test_refine_end_voxel_through_the_cell_table(cuda, frames, occupancy):
     last = torch.where(inside, torch.arange(V)[None, :], torch.zeros(1, dtype=torch.long)).max(1).values
     argv = torch.cat((pair_vox.long(), torch.zeros(1, dtype=torch.long)))[mid]
     assert torch.equal(got_ev.cpu().long(), torch.maximum(last, argv))
+
+
+@pytest.mark.parametrize("frames,occupancy", [(1, 0.1), (3, 0.4), (2, 1.0)])
+def test_refine_end_voxel_through_the_cell_table(cuda, frames, occupancy):
+    """LidfRefineArgs.voxel_coord / lidf_refine(grid=): the end voxel of a ray looked up in the cell table of
+    get_occ_vox_bound's grid instead of testing every ray against every voxel (the reference's pcl_aabb +
+    scatter max, models/pipeline.py:939-944). Same ids and — the rest of the iteration being the same kernels —
+    bit-identical positions, on points inside cells, exactly on cell faces / edges / corners (inclusive bounds:
+    the larger voxel wins), outside the grid, far away, +-inf and NaN (a NaN coordinate fails no comparison of
+    the reference's predicate: "inside" every voxel of its image), rays without a pair, random arg-max pairs.
+    (Other grids: tests/test_grids_gpu.py.)"""
+    check_end_voxel_lookup(cuda, frames, occupancy)
