@@ -69,7 +69,6 @@ departure from the stated contracts: lidf_depth_metrics_kernel reset its ticket 
 workspace it promises to leave as it found it (harmless to the next call, which overwrites them before reading, but
 not what the header says); the last workgroup now clears them too.
 """
-import functools
 import zlib
 
 import numpy as np
@@ -77,8 +76,15 @@ import pytest
 import torch
 
 import ws_poison
-from util import (K_BIAS, TOL, assert_f64_close, k_for, make_module, make_pointnet, oracle_grads, oracle_query, orc,
-                  run_query, tf32_off, to_dev)
+from entry_cases import (QUERY_KEYS, check_query as _check_query, close_rel as _close_rel, intr as _intr,
+                         mask_2x16x24 as _mask_2x16x24, pointnet_case as _pointnet_case,
+                         pointnet_train_case as _pointnet_train_case, query_loss as _query_loss,
+                         query_scene as _query_scene, query_scene_gf32 as _query_scene_gf32,
+                         query_train_case as _query_train_case, refine_case as _refine_case,
+                         refine_oracle as _refine_oracle, refine_train_scene, same, scan_values as values, step_result as _step_result,
+                         voxel_points as _voxel_points, voxel_ref as _voxel_ref)
+from util import (K_BIAS, TOL, assert_f64_close, k_for, make_module, make_pointnet, oracle_grads, orc, run_query,
+                  tf32_off, to_dev)
 
 pytestmark = pytest.mark.gpu
 
@@ -90,34 +96,6 @@ def poison(monkeypatch, request):
     """_lib.workspace replaced for this test; the random bytes are seeded by the test's id."""
     with tf32_off():
         yield ws_poison.Poisoner("zeros", seed=zlib.crc32(request.node.nodeid.encode())).install(monkeypatch)
-
-
-def _bits(t):
-    t = t.detach().contiguous().reshape(-1)
-    if t.is_floating_point():
-        return t.view({2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
-    return t
-
-
-def same(got, base, what="out"):
-    """Bit for bit (NaN payloads included): tensors, and dicts / lists / tuples of them."""
-    if torch.is_tensor(base):
-        assert torch.is_tensor(got) and got.shape == base.shape and got.dtype == base.dtype, what
-        if not torch.equal(_bits(got), _bits(base)):
-            d = (got.double() - base.double()).abs()
-            raise AssertionError("%s differs from the zero-filled run: %d of %d entries, max |d| %g"
-                                 % (what, int((_bits(got) != _bits(base)).sum()), base.numel(),
-                                    float(d[d == d].max()) if bool((d == d).any()) else float("nan")))
-    elif isinstance(base, dict):
-        assert set(got) == set(base), what
-        for k in base:
-            same(got[k], base[k], "%s[%r]" % (what, k))
-    elif isinstance(base, (list, tuple)):
-        assert len(got) == len(base), what
-        for i, (a, b) in enumerate(zip(got, base)):
-            same(a, b, "%s[%d]" % (what, i))
-    else:
-        assert got == base or (got != got and base != base), (what, got, base)
 
 
 def drive(poison, mode, run, donor=None):
@@ -137,12 +115,6 @@ def drive(poison, mode, run, donor=None):
     return base, got
 
 
-def _close_rel(a, b, what, rel, floor):
-    scale = max(floor, b.abs().max().item())
-    err = (a - b).abs().max().item()
-    assert err <= rel * scale, (what, err, scale)
-
-
 # ------------------------------------------------------------------------------------------------------------------
 # Geometry
 # ------------------------------------------------------------------------------------------------------------------
@@ -151,9 +123,6 @@ def _close_rel(a, b, what, rel, floor):
 def test_exclusive_scan(cuda, poison, n, mode):
     from implicit_depth_amd import _lib
     L = _lib.lib()
-
-    def values(m):
-        return torch.randint(0, 30, (m,), generator=torch.Generator().manual_seed(m), dtype=torch.int32)
 
     def scan(m):
         xd = values(m).to(cuda)
@@ -170,19 +139,6 @@ def test_exclusive_scan(cuda, poison, n, mode):
     ref[1:] = torch.cumsum(values(n).long(), 0)
     assert (got.cpu().long() == ref).all()
     same(got, base)
-
-
-def _voxel_points(n, B):
-    g = torch.Generator().manual_seed(n + B)                          # test_voxelize_random's points
-    xyz = (torch.rand(n, 3, generator=g) - 0.5) * 3.0 + torch.tensor([0.0, 0.0, 1.0])
-    xyz[:5] = torch.tensor([-1.125, -1.125, -0.125])
-    xyz[5:8] = torch.tensor([1.125, 0.0, 1.0])
-    return xyz, torch.randint(0, B, (n,), generator=g)
-
-
-@functools.lru_cache(maxsize=None)
-def _voxel_ref(n, B):
-    return orc.occupied_voxels(*_voxel_points(n, B))
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -236,15 +192,6 @@ def test_ray_aabb_grid_walk(cuda, poison, mode):
     assert (got[0].cpu().long() == off_ref).all() and (got[1].cpu().long() == pr_ref).all()
     assert (got[2].cpu().long() == pv_ref).all() and (got[3].cpu() == pt_ref).all()
     same(got, base)
-
-
-def _mask_2x16x24(seed=1624, p=0.5):
-    return (np.random.default_rng(seed).random((2, 16, 24)) < p).astype(np.uint8)
-
-
-def _intr(bs, h, w, dev):
-    from test_miss_window_gpu import _intr as intr
-    return intr(bs, h, w, dev)
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -505,28 +452,6 @@ def test_wgrad_without_workspace_reference_only(cuda):
 # ------------------------------------------------------------------------------------------------------------------
 # Query
 # ------------------------------------------------------------------------------------------------------------------
-QUERY_KEYS = ("pred_offset", "pred_prob_end", "pair_pred_pos", "pred_pos", "pred_prob_end_softmax", "max_pair_id",
-              "depth", "rayfeat")
-
-
-@functools.lru_cache(maxsize=None)
-def _query_scene():
-    scene = orc.synthetic_scene(2, 13, 17, 6, seed=1317, ragged=True)
-    return scene, oracle_query(scene)
-
-
-def _check_query(scene, ref, got):
-    for k in ("pred_offset", "pred_prob_end", "pair_pred_pos", "pred_pos"):
-        err = (got[k].cpu() - ref[k]).abs().max().item()
-        assert err <= TOL, (k, err)
-    assert (got["pred_prob_end_softmax"].cpu() - ref["pred_prob_end_softmax"]).abs().max().item() <= 1e-5
-    gid, rid, sm, P = got["max_pair_id"].cpu(), ref["max_pair_id"], ref["pred_prob_end_softmax"], scene["P"]
-    for r in (gid != rid).nonzero().flatten().tolist():     # only float-noise ties may differ
-        assert gid[r] < P and rid[r] < P and abs(sm[gid[r]] - sm[rid[r]]) <= 1e-6
-    depth_ref = ref["pred_pos"][:, 2].reshape(scene["B"], scene["h"], scene["w"])
-    assert (got["depth"].cpu() - depth_ref).abs().mean().item() <= TOL
-
-
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("precision", ["f32", "f16x3"])
 def test_lidf_query(cuda, poison, precision, mode):
@@ -540,14 +465,6 @@ def test_lidf_query(cuda, poison, precision, mode):
     base, got = drive(poison, mode, run, donor=lambda: run(big))
     _check_query(scene, ref, got)
     same(got, base)
-
-
-@functools.lru_cache(maxsize=None)
-def _query_scene_gf32():
-    scene = dict(_query_scene()[0])
-    D = scene["D"]
-    scene["prob_p"], scene["off_p"] = orc.init_decoder("IMNET", D, 7, 5.0, gf=32), orc.init_decoder("IEF", D, 8, 5.0, gf=32)
-    return scene, oracle_query(scene)
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -574,34 +491,6 @@ def test_lidf_query_generic_gf32(cuda, poison, mode):
     base, got = drive(poison, mode, run, donor=lambda: run(big))
     _check_query(scene, ref, got)
     same(got, base)
-
-
-@functools.lru_cache(maxsize=None)
-def _query_train_case(pos_loss_only):
-    """tests/test_query_train_gpu.py::test_query_gradients' scene with oracle autograd on the CPU."""
-    scene = orc.synthetic_scene(2, 12, 16, 8, seed=71, ragged=True)
-    R, P = scene["R"], scene["P"]
-    gen = torch.Generator().manual_seed(72)
-    w = {"prob": torch.randn(P, generator=gen), "off": torch.randn(P, generator=gen), "pos": torch.randn(R, 3, generator=gen)}
-    if pos_loss_only:      # offsets="selected": pred_offset exists at the selected pairs only (_ref_loss)
-        w["off"] = torch.zeros(P)
-    pp = {k: v.clone().requires_grad_(True) for k, v in scene["prob_p"].items()}
-    po = {k: v.clone().requires_grad_(True) for k, v in scene["off_p"].items()}
-    fg = scene["feat_grid"].clone().requires_grad_(True)
-    vf = scene["vox_feat"].clone().requires_grad_(True)
-    ref = orc.query(scene["ray_dir"], scene["ray_pix"], scene["ray_bid"], scene["pair_ray"].long(),
-                    scene["pair_vox"].long(), scene["pair_t"], scene["pair_off"], fg, vf, pp, po, fast_roi=True,
-                    vox_center=scene["vox_center"], pos_rel=True, offset_range=(-0.2, 0.2), part_size=0.25)
-    _query_loss(ref, w, pos_loss_only).backward()
-    g = {"feat_grid": fg.grad, "vox_feat": vf.grad}
-    g.update({"prob." + k: v.grad for k, v in pp.items()})
-    g.update({"off." + k: v.grad for k, v in po.items()})
-    return scene, w, {k: ref[k].detach() for k in ("pred_offset", "pred_prob_end", "pair_pred_pos", "pred_pos")}, g
-
-
-def _query_loss(out, w, pos_loss_only):
-    loss = (out["pred_prob_end"][:, 0] * w["prob"]).sum() + (out["pred_pos"] * w["pos"]).sum()
-    return loss if pos_loss_only else loss + (out["pred_offset"][:, 0] * w["off"]).sum()
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -711,15 +600,6 @@ def test_ray_features_backward_without_workspace_reference_only(cuda):
 # ------------------------------------------------------------------------------------------------------------------
 # PointNet
 # ------------------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def _pointnet_case(n, v):
-    g = torch.Generator().manual_seed(n + v)
-    p = orc.init_pointnet(7, 1.5)
-    inp = torch.randn(n, 6, generator=g)
-    vox = torch.randint(0, v, (n,), generator=g)
-    return p, inp, vox, orc.pointnet2stage(p, inp, vox, v)
-
-
 # (3000, 40): the LDS table; (2000, 300): sorted walk with a 32-row window, V > 288; (600, 16385): the global-atomic
 # tables beyond 16,384 voxels
 @pytest.mark.parametrize("mode", MODES)
@@ -739,22 +619,6 @@ def test_pointnet_inference(cuda, poison, n, v, donor, mode):
     ref = _pointnet_case(n, v)[3]
     assert got.shape == ref.shape and (got.cpu() - ref).abs().max().item() <= 2e-5
     same(got, base)
-
-
-@functools.lru_cache(maxsize=None)
-def _pointnet_train_case(n, v):
-    g = torch.Generator().manual_seed(n + v)
-    p = orc.init_pointnet(7, 1.5)
-    inp = torch.randn(n, 6, generator=g)
-    vox = torch.randint(0, v, (n,), generator=g)
-    wgt = torch.randn(v, 128, generator=g)
-    pr = {k: t.clone().requires_grad_(True) for k, t in p.items()}
-    xi = inp.clone().requires_grad_(True)
-    ref = orc.pointnet2stage(pr, xi, vox, v)
-    (ref * wgt).sum().backward()
-    grads = {k: t.grad for k, t in pr.items()}
-    grads["inp"] = xi.grad
-    return p, inp, vox, wgt, ref.detach(), grads
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -787,37 +651,6 @@ def test_pointnet_training(cuda, poison, n, v, donor, mode):
 # ------------------------------------------------------------------------------------------------------------------
 # Stage 2
 # ------------------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def _refine_case():
-    """tests/test_refine_gpu.py::test_refine_synthetic_vs_oracle's scene."""
-    scene = orc.synthetic_scene(2, 12, 16, 6, seed=21, ragged=True)
-    g = torch.Generator().manual_seed(3)
-    vb = torch.cat((scene["vox_center"] - 0.125, scene["vox_center"] + 0.125), 1)
-    vbid = torch.arange(2).repeat_interleave(729).int()
-    rgb = torch.randn(2, 3, 12, 16, generator=g)
-    valid_inp = torch.randn(500, 6, generator=g) * 0.2
-    valid_vox = torch.randint(0, scene["V"], (500,), generator=g).int()
-    pnet_p = orc.init_pointnet(5, 1.5)
-    offr_p = orc.randomize_biases(orc.init_decoder("IEF", 334, 77, 5.0), 78)
-    return scene, vb, vbid, rgb, valid_inp, valid_vox, pnet_p, offr_p
-
-
-_REFINE_ORACLE = {}
-
-
-def _refine_oracle(pos, mid):
-    """Two oracle iterations from the product's own stage 1 (the same tensors in every case: computed once)."""
-    if "out" not in _REFINE_ORACLE or not torch.equal(_REFINE_ORACLE["in"], pos):
-        scene, vb, vbid, rgb, valid_inp, valid_vox, pnet_p, offr_p = _refine_case()
-        start = pos
-        for _ in range(2):
-            pos, ev, _ = orc.refine_step(pos, scene["ray_dir"], scene["ray_pix"], scene["ray_bid"], scene["ray_flat"],
-                                         mid, scene["pair_vox"], vb, vbid, rgb, scene["feat_grid"], valid_inp,
-                                         valid_vox, pnet_p, offr_p)
-        _REFINE_ORACLE.update({"in": start, "out": (pos, ev)})
-    return _REFINE_ORACLE["out"]
-
-
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("cell_table", [False, True])
 def test_lidf_refine_two_iterations(cuda, poison, cell_table, mode):
@@ -859,31 +692,13 @@ def test_lidf_refine_two_iterations(cuda, poison, cell_table, mode):
 def test_lidf_refine_train(cuda, poison, mode):
     """tests/test_train_gpu.py::test_refine_train_fused_step_vs_composed's scene (cell table on): the fused step,
     forward and backward, against the step composed from the modules' own autograd functions."""
-    from implicit_depth_amd.query import _lidf_refine_train_composed, get_occ_vox_bound, lidf_refine_train
-    g = torch.Generator().manual_seed(17)
-    B, h, w, R, P = 2, 20, 24, 700, 900
-    pts = torch.rand(600, 3, generator=g) * torch.tensor([1.6, 1.6, 1.6]) + torch.tensor([-0.8, -0.8, 0.2])
-    pb = torch.randint(0, B, (600,), generator=g).int()
+    from implicit_depth_amd.query import _lidf_refine_train_composed, lidf_refine_train
     poison.begin("zeros")
-    occ = get_occ_vox_bound(pts.to(cuda), pb.to(cuda), B, res=8)
-    vb, vbid = occ["voxel_bound"], occ["occ_vox_bid"].int().contiguous()
-    V = vb.shape[0]
-    bid = torch.randint(0, B, (R,), generator=g)
-    ctr = ((vb[:, :3] + vb[:, 3:]) / 2).cpu()
-    own = [torch.nonzero(vbid.cpu() == b)[:, 0] for b in range(B)]
-    pick = torch.stack([own[int(b)][torch.randint(0, own[int(b)].numel(), (1,), generator=g)][0] for b in bid])
-    pos0 = ctr[pick] + (torch.rand(R, 3, generator=g) - 0.5) * 0.3
-    ray_dir = torch.nn.functional.normalize(torch.randn(R, 3, generator=g), dim=1)
-    flat = torch.randint(0, h * w, (R,), generator=g)
-    ray_pix = torch.stack((flat % w, flat // w), 1).int()
-    pair_vox = torch.randint(0, V, (P,), generator=g).int()
-    mid = torch.randint(0, P + 1, (R,), generator=g)
-    rgb, feat = torch.randn(B, 3, h, w, generator=g), torch.randn(B, 32, h, w, generator=g)
-    valid_inp = torch.randn(500, 6, generator=g) * 0.2
-    valid_vox = torch.randint(0, V, (500,), generator=g).int()
-    wgt = torch.randn(R, 3, generator=g).to(cuda)
-    pnet_p = orc.init_pointnet(5, 1.5)
-    dec_p = orc.randomize_biases(orc.init_decoder("IEF", 334, 77, 5.0), 78)
+    sc = refine_train_scene(cuda)
+    occ, vb, vbid, V, bid, pos0, ray_dir, flat, ray_pix, pair_vox, mid, rgb, feat, valid_inp, valid_vox = (
+        sc[k] for k in ("occ", "vb", "vbid", "V", "bid", "pos0", "ray_dir", "flat", "ray_pix", "pair_vox", "mid", "rgb",
+                        "feat", "valid_inp", "valid_vox"))
+    wgt, pnet_p, dec_p = sc["wgt"].to(cuda), sc["pnet_p"], sc["dec_p"]
 
     def step(fn, n_valid=500, **kw):
         pnet, dec = make_pointnet(pnet_p, cuda).train(), make_module("IEF", dec_p, 334, cuda).train()
@@ -922,16 +737,6 @@ def test_lidf_refine_train(cuda, poison, mode):
 # ------------------------------------------------------------------------------------------------------------------
 # Losses
 # ------------------------------------------------------------------------------------------------------------------
-def _step_result(dd, loss, feat, mods, keys):
-    res = {"loss." + k: loss[k].detach() for k in loss}
-    res.update({k: dd[k].detach() for k in keys})
-    if feat is not None and feat.grad is not None:
-        res["full_rgb_feat"] = feat.grad
-    for i, m in enumerate(mods):
-        res.update({"m%d.%s" % (i, k): q.grad for k, q in m.named_parameters() if q.grad is not None})
-    return res
-
-
 @pytest.mark.parametrize("mode", MODES)
 def test_stage1_training_step(cuda, poison, mode):
     """pipeline.lidf_forward_train on the g9 fixture (test_train_step_gpu::test_whole_step_against_the_reference)."""
