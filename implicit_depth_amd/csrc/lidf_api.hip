@@ -2094,6 +2094,62 @@ LIDF_API int lidf_roi_align_f32(const float* feat_grid, int32_t batch, int32_t c
     return LIDF_OK;
 }
 
+// ---- its adjoint: d_feat_grid from d_out, as a gather over a pixel -> ray table (lidf_train_widths.hip) ----
+LIDF_API size_t lidf_roi_align_backward_workspace_bytes(int32_t batch, int32_t height, int32_t width) {
+    return lidf_roi_align_backward_ws_bytes(batch, height, width);
+}
+
+LIDF_API int lidf_roi_align_backward_f32(const float* d_out, int64_t ld_dout, const int32_t* ray_pix,
+                                           const int32_t* ray_bid, int64_t n_rays, int32_t batch, int32_t channels,
+                                           int32_t height, int32_t width, int32_t roi_inp_bbox,
+                                           int32_t roi_out_bbox, float* d_feat_grid, void* workspace,
+                                           size_t workspace_bytes, lidf_stream_t stream) {
+    if (batch < 0 || channels < 0 || height < 0 || width < 0 || n_rays < 0 || roi_inp_bbox < 0 ||
+        roi_out_bbox <= 0 || roi_out_bbox > 64)
+        return LIDF_ERR_BAD_ARG;
+    const int64_t nel = (int64_t)batch * channels * height * width;
+    if (nel == 0) return LIDF_OK;                       // an empty gradient: nothing to write
+    if (!d_feat_grid) return LIDF_ERR_BAD_ARG;
+    if (n_rays > 0 && (!d_out || !ray_pix || !ray_bid ||
+                       ld_dout < (int64_t)channels * roi_out_bbox * roi_out_bbox))
+        return LIDF_ERR_BAD_ARG;
+    if ((int64_t)batch * height * width > 0x3fffffffLL || n_rays > 0x7fffffffLL) return LIDF_ERR_UNSUPPORTED;
+    if (n_rays > 0 && (!workspace || workspace_bytes < lidf_roi_align_backward_ws_bytes(batch, height, width)))
+        return LIDF_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_rays == 0) {
+        CHECK_HIP(hipMemsetAsync(d_feat_grid, 0, (size_t)nel * 4, st));
+        return LIDF_OK;
+    }
+    CHECK_HIP(lidf_launch_roi_align_backward(d_out, ld_dout, ray_pix, ray_bid, n_rays, batch, channels, height,
+                                             width, roi_inp_bbox / 2, roi_out_bbox, d_feat_grid, workspace, st));
+    return LIDF_OK;
+}
+
+// ---- adjoint of the two gathered terms of lidf_linear_gather2_f32 ------------------------------------------------
+LIDF_API size_t lidf_gather2_backward_workspace_bytes(int64_t n, int64_t n_idx_rows, int32_t ncols) {
+    if (n <= 0 || n_idx_rows <= 0 || ncols <= 0 || ncols % 4) return 0;
+    return lidf_seg_sum_idx_any_ws_bytes(n, n_idx_rows, ncols);
+}
+
+LIDF_API int lidf_gather2_backward_f32(const float* dz, int64_t n, int32_t ncols, const int32_t* seg_off,
+                                         int64_t n_seg, float* d_addrows2, const int32_t* idx, int64_t n_idx_rows,
+                                         float* d_addrows, void* workspace, size_t workspace_bytes,
+                                         lidf_stream_t stream) {
+    if (n < 0 || n_seg < 0 || n_idx_rows < 0 || ncols <= 0 || ncols % 4) return LIDF_ERR_BAD_ARG;
+    const bool seg = d_addrows2 && n_seg > 0, by_idx = d_addrows && n_idx_rows > 0;
+    if (!seg && !by_idx) return LIDF_OK;                // neither table has a row to write
+    if (seg && !seg_off) return LIDF_ERR_BAD_ARG;
+    if (n > 0 && (!dz || (by_idx && !idx))) return LIDF_ERR_BAD_ARG;
+    if (((uintptr_t)dz | (uintptr_t)d_addrows | (uintptr_t)d_addrows2) & 15) return LIDF_ERR_BAD_ARG;
+    if (n > 0x7fffffffLL || n_seg > 0x7fffffffLL || n_idx_rows > 0x7fffffffLL) return LIDF_ERR_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    if (seg) CHECK_HIP(lidf_launch_seg_sum_ray(dz, ncols, seg_off, n_seg, d_addrows2, st));
+    if (by_idx)
+        CHECK_HIP(lidf_launch_seg_sum_idx_any(dz, ncols, idx, n, n_idx_rows, d_addrows, workspace, workspace_bytes, st));
+    return LIDF_OK;
+}
+
 // ---- a linear layer of any width (the modules at widths other than the shipped ones) ---------------
 LIDF_API size_t lidf_linear_workspace_bytes(int32_t k) {
     return k > 0 ? linex_stream_bytes(k) : 0;

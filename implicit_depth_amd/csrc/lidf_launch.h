@@ -220,6 +220,15 @@ hipError_t lidf_launch_segmax_backward(const float* dp, const int* arg, const in
 hipError_t lidf_launch_seg_sum_rows(const float* S, const int* idx, long long N, int F, float* out, hipStream_t st);
 hipError_t lidf_launch_embed_backward(const float* x, const float* g, long long n, int L, float* dx, hipStream_t st);
 
+// ---- lidf_train_widths.hip
+size_t lidf_roi_align_backward_ws_bytes(long long B, long long H, long long W);
+hipError_t lidf_launch_roi_align_backward(const float* d_out, long long ld, const int* ray_pix, const int* ray_bid,
+                                          long long R, int B, int Cn, int H, int W, int half, int S, float* d_feat,
+                                          void* ws, hipStream_t st);
+size_t lidf_seg_sum_idx_any_ws_bytes(long long n, long long V, int F);
+hipError_t lidf_launch_seg_sum_idx_any(const float* S, int F, const int* idx, long long n, long long V, float* out,
+                                       void* ws, size_t ws_bytes, hipStream_t st);
+
 // ---- lidf_dgrad.hip
 hipError_t lidf_launch_dgrad_chain(const float* w3, const float* w2, const float* dz3, const unsigned* m2,
                                    const unsigned* m1, long long n, float slope, float* dz2, float* dz1,

@@ -11,8 +11,11 @@ Same results as the reference's modules to the tolerance of the fast path (the s
 inside a dot product differs from cuBLAS as it does there). The decoders also train at other
 widths: every layer is an autograd function whose backward runs lidf_linear_f32 (input gradient)
 and lidf_wgrad_f32 (weight and bias gradients), the PointNet's two poolings and its gather are
-torch indexing that autograd differentiates itself; the fused query / stage-2 calls train at the
-shipped widths only.
+torch indexing that autograd differentiates itself. The stage-1 query trains at other widths through
+query_train below (query.lidf_query_train sends every configuration its fixed-width kernels are not
+built for here): the factorised layer 1 under autograd, with lidf_roi_align_backward_f32 and
+lidf_gather2_backward_f32 as the adjoints of the ROI pooling and of the two gathered tables; stage 2 has
+query._lidf_refine_train_composed. The fused single-launch training kernels stay at the shipped widths.
 
 Round 6: a decoder of gf_dim 32, 64 or 128 with a 1-wide head runs its inference as ONE register-chained launch
 (lidf_decoder_chain_f32, csrc/lidf_chain16.hip: 16-row sub-tiles of the 16 x 16 x 4 matrix instruction, activations
@@ -452,10 +455,271 @@ def pointnet_forward_train(mod, inp_feat, vox2point_idx, n_vox):
     """PointNet2Stage.forward under autograd at any width: the reference's sequence (models/pointnet.py:
     22-38) with every nn.Linear as a _LinearFn. The scatter-max and the gather are device-side torch
     indexing (scatter_reduce 'amax' / index): their backward routes a voxel's gradient to its maximal
-    point as torch_scatter does (exactly equal positive maxima — ties — share it instead)."""
+    point as torch_scatter does (exactly equal positive maxima — ties — share it instead). A layer of fewer than 32
+    outputs (point_lin1 at gf_dim 16) takes the column-sum form of its weight gradient (_train_lin), so that the
+    whole training step at other widths gives the same bits in every run."""
     from .pointnet import _segment_max
     idx = vox2point_idx.long()
-    f2 = _lin(_lin(inp_feat, mod.point_lin1, 1), mod.point_lin2, 1)
-    g1 = _lin(_segment_max(f2, idx, n_vox), mod.vox_lin1, 1)
-    f5 = _lin(_lin(torch.cat((g1[idx], f2), -1), mod.point_lin3, 1), mod.point_lin4, 1)
-    return _lin(_segment_max(f5, idx, n_vox), mod.vox_lin2, 1)
+    f2 = _train_lin(_train_lin(inp_feat, mod.point_lin1, 1), mod.point_lin2, 1)
+    g1 = _train_lin(_segment_max(f2, idx, n_vox), mod.vox_lin1, 1)
+    f5 = _train_lin(_train_lin(torch.cat((g1[idx], f2), -1), mod.point_lin3, 1), mod.point_lin4, 1)
+    return _train_lin(_segment_max(f5, idx, n_vox), mod.vox_lin2, 1)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# The query under autograd at any width (get_embedding + get_pred for the stage-1 training step)
+# ------------------------------------------------------------------------------------------------------------------
+def _leaky_mask(g, out, slope):
+    return g * torch.where(out > 0, torch.ones((), device=g.device), torch.full((), slope, device=g.device))
+
+
+def _wgrad_into(a, b, c, col0=0, db=None):
+    """c[:, col0 : col0 + b.shape[1]] += a^T b, db += column sums of a (lidf_wgrad_f32 straight into the column
+    block of a wider gradient through ldc)."""
+    n, m, k = a.shape[0], a.shape[1], b.shape[1]
+    if n == 0:
+        return
+    L = _lib.lib()
+    b = b if b.stride(1) == 1 else b.contiguous()
+    wsb = L.lidf_wgrad_workspace_bytes()
+    ws = _lib.workspace(wsb, a.device)
+    with torch.cuda.device(a.device):
+        _lib.check(L.lidf_wgrad_f32(_lib.ptr(a), a.stride(0) if n > 1 else m, m, _lib.ptr(b),
+                                    b.stride(0) if n > 1 else k, k, n, c.data_ptr() + 4 * col0, c.stride(0),
+                                    _lib.ptr(db), _lib.ptr(ws), wsb, _lib.current_stream(a.device)))
+
+
+def gather2_backward(dz, seg_off=None, n_seg=0, idx=None, n_idx_rows=0):
+    """(d_addrows2 [n_seg, F], d_addrows [n_idx_rows, F]) of dz [n, F] through lidf_gather2_backward_f32: sums over
+    the row ranges of the CSR offsets seg_off and sums by the row index idx; either may be left out (None)."""
+    n, F = dz.shape
+    dev = dz.device
+    L = _lib.lib()
+    d2 = torch.empty((n_seg, F), dtype=torch.float32, device=dev) if seg_off is not None else None
+    d1 = torch.empty((n_idx_rows, F), dtype=torch.float32, device=dev) if idx is not None else None
+    wsb = L.lidf_gather2_backward_workspace_bytes(n, n_idx_rows, F) if idx is not None else 0
+    ws = _lib.workspace(wsb, dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.lidf_gather2_backward_f32(_lib.ptr(dz), n, F, _lib.ptr(seg_off), n_seg, _lib.ptr(d2),
+                                               _lib.ptr(idx), n_idx_rows, _lib.ptr(d1), _lib.ptr(ws), wsb,
+                                               _lib.current_stream(dev)))
+    return d2, d1
+
+
+class _RoiAlignFn(torch.autograd.Function):
+    """The per-ray ROI feature [R, C S^2] (lidf_roi_align_f32) with its adjoint to the feature map
+    (lidf_roi_align_backward_f32: a gather, bit-reproducible for rays on distinct pixels). The backward runs only
+    when feat_grid needs a gradient."""
+
+    @staticmethod
+    def forward(ctx, feat_grid, ray_pix, ray_bid, roi_inp_bbox, roi_out_bbox):
+        ctx.save_for_backward(ray_pix, ray_bid)
+        ctx.cfg = (tuple(feat_grid.shape), int(roi_inp_bbox), int(roi_out_bbox))
+        return roi_align_rays(feat_grid, ray_pix, ray_bid, roi_inp_bbox, roi_out_bbox)
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 5
+        ray_pix, ray_bid = ctx.saved_tensors
+        (B, Cn, h, w), inp, outb = ctx.cfg
+        g = g.detach().contiguous().float()
+        dev = g.device
+        d_feat = torch.empty((B, Cn, h, w), dtype=torch.float32, device=dev)
+        L = _lib.lib()
+        wsb = L.lidf_roi_align_backward_workspace_bytes(B, h, w)
+        ws = _lib.workspace(wsb, dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.lidf_roi_align_backward_f32(_lib.ptr(g), g.shape[1], _lib.ptr(ray_pix), _lib.ptr(ray_bid),
+                                                     g.shape[0], B, Cn, h, w, inp, outb, _lib.ptr(d_feat),
+                                                     _lib.ptr(ws), wsb, _lib.current_stream(dev)))
+        return d_feat, None, None, None, None
+
+
+class _Layer1Fn(torch.autograd.Function):
+    """Layer 1 of a decoder in its factorised form, per pair: act(W1[:, pair columns] PE(p) + voxpart[voxel(p)] +
+    raypart[ray(p)]) with voxpart = W1[:, voxel columns] vox_feat + b1 [V, 4 gf] and raypart = W1[:, ROI columns] roi +
+    W1[:, direction columns] embed(dir) [R, 4 gf] (lidf_linear_f32 / lidf_linear_gather2_f32). No [P, D] row is formed,
+    and no row gradient: the backward reduces dZ1 to the two tables (lidf_gather2_backward_f32, fixed order) before it
+    meets a weight, forms the pair-column block of dW1 straight from the embedding rows (lidf_wgrad_f32 into the
+    column block) and the other blocks, d vox_feat and d roi from the tables."""
+
+    @staticmethod
+    def forward(ctx, vox_feat, roi, w1, b1, edir, pe, pair_off, pair_ray, pair_vox, act):
+        vf, rf = vox_feat.detach().contiguous(), roi.detach().contiguous()
+        Cv, Cr, E2, Ed = vf.shape[1], rf.shape[1], pe.shape[1], edir.shape[1]
+        R = rf.shape[0]
+        ray_rows = torch.arange(R, dtype=torch.int32, device=vf.device)
+        voxpart = linear_hip(vf, w1, b1, k=Cv)
+        rp = linear_hip(rf, w1, None, w_col0=Cv, k=Cr)
+        raypart = linear_hip(edir, w1, None, w_col0=Cv + Cr + E2, k=Ed, addrows=rp, addidx=ray_rows)
+        out = linear_hip(pe, w1, None, act=1 if act else 0, slope=0.02 if act else 0.0, w_col0=Cv + Cr, k=E2,
+                         addrows=voxpart, addidx=pair_vox, addrows2=raypart, addidx2=pair_ray)
+        ctx.act = act
+        ctx.save_for_backward(vox_feat, roi, w1, edir, pe, pair_off, pair_vox, out if act else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        vox_feat, roi, w1, edir, pe, pair_off, pair_vox, out = ctx.saved_tensors
+        vf, rf, w = vox_feat.detach().contiguous(), roi.detach().contiguous(), w1.detach()
+        Cv, Cr, E2, Ed = vf.shape[1], rf.shape[1], pe.shape[1], edir.shape[1]
+        V, R = vf.shape[0], rf.shape[0]
+        dz = g.detach().contiguous().float()
+        if ctx.act:
+            dz = _leaky_mask(dz, out, 0.02)
+        d_ray, d_vox = gather2_backward(dz, pair_off, R, pair_vox, V)
+        dvf = droi = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dvf = linear_hip(d_vox, w[:, :Cv].t().contiguous())
+        if ctx.needs_input_grad[1]:
+            droi = linear_hip(d_ray, w[:, Cv:Cv + Cr].t().contiguous())
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+            dw = torch.zeros(w.shape, dtype=torch.float32, device=dz.device)
+            db = torch.zeros((w.shape[0],), dtype=torch.float32, device=dz.device)
+            _wgrad_into(d_vox, vf, dw, 0, db)          # (b1 enters once per voxel row: its gradient is the tables' sum)
+            _wgrad_into(d_ray, rf, dw, Cv)
+            _wgrad_into(dz, pe, dw, Cv + Cr)
+            _wgrad_into(d_ray, edir, dw, Cv + Cr + E2)
+        return dvf, droi, dw, db, None, None, None, None, None, None
+
+
+class _EncLayer1Fn(torch.autograd.Function):
+    """One pass of an IEF's layer 1: leaky(base + W1[:, enc columns] enc) — the 16 offset-encoding columns as their
+    own small product added to the kept pass-independent base (lidf_linear_f32 with the base as its gathered term)."""
+
+    @staticmethod
+    def forward(ctx, enc, w1, base, col0, rows):
+        e = enc.detach().contiguous()
+        out = linear_hip(e, w1, None, act=1, slope=0.02, addrows=base.detach(), addidx=rows, w_col0=col0,
+                         k=e.shape[1])
+        ctx.col0 = col0
+        ctx.save_for_backward(enc, w1, out)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        enc, w1, out = ctx.saved_tensors
+        e, w = enc.detach().contiguous(), w1.detach()
+        c0, k = ctx.col0, enc.shape[1]
+        dz = _leaky_mask(g.detach().contiguous().float(), out, 0.02)
+        denc = dw = None
+        if ctx.needs_input_grad[0]:
+            denc = linear_hip(dz, w[:, c0:c0 + k].t().contiguous())
+        if ctx.needs_input_grad[1]:
+            dw = torch.zeros(w.shape, dtype=torch.float32, device=dz.device)
+            _wgrad_into(dz, e, dw, c0)
+        return denc, dw, dz if ctx.needs_input_grad[2] else None, None, None
+
+
+class _NarrowLinearFn(torch.autograd.Function):
+    """act(x W^T + b) for the layers lidf_wgrad_f32's fixed-order block path does not take (fewer than 32 outputs or fewer
+    than 4 inputs: the 1-wide output layer, offset_enc = Linear(1, 16)): the weight and bias gradients are the column
+    sums of the per-row products [g_o x_j | g_o], formed by lidf_gather2_backward_f32 onto a single destination row —
+    chunk sums in row order, chunks in order — so that these gradients too are bit-identical from run to run."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, act, slope):
+        out = linear_hip(x.detach(), weight, bias, act=act, slope=slope)
+        ctx.cfg = (act, slope)
+        ctx.save_for_backward(x, weight, out if act else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w, out = ctx.saved_tensors
+        x, w = x.detach(), w.detach()
+        g = g.detach().contiguous().float()
+        if ctx.cfg[0]:
+            g = _leaky_mask(g, out, ctx.cfg[1])
+        n, nout, k = x.shape[0], w.shape[0], w.shape[1]
+        dx = linear_hip(g, w.t().contiguous()) if ctx.needs_input_grad[0] else None
+        F = (nout * k + nout + 3) // 4 * 4
+        prod = torch.zeros((n, F), dtype=torch.float32, device=g.device)
+        prod[:, :nout * k] = (g[:, :, None] * x[:, None, :]).reshape(n, nout * k)
+        prod[:, nout * k:nout * k + nout] = g
+        _, s = gather2_backward(prod, idx=torch.zeros((n,), dtype=torch.int32, device=g.device), n_idx_rows=1)
+        return dx, s[0, :nout * k].reshape(nout, k).clone(), s[0, nout * k:nout * k + nout].clone(), None, None
+
+
+def _train_lin(x, layer, act=0, slope=0.0):
+    """A layer under autograd: _LinearFn where lidf_wgrad_f32 sums in a fixed order, the column-sum form for the
+    narrow ones."""
+    nout, k = layer.weight.shape
+    if (nout < 32 or k < 4) and layer.bias is not None and nout * (k + 1) <= 1024:
+        return _NarrowLinearFn.apply(x, layer.weight, layer.bias, act, slope)
+    return _LinearFn.apply(x, layer.weight, layer.bias, act, slope)
+
+
+def _decoder_train_from_layer1(mod, layer1, n, dev):
+    """decoder_forward_train behind the factorised layer 1. layer1(act) -> [n, 4 gf] under autograd."""
+    from .decoders import IEF, _init_offset_value
+
+    def rest(h):
+        h = _train_lin(h, mod.linear_2, 1, 0.02)
+        h = _train_lin(h, mod.linear_3, 1, 0.02)
+        return _train_lin(h, mod.linear_4)
+    if not isinstance(mod, IEF):
+        return _out_act(mod, rest(layer1(True)))
+    base = layer1(False)
+    rows = torch.arange(n, dtype=torch.int32, device=dev)
+    off = torch.full((n, 1), _init_offset_value(mod), dtype=torch.float32, device=dev)
+    for _ in range(int(mod.n_iter)):   # (the passes share every parameter: autograd adds their gradients up)
+        enc = _train_lin(off, mod.offset_enc)
+        off = off + rest(_EncLayer1Fn.apply(enc, mod.linear_1.weight, base, int(mod.inp_dim), rows))
+    return _out_act(mod, off)
+
+
+def query_train(ray_dir, ray_pix, ray_bid, pair_off, pair_ray, pair_vox, pair_t, feat_grid, vox_feat, prob_dec,
+                offset_dec, multires=8, multires_views=4, roi_inp_bbox=8, roi_out_bbox=2, offset_range=(0.0, 1.0),
+                part_size=0.25, vox_center=None, pos_rel=False, max_pair_id=None, offsets="all"):
+    """get_embedding + get_pred (models/pipeline.py:338-466) under autograd at any rgb_out / roi_out_bbox / pnet_out /
+    gf_dim / multires: what query.lidf_query_train is at the shipped widths. Gradients reach feat_grid (through
+    _RoiAlignFn), vox_feat and every parameter of both decoders. Layer 1 keeps the factorised form of `query` — the
+    per-voxel and per-ray tables, only the 2E position-embedding columns per pair (_Layer1Fn) —, the layers behind it
+    are one autograd function each, an IEF's passes add their 16 encoded-offset columns to the kept base
+    (_EncLayer1Fn), and the tail is query._QueryTailFn (pair positions, per-ray softmax / arg-max over the detached
+    logits, the max_pair_id override). Every launch goes to the caller's current stream.
+    Run-to-run: bit-identical gradients when the rays are distinct pixels, both decoders have gf_dim >= 32 and
+    multires_views >= 1 (lidf_roi_align_backward_f32, lidf_gather2_backward_f32 and lidf_wgrad_f32's block path sum
+    in fixed orders; a 3-column direction block or a layer of fewer than 32 outputs falls to lidf_wgrad_f32's
+    atomics beyond 512 rows) and at most 16,384 voxel rows.
+    Returns lidf_query_train's dict."""
+    from .decoders import get_embedder
+    from .query import _QueryTailFn
+    if offsets != "all":
+        raise RuntimeError("offsets=%r runs inside the fixed-width training kernel only (gf_dim 64, rgb_out 32, "
+                           "roi_out_bbox 2, pnet_out 128); at other widths the offset decoder runs on every pair"
+                           % (offsets,))
+    if prob_dec.linear_4.out_features != 1 or offset_dec.linear_4.out_features != 1:
+        raise RuntimeError("the query takes decoders with out_dim == 1 (got prob_dec %d, offset_dec %d)"
+                           % (prob_dec.linear_4.out_features, offset_dec.linear_4.out_features))
+    dev = ray_dir.device
+    R, P = ray_dir.shape[0], pair_ray.shape[0]
+    E = 3 + 6 * multires
+    L = _lib.lib()
+    roi = _RoiAlignFn.apply(feat_grid, ray_pix, ray_bid, roi_inp_bbox, roi_out_bbox)
+    edir = get_embedder(multires_views)[0](ray_dir.detach().contiguous()).detach()   # a constant of the step
+    D = vox_feat.shape[1] + roi.shape[1] + 2 * E + edir.shape[1]
+    for dec in (prob_dec, offset_dec):
+        if D != dec.inp_dim or dec.linear_1.in_features < D:
+            raise RuntimeError("decoder inp_dim must be %d for this configuration" % D)
+    pe = torch.empty((P, 2 * E), dtype=torch.float32, device=dev)
+    if P:
+        with torch.cuda.device(dev):
+            _lib.check(L.lidf_pe_rows_f32(_lib.ptr(pair_ray), _lib.ptr(pair_vox), _lib.ptr(pair_t), _lib.ptr(ray_dir),
+                                          _lib.ptr(vox_center), 1 if pos_rel else 0, multires, P, _lib.ptr(pe),
+                                          _lib.current_stream(dev)))
+    outs = []
+    for dec in (prob_dec, offset_dec):
+        l1 = dec.linear_1
+
+        def layer1(act, l1=l1):
+            return _Layer1Fn.apply(vox_feat, roi, l1.weight, l1.bias, edir, pe, pair_off, pair_ray, pair_vox, act)
+        outs.append(_decoder_train_from_layer1(dec, layer1, P, dev))
+    pred_prob, pred_offset = outs
+    pair_pred_pos, sm, mid, pred_pos = _QueryTailFn.apply(
+        pred_offset, pred_prob, pair_off, pair_ray, pair_t, ray_dir, float(offset_range[0]), float(offset_range[1]),
+        float(part_size), max_pair_id)
+    return {"pred_offset": pred_offset, "pred_prob_end": pred_prob, "pair_pred_pos": pair_pred_pos,
+            "pred_prob_end_softmax": sm, "max_pair_id": mid, "pred_pos": pred_pos}

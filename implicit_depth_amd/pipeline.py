@@ -284,8 +284,8 @@ def lidf_forward_train(batch, full_rgb_feat, pnet_model, prob_dec, offset_dec, o
         dd["miss_ray_dir"], dd["ray_pix"], dd["ray_bid"], dd["pair_off"], dd["pair_ray"], dd["pair_vox"],
         dd["pair_t"], full_rgb_feat,
         dd["occ_voxel_feat"], prob_dec, offset_dec, multires=opt.multires, multires_views=opt.multires_views,
-        roi_inp_bbox=opt.roi_inp_bbox, offset_range=opt.offset_range, part_size=dd["part_size"],
-        vox_center=_vox_center(dd, opt), pos_rel=opt.intersect_pos_type == "rel",
+        roi_inp_bbox=opt.roi_inp_bbox, roi_out_bbox=opt.roi_out_bbox, offset_range=opt.offset_range,
+        part_size=dd["part_size"], vox_center=_vox_center(dd, opt), pos_rel=opt.intersect_pos_type == "rel",
         max_pair_id=dd["gt_max_pair_id"] if epoch < opt.maxpool_label_epo else None))
     return True, dd, lidf_loss(dd, loss_opt, "train", epoch)
 

@@ -1228,7 +1228,7 @@ class _QueryTrainFn(torch.autograd.Function):
 def lidf_query_train(ray_dir, ray_pix, ray_bid, pair_off, pair_ray, pair_vox, pair_t, feat_grid,
                      vox_feat, prob_dec, offset_dec, multires=8, multires_views=4, roi_inp_bbox=8,
                      offset_range=(0.0, 1.0), part_size=0.25, vox_center=None, pos_rel=False,
-                     factorised=True, max_pair_id=None, offsets="all"):
+                     factorised=True, max_pair_id=None, offsets="all", roi_out_bbox=2):
     """Differentiable get_embedding + get_pred (models/pipeline.py:338-466) for training
     (train_lidf.py:393-396): gradients reach feat_grid (through RoIAlign), vox_feat and every
     decoder parameter, all through liblidf_hip — ROI pooling, the decoder input rows, the decoders'
@@ -1245,6 +1245,10 @@ def lidf_query_train(ray_dir, ray_pix, ray_bid, pair_off, pair_ray, pair_vox, pa
     forward as well — pred_offset / pair_pred_pos are zero at every other pair, which nothing in the reference reads
     (pred_offset is a local of get_pred, pair_pred_pos is stored at pipeline.py:461 and never used); pred_pos, the
     logits and every gradient of a loss on them are those of offsets="all".
+    Widths other than the shipped configuration — rgb_out (feat_grid's channels), roi_out_bbox, pnet_out (vox_feat's
+    columns), decoders of another gf_dim — take generic.query_train under factorised=True: the same factorised
+    layer 1, the layers behind it one autograd function each (it refuses offsets="selected" and a head wider than 1).
+    factorised=False stays the shipped-feature-width rows route.
     Returns pred_offset, pred_prob_end [P,1], pair_pred_pos [P,3], pred_prob_end_softmax [P],
     max_pair_id [R] (P for an empty ray) and pred_pos [R,3]."""
     if offsets not in ("all", "selected"):
@@ -1262,11 +1266,27 @@ def lidf_query_train(ray_dir, ray_pix, ray_bid, pair_off, pair_ray, pair_vox, pa
             _f32(t, n)
     for t, n in ((pair_off, "pair_off"), (pair_ray, "pair_ray"), (pair_vox, "pair_vox")):
         _i32(t, n)
-    if feat_grid.dim() != 4 or feat_grid.shape[1] != 32:
-        raise RuntimeError("feat_grid must be [B,32,h,w] (rgb_out=32)")
-    if vox_feat.dim() != 2 or vox_feat.shape[1] != 128:
-        raise RuntimeError("vox_feat must be [V,128] (pnet_out=128)")
+    if feat_grid.dim() != 4 or vox_feat.dim() != 2:
+        raise RuntimeError("feat_grid must be [B,rgb_out,h,w] and vox_feat [V,pnet_out]")
     R, P = ray_dir.shape[0], pair_ray.shape[0]
+    from .decoders import is_shipped
+    # the fixed-width route (one training launch per decoder) is built for rgb_out 32, roi_out_bbox 2, pnet_out 128 and
+    # decoders of gf_dim 64 with a 1-wide head; every other configuration runs generic.query_train — the factorised
+    # layer 1 and the layers behind it as one autograd function each
+    fixed_feat = feat_grid.shape[1] == 32 and vox_feat.shape[1] == 128 and roi_out_bbox == 2
+    if factorised and not (fixed_feat and is_shipped(prob_dec) and is_shipped(offset_dec)):
+        if pair_off.shape[0] != R + 1 or ray_pix.shape != (R, 2) or ray_bid.shape != (R,):
+            raise RuntimeError("pair_off / ray_pix / ray_bid must be [R+1] / [R,2] / [R]")
+        from . import generic
+        return generic.query_train(ray_dir, ray_pix, ray_bid, pair_off, pair_ray, pair_vox, pair_t, feat_grid,
+                                   vox_feat, prob_dec, offset_dec, multires, multires_views, roi_inp_bbox,
+                                   roi_out_bbox, offset_range, part_size, vox_center, pos_rel, max_pair_id, offsets)
+    if feat_grid.shape[1] != 32:
+        raise RuntimeError("feat_grid must be [B,32,h,w] (rgb_out=32)")
+    if vox_feat.shape[1] != 128:
+        raise RuntimeError("vox_feat must be [V,128] (pnet_out=128)")
+    if roi_out_bbox != 2:
+        raise RuntimeError("factorised=False materialises the shipped [P,385] rows: roi_out_bbox must be 2")
     if pair_off.shape[0] != R + 1 or ray_pix.shape != (R, 2) or ray_bid.shape != (R,):
         raise RuntimeError("pair_off / ray_pix / ray_bid must be [R+1] / [R,2] / [R]")
     dev = ray_dir.device

@@ -738,6 +738,46 @@ int lidf_roi_align_f32(const float* feat_grid, int32_t batch, int32_t channels, 
                        const int32_t* ray_pix, const int32_t* ray_bid, int64_t n_rays, int32_t roi_inp_bbox,
                        int32_t roi_out_bbox, float* out, int64_t ld_out, lidf_stream_t stream);
 
+/* Its adjoint: d_feat_grid [B, C, H, W] from d_out [R, C*S*S] (row stride ld_dout >= C*S*S), the forward's boxes,
+ * sampling and column order. Every element of d_feat_grid is written, zeros included: the caller does no memset.
+ * A gather, not a scatter: a pixel -> ray table is built in the workspace, then every feature pixel visits the rays
+ * centred within roi_inp_bbox / 2 + 1 of it, forms its separable tap weights for each of the ray's bins from the
+ * ray's own clamped box and sums weight * d_out over them in a fixed order of the source pixels. No float atomics.
+ * Reproducibility: when no two rays share a (frame, pixel) — every caller in pipeline.py: miss rays are distinct
+ * pixels — the result is bit-identical from run to run. Rays that share a pixel are added in an order that is not
+ * fixed (their slots in the table are handed out by an integer atomic): the result then equals the sum to float32
+ * rounding of that addition only, not bit for bit. The result never depends on the workspace's contents at entry.
+ * Rays whose frame or pixel lies outside the image contribute nothing. More rays than pixels go through in chunks
+ * of B*H*W rays. n_rays == 0 writes zeros. An empty d_feat_grid (a zero extent) returns LIDF_OK at once.
+ *   workspace  lidf_roi_align_backward_workspace_bytes(batch, height, width)
+ * (additive, ABI unchanged)                                                                                     */
+size_t lidf_roi_align_backward_workspace_bytes(int32_t batch, int32_t height, int32_t width);
+int lidf_roi_align_backward_f32(const float* d_out, int64_t ld_dout, const int32_t* ray_pix, const int32_t* ray_bid,
+                                int64_t n_rays, int32_t batch, int32_t channels, int32_t height, int32_t width,
+                                int32_t roi_inp_bbox, int32_t roi_out_bbox, float* d_feat_grid, void* workspace,
+                                size_t workspace_bytes, lidf_stream_t stream);
+
+/* Adjoint of the two gathered terms of lidf_linear_gather2_f32: from dz [n, ncols] (dense rows, dL/d of the layer's
+ * pre-activation)
+ *   d_addrows2 [n_seg, ncols]      = sums over the contiguous row ranges seg_off[s] .. seg_off[s + 1]  (a CSR offset
+ *                                    array of n_seg + 1 entries: the per-ray table with pair_off)
+ *   d_addrows  [n_idx_rows, ncols] = sums over the rows with idx[p] == v  (the per-voxel table with pair_vox; rows
+ *                                    whose index lies outside [0, n_idx_rows) are left out)
+ * Both tables are overwritten, a destination without rows gets zeros; either table may be NULL. ncols must be a
+ * multiple of 4 (layer 1 is 4 gf_dim wide), the three arrays 16-byte aligned.
+ * Reproducibility: no float atomics and a fixed summation order — the range sums add their rows in order; the index
+ * sums sort the rows by index with a stable counting sort, add every index's rows in chunks of 128 sorted rows (four
+ * interleaved lanes, added in order) and the chunks in order — so both tables are bit-identical from run to run and
+ * independent of the workspace's contents at entry. This holds up to 16,384 index rows (the sort's histogram lives
+ * in LDS) with a workspace of lidf_gather2_backward_workspace_bytes(n, n_idx_rows, ncols) bytes. Above that bound
+ * (the size function returns 0), or with a NULL / short workspace, d_addrows is zeroed and the rows are added with
+ * float atomics: correct to rounding, not bit-reproducible. d_addrows2 is never affected.
+ * (additive, ABI unchanged)                                                                                     */
+size_t lidf_gather2_backward_workspace_bytes(int64_t n, int64_t n_idx_rows, int32_t ncols);
+int lidf_gather2_backward_f32(const float* dz, int64_t n, int32_t ncols, const int32_t* seg_off, int64_t n_seg,
+                              float* d_addrows2, const int32_t* idx, int64_t n_idx_rows, float* d_addrows,
+                              void* workspace, size_t workspace_bytes, lidf_stream_t stream);
+
 /* ---- Eval depth metrics ----------------------------------------------------------------------
  * Replaces the bs == 1 evaluation branch of LIDF.compute_loss (models/pipeline.py:577-627): the
  * predicted depth map, the ground-truth depth map and the segmentation mask ([src_h, src_w],
