@@ -300,6 +300,11 @@ SIGNATURES = {
     "lidf_refine_train_forward_f32": (C.c_int, [C.POINTER(LidfRefineArgs), C.c_int32, _P, _SZ, _P]),
     "lidf_refine_train_backward_f32": (C.c_int, [C.POINTER(LidfRefineArgs), C.c_int32, _P, _SZ, _P, _P, _P,
                                                  C.POINTER(LidfPointNetGrads), C.POINTER(LidfDecoderGrads), _P]),
+    "lidf_refine_step_workspace_bytes": (_SZ, [_I, _P]),
+    "lidf_refine_step_forward_f32": (_I, [_P, _P, _P, _I64, _P, _P, _I64, _P, _P, _P, _I, _I, _I, _I64, _I64, _I, _I,
+                                          _I, _P, _P, _P, C.c_float, _I, _P, _P, _P, _P, _I64, _P, _SZ, _P]),
+    "lidf_refine_step_backward_f32": (_I, [_P, _P, C.c_float, C.c_float, _P, _P, _P, _P, _I, _P, _I, _P, _P, _I64,
+                                           _P]),
     "lidf_query_tail_f32": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, C.c_float, C.c_float, C.c_float,
                                       _P, _P, _P, _P, _P, _P]),
     "lidf_query_tail_backward_f32": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, C.c_float, C.c_float,

@@ -400,3 +400,87 @@ LIDF_API int lidf_refine_train_backward_f32(const LidfRefineArgs* q, int32_t for
     }
     return LIDF_OK;
 }
+
+// ---- the per-ray step of one iteration as entries of their own (the any-width route, generic.refine_train) -------
+// cells of a grid of `batch` frames: 0 = not a grid, -1 = more than the int32 table index holds
+static long long rstep_n_cells(int32_t batch, const int32_t* grid_res) {
+    if (!grid_res || batch <= 0) return 0;
+    long long nc = batch;
+    for (int k = 0; k < 3; ++k) {
+        if (grid_res[k] <= 0) return 0;
+        nc *= grid_res[k];
+        if (nc > 0x7fffffffLL) return -1;
+    }
+    return nc;
+}
+
+LIDF_API size_t lidf_refine_step_workspace_bytes(int32_t batch, const int32_t* grid_res) {
+    const long long nc = rstep_n_cells(batch, grid_res);
+    return nc > 0 ? (size_t)nc * 4 : 0;
+}
+
+LIDF_API int lidf_refine_step_forward_f32(const float* pos, const int64_t* max_pair_id, const int32_t* pair_vox,
+                                            int64_t n_pairs, const float* voxel_bound, const int32_t* voxel_bid,
+                                            int64_t n_vox, const int32_t* ray_bid, const int32_t* ray_flat,
+                                            const float* rgb_img, int32_t batch, int32_t height, int32_t width,
+                                            int64_t n_rays, int64_t n_valid, int32_t pnet_pos_rel, int32_t pos_rel,
+                                            int32_t multires, const int32_t* voxel_coord, const int32_t* grid_res,
+                                            const float* grid_xmin, float grid_part, int32_t cell_table_ready,
+                                            int32_t* end_voxel, float* pnet_inp, int32_t* pnet_vox, float* pe,
+                                            int64_t ld_pe, void* workspace, size_t workspace_bytes,
+                                            lidf_stream_t stream) {
+    if (n_rays < 0 || n_pairs < 0 || n_vox < 0 || n_valid < 0 || multires < 0 || multires > 16)
+        return LIDF_ERR_BAD_ARG;
+    if (n_rays == 0) return LIDF_OK;
+    if (n_vox == 0 || batch <= 0 || height <= 0 || width <= 0 || ld_pe < 3 + 6 * multires) return LIDF_ERR_BAD_ARG;
+    if (!pos || !max_pair_id || !voxel_bound || !voxel_bid || !ray_bid || !ray_flat || !rgb_img || !end_voxel ||
+        !pnet_inp || !pnet_vox || !pe || (n_pairs > 0 && !pair_vox))
+        return LIDF_ERR_BAD_ARG;
+    if (((uintptr_t)pos | (uintptr_t)pnet_inp | (uintptr_t)pe) & 3) return LIDF_ERR_BAD_ARG;
+    if (n_rays + n_valid > 0x15555555LL || n_vox > 0x7fffffffLL || n_pairs > 0x7fffffffLL) return LIDF_ERR_UNSUPPORTED;
+    CellLookup cells = {};
+    if (voxel_coord) {   // the end voxels through the cell table, which lives in the workspace
+        const long long nc = rstep_n_cells(batch, grid_res);
+        if (nc == 0 || !grid_xmin || !(grid_part > 0.f)) return LIDF_ERR_BAD_ARG;
+        if (nc < 0) return LIDF_ERR_UNSUPPORTED;
+        if (!workspace || workspace_bytes < (size_t)nc * 4) return LIDF_ERR_WORKSPACE;
+        for (int k = 0; k < 3; ++k) {
+            cells.g.xmin[k] = grid_xmin[k];
+            cells.g.r[k] = grid_res[k];
+        }
+        cells.g.crop = grid_part;
+        cells.g.B = batch;
+        cells.coord = voxel_coord;
+        cells.table = (int*)workspace;
+        cells.ready = cell_table_ready;
+    }
+    RayStepArgs a = {};
+    a.pos = pos; a.max_pair_id = (const long long*)max_pair_id; a.pair_vox = pair_vox;
+    a.R = n_rays; a.P = n_pairs; a.V = n_vox; a.n_valid = n_valid;
+    a.vbound = voxel_bound; a.vox_bid = voxel_bid; a.ray_bid = ray_bid; a.ray_flat = ray_flat;
+    a.rgb = rgb_img; a.hw = (long long)height * width;
+    a.pnet_rel = pnet_pos_rel ? 1 : 0; a.pos_rel = pos_rel ? 1 : 0; a.L = multires;
+    a.end_voxel = end_voxel; a.pnet_inp = pnet_inp; a.pnet_vox = pnet_vox; a.pe = pe; a.ld_pe = ld_pe;
+    CHECK_HIP(lidf_launch_refine_raystep(a, voxel_coord ? &cells : nullptr, (hipStream_t)stream));
+    return LIDF_OK;
+}
+
+LIDF_API int lidf_refine_step_backward_f32(const float* g_pos, const float* ray_dir, float offset_range0,
+                                             float offset_range1, float* d_off, const float* pos,
+                                             const int32_t* end_voxel, const float* voxel_bound, int32_t pos_rel,
+                                             const float* d_pe, int32_t multires, const float* d_pnet_rows,
+                                             float* d_pos, int64_t n_rays, lidf_stream_t stream) {
+    if (n_rays < 0 || multires < 0 || multires > 16) return LIDF_ERR_BAD_ARG;
+    if (n_rays == 0 || (!d_off && !d_pos)) return LIDF_OK;
+    if (!g_pos || (d_off && !ray_dir)) return LIDF_ERR_BAD_ARG;
+    if (d_pos && d_pe && (!pos || (pos_rel && (!end_voxel || !voxel_bound)))) return LIDF_ERR_BAD_ARG;
+    if (n_rays > 0x15555555LL) return LIDF_ERR_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    if (d_off)
+        CHECK_HIP(lidf_launch_refine_train_goff(g_pos, ray_dir, offset_range1 - offset_range0, n_rays, nullptr, 0,
+                                                d_off, st));
+    if (d_pos)
+        CHECK_HIP(lidf_launch_refine_train_dcur(g_pos, pos, end_voxel, voxel_bound, pos_rel ? 1 : 0, d_pe, multires,
+                                                d_pnet_rows, n_rays, d_pos, st));
+    return LIDF_OK;
+}

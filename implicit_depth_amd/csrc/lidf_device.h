@@ -440,6 +440,29 @@ struct RefineStepArgs {
     long long nzero0, nzero1;
 };
 
+// Arguments of lidf_refine_raystep_kernel (lidf_refine.hip): the per-ray step of one refine iteration with host
+// counts, for the any-width training route (lidf_refine_step_forward_f32).
+struct RayStepArgs {
+    const float* pos;          // [R,3] the position this iteration starts from
+    const long long* max_pair_id;
+    const int* pair_vox;
+    long long R, P, V, n_valid;
+    const float* vbound;
+    const int* vox_bid;
+    const int *ray_bid, *ray_flat;
+    const float* rgb;
+    long long hw;
+    int pnet_rel, pos_rel, L;
+    int* end_voxel;            // [R]
+    float* pnet_inp;           // [n_valid + R, 6]: rows n_valid.. are written
+    int* pnet_vox;             // [n_valid + R]
+    float* pe;                 // [R, E] at row stride ld_pe
+    long long ld_pe;
+    int mode;                  // how the rows leave: 0 one 16-byte aligned run, 1 16-byte aligned rows, 2 scalar stores
+    GridSpec g;                // the cell-table form only
+    const int* cell_table;
+};
+
 // Arguments of the stage-2 decoder on 16 x 16 x 4 tiles (lidf_ief16.hip).
 struct Ief16Args {
     const float* stream;   // (16 KQ + IEF16_PASS_QUADS) KiB

@@ -134,6 +134,7 @@ hipError_t lidf_launch_frame_select(const float* valid_mask, const int* ray_bid,
 
 // ---- lidf_refine.hip
 hipError_t lidf_launch_refine_step(const RefineStepArgs& a, long long R_cap, hipStream_t st);
+hipError_t lidf_launch_refine_raystep(const RayStepArgs& a, const CellLookup* cells, hipStream_t st);
 hipError_t lidf_launch_refine_prep(const float* pred_pos, const long long* max_pair_id, const int* pair_vox,
                                    long long P, const float* vbound, const int* vox_bid, long long V,
                                    const int* ray_bid, const int* ray_flat, const float* rgb, long long hw,

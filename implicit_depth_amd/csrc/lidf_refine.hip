@@ -69,17 +69,10 @@ __global__ void lidf_cell_table_kernel(const int* __restrict__ voxel_coord, cons
     atomicMax(cell_table + (((long long)b * g.r[0] + cx) * g.r[1] + cy) * g.r[2] + cz, (int)v);
 }
 
-__global__ void __launch_bounds__(256) lidf_refine_endvox_cells_kernel(
-    const float* __restrict__ pred_pos, const long long* __restrict__ max_pair_id,
-    const int* __restrict__ pair_vox, long long P, const float* __restrict__ vbound,
-    const int* __restrict__ vox_bid, long long V, GridSpec g, const int* __restrict__ cell_table,
-    const int* __restrict__ ray_bid, long long R, int* __restrict__ end_voxel) {
-    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= R) return;
-    const float x = pred_pos[3 * r], y = pred_pos[3 * r + 1], z = pred_pos[3 * r + 2];
-    const int bid = ray_bid[r];
-    const long long m = max_pair_id[r];
-    int ev = (m >= 0 && m < P) ? pair_vox[m] : 0;
+// ev raised to the largest voxel of frame bid whose box contains (x, y, z), through the cell table
+__device__ __forceinline__ int endvox_by_cells(float x, float y, float z, int bid, int ev,
+                                               const float* __restrict__ vbound, const int* __restrict__ vox_bid,
+                                               long long V, const GridSpec& g, const int* __restrict__ cell_table) {
     const float pp[3] = {x, y, z};
     int q[3];
     bool near = bid >= 0 && bid < g.B;
@@ -106,7 +99,20 @@ __global__ void __launch_bounds__(256) lidf_refine_endvox_cells_kernel(
         for (int i = 0; i < 27; ++i)
             if (cv[i] > ev && inside_box(x, y, z, vbound + 6 * (size_t)cv[i])) ev = cv[i];
     }
-    end_voxel[r] = ev;
+    return ev;
+}
+
+__global__ void __launch_bounds__(256) lidf_refine_endvox_cells_kernel(
+    const float* __restrict__ pred_pos, const long long* __restrict__ max_pair_id,
+    const int* __restrict__ pair_vox, long long P, const float* __restrict__ vbound,
+    const int* __restrict__ vox_bid, long long V, GridSpec g, const int* __restrict__ cell_table,
+    const int* __restrict__ ray_bid, long long R, int* __restrict__ end_voxel) {
+    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= R) return;
+    const long long m = max_pair_id[r];
+    const int ev = (m >= 0 && m < P) ? pair_vox[m] : 0;
+    end_voxel[r] = endvox_by_cells(pred_pos[3 * r], pred_pos[3 * r + 1], pred_pos[3 * r + 2], ray_bid[r], ev, vbound,
+                                   vox_bid, V, g, cell_table);
 }
 
 // Pass 2, one thread per ray: pnet_vox, pnet_inp from the end voxel.
@@ -318,6 +324,152 @@ __global__ void __launch_bounds__(256) lidf_refine_step_kernel(RefineStepArgs a)
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// The same per-ray step with HOST counts, for the any-width training route (generic.refine_train through
+// lidf_refine_step_forward_f32): lidf_refine_step_kernel without the frame path's device counts, position update and
+// scratch zeroing, and with the embedding block as a buffer of its own at a caller row stride. A workgroup owns 64
+// rays.
+//   phase 1 (one thread per ray): the end voxel — through the cell table (CELLS: endvox_by_cells), or as
+//     lidf_refine_endvox_kernel left it in end_voxel —, the PointNet row [pos (- centre) | rgb] and its voxel
+//     index behind the n_valid rows of the caller's buffers (lidf_refine_prep_kernel's expressions);
+//   phase 2 (one thread per ray and axis): the coordinate's 1 + 2 L entries of embed(pos (- centre)) into LDS — one
+//     revolution reduction per coordinate, sin and cos of every octave from it (to_rev / rev_sincos: pe_value's
+//     arithmetic, so the bits of lidf_refine_rows_kernel's per-column form; lidf_pe_rows_kernel is the model);
+//   phase 3 (all threads): the 64 x E block leaves as whole 16-byte pieces where the caller's stride and alignment
+//     allow (mode 0: ld_pe == E, the workgroup's rows are one aligned run; mode 1: aligned rows, the last 1-3 columns
+//     of a row as single stores), else as single stores along the rows. Columns E .. ld_pe of a row are not written.
+// ------------------------------------------------------------------------------------------------
+#define RSTEP_RAYS 64
+template <bool CELLS>
+__global__ void __launch_bounds__(256) lidf_refine_raystep_kernel(RayStepArgs a) {
+    __shared__ __attribute__((aligned(16))) float s_rows[RSTEP_RAYS * (3 + 6 * 16 + 1)];
+    __shared__ float s_q[RSTEP_RAYS * 3];
+    const long long r0w = (long long)blockIdx.x * RSTEP_RAYS;
+    const int nr = (int)min((long long)RSTEP_RAYS, a.R - r0w);
+    if ((int)threadIdx.x < nr) {
+        const long long r = r0w + threadIdx.x;
+        const float x = a.pos[3 * r], y = a.pos[3 * r + 1], z = a.pos[3 * r + 2];
+        const int bid = a.ray_bid[r];
+        int ev;
+        if (CELLS) {
+            const long long m = a.max_pair_id[r];
+            ev = (m >= 0 && m < a.P) ? a.pair_vox[m] : 0;
+            ev = endvox_by_cells(x, y, z, bid, ev, a.vbound, a.vox_bid, a.V, a.g, a.cell_table);
+            a.end_voxel[r] = ev;
+        } else {
+            ev = a.end_voxel[r];
+        }
+        const float* vb = a.vbound + 6 * (size_t)ev;
+        const float cx = (vb[0] + vb[3]) / 2.f, cy = (vb[1] + vb[4]) / 2.f, cz = (vb[2] + vb[5]) / 2.f;
+        const long long row = a.n_valid + r;
+        a.pnet_vox[row] = ev;
+        float* pi = a.pnet_inp + 6 * (size_t)row;
+        pi[0] = a.pnet_rel ? x - cx : x;
+        pi[1] = a.pnet_rel ? y - cy : y;
+        pi[2] = a.pnet_rel ? z - cz : z;
+        const float* px = a.rgb + (size_t)bid * 3 * a.hw + a.ray_flat[r];
+        pi[3] = px[0];
+        pi[4] = px[a.hw];
+        pi[5] = px[2 * a.hw];
+        s_q[3 * threadIdx.x] = a.pos_rel ? x - cx : x;
+        s_q[3 * threadIdx.x + 1] = a.pos_rel ? y - cy : y;
+        s_q[3 * threadIdx.x + 2] = a.pos_rel ? z - cz : z;
+    }
+    __syncthreads();
+    const int E = 3 + 6 * a.L;
+    const int ls = a.mode == 1 ? (E + 3) & ~3 : E;      // row stride in LDS (mode 1: every row 16-byte aligned)
+    for (int i = threadIdx.x; i < 3 * nr; i += 256) {
+        const int rr = i / 3, c = i - 3 * rr;
+        const float q = s_q[i];
+        float* row = s_rows + rr * ls;
+        row[c] = q;
+        const Rev rv = to_rev(q);
+        for (int o = 0; o < a.L; ++o) {
+            float sn, cs;
+            rev_sincos(rv, (float)(1 << o), sn, cs);
+            row[3 + 6 * o + c] = sn;
+            row[6 + 6 * o + c] = cs;
+        }
+    }
+    __syncthreads();
+    float* dst = a.pe + (size_t)r0w * a.ld_pe;
+    if (a.mode == 0) {          // (64 E floats per workgroup: every run starts 16-byte aligned)
+        const int total = nr * E;
+        for (int i = 4 * threadIdx.x; i + 3 < total; i += 1024) *(f32x4*)(dst + i) = *(const f32x4*)(s_rows + i);
+        if ((int)threadIdx.x < (total & 3)) dst[(total & ~3) + threadIdx.x] = s_rows[(total & ~3) + threadIdx.x];
+    } else if (a.mode == 1) {
+        const int eq = ls / 4;
+        for (int i = threadIdx.x; i < nr * eq; i += 256) {
+            const int rr = i / eq, c = 4 * (i - rr * eq);
+            float* d = dst + (size_t)rr * a.ld_pe + c;
+            const float* s = s_rows + rr * ls + c;
+            if (c + 3 < E) {
+                *(f32x4*)d = *(const f32x4*)s;
+            } else {
+                for (int j = 0; c + j < E; ++j) d[j] = s[j];
+            }
+        }
+    } else {
+        for (int i = threadIdx.x; i < nr * E; i += 256) {
+            const int rr = i / E, k = i - rr * E;
+            dst[(size_t)rr * a.ld_pe + k] = s_rows[i];
+        }
+    }
+}
+
+// the cell table of a voxel list (stepwise API): cell -> largest voxel index, -1 = empty
+static hipError_t fill_cell_table(const CellLookup* cells, const int* vox_bid, long long V, hipStream_t st) {
+    if (cells->ready) return hipSuccess;
+    const long long nc = (long long)cells->g.B * cells->g.r[0] * cells->g.r[1] * cells->g.r[2];
+    hipError_t e = hipMemsetAsync(cells->table, 0xff, (size_t)nc * 4, st);
+    if (e != hipSuccess) return e;
+    if (V > 0)
+        hipLaunchKernelGGL(lidf_cell_table_kernel, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st,
+                           cells->coord, vox_bid, V, cells->g, cells->table);
+    return hipSuccess;
+}
+
+// lidf_refine_endvox_kernel over a zeroed end_voxel: every ray against every voxel
+static void launch_endvox_every(const float* pred_pos, const long long* max_pair_id, const int* pair_vox, long long P,
+                                const float* vbound, const int* vox_bid, long long V, const int* ray_bid,
+                                long long R, int* end_voxel, const int* dims, hipStream_t st) {
+    // slices of at least 64 voxels, enough of them for ~8 wavefronts per SIMD
+    const long long waves = (R + 63) / 64;
+    long long slices = (8 * 1024 + waves - 1) / waves;
+    const long long max_slices = (V + 63) / 64;
+    if (slices > max_slices) slices = max_slices;
+    if (slices < 1) slices = 1;
+    const long long per_slice = (V + slices - 1) / slices;
+    slices = V > 0 ? (V + per_slice - 1) / per_slice : 1;
+    hipLaunchKernelGGL(lidf_refine_endvox_kernel, dim3((unsigned)((R + 255) / 256), (unsigned)slices),
+                       dim3(256), 0, st, pred_pos, max_pair_id, pair_vox, P, vbound, vox_bid, V,
+                       per_slice, ray_bid, R, end_voxel, dims);
+}
+
+// a: everything but mode / g / cell_table, which are set here. cells (optional): the end voxels through its table.
+extern "C" hipError_t lidf_launch_refine_raystep(const RayStepArgs& a_in, const CellLookup* cells, hipStream_t st) {
+    RayStepArgs a = a_in;
+    if (a.R <= 0) return hipSuccess;
+    const int E = 3 + 6 * a.L;
+    const bool al = ((uintptr_t)a.pe & 15) == 0;
+    a.mode = (al && a.ld_pe == E) ? 0 : ((al && a.ld_pe % 4 == 0) ? 1 : 2);
+    const dim3 grid((unsigned)((a.R + RSTEP_RAYS - 1) / RSTEP_RAYS));
+    if (cells && cells->table) {
+        hipError_t e = fill_cell_table(cells, a.vox_bid, a.V, st);
+        if (e != hipSuccess) return e;
+        a.g = cells->g;
+        a.cell_table = cells->table;
+        hipLaunchKernelGGL(lidf_refine_raystep_kernel<true>, grid, dim3(256), 0, st, a);
+        return hipGetLastError();
+    }
+    hipError_t e = hipMemsetAsync(a.end_voxel, 0, (size_t)a.R * 4, st);
+    if (e != hipSuccess) return e;
+    launch_endvox_every(a.pos, a.max_pair_id, a.pair_vox, a.P, a.vbound, a.vox_bid, a.V, a.ray_bid, a.R, a.end_voxel,
+                        nullptr, st);
+    hipLaunchKernelGGL(lidf_refine_raystep_kernel<false>, grid, dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
 extern "C" hipError_t lidf_launch_refine_step(const RefineStepArgs& a, long long R_cap, hipStream_t st) {
     if (R_cap <= 0) return hipSuccess;
     hipLaunchKernelGGL(lidf_refine_step_kernel, dim3((unsigned)((R_cap + STEP_RAYS - 1) / STEP_RAYS)), dim3(256), 0, st, a);
@@ -353,14 +505,8 @@ extern "C" hipError_t lidf_launch_refine_prep_dev(const float* pred_pos, const l
                                                   const CellLookup* cells) {
     if (R <= 0) return hipSuccess;
     if (cells && cells->table) {   // end voxel through the cell table (stepwise API with a grid)
-        const long long nc = (long long)cells->g.B * cells->g.r[0] * cells->g.r[1] * cells->g.r[2];
-        if (!cells->ready) {
-            hipError_t e = hipMemsetAsync(cells->table, 0xff, (size_t)nc * 4, st);
-            if (e != hipSuccess) return e;
-            if (V > 0)
-                hipLaunchKernelGGL(lidf_cell_table_kernel, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st,
-                                   cells->coord, vox_bid, V, cells->g, cells->table);
-        }
+        hipError_t e = fill_cell_table(cells, vox_bid, V, st);
+        if (e != hipSuccess) return e;
         hipLaunchKernelGGL(lidf_refine_endvox_cells_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st,
                            pred_pos, max_pair_id, pair_vox, P, vbound, vox_bid, V, cells->g, cells->table, ray_bid,
                            R, end_voxel);
@@ -374,17 +520,7 @@ extern "C" hipError_t lidf_launch_refine_prep_dev(const float* pred_pos, const l
         hipError_t e = hipMemsetAsync(end_voxel, 0, (size_t)R * 4, st);
         if (e != hipSuccess) return e;
     }
-    // slices of at least 64 voxels, enough of them for ~8 wavefronts per SIMD
-    const long long waves = (R + 63) / 64;
-    long long slices = (8 * 1024 + waves - 1) / waves;
-    const long long max_slices = (V + 63) / 64;
-    if (slices > max_slices) slices = max_slices;
-    if (slices < 1) slices = 1;
-    const long long per_slice = (V + slices - 1) / slices;
-    slices = V > 0 ? (V + per_slice - 1) / per_slice : 1;
-    hipLaunchKernelGGL(lidf_refine_endvox_kernel, dim3((unsigned)((R + 255) / 256), (unsigned)slices),
-                       dim3(256), 0, st, pred_pos, max_pair_id, pair_vox, P, vbound, vox_bid, V,
-                       per_slice, ray_bid, R, end_voxel, dims);
+    launch_endvox_every(pred_pos, max_pair_id, pair_vox, P, vbound, vox_bid, V, ray_bid, R, end_voxel, dims, st);
     hipLaunchKernelGGL(lidf_refine_prep_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st,
                        pred_pos, vbound, ray_bid, ray_flat, rgb, hw, pnet_rel, R, pnet_inp, pnet_vox,
                        end_voxel, pnet_select, dims, row0_dev);

@@ -14,8 +14,9 @@ and lidf_wgrad_f32 (weight and bias gradients), the PointNet's two poolings and 
 torch indexing that autograd differentiates itself. The stage-1 query trains at other widths through
 query_train below (query.lidf_query_train sends every configuration its fixed-width kernels are not
 built for here): the factorised layer 1 under autograd, with lidf_roi_align_backward_f32 and
-lidf_gather2_backward_f32 as the adjoints of the ROI pooling and of the two gathered tables; stage 2 has
-query._lidf_refine_train_composed. The fused single-launch training kernels stay at the shipped widths.
+lidf_gather2_backward_f32 as the adjoints of the ROI pooling and of the two gathered tables; stage 2 trains through refine_train (a decoder row is a
+stage-1 pair with one pair per ray: the same factorised layer 1, and lidf_refine_step_forward_f32 / _backward_f32 for
+the per-ray step of an iteration). The fused single-launch training kernels stay at the shipped widths.
 
 Round 6: a decoder of gf_dim 32, 64 or 128 with a 1-wide head runs its inference as ONE register-chained launch
 (lidf_decoder_chain_f32, csrc/lidf_chain16.hip: 16-row sub-tiles of the 16 x 16 x 4 matrix instruction, activations
@@ -24,6 +25,7 @@ take it; LIDF_CHAIN16=0 keeps the layer-by-layer path (A/B, and the definition t
 
 Nothing here is used when the widths are the shipped ones.
 """
+import ctypes
 import os
 
 import torch
@@ -723,3 +725,287 @@ def query_train(ray_dir, ray_pix, ray_bid, pair_off, pair_ray, pair_vox, pair_t,
         float(part_size), max_pair_id)
     return {"pred_offset": pred_offset, "pred_prob_end": pred_prob, "pair_pred_pos": pair_pred_pos,
             "pred_prob_end_softmax": sm, "max_pair_id": mid, "pred_pos": pred_pos}
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Stage 2 under autograd at any width (forward_times x get_pred_refine for the stage-2 training step)
+# ------------------------------------------------------------------------------------------------------------------
+def refine_step_forward(pos, st, table_ready=False):
+    """lidf_refine_step_forward_f32 on the step constants st (refine_train builds them): (end_voxel [R] i32,
+    pnet_inp [Nv + R, 6], pnet_vox [Nv + R] i32, pe [R, E]) — the valid points' rows copied in front."""
+    dev = pos.device
+    R, Nv, E = pos.shape[0], st["valid_inp"].shape[0], 3 + 6 * st["multires"]
+    B, _, h, w = st["rgb_img"].shape
+    pn_inp = torch.empty((Nv + R, 6), dtype=torch.float32, device=dev)
+    pn_vox = torch.empty((Nv + R,), dtype=torch.int32, device=dev)
+    pn_inp[:Nv] = st["valid_inp"]
+    pn_vox[:Nv] = st["valid_vox"]
+    end_voxel = torch.empty((R,), dtype=torch.int32, device=dev)
+    pe = torch.empty((R, E), dtype=torch.float32, device=dev)
+    cells = st["cells"]
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().lidf_refine_step_forward_f32(
+            _lib.ptr(pos), _lib.ptr(st["max_pair_id"]), _lib.ptr(st["pair_vox"]), st["pair_vox"].shape[0],
+            _lib.ptr(st["voxel_bound"]), _lib.ptr(st["voxel_bid"]), st["voxel_bound"].shape[0], _lib.ptr(st["ray_bid"]),
+            _lib.ptr(st["ray_flat"]), _lib.ptr(st["rgb_img"]), B, h, w, R, Nv, 1 if st["pnet_pos_rel"] else 0,
+            1 if st["pos_rel"] else 0, st["multires"],
+            _lib.ptr(cells["coord"]) if cells else None, cells["res"] if cells else None,
+            cells["xmin"] if cells else None, cells["part"] if cells else 0.0, 1 if (cells and table_ready) else 0,
+            _lib.ptr(end_voxel), _lib.ptr(pn_inp), _lib.ptr(pn_vox), _lib.ptr(pe), E,
+            _lib.ptr(cells["table"]) if cells else None, 4 * cells["table"].numel() if cells else 0,
+            _lib.current_stream(dev)))
+    return end_voxel, pn_inp, pn_vox, pe
+
+
+def refine_step_backward(g_pos, st, d_off=False, pos=None, end_voxel=None, d_pe=None, d_rows=None, d_pos=False):
+    """lidf_refine_step_backward_f32: (d_off [R] or None, d_pos [R, 3] or None). d_rows: the gradient of the whole
+    pnet_inp [Nv + R, 6] (its predicted rows are read)."""
+    dev = g_pos.device
+    R, Nv = g_pos.shape[0], st["valid_inp"].shape[0]
+    o = torch.empty((R,), dtype=torch.float32, device=dev) if d_off else None
+    dp = torch.empty((R, 3), dtype=torch.float32, device=dev) if d_pos else None
+    r0, r1 = st["offset_range"]
+    rows = ctypes.c_void_p(d_rows.data_ptr() + 24 * Nv) if d_rows is not None else None
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().lidf_refine_step_backward_f32(
+            _lib.ptr(g_pos), _lib.ptr(st["ray_dir"]), float(r0), float(r1), _lib.ptr(o), _lib.ptr(pos),
+            _lib.ptr(end_voxel), _lib.ptr(st["voxel_bound"]), 1 if st["pos_rel"] else 0, _lib.ptr(d_pe),
+            st["multires"], rows, _lib.ptr(dp), R, _lib.current_stream(dev)))
+    return o, dp
+
+
+def _f32c(g):
+    """An incoming gradient as a dense float32 tensor (None stays None)."""
+    return None if g is None else g.detach().contiguous().float()
+
+
+class _RayStepFn(torch.autograd.Function):
+    """The per-ray step of one iteration (lidf_refine_step_forward_f32): from the position entering the iteration the
+    end voxels, the PointNet rows of valid + predicted points and embed(pos (- centre)). The position itself is
+    handed through as the first output, so that the gradient of the additive update (_FinishFn) arrives here together
+    with those of the rows and of the embedding and d pos = g + embed'(x)^T d_pe + d_rows[:, 0:3] is ONE launch
+    (lidf_refine_step_backward_f32), no row gradient gathered or added by torch."""
+
+    @staticmethod
+    def forward(ctx, cur, st, table_ready):
+        x = cur.detach().contiguous()
+        end_voxel, pn_inp, pn_vox, pe = refine_step_forward(x, st, table_ready)
+        ctx.st = st
+        ctx.save_for_backward(x, end_voxel)
+        ctx.mark_non_differentiable(end_voxel, pn_vox)
+        return x.view_as(x), pn_inp, pe, end_voxel, pn_vox
+
+    @staticmethod
+    def backward(ctx, g_pos, g_rows, g_pe, _g_end, _g_vox):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        x, end_voxel = ctx.saved_tensors
+        g = _f32c(g_pos) if g_pos is not None else torch.zeros_like(x)
+        _, d_pos = refine_step_backward(g, ctx.st, pos=x, end_voxel=end_voxel, d_pe=_f32c(g_pe), d_rows=_f32c(g_rows),
+                                        d_pos=True)
+        return d_pos, None, None
+
+
+class _FinishFn(torch.autograd.Function):
+    """pos + (off (r1 - r0) + r0) dir (pipeline.py:1028-1029); backward: d off = (r1 - r0) <g, dir>
+    (lidf_refine_step_backward_f32), d pos = g."""
+
+    @staticmethod
+    def forward(ctx, pos, off, st):
+        r0, r1 = st["offset_range"]
+        ctx.st = st
+        return pos.detach() + (off.detach() * (r1 - r0) + r0) * st["ray_dir"]
+
+    @staticmethod
+    def backward(ctx, g):
+        g = g.detach().contiguous().float()
+        d_off = None
+        if ctx.needs_input_grad[1]:
+            d_off = refine_step_backward(g, ctx.st, d_off=True)[0].view(-1, 1)
+        return g if ctx.needs_input_grad[0] else None, d_off, None
+
+
+TABLE_CHUNK = 16   # columns per launch of a layer-1 table product
+
+
+def _table_product(x, w, bias, col0, k, addrows=None, addidx=None):
+    """x[:, :k] W[:, col0 : col0 + k]^T (+ bias) (+ addrows[addidx]) for a layer-1 table of the refine step, the
+    contraction split into runs of TABLE_CHUNK columns: every launch starts its matrix-instruction sums at zero and
+    adds the previous runs' result in its epilogue. lidf_linear_f32 carries ONE accumulator chain over k, whose
+    rounding grows with the chain's length and the running sum's size; a table row is shared by every iteration (the
+    per-ray table) or by every ray of a voxel (the per-voxel table), so its rounding does not average out over the rows
+    of a gradient sum the way a per-row product's does, and the second iteration's 2^7 octave multiplies it. Measured at
+    (32, 2, 128, 16, 64, IEF): dec.linear_4.weight 4.04 x the float32 oracle's error with one chain of 128 columns;
+    runs of 16 hold every case of tests/test_refine_widths_gpu.py, the worst at 3.46."""
+    rows = None
+    out = None
+    for c0 in range(0, k, TABLE_CHUNK):
+        kk = min(TABLE_CHUNK, k - c0)
+        if out is None:
+            out = linear_hip(x[:, c0:], w, bias, w_col0=col0 + c0, k=kk, addrows=addrows, addidx=addidx)
+        else:
+            if rows is None:
+                rows = torch.arange(x.shape[0], dtype=torch.int32, device=x.device)
+            out = linear_hip(x[:, c0:], w, None, w_col0=col0 + c0, k=kk, addrows=out, addidx=rows)
+    return out
+
+
+class _RayPartFn(torch.autograd.Function):
+    """raypart = W1[:, ROI columns] roi + W1[:, direction columns] embed(dir) [R, 4 gf]: the part of a stage-2
+    decoder's layer 1 that depends on feat_grid and W1 only — formed once per step, shared by the iterations. Its
+    gradient is the iterations' dZ1 summed (by autograd); from it d roi and the two column blocks of dW1."""
+
+    @staticmethod
+    def forward(ctx, roi, w1, edir, col_roi, col_dir):
+        rf = roi.detach().contiguous()
+        rows = torch.arange(rf.shape[0], dtype=torch.int32, device=rf.device)
+        rp = _table_product(rf, w1, None, col_roi, rf.shape[1])
+        ctx.cols = (col_roi, col_dir)
+        ctx.save_for_backward(roi, w1, edir)
+        return _table_product(edir, w1, None, col_dir, edir.shape[1], addrows=rp, addidx=rows)
+
+    @staticmethod
+    def backward(ctx, g):
+        roi, w1, edir = ctx.saved_tensors
+        rf, w = roi.detach().contiguous(), w1.detach()
+        col_roi, col_dir = ctx.cols
+        d_ray = g.detach().contiguous().float()
+        droi = dw = None
+        if ctx.needs_input_grad[0]:
+            droi = linear_hip(d_ray, w[:, col_roi:col_roi + rf.shape[1]].t().contiguous())
+        if ctx.needs_input_grad[1]:
+            dw = torch.zeros(w.shape, dtype=torch.float32, device=d_ray.device)
+            _wgrad_into(d_ray, rf, dw, col_roi)
+            _wgrad_into(d_ray, edir, dw, col_dir)
+        return droi, dw, None, None, None
+
+
+class _RefineLayer1Fn(torch.autograd.Function):
+    """Layer 1 of a stage-2 decoder, factorised as _Layer1Fn with exactly one pair per ray:
+    act(W1[:, position columns] embed(pos) + voxpart[end_voxel] + raypart) with voxpart = W1[:, voxel columns]
+    occ_voxel_feat + b1 [V, 4 gf]. No [R, D] row and no row gradient: the backward sums dZ1 by end voxel
+    (lidf_gather2_backward_f32: sorted, fixed order) for d occ_voxel_feat and the voxel block of dW1, hands dZ1 itself to
+    raypart, and — unlike stage 1, where the per-row operand is a constant — forms d embed = dZ1 W1[:, position
+    columns] for the position's gradient."""
+
+    @staticmethod
+    def forward(ctx, occ, raypart, w1, b1, pe, end_voxel, col_pos, act):
+        vf = occ.detach().contiguous()
+        rows = torch.arange(pe.shape[0], dtype=torch.int32, device=pe.device)
+        voxpart = _table_product(vf, w1, b1, 0, vf.shape[1])
+        out = linear_hip(pe.detach(), w1, None, act=1 if act else 0, slope=0.02 if act else 0.0, w_col0=col_pos,
+                         k=pe.shape[1], addrows=voxpart, addidx=end_voxel, addrows2=raypart.detach(), addidx2=rows)
+        ctx.cfg = (col_pos, act)
+        ctx.save_for_backward(occ, w1, pe, end_voxel, out if act else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        occ, w1, pe, end_voxel, out = ctx.saved_tensors
+        vf, w, x = occ.detach().contiguous(), w1.detach(), pe.detach()
+        col_pos, act = ctx.cfg
+        Cv, E = vf.shape[1], x.shape[1]
+        dz = g.detach().contiguous().float()
+        if act:
+            dz = _leaky_mask(dz, out, 0.02)
+        _, d_vox = gather2_backward(dz, idx=end_voxel, n_idx_rows=vf.shape[0])
+        docc = dpe = dw = db = None
+        if ctx.needs_input_grad[0]:
+            docc = linear_hip(d_vox, w[:, :Cv].t().contiguous())
+        if ctx.needs_input_grad[4]:
+            dpe = linear_hip(dz, w[:, col_pos:col_pos + E].t().contiguous())
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+            dw = torch.zeros(w.shape, dtype=torch.float32, device=dz.device)
+            db = torch.zeros((w.shape[0],), dtype=torch.float32, device=dz.device)
+            _wgrad_into(d_vox, vf, dw, 0, db)          # (b1 enters once per voxel row: its gradient is the table's sum)
+            _wgrad_into(dz, x, dw, col_pos)
+        return docc, dz if ctx.needs_input_grad[1] else None, dw, db, dpe, None, None, None
+
+
+def refine_train(ray_dir, ray_pix, ray_bid, ray_flat, pred_pos, max_pair_id, pair_vox, voxel_bound, voxel_bid, rgb_img,
+                 feat_grid, valid_inp, valid_vox, pnet_model, offset_dec, forward_times=2, multires=8, multires_views=4,
+                 roi_inp_bbox=8, roi_out_bbox=2, offset_range=(-0.2, 0.2), pos_rel=False, pnet_pos_rel=True,
+                 perturb_noise=None, grid=None):
+    """forward_times x RefineNet.get_pred_refine (models/pipeline.py:922-1030, exp_type 'train') under autograd at any
+    rgb_out / roi_out_bbox / roi_inp_bbox, PointNet2Stage(6, pnet_out, pnet_gf), IEF (any n_iter) or IMNet of any
+    gf_dim with a 1-wide head, use_sigmoid on or off, multires / multires_views 0..16: what query.lidf_refine_train is
+    at the shipped widths, with its arguments, returns and gradient targets (every parameter of pnet_model and
+    offset_dec, pred_pos and feat_grid when they require grad; valid_inp carries none).
+    A decoder row is a stage-1 pair with one pair per ray, so layer 1 keeps the factorised form (_RefineLayer1Fn /
+    _RayPartFn): a per-voxel table gathered by end_voxel, a per-ray table formed once per step, and the E columns of
+    embed(pos) as the per-row operand — no [R, D] row and no row gradient, forward or backward. Per iteration the rays
+    take one call each way (lidf_refine_step_forward_f32 / _backward_f32: end voxel, PointNet rows, embedding; d off,
+    d pos); the PointNet runs the module's own training path (generic.pointnet_forward_train where a width differs),
+    layers 2-4 and an IEF's passes are query_train's (_decoder_train_from_layer1). Every launch goes to the caller's
+    current stream. Run-to-run: as query_train — bit-identical gradients for rays on distinct pixels, gf_dim >= 32,
+    multires_views >= 1 and at most 16,384 voxels.
+    Returns pred_pos_refine [R, 3] (with grad) and the last end_voxel_id [R] i32."""
+    from .decoders import get_embedder
+    from .query import _as_i32, _cell_lookup, _f32
+    if offset_dec.linear_4.out_features != 1:
+        raise RuntimeError("the refine step takes a decoder with out_dim == 1 (got %d): its output is the offset "
+                           "along the ray" % offset_dec.linear_4.out_features)
+    if pnet_model.input_channels != 6:
+        raise RuntimeError("pnet_model.input_channels must be 6 (the predicted points' rows are xyz + rgb), got %d"
+                           % pnet_model.input_channels)
+    E, Ed = 3 + 6 * multires, 3 + 6 * multires_views
+    if not (0 <= multires <= 16 and 0 <= multires_views <= 16):
+        raise RuntimeError("multires / multires_views must lie in 0..16")
+    if feat_grid.dim() != 4:
+        raise RuntimeError("feat_grid must be [B,rgb_out,h,w]")
+    Cv, Cr = pnet_model.vox_lin2.out_features, feat_grid.shape[1] * roi_out_bbox * roi_out_bbox
+    D = Cv + Cr + E + Ed
+    if offset_dec.inp_dim != D or offset_dec.linear_1.in_features < D:
+        raise RuntimeError("refine offset_dec inp_dim must be %d (pnet_out %d + rgb_out %d x roi_out_bbox^2 %d + "
+                           "E %d + Ed %d), got %d" % (D, Cv, feat_grid.shape[1], roi_out_bbox * roi_out_bbox, E, Ed,
+                                                      offset_dec.inp_dim))
+    ray_pix, ray_bid = _as_i32(ray_pix, "ray_pix"), _as_i32(ray_bid, "ray_bid")
+    ray_flat, voxel_bid = _as_i32(ray_flat, "ray_flat"), _as_i32(voxel_bid, "voxel_bid")
+    pair_vox, valid_vox = _as_i32(pair_vox, "pair_vox"), _as_i32(valid_vox, "valid_vox")
+    ts = dict(ray_dir=ray_dir, ray_pix=ray_pix, ray_bid=ray_bid, ray_flat=ray_flat, max_pair_id=max_pair_id,
+              pair_vox=pair_vox, voxel_bound=voxel_bound, voxel_bid=voxel_bid, rgb_img=rgb_img, valid_inp=valid_inp,
+              valid_vox=valid_vox)
+    _lib.require_cuda(pred_pos, feat_grid, *ts.values(), names=["pred_pos", "feat_grid"] + list(ts))
+    for n in ("ray_dir", "voxel_bound", "rgb_img", "valid_inp"):
+        _f32(ts[n], n)
+    _f32(pred_pos, "pred_pos"), _f32(feat_grid, "feat_grid")
+    if max_pair_id.dtype != torch.int64:
+        raise RuntimeError("max_pair_id must be int64")
+    R, V, Nv = ray_dir.shape[0], voxel_bound.shape[0], valid_inp.shape[0]
+    if (tuple(ray_dir.shape) != (R, 3) or tuple(pred_pos.shape) != (R, 3) or tuple(max_pair_id.shape) != (R,)
+            or tuple(ray_bid.shape) != (R,) or tuple(ray_flat.shape) != (R,) or tuple(ray_pix.shape) != (R, 2)):
+        raise RuntimeError("ray_dir / pred_pos must be [R,3]; ray_pix [R,2]; ray_bid / ray_flat / max_pair_id [R]")
+    if tuple(voxel_bound.shape) != (V, 6) or tuple(voxel_bid.shape) != (V,):
+        raise RuntimeError("voxel_bound / voxel_bid must be [V,6] / [V]")
+    if tuple(valid_inp.shape) != (Nv, 6) or tuple(valid_vox.shape) != (Nv,):
+        raise RuntimeError("valid_inp / valid_vox must be [Nv,6] / [Nv]")
+    if rgb_img.dim() != 4 or rgb_img.shape[1] != 3:
+        raise RuntimeError("rgb_img must be [B,3,h,w]")
+    if valid_inp.requires_grad:
+        raise RuntimeError("refine_train: valid_inp carries no gradient (the valid points are inputs of the frozen "
+                           "stage 1, trainers/train_refine.py:73)")
+    dev = ray_dir.device
+    cur = pred_pos
+    if perturb_noise is not None:
+        cur = cur + float(perturb_noise) * ray_dir
+    if R == 0:   # nothing to refine: empty outputs that still carry a graph to every parameter
+        zero = sum(q.sum() for m in (pnet_model, offset_dec) for q in m.parameters()) * 0.0
+        return cur + zero + 0.0 * feat_grid.sum(), torch.empty((0,), dtype=torch.int32, device=dev)
+    st = {k: v.detach() for k, v in ts.items()}
+    st.update(multires=int(multires), pos_rel=bool(pos_rel), pnet_pos_rel=bool(pnet_pos_rel),
+              offset_range=(float(offset_range[0]), float(offset_range[1])),
+              cells=_cell_lookup(grid, V, rgb_img.shape[0], dev, voxel_bound))
+    l1 = offset_dec.linear_1
+    roi = _RoiAlignFn.apply(feat_grid, ray_pix, ray_bid, roi_inp_bbox, roi_out_bbox)
+    edir = get_embedder(multires_views)[0](ray_dir.detach().contiguous()).detach()   # a constant of the step
+    raypart = _RayPartFn.apply(roi, l1.weight, edir, Cv, Cv + Cr + E)
+    end_voxel = None
+    for it in range(int(forward_times)):
+        pos, pn_inp, pe, end_voxel, pn_vox = _RayStepFn.apply(cur, st, it > 0)
+        occ = pnet_model(pn_inp, pn_vox, n_vox=V)
+
+        def layer1(act, occ=occ, pe=pe, end_voxel=end_voxel):
+            return _RefineLayer1Fn.apply(occ, raypart, l1.weight, l1.bias, pe, end_voxel, Cv + Cr, act)
+        off = _decoder_train_from_layer1(offset_dec, layer1, R, dev)
+        cur = _FinishFn.apply(pos, off, st)
+    return cur, end_voxel

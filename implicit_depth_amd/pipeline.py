@@ -294,7 +294,7 @@ def refine_forward_train(dd, pnet_model_refine, offset_dec_refine, opt=None, los
     """RefineNet.forward('train', epoch, data_dict) (models/pipeline.py:1032-1041) on the data_dict of the frozen
     stage 1 (train_refine_step's, or lidf_forward_train's): returns (data_dict, loss_dict_refine).
     opt.refine_forward_times x get_pred_refine under autograd (query.lidf_refine_train: one node, two library
-    calls), the perturbation of the first iteration drawn with the reference's own np.random calls — only when
+    calls at the shipped widths, generic.refine_train at another rgb_out / roi_out_bbox / pnet_out), the perturbation of the first iteration drawn with the reference's own np.random calls — only when
     opt.refine_perturb is set, as the reference's `and` short-circuits — then losses.refine_loss. Adds
     pred_pos_refine [R,3], end_voxel_id [R] and refine_perturb_noise (the scalar drawn, None for none) to data_dict;
     loss_dict_refine['loss_net'].backward() reaches every parameter of the two modules. The end voxels go through
@@ -310,7 +310,7 @@ def refine_forward_train(dd, pnet_model_refine, offset_dec_refine, opt=None, los
         dd["pair_vox"], dd["voxel_bound"], dd["voxel_bid"], dd["rgb_img"], dd["full_rgb_feat"],
         valid_inp.contiguous(), dd["revidx"].to(torch.int32).contiguous(), pnet_model_refine, offset_dec_refine,
         forward_times=opt.refine_forward_times, multires=opt.multires, multires_views=opt.multires_views,
-        roi_inp_bbox=opt.roi_inp_bbox, offset_range=opt.refine_offset_range,
+        roi_inp_bbox=opt.roi_inp_bbox, roi_out_bbox=opt.roi_out_bbox, offset_range=opt.refine_offset_range,
         pos_rel=opt.refine_intersect_pos_type == "rel", pnet_pos_rel=opt.refine_pnet_pos_type == "rel",
         perturb_noise=noise,
         grid=dd if all(k in dd for k in ("voxel_coord", "grid_dims", "xmin", "part_size")) else None)

@@ -1452,7 +1452,8 @@ class _RefineTrainFn(torch.autograd.Function):
 def lidf_refine_train(ray_dir, ray_pix, ray_bid, ray_flat, pred_pos, max_pair_id, pair_vox, voxel_bound,
                       voxel_bid, rgb_img, feat_grid, valid_inp, valid_vox, pnet_model, offset_dec,
                       forward_times=2, multires=8, multires_views=4, roi_inp_bbox=8,
-                      offset_range=(-0.2, 0.2), pos_rel=False, pnet_pos_rel=True, perturb_noise=None, grid=None):
+                      offset_range=(-0.2, 0.2), pos_rel=False, pnet_pos_rel=True, perturb_noise=None, grid=None,
+                      roi_out_bbox=2, factorised=None):
     """Differentiable RefineNet.forward (models/pipeline.py:922-1041, exp_type 'train'): the same
     arguments as lidf_refine; gradients reach every parameter of pnet_model (PointNet2Stage) and
     offset_dec (IEF / IMNet) — through the second and later iterations also via the refined position
@@ -1463,15 +1464,32 @@ def lidf_refine_train(ray_dir, ray_pix, ray_bid, ray_flat, pred_pos, max_pair_id
     The whole step is two library calls (lidf_refine_train_forward_f32 / _backward_f32, one autograd node):
     one multi-pack of every weight stream per step, the decoder in its factorised form (per-voxel / per-ray /
     embed(pos) parts of layer 1; no [R, 334] row or input gradient is formed), parameter gradients summed
-    over the iterations inside the call, no torch op between the launches. Widths other than the shipped
-    ones (and decoders that are neither IEF nor IMNet of gf_dim 64) take the composed path
-    (_lidf_refine_train_composed: the modules' own autograd functions joined by torch ops).
+    over the iterations inside the call, no torch op between the launches.
+    Other configurations, factorised=None (default): a decoder gf_dim, a PointNet gf_dim or multires == 0 other than
+    the shipped one at the shipped feature widths (rgb_out 32, roi_out_bbox 2, pnet_out 128) takes the composed path
+    (_lidf_refine_train_composed: the modules' own autograd functions joined by torch ops, [R, D] rows); every other
+    rgb_out / roi_out_bbox / pnet_out takes generic.refine_train — the factorised layer 1 under autograd, the per-ray
+    step through lidf_refine_step_forward_f32 / _backward_f32; it refuses, with the reason, a decoder with
+    out_dim != 1, a PointNet whose input_channels is not 6 and an inp_dim other than pnet_out + rgb_out
+    roi_out_bbox^2 + E + Ed. factorised=True sends every configuration there, the shipped one too (how it is compared
+    with the fused node); factorised=False never does.
     perturb_noise: the scalar of refine_perturb_noise() — or None — applied in the first iteration
     (pipeline.py:937). grid: as lidf_refine (the end voxels through the cell table).
     Returns pred_pos_refine [R,3] (with grad) and the last end_voxel_id [R] i32."""
     from .decoders import is_shipped
     from .pointnet import is_shipped as pnet_shipped, pointnet_params
     E, Ed = 3 + 6 * multires, 3 + 6 * multires_views
+    # the feature widths the fused node and the composed path are built for; every other one has generic.refine_train
+    fixed_feat = (feat_grid.dim() == 4 and feat_grid.shape[1] == 32 and roi_out_bbox == 2
+                  and pnet_model.vox_lin2.out_features == 128)
+    if factorised or (factorised is None and not fixed_feat):
+        from . import generic
+        return generic.refine_train(ray_dir, ray_pix, ray_bid, ray_flat, pred_pos, max_pair_id, pair_vox, voxel_bound,
+                                    voxel_bid, rgb_img, feat_grid, valid_inp, valid_vox, pnet_model, offset_dec,
+                                    forward_times, multires, multires_views, roi_inp_bbox, roi_out_bbox, offset_range,
+                                    pos_rel, pnet_pos_rel, perturb_noise, grid)
+    if roi_out_bbox != 2:
+        raise RuntimeError("factorised=False keeps the shipped-feature-width paths: roi_out_bbox must be 2")
     if not (is_shipped(offset_dec) and pnet_shipped(pnet_model) and feat_grid.shape[1] == 32
             and multires > 0 and offset_dec.inp_dim == 256 + E + Ed):
         return _lidf_refine_train_composed(ray_dir, ray_pix, ray_bid, ray_flat, pred_pos, max_pair_id, pair_vox,

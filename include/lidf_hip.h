@@ -1023,6 +1023,53 @@ int lidf_refine_train_backward_f32(const LidfRefineArgs* args, int32_t forward_t
                                    const LidfPointNetGrads* pnet_grads, const LidfDecoderGrads* dec_grads,
                                    lidf_stream_t stream);
 
+/* ---- Stage 2, the per-ray step of one iteration on its own (the any-width training route) -------------------
+ * What one get_pred_refine does per ray that depends on no network width (models/pipeline.py:939-996, :1019-1029),
+ * with host counts, for a caller that runs the PointNet and the decoder itself (generic.refine_train).
+ *
+ * forward, for n_rays rays at pos [R,3]:
+ *   end_voxel [R]   the arg-max pair's voxel pair_vox[max_pair_id[r]] (0 for max_pair_id outside [0, n_pairs): the
+ *                   dummy row), raised to the largest voxel of the ray's frame whose box contains pos — the
+ *                   reference's inclusive test; max(first, lidf_pcl_aabb_last_f32). voxel_coord [V,3] (optional,
+ *                   with grid_res / grid_xmin / grid_part: get_occ_vox_bound's grid, as LidfRefineArgs.voxel_coord)
+ *                   selects the cell-table lookup: equal results, O(R) instead of O(R V). The table lives in the
+ *                   workspace, lidf_refine_step_workspace_bytes(batch, grid_res) bytes, and is rebuilt by every call
+ *                   unless cell_table_ready != 0 (the workspace still holds the table an earlier call built from the
+ *                   same voxel list). Without voxel_coord no workspace is read (NULL / 0 are fine).
+ *   pnet_inp [n_valid + R, 6], pnet_vox [n_valid + R]
+ *                   rows n_valid .. n_valid + R - 1 receive [pos (- centre of the end voxel when pnet_pos_rel) | rgb of
+ *                   the ray's pixel] and the end voxel; the first n_valid rows are the caller's (not touched).
+ *   pe [R, E] at row stride ld_pe >= E = 3 + 6 multires
+ *                   embed(pos (- centre when pos_rel)) with the expressions of the fused route's rows, so both routes
+ *                   feed their decoders the same numbers; multires == 0: the three raw columns. Rows leave as whole
+ *                   16-byte pieces when pe is 16-byte aligned and ld_pe == E or ld_pe % 4 == 0, as single stores
+ *                   otherwise (same values). Columns E .. ld_pe - 1 of a row are not written.
+ * backward, either output optional (NULL: not formed), one launch each, no atomics, fixed order:
+ *   d_off [R]   = (offset_range1 - offset_range0) <g_pos, ray_dir>    (the decoder's output activation is the caller's)
+ *   d_pos [R,3] = g_pos + embed'(x)^T d_pe + d_pnet_rows[:, 0:3], x = pos (- centre of end_voxel when pos_rel);
+ *                 d_pe [R, E] dense (NULL: that term is left out, pos / end_voxel / voxel_bound are then not read),
+ *                 d_pnet_rows (optional): the gradient of the R predicted rows of pnet_inp, row stride 6 — the
+ *                 caller passes d_pnet_inp + 6 n_valid.
+ * Before any HIP call: LIDF_ERR_BAD_ARG for a negative count, multires outside 0..16, and (n_rays > 0) a missing
+ * pointer, n_vox == 0, batch / height / width < 1, ld_pe < E, pos / pnet_inp / pe not 4-byte aligned, or a grid
+ * without grid_res / grid_xmin / a positive grid_part; LIDF_ERR_UNSUPPORTED for n_rays + n_valid > 0x15555555 or
+ * a grid of more than 2^31 - 1 cells; LIDF_ERR_WORKSPACE for a grid with a missing or short workspace.
+ * n_rays == 0 returns LIDF_OK without a launch. (additive, ABI unchanged)                                        */
+size_t lidf_refine_step_workspace_bytes(int32_t batch, const int32_t* grid_res);
+int lidf_refine_step_forward_f32(const float* pos, const int64_t* max_pair_id, const int32_t* pair_vox,
+                                 int64_t n_pairs, const float* voxel_bound, const int32_t* voxel_bid, int64_t n_vox,
+                                 const int32_t* ray_bid, const int32_t* ray_flat, const float* rgb_img, int32_t batch,
+                                 int32_t height, int32_t width, int64_t n_rays, int64_t n_valid, int32_t pnet_pos_rel,
+                                 int32_t pos_rel, int32_t multires, const int32_t* voxel_coord,
+                                 const int32_t* grid_res, const float* grid_xmin, float grid_part,
+                                 int32_t cell_table_ready, int32_t* end_voxel, float* pnet_inp, int32_t* pnet_vox,
+                                 float* pe, int64_t ld_pe, void* workspace, size_t workspace_bytes,
+                                 lidf_stream_t stream);
+int lidf_refine_step_backward_f32(const float* g_pos, const float* ray_dir, float offset_range0, float offset_range1,
+                                  float* d_off, const float* pos, const int32_t* end_voxel, const float* voxel_bound,
+                                  int32_t pos_rel, const float* d_pe, int32_t multires, const float* d_pnet_rows,
+                                  float* d_pos, int64_t n_rays, lidf_stream_t stream);
+
 /* ---- Per-pair / per-ray tail of get_pred with its adjoint --------------------------------------
  * models/pipeline.py:437-454 for the training path (the inference path has it inside
  * lidf_query_f32): pair_pred_pos = dir t_enter + ((off (r1-r0) + r0) sqrt(3) part_size) dir, the
