@@ -143,6 +143,17 @@ class LidfFrameArgs(C.Structure):
     ]
 
 
+class LidfFrameWidths(C.Structure):
+    """struct LidfFrameWidths (include/lidf_hip.h): the frame with decoders of gf_dim 32 / 64 / 128."""
+    _fields_ = [
+        ("prob_gf", C.c_int32), ("off_gf", C.c_int32), ("refine_gf", C.c_int32),
+        ("pe_slab_pairs", C.c_int64),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+        ("pack_blob", C.c_void_p), ("pack_blob_bytes", C.c_size_t), ("pack_guard", C.c_void_p),
+        ("prob_bias", C.c_void_p), ("off_bias", C.c_void_p), ("refine_bias", C.c_void_p),
+    ]
+
+
 class LidfLossArgs(C.Structure):
     """struct LidfLossArgs (include/lidf_hip.h)."""
     _fields_ = [
@@ -263,6 +274,11 @@ SIGNATURES = {
     "lidf_frame_workspace_bytes": (_SZ, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _I64,
                                          C.c_int32, C.c_int32]),
     "lidf_frame_f32": (C.c_int, [C.POINTER(LidfFrameArgs), _P]),
+    "lidf_frame_widths_workspace_bytes": (_SZ, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _I64,
+                                                C.c_int32, C.c_int32, C.c_int32, C.POINTER(LidfFrameWidths)]),
+    "lidf_frame_widths_pack_bytes": (_SZ, [C.c_int32, C.c_int32, C.POINTER(LidfFrameWidths)]),
+    "lidf_frame_widths_pack_guard_bytes": (_SZ, []),
+    "lidf_frame_widths_f32": (C.c_int, [C.POINTER(LidfFrameArgs), C.POINTER(LidfFrameWidths), _P]),
     "lidf_event_create": (C.c_int, [C.POINTER(C.c_void_p)]),
     "lidf_event_destroy": (C.c_int, [_P]),
     "lidf_frame_pack_bytes": (_SZ, []),

@@ -1600,7 +1600,18 @@ static int frame_pack_guarded(const LidfFrameArgs* a, char* blob, char* guards, 
 struct ForkState {
     bool open = false;
 };
-static int frame_impl(const LidfFrameArgs* a_in, lidf_stream_t stream, ForkState* fork);
+static int frame_impl(const LidfFrameArgs* a_in, lidf_stream_t stream, ForkState* fork,
+                      const LidfFrameWidths* wd = nullptr);
+// the any-width route of the frame (lidf_frame_widths_f32, defined behind lidf_decoder_chain_f32)
+static int frame_widths_check(const LidfFrameArgs* a, const LidfFrameWidths* wd);
+static int frame_widths_pack(const LidfFrameArgs* a, const LidfFrameWidths* wd, char* pnet_blob, char* pnet_blob_r,
+                             hipStream_t st);
+static int frame_widths_query(const LidfFrameArgs* a, const LidfFrameWidths* wd, int64_t N, int64_t C,
+                              const float* vox_center, int cus, hipStream_t st);
+static int frame_widths_refine_tables(const LidfFrameArgs* a, const LidfFrameWidths* wd, int64_t N, hipStream_t st);
+static int frame_widths_refine_decoder(const LidfFrameArgs* a, const LidfFrameWidths* wd, int64_t N, int64_t C,
+                                       const float* vox_feat_r, const float* inp_embed, float* offv, int cus,
+                                       hipStream_t st);
 
 LIDF_API int lidf_frame_f32(const LidfFrameArgs* a_in, lidf_stream_t stream) {
     ForkState fork;
@@ -1635,7 +1646,7 @@ static inline int frame_fail_stage(const LidfFrameArgs* a) {
 }
 #define FRAME_FAIL_AFTER(k) do { if (fail_stage == (k)) return LIDF_ERR_HIP; } while (0)
 
-static int frame_impl(const LidfFrameArgs* a_in, lidf_stream_t stream, ForkState* fork) {
+static int frame_impl(const LidfFrameArgs* a_in, lidf_stream_t stream, ForkState* fork, const LidfFrameWidths* wd) {
     if (!a_in) return LIDF_ERR_BAD_ARG;
     LidfFrameArgs a_loc = *a_in;
     LidfFrameArgs* a = &a_loc;
@@ -1651,7 +1662,7 @@ static int frame_impl(const LidfFrameArgs* a_in, lidf_stream_t stream, ForkState
         a->pack_mode != LIDF_FRAME_PACK_TRUSTED)
         return LIDF_ERR_BAD_ARG;
     if (!a->rgb || !a->xyz_corrupt || !a->valid_mask || !a->intr || !a->feat_grid || !a->pnet || !a->prob ||
-        !a->off || (!own_pack && !a->packed_query) || !a->counts)
+        !a->off || (!wd && !own_pack && !a->packed_query) || !a->counts)
         return LIDF_ERR_BAD_ARG;
     if (!a->valid_bid || !a->valid_flat || !a->valid_xyz || !a->valid_rgb || !a->occ_bid_coord ||
         !a->voxel_bound || !a->valid_v_pid || !a->revidx || !a->valid_v_rel_coord || !a->pnet_inp ||
@@ -1663,11 +1674,15 @@ static int frame_impl(const LidfFrameArgs* a_in, lidf_stream_t stream, ForkState
         return LIDF_ERR_BAD_ARG;
     const bool rf = a->refine_times > 0;
     const bool split = a->precision == LIDF_PRECISION_F16X3;
-    if (rf && (!a->pnet_refine || !a->off_refine || (!split && !own_pack && !a->packed_refine) ||
+    if (rf && (!a->pnet_refine || !a->off_refine || (!wd && !split && !own_pack && !a->packed_refine) ||
                !a->pred_pos_refine || !a->end_voxel_id || !a->pred_depth_refine))
         return LIDF_ERR_BAD_ARG;
     int rc, cus;
-    if ((rc = check_query_model(a->prob, a->off, a->multires, a->multires_views, a->precision))) return rc;
+    if (wd) {   // decoders of gf_dim 32 / 64 / 128 (lidf_frame_widths_f32): its own refusals and workspaces
+        if ((rc = frame_widths_check(a, wd))) return rc;
+    } else if ((rc = check_query_model(a->prob, a->off, a->multires, a->multires_views, a->precision))) {
+        return rc;
+    }
     if (rf && (rc = check_decoder(a->off_refine))) return rc;
     if ((rc = check_pointnet_w(a->pnet)) || (rf && (rc = check_pointnet_w(a->pnet_refine)))) return rc;
     if ((rc = cu_count(&cus))) return rc;
@@ -1701,7 +1716,9 @@ static int frame_impl(const LidfFrameArgs* a_in, lidf_stream_t stream, ForkState
     if (own_pack) {
         const FramePackLay pl = frame_pack_lay();
         char* blob = (char*)a->pack_blob;
-        if (a->pack_mode == LIDF_FRAME_PACK_GUARDED) {
+        if (wd) {
+            if ((rc = frame_widths_pack(a, wd, blob + pl.pnet, rf ? blob + pl.pnet_r : nullptr, st))) return rc;
+        } else if (a->pack_mode == LIDF_FRAME_PACK_GUARDED) {
             rc = frame_pack_guarded(a, blob, (char*)a->pack_guard, two ? sx : st);
             if (two && !rc) {   // (first record of ev_join: the weight streams are valid; a failure joins at the exit)
                 if (hipEventRecord((hipEvent_t)a->ev_join, sx) != hipSuccess) rc = LIDF_ERR_HIP;
@@ -1713,6 +1730,8 @@ static int frame_impl(const LidfFrameArgs* a_in, lidf_stream_t stream, ForkState
         pn_loc.packed = blob + pl.pnet;
         pnr_loc.packed = blob + pl.pnet_r;
         a->packed_refine = blob + pl.refine;
+    } else if (wd) {
+        if ((rc = frame_widths_pack(a, wd, nullptr, nullptr, st))) return rc;   // (the chain streams: every call)
     }
     if (two)
         CHECK_HIP(lidf_launch_rayfeat_phase(a->feat_grid, (float*)(ws + f.query + qw.box), B, h, w, a->ray_dir,
@@ -1828,7 +1847,10 @@ static int frame_impl(const LidfFrameArgs* a_in, lidf_stream_t stream, ForkState
     // to its 220 and 128 KiB, in the matrix-pipe slots its one wavefront per SIMD leaves free, and in its tail)
     const bool xr_aside = two && rf && !split;
     void* const* pev = a->profile_events;   // (benchmarks: HIP events around the matrix launches)
-    if ((rc = query_impl(&q, pev ? pev[0] : nullptr, pev ? pev[1] : nullptr, stream, counts,
+    if (wd) {
+        if ((rc = frame_widths_query(a, wd, N, C, vox_center, cus, st))) return rc;
+        if (rf && (rc = frame_widths_refine_tables(a, wd, N, st))) return rc;
+    } else if ((rc = query_impl(&q, pev ? pev[0] : nullptr, pev ? pev[1] : nullptr, stream, counts,
                          (rf && !split && !xr_aside) ? &xr : nullptr,
                          two ? (QP_RAYTAB | QP_MAIN) : QP_ALL, xr_aside ? a->ev_fork : nullptr)))
         return rc;
@@ -1864,6 +1886,8 @@ static int frame_impl(const LidfFrameArgs* a_in, lidf_stream_t stream, ForkState
         // f32: per iteration ONE per-ray launch (the previous iteration's finish, end voxel through the
         // cell table, PointNet rows, embed(pos) rows, the max-pool tables zeroed), the PointNet in four
         // (its last per-voxel launch also forms the voxel columns of the decoder's layer 1), the decoder.
+        // (any-width route: the PointNet without that tail — the voxel table is a launch of its own at 4 gf
+        // columns —, the decoder as one chain launch)
         const VoxTail tail = {(const float*)a->packed_refine, (128 + 2 + 7) / 8, 8, voxpart_r};
         for (int it = 0; it < a->refine_times; ++it) {
             RefineStepArgs sa = {};
@@ -1886,8 +1910,12 @@ static int frame_impl(const LidfFrameArgs* a_in, lidf_stream_t stream, ForkState
             if (it > 0) cur = sa.cur_pos;
             if ((rc = pointnet_frame(a->pnet_refine, pn_inp, a->revidx, 2 * N, counts + LIDF_FC_PNET_REFINE, C,
                                      v_lds, counts + LIDF_FC_VOX, vox_feat_r, ws + f.pnet, cus, st, sort_cap,
-                                     &tail)))
+                                     wd ? nullptr : &tail)))
                 return rc;
+            if (wd) {
+                if ((rc = frame_widths_refine_decoder(a, wd, N, C, vox_feat_r, inp_embed, offv, cus, st))) return rc;
+                continue;
+            }
             if ((rc = refine_ief_factorised(a->off_refine, D, vox_feat_r, C, inp_embed, a->end_voxel_id, N,
                                             offv, voxpart_r, (char*)a->packed_refine, st, 2,
                                             counts + LIDF_FC_RAYS, counts + LIDF_FC_VOX,
@@ -2160,7 +2188,8 @@ static int linear_impl(const float* x, int64_t ldx, int64_t n, int32_t k, const 
                        const float* addrows, const int32_t* addidx, int64_t ld_add,
                        const float* addrows2, const int32_t* addidx2, int64_t ld_add2, float* out,
                        int64_t ld_out, float* pool, const int32_t* poolidx, int64_t ld_pool,
-                       void* workspace, size_t workspace_bytes, lidf_stream_t stream);
+                       void* workspace, size_t workspace_bytes, lidf_stream_t stream,
+                       const int* n_dev = nullptr);
 
 LIDF_API int lidf_linear_f32(const float* x, int64_t ldx, int64_t n, int32_t k, const float* w, int64_t ldw,
                                const float* b, int32_t nout, int32_t act, float slope,
@@ -2187,7 +2216,8 @@ static int linear_impl(const float* x, int64_t ldx, int64_t n, int32_t k, const 
                        const float* addrows, const int32_t* addidx, int64_t ld_add,
                        const float* addrows2, const int32_t* addidx2, int64_t ld_add2, float* out,
                        int64_t ld_out, float* pool, const int32_t* poolidx, int64_t ld_pool,
-                       void* workspace, size_t workspace_bytes, lidf_stream_t stream) {
+                       void* workspace, size_t workspace_bytes, lidf_stream_t stream, const int* n_dev) {
+    // n_dev (the any-width frame route): the row count on the device, n then bounds the launches
     if (n < 0 || k <= 0 || nout <= 0 || ldx < k || ldw < k || act < 0 || act > 1) return LIDF_ERR_BAD_ARG;
     if (k > (1 << 20) || nout > (1 << 20) || ld_add > 0x7fffffffLL || ld_add2 > 0x7fffffffLL ||
         ld_pool > 0x7fffffffLL)
@@ -2221,6 +2251,7 @@ static int linear_impl(const float* x, int64_t ldx, int64_t n, int32_t k, const 
         CHECK_HIP(pack_stream(lay, nw, nw, m, (float*)workspace, nullptr, st));
         LinearArgs a = {};
         a.stream = (const float*)workspace; a.kq1 = m.KQ1; a.X = x; a.ldx = ldx; a.n = n;
+        a.n_dev = n_dev;
         a.D = m.D; a.has_bias = b ? 1 : 0;
         a.addrows = addrows ? addrows + c0 : nullptr; a.addidx = addidx; a.ld_add = (int)ld_add;
         a.addrows2 = addrows2 ? addrows2 + c0 : nullptr; a.addidx2 = addidx2; a.ld_add2 = (int)ld_add2;
@@ -2256,6 +2287,8 @@ LIDF_API int lidf_decoder_chain_f32(const LidfDecoder* dec, int32_t gf_dim, int3
     if (dec->is_ief && (!dec->wenc || !dec->benc || dec->n_iter < 1 || dec->n_iter > 64)) return LIDF_ERR_BAD_ARG;
     if (n == 0) return LIDF_OK;
     if (!x || !out || (vox_idx && !voxpart) || (ray_idx && !raypart)) return LIDF_ERR_BAD_ARG;
+    // (the kernel loads the table rows as aligned 16-byte pieces; a row is 256 gf_dim / 16 bytes)
+    if (((uintptr_t)voxpart | (uintptr_t)raypart) & 15) return LIDF_ERR_BAD_ARG;
     if (k > (1 << 16)) return LIDF_ERR_UNSUPPORTED;
     const size_t need = lidf_decoder_chain_workspace_bytes(gf_dim, k);
     if (!workspace || workspace_bytes < need) return LIDF_ERR_WORKSPACE;
@@ -2283,6 +2316,354 @@ LIDF_API int lidf_decoder_chain_f32(const LidfDecoder* dec, int32_t gf_dim, int3
     a.out = out;
     CHECK_HIP(lidf_launch_chain16(gf_dim, a, cus, st));
     return LIDF_OK;
+}
+
+// ---- the frame with decoders of gf_dim 32 / 64 / 128 (lidf_frame_widths_f32) ---------------------------------
+// frame_impl's steps 0-4 and the per-ray launches of stage 2 are width-independent; what follows replaces the
+// weight streams, the query (step 5) and the decoder of a refine iteration by the any-width launches of the
+// stepwise path (generic.py: three lidf_linear_kernel table launches per decoder, lidf_pe_rows_kernel,
+// lidf_chain16_kernel), every one of them sized for its capacity and reading its row count on the device.
+// RULE of every launch issued here: no element of pair_ray, pair_vox, pair_t, end_voxel_id or any other index
+// array at or beyond its device-side count is dereferenced (the kernels clamp their row index to count - 1 or
+// predicate the load); a row beyond the count may be left unwritten, it is never read.
+static inline bool widths_gf_ok(int gf) { return gf == 32 || gf == 64 || gf == 128; }
+#define WIDTHS_GUARDS 3   // prob, off, off_refine
+
+struct WidthsWs {
+    size_t lin, iota, rp, bias, voxpart[2], raypart[2], pe, voxpart_r, raypart_r, total;
+    int64_t slab;
+};
+static WidthsWs widths_ws(int B, int h, int w, const int32_t* res, int64_t max_pairs, int refine_times, int L,
+                          const LidfFrameWidths* wd) {
+    WidthsWs W;
+    const size_t N = (size_t)B * h * w, C = (size_t)B * res[0] * res[1] * res[2];
+    const int gfs[2] = {wd->prob_gf, wd->off_gf};
+    int gmax = gfs[0] > gfs[1] ? gfs[0] : gfs[1];
+    const bool rf = refine_times > 0;
+    if (rf && wd->refine_gf > gmax) gmax = wd->refine_gf;
+    W.slab = wd->pe_slab_pairs > 0 ? wd->pe_slab_pairs : LIDF_FRAME_PE_SLAB;
+    if (W.slab > max_pairs) W.slab = max_pairs;
+    size_t o = 0;
+    W.lin = o;  o += align_up(linex_stream_bytes(128), 256);      // the table launches' weight stream (k <= 128)
+    W.iota = o; o += align_up(N * 4, 256);                        // row r -> r: the gathered term of the ray tables
+    W.rp = o;   o += align_up(N * 4 * gmax * 4, 256);             // W1[:, ROI] roi, before the direction columns
+    W.bias = o; o += align_up((size_t)3 * 512 * 4, 256);          // the bias rows the library forms itself
+    for (int i = 0; i < 2; ++i) {
+        W.voxpart[i] = o; o += align_up(C * 4 * gfs[i] * 4, 256);
+        W.raypart[i] = o; o += align_up(N * 4 * gfs[i] * 4, 256);
+    }
+    // (16 floats of slack behind the rows: the chain launch reads whole 16-column groups of the last row)
+    W.pe = o;   o += align_up((size_t)W.slab * 2 * (3 + 6 * L) * 4 + 64, 256);
+    W.voxpart_r = o; o += rf ? align_up(C * 4 * wd->refine_gf * 4, 256) : 0;
+    W.raypart_r = o; o += rf ? align_up(N * 4 * wd->refine_gf * 4, 256) : 0;
+    W.total = o;
+    return W;
+}
+static bool widths_args_ok(const LidfFrameWidths* wd, int refine_times, int L, int Lv) {
+    return wd && widths_gf_ok(wd->prob_gf) && widths_gf_ok(wd->off_gf) &&
+           (refine_times <= 0 || widths_gf_ok(wd->refine_gf)) && wd->pe_slab_pairs >= 0 && L >= 0 &&
+           L <= LIDF_MAX_L_FUSED && Lv >= 0 && Lv <= 16;
+}
+
+LIDF_API size_t lidf_frame_widths_workspace_bytes(int32_t batch, int32_t height, int32_t width, const int32_t* res,
+                                                  int64_t max_pairs, int32_t refine_times, int32_t multires,
+                                                  int32_t multires_views, const LidfFrameWidths* wd) {
+    if (batch <= 0 || height <= 0 || width <= 0 || !res || res[0] <= 0 || res[1] <= 0 || res[2] <= 0 ||
+        max_pairs <= 0 || refine_times < 0 || !widths_args_ok(wd, refine_times, multires, multires_views))
+        return 0;
+    return widths_ws(batch, height, width, res, max_pairs, refine_times, multires, wd).total;
+}
+
+// the three chain streams (stream | layer-4 operands each, as lidf_decoder_chain_f32's workspace)
+struct WidthsPack { size_t dec[3], total; };
+static WidthsPack widths_pack_lay(int L, bool rf, const LidfFrameWidths* wd) {
+    WidthsPack p;
+    const int E = 3 + 6 * L;
+    size_t o = 0;
+    p.dec[0] = o; o += align_up(lidf_decoder_chain_workspace_bytes(wd->prob_gf, 2 * E), 256);
+    p.dec[1] = o; o += align_up(lidf_decoder_chain_workspace_bytes(wd->off_gf, 2 * E), 256);
+    p.dec[2] = o; o += rf ? align_up(lidf_decoder_chain_workspace_bytes(wd->refine_gf, E), 256) : 0;
+    p.total = o;
+    return p;
+}
+LIDF_API size_t lidf_frame_widths_pack_bytes(int32_t multires, int32_t multires_views, const LidfFrameWidths* wd) {
+    // (sized with the third stream whatever refine_times a later call passes: refine_gf outside the widths = none)
+    if (!wd || !widths_args_ok(wd, widths_gf_ok(wd->refine_gf) ? 1 : 0, multires, multires_views)) return 0;
+    return widths_pack_lay(multires, widths_gf_ok(wd->refine_gf), wd).total;
+}
+LIDF_API size_t lidf_frame_widths_pack_guard_bytes(void) { return (size_t)WIDTHS_GUARDS * FRAME_GUARD_STRIDE; }
+
+static int frame_widths_check(const LidfFrameArgs* a, const LidfFrameWidths* wd) {
+    const bool rf = a->refine_times > 0;
+    if (a->multires < 0 || a->multires > LIDF_MAX_L_FUSED || a->multires_views < 0 || a->multires_views > 16)
+        return LIDF_ERR_UNSUPPORTED;
+    if (!widths_gf_ok(wd->prob_gf) || !widths_gf_ok(wd->off_gf) || (rf && !widths_gf_ok(wd->refine_gf)))
+        return LIDF_ERR_UNSUPPORTED;
+    if (wd->pe_slab_pairs < 0) return LIDF_ERR_BAD_ARG;
+    // built for the shipped widths alone: the split-f16 products, the offsets of the selected pairs, the side stream
+    if (a->precision != LIDF_PRECISION_F32 || a->offsets_selected || a->aux_stream || a->ev_fork || a->ev_join)
+        return LIDF_ERR_UNSUPPORTED;
+    int rc;
+    if ((rc = check_decoder(a->prob)) || (rc = check_decoder(a->off))) return rc;
+    const WidthsWs W = widths_ws(a->batch, a->height, a->width, a->res, a->max_pairs, a->refine_times, a->multires, wd);
+    if (!wd->workspace || wd->workspace_bytes < W.total) return LIDF_ERR_WORKSPACE;
+    if (!wd->pack_blob || wd->pack_blob_bytes < widths_pack_lay(a->multires, rf, wd).total) return LIDF_ERR_WORKSPACE;
+    if (a->pack_mode != LIDF_FRAME_PACK_CALLER && !wd->pack_guard) return LIDF_ERR_WORKSPACE;
+    if (((uintptr_t)wd->workspace | (uintptr_t)wd->pack_blob) & 15) return LIDF_ERR_BAD_ARG;
+    // (LidfFrameArgs' own workspace and blob, which frame_impl checks again behind its first HIP call: here every
+    // size error of this entry is reported before one)
+    const size_t Cc = (size_t)a->batch * a->res[0] * a->res[1] * a->res[2];
+    if (!a->workspace || a->workspace_bytes < frame_ws(a->batch, a->height, a->width, a->res, a->max_pairs,
+                                                       frame_lds_voxels(a->lds_voxels, Cc), a->refine_times).total)
+        return LIDF_ERR_WORKSPACE;
+    if (a->pack_mode != LIDF_FRAME_PACK_CALLER &&
+        (!a->pack_blob || !a->pack_guard || a->pack_blob_bytes < frame_pack_lay().total))
+        return LIDF_ERR_WORKSPACE;
+    // stage 2 hands the chain launch the embed(pos) columns [256, 256 + E) of inp_embed (row stride D): whole
+    // 16-column groups are read, so the last row must be readable up to column 256 + 16 ceil(E / 16) — inside the
+    // buffer, whose rows are sized for 256 + 2 (3 + 6 * 16) columns
+    const int E = 3 + 6 * a->multires;
+    if (rf && 256 + (E + 15) / 16 * 16 > 256 + 2 * (3 + 6 * 16)) return LIDF_ERR_UNSUPPORTED;
+    return LIDF_OK;
+}
+
+// one decoder's parameter buffers as fingerprint segments, at its own width
+static int widths_decoder_segs(const LidfDecoder* d, int dcore, int gf, const float** ptrs, long long* n, int k) {
+    const int d_in = dcore + (d->is_ief ? 16 : 0);
+    const float* p[10] = {d->w1, d->b1, d->w2, d->b2, d->w3, d->b3, d->w4, d->b4, d->wenc, d->benc};
+    const long long c[10] = {(long long)4 * gf * d_in, 4 * gf, (long long)2 * gf * 4 * gf, 2 * gf,
+                             (long long)gf * 2 * gf, gf, gf, 1, 16, 16};
+    for (int i = 0; i < (d->is_ief ? 10 : 8); ++i) { ptrs[k] = p[i]; n[k] = c[i]; ++k; }
+    return k;
+}
+static int widths_chain_pack(const LidfDecoder* dec, int gf, int inp_dim, int k, int c0, char* dst, hipStream_t st) {
+    StreamLayout lay = {};
+    lay.nets = 1; lay.mode = LIDF_MODE_CHAIN16;
+    lay.total = (int)(chain16_stream_bytes(gf, k) / 4);
+    L1Map m = {};
+    m.n0 = k; m.c0 = c0; m.nt = gf / 16;
+    const NetW nw = to_netw(dec, inp_dim);
+    CHECK_HIP(pack_stream(lay, nw, nw, m, (float*)dst, (float*)(dst + align_up(chain16_stream_bytes(gf, k), 256)), st));
+    return LIDF_OK;
+}
+
+// The weight streams of the any-width frame. GUARDED: two fingerprint launches — the PointNets into guards 1 / 2
+// of LidfFrameArgs.pack_guard (the slots lidf_frame_f32 keeps them in), the three decoders into
+// LidfFrameWidths.pack_guard — and the early-exit packs under them; TRUSTED: nothing; CALLER (pnet_blob NULL):
+// the chain streams packed without a check, the PointNet streams are the caller's.
+static int frame_widths_pack(const LidfFrameArgs* a, const LidfFrameWidths* wd, char* pnet_blob, char* pnet_blob_r,
+                             hipStream_t st) {
+    if (a->pack_mode == LIDF_FRAME_PACK_TRUSTED) return LIDF_OK;
+    const bool rf = a->refine_times > 0, guard = a->pack_mode == LIDF_FRAME_PACK_GUARDED;
+    const int L = a->multires, Lv = a->multires_views, E = 3 + 6 * L;
+    const WidthsPack pl = widths_pack_lay(L, rf, wd);
+    const LidfDecoder* decs[3] = {a->prob, a->off, rf ? a->off_refine : nullptr};
+    const int gfs[3] = {wd->prob_gf, wd->off_gf, wd->refine_gf};
+    const int dims[3] = {query_D(L, Lv), query_D(L, Lv), refine_D(L, Lv)};
+    const int ks[3] = {2 * E, 2 * E, E};
+    char* guards = (char*)wd->pack_guard;
+    char* pguards = (char*)a->pack_guard + FRAME_GUARD_STRIDE;
+    const size_t gbytes = (size_t)WIDTHS_GUARDS * FRAME_GUARD_STRIDE;
+    const int nd = rf ? 3 : 2;
+    if (guard) {
+        const float* ptrs[LIDF_FP_MULTI_SEGS];
+        long long cnt[LIDF_FP_MULTI_SEGS];
+        int grp[LIDF_FP_MULTI_SEGS];
+        unsigned long long salts[LIDF_FP_GROUPS] = {};
+        int k = 0;
+        for (int i = 0; i < nd; ++i) {
+            const int k0 = k;
+            k = widths_decoder_segs(decs[i], dims[i], gfs[i], ptrs, cnt, k);
+            for (int j = k0; j < k; ++j) grp[j] = i;
+            salts[i] = decoder_salt(salt_mix(0xC4A1E16ull + i, ((unsigned long long)gfs[i] << 40) |
+                                                                  ((unsigned long long)L << 20) | (unsigned long long)Lv),
+                                    decs[i]);
+        }
+        CHECK_HIP(lidf_launch_fingerprint_multi(ptrs, cnt, grp, k, salts, nd, guards, FRAME_GUARD_STRIDE, st));
+        k = pnet_segs(a->pnet, ptrs, cnt, 0);
+        for (int j = 0; j < k; ++j) grp[j] = 0;
+        salts[0] = salts[1] = PNET_SALT;
+        if (rf) {
+            const int k0 = k;
+            k = pnet_segs(a->pnet_refine, ptrs, cnt, k);
+            for (int j = k0; j < k; ++j) grp[j] = 1;
+        }
+        CHECK_HIP(lidf_launch_fingerprint_multi(ptrs, cnt, grp, k, salts, rf ? 2 : 1, pguards, FRAME_GUARD_STRIDE, st));
+    }
+    int rc = LIDF_OK;
+    JobScope js;
+    for (int i = 0; i < nd && !rc; ++i) {
+        GuardScope g(guard ? (const LidfPackGuardState*)(guards + (size_t)i * FRAME_GUARD_STRIDE) : nullptr);
+        // (the per-row operand columns start behind [vox feat 128 | ROI 128] in both stages' rows)
+        rc = widths_chain_pack(decs[i], gfs[i], dims[i], ks[i], 256, (char*)wd->pack_blob + pl.dec[i], st);
+    }
+    if (!rc && pnet_blob) {
+        GuardScope g(guard ? (const LidfPackGuardState*)pguards : nullptr);
+        rc = pointnet_pack_into(a->pnet, pnet_blob, st);
+    }
+    if (!rc && pnet_blob_r) {
+        GuardScope g(guard ? (const LidfPackGuardState*)(pguards + FRAME_GUARD_STRIDE) : nullptr);
+        rc = pointnet_pack_into(a->pnet_refine, pnet_blob_r, st);
+    }
+    if (!rc && flush_jobs(js.jobs, st) != hipSuccess) rc = LIDF_ERR_HIP;
+    if (rc && guard) {
+        (void)hipMemsetAsync(pguards, 0, (size_t)2 * FRAME_GUARD_STRIDE, st);
+        return guard_fail(guards, gbytes, st, rc);
+    }
+    return rc;
+}
+
+// b1 (+ the IEF's constant) of one decoder: the caller's row, b1 itself, or formed here into `scratch`
+static int widths_bias_row(const LidfDecoder* d, int gf, int dcore, const float* given, float* scratch,
+                           const float** out, hipStream_t st) {
+    if (given) { *out = given; return LIDF_OK; }
+    if (!d->is_ief) { *out = d->b1; return LIDF_OK; }
+    CHECK_HIP(lidf_launch_chain16_bias_row(d->b1, d->w1 + dcore, dcore + 16, d->benc, 4 * gf, scratch, st));
+    *out = scratch;
+    return LIDF_OK;
+}
+
+static inline int widths_linear(const float* x, int64_t ldx, int64_t n, const int* n_dev, int k, const float* w,
+                                int ldw, const float* b, int nout, const float* addrows, const int* addidx, float* out,
+                                char* lin, hipStream_t st) {
+    return linear_impl(x, ldx, n, k, w, ldw, b, nout, 0, 0.f, addrows, addidx, nout, nullptr, nullptr, 0, out, nout,
+                       nullptr, nullptr, 0, lin, linex_stream_bytes(128), (lidf_stream_t)st, n_dev);
+}
+
+// step 5 of the frame at any decoder width: per-ray features, the layer-1 tables of both decoders, the slabs of
+// [position embedding rows, one chain launch per decoder], pair positions, the per-ray reduce
+static int frame_widths_query(const LidfFrameArgs* a, const LidfFrameWidths* wd, int64_t N, int64_t C,
+                              const float* vox_center, int cus, hipStream_t st) {
+    const int L = a->multires, Lv = a->multires_views, E = 3 + 6 * L, Ed = 3 + 6 * Lv, D = query_D(L, Lv);
+    const bool rf = a->refine_times > 0;
+    const WidthsWs W = widths_ws(a->batch, a->height, a->width, a->res, a->max_pairs, a->refine_times, L, wd);
+    const WidthsPack pl = widths_pack_lay(L, rf, wd);
+    char* ws = (char*)wd->workspace;
+    const int* counts = a->counts;
+    const int* n_rays = counts + LIDF_FC_RAYS;
+    const int* n_pairs = counts + LIDF_FC_PAIRS;
+    const int* n_vox = counts + LIDF_FC_VOX;
+    int rc;
+    // per-ray features [ROI 2 x 2 of the feature map | embed(dir)], rows < counts[RAYS]. Without the box-sum
+    // image: every bin is summed in the reference's sample order, the bits of the stepwise path at these widths
+    CHECK_HIP(lidf_launch_rayfeat_phase(a->feat_grid, nullptr, a->batch, a->height, a->width, a->ray_dir, a->ray_pix,
+                                        a->ray_bid, N, n_rays, a->roi_inp_bbox / 2, Lv, a->rayfeat, 128 + Ed, 0, st));
+    int* iota = (int*)(ws + W.iota);
+    CHECK_HIP(lidf_launch_iota(iota, N, st));
+    const LidfDecoder* decs[2] = {a->prob, a->off};
+    const int gfs[2] = {wd->prob_gf, wd->off_gf};
+    const float* given[2] = {wd->prob_bias, wd->off_bias};
+    float* rp = (float*)(ws + W.rp);
+    for (int i = 0; i < 2; ++i) {
+        const LidfDecoder* d = decs[i];
+        const int nout = 4 * gfs[i], ld1 = D + (d->is_ief ? 16 : 0);
+        const float* bias;
+        if ((rc = widths_bias_row(d, gfs[i], D, given[i], (float*)(ws + W.bias) + 512 * i, &bias, st))) return rc;
+        // voxpart [C, 4 gf] = W1[:, 0:128] occ_voxel_feat + bias row, rows < counts[VOX]
+        if ((rc = widths_linear(a->occ_voxel_feat, 128, C, n_vox, 128, d->w1, ld1, bias, nout, nullptr, nullptr,
+                                (float*)(ws + W.voxpart[i]), ws + W.lin, st)))
+            return rc;
+        // rp = W1[:, ROI columns] rayfeat[:, :128]; raypart [N, 4 gf] = W1[:, dir columns] rayfeat[:, 128:] + rp
+        // (rows < counts[RAYS]; the gathered term's index is the row itself: iota below the count)
+        if ((rc = widths_linear(a->rayfeat, 128 + Ed, N, n_rays, 128, d->w1 + 128, ld1, nullptr, nout, nullptr,
+                                nullptr, rp, ws + W.lin, st)))
+            return rc;
+        if ((rc = widths_linear(a->rayfeat + 128, 128 + Ed, N, n_rays, Ed, d->w1 + 256 + 2 * E, ld1, nullptr, nout, rp,
+                                iota, (float*)(ws + W.raypart[i]), ws + W.lin, st)))
+            return rc;
+    }
+    // the slabs: every launch reads counts[PAIRS] and works on clamp(P - p0, 0, rows of the slab) rows; no
+    // element of pair_ray / pair_vox / pair_t at or beyond counts[PAIRS] is dereferenced
+    float* pe = (float*)(ws + W.pe);
+    float* outs[2] = {a->pred_prob, a->pred_offset};
+    for (int64_t p0 = 0; p0 < a->max_pairs; p0 += W.slab) {
+        const int64_t rows = a->max_pairs - p0 < W.slab ? a->max_pairs - p0 : W.slab;
+        CHECK_HIP(lidf_launch_pe_rows(a->pair_ray + p0, a->pair_vox + p0, a->pair_t + 2 * p0, a->ray_dir, vox_center,
+                                      a->pos_rel ? 1 : 0, L, rows, pe, st, n_pairs, p0));
+        for (int i = 0; i < 2; ++i) {
+            const LidfDecoder* d = decs[i];
+            const char* blob = (const char*)wd->pack_blob + pl.dec[i];
+            Chain16Args c = {};
+            c.stream = (const float*)blob;
+            c.aux = (const float*)(blob + align_up(chain16_stream_bytes(gfs[i], 2 * E), 256));
+            c.KQ = (2 * E + 15) / 16; c.E = 2 * E; c.n = rows;
+            c.X = pe; c.ldx = 2 * E;
+            c.vox = a->pair_vox + p0; c.voxpart = (const float*)(ws + W.voxpart[i]);
+            c.ray = a->pair_ray + p0; c.raypart = (const float*)(ws + W.raypart[i]);
+            c.npass = d->is_ief ? d->n_iter : 1;
+            c.init = d->is_ief ? d->init_offset : 0.f;
+            c.sigmoid = d->use_sigmoid;
+            c.out = outs[i] + p0;
+            c.n_dev = n_pairs; c.row0 = p0;
+            CHECK_HIP(lidf_launch_chain16(gfs[i], c, cus, st));
+        }
+    }
+    // pair positions (lidf_query_tail_f32's launch), then the per-ray softmax / arg-max / select / depth
+    CHECK_HIP(lidf_launch_pair_pos(a->pred_offset, a->pair_ray, a->pair_t, a->ray_dir, a->max_pairs, a->offset_range0,
+                                   a->offset_range1 - a->offset_range0, 1.7320508075688772f, a->part_size,
+                                   a->pair_pred_pos, st, n_pairs));
+    CHECK_HIP(lidf_launch_ray_reduce_dev(a->pred_prob, a->pair_pred_pos, a->pair_off, N, a->max_pairs, counts,
+                                         n_pairs, a->ray_bid, a->ray_flat, (long long)a->height * a->width,
+                                         a->pred_prob_softmax, (long long*)a->max_pair_id, a->pred_pos, a->pred_depth,
+                                         st, nullptr, nullptr, nullptr, nullptr, nullptr));
+    return LIDF_OK;
+}
+
+// stage 2, once per frame: raypart_r [N, 4 gf] = W1r[:, ROI | dir columns] rayfeat[r], rows < counts[RAYS]
+static int frame_widths_refine_tables(const LidfFrameArgs* a, const LidfFrameWidths* wd, int64_t N, hipStream_t st) {
+    const int L = a->multires, Lv = a->multires_views, E = 3 + 6 * L, Ed = 3 + 6 * Lv, D = refine_D(L, Lv);
+    const WidthsWs W = widths_ws(a->batch, a->height, a->width, a->res, a->max_pairs, a->refine_times, L, wd);
+    char* ws = (char*)wd->workspace;
+    const LidfDecoder* d = a->off_refine;
+    const int nout = 4 * wd->refine_gf, ld1 = D + (d->is_ief ? 16 : 0);
+    const int* n_rays = a->counts + LIDF_FC_RAYS;
+    float* rp = (float*)(ws + W.rp);
+    int rc;
+    if ((rc = widths_linear(a->rayfeat, 128 + Ed, N, n_rays, 128, d->w1 + 128, ld1, nullptr, nout, nullptr, nullptr,
+                            rp, ws + W.lin, st)))
+        return rc;
+    return widths_linear(a->rayfeat + 128, 128 + Ed, N, n_rays, Ed, d->w1 + 256 + E, ld1, nullptr, nout, rp,
+                         (const int*)(ws + W.iota), (float*)(ws + W.raypart_r), ws + W.lin, st);
+}
+
+// stage 2, per iteration behind the PointNet: voxpart_r [C, 4 gf] (rows < counts[VOX]), then the decoder as one
+// chain launch on the embed(pos) columns — rows < counts[RAYS]; end_voxel_id beyond them is never read
+static int frame_widths_refine_decoder(const LidfFrameArgs* a, const LidfFrameWidths* wd, int64_t N, int64_t C,
+                                       const float* vox_feat_r, const float* inp_embed, float* offv, int cus,
+                                       hipStream_t st) {
+    const int L = a->multires, Lv = a->multires_views, E = 3 + 6 * L, D = refine_D(L, Lv), gf = wd->refine_gf;
+    const WidthsWs W = widths_ws(a->batch, a->height, a->width, a->res, a->max_pairs, a->refine_times, L, wd);
+    const WidthsPack pl = widths_pack_lay(L, true, wd);
+    char* ws = (char*)wd->workspace;
+    const LidfDecoder* d = a->off_refine;
+    const int ld1 = D + (d->is_ief ? 16 : 0);
+    const float* bias;
+    int rc;
+    if ((rc = widths_bias_row(d, gf, D, wd->refine_bias, (float*)(ws + W.bias) + 1024, &bias, st))) return rc;
+    if ((rc = widths_linear(vox_feat_r, 128, C, a->counts + LIDF_FC_VOX, 128, d->w1, ld1, bias, 4 * gf, nullptr, nullptr,
+                            (float*)(ws + W.voxpart_r), ws + W.lin, st)))
+        return rc;
+    const char* blob = (const char*)wd->pack_blob + pl.dec[2];
+    Chain16Args c = {};
+    c.stream = (const float*)blob;
+    c.aux = (const float*)(blob + align_up(chain16_stream_bytes(gf, E), 256));
+    c.KQ = (E + 15) / 16; c.E = E; c.n = N;
+    c.X = inp_embed + 256; c.ldx = D;
+    c.vox = a->end_voxel_id; c.voxpart = (const float*)(ws + W.voxpart_r);
+    c.ray = nullptr; c.raypart = (const float*)(ws + W.raypart_r);
+    c.npass = d->is_ief ? d->n_iter : 1;
+    c.init = d->is_ief ? d->init_offset : 0.f;
+    c.sigmoid = d->use_sigmoid;
+    c.out = offv;
+    c.n_dev = a->counts + LIDF_FC_RAYS; c.row0 = 0;
+    CHECK_HIP(lidf_launch_chain16(gf, c, cus, st));
+    return LIDF_OK;
+}
+
+LIDF_API int lidf_frame_widths_f32(const LidfFrameArgs* args, const LidfFrameWidths* wd, lidf_stream_t stream) {
+    if (!args || !wd) return LIDF_ERR_BAD_ARG;
+    ForkState fork;   // (never opened: this route refuses a side stream)
+    return frame_impl(args, stream, &fork, wd);
 }
 
 // partial blocks of the weight-gradient reduction: 512 row slices x (128 x 256 block + its bias part)

@@ -265,7 +265,16 @@ template <int G, int SLOTS, int NT>
 __global__ void __launch_bounds__(256 * SLOTS) lidf_chain16_kernel(Chain16Args a) {
     constexpr int T1 = 4 * G, T2 = 2 * G, T3 = G;
     constexpr int PASSQ = ((T2 + 3) / 4 + T1 * T2 + T1 / 4 + (T3 + 3) / 4 + T2 * T3 + C16_RING - 1) / C16_RING * C16_RING;
-    const long long AN = a.n;
+    // device-side row count (the any-width frame route: a.n is the capacity the grid was sized from, the lists start
+    // at row a.row0 of the counted array): rows = clamp(*n_dev - row0, 0, n). Every row index below is clamped to
+    // AN - 1, so no element of vox / ray / X at or beyond the count is dereferenced; a wavefront whose balanced
+    // range is empty (all of them when AN == 0) leaves before it touches the ring.
+    long long an = a.n;
+    if (a.n_dev) {
+        const long long m = (long long)*a.n_dev - a.row0;
+        an = m < an ? (m > 0 ? m : 0) : an;
+    }
+    const long long AN = an;
     const int lane = threadIdx.x & 63;
     const long long nhalf = (AN + 15) / 16;
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -304,6 +313,27 @@ __global__ void __launch_bounds__(256 * SLOTS) lidf_chain16_kernel(Chain16Args a
             c16_tiles<G, 1>(a, AN, t, srs, vq, ring, pos, base, xpre);
         }
     }
+}
+
+// The one-row voxpart table of a chain launch whose layer 1 has no per-voxel columns, and the bias of the table
+// launches that have them: out[f] = b1[f] + W1[f, enc columns] . benc (the IEF's constant; an IMNet's row is b1).
+__global__ void __launch_bounds__(256) lidf_chain16_bias_row_kernel(const float* __restrict__ b1,
+                                                                    const float* __restrict__ w1enc, int ld1,
+                                                                    const float* __restrict__ benc, int nout,
+                                                                    float* __restrict__ out) {
+    const int f = blockIdx.x * 256 + threadIdx.x;
+    if (f >= nout) return;
+    float c = 0.f;
+    for (int j = 0; j < 16; ++j) c = fmaf(w1enc[(size_t)f * ld1 + j], benc[j], c);
+    out[f] = b1[f] + c;
+}
+
+extern "C" hipError_t lidf_launch_chain16_bias_row(const float* b1, const float* w1enc, int ld1, const float* benc,
+                                                   int nout, float* out, hipStream_t st) {
+    if (nout <= 0) return hipSuccess;
+    hipLaunchKernelGGL(lidf_chain16_bias_row_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, st, b1,
+                       w1enc, ld1, benc, nout, out);
+    return hipGetLastError();
 }
 
 extern "C" hipError_t lidf_launch_chain16(int gf, const Chain16Args& a, int cus, hipStream_t st) {

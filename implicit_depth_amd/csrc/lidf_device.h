@@ -499,6 +499,8 @@ struct Chain16Args {
     float init;
     int sigmoid;
     float* out;            // [n]
+    const int* n_dev;      // optional device-side count: rows = clamp(*n_dev - row0, 0, n) (n = capacity of the launch)
+    long long row0;        // first row of this launch in the counted list (the slabs of a frame's pairs)
 };
 static inline int lidf_chain16_pass_quads(int G) {
     const int T1 = 4 * G, T2 = 2 * G, T3 = G;

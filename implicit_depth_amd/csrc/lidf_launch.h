@@ -192,7 +192,8 @@ hipError_t lidf_launch_rayfeat_backward(const float* d_rayfeat, int ld_rf, const
                                         long long R, int half, int B, int H, int W, float* d_feat, float* gimg,
                                         int* aux, hipStream_t st);
 hipError_t lidf_launch_pe_rows(const int* pair_ray, const int* pair_vox, const float* pair_t, const float* ray_dir,
-                               const float* vox_center, int pos_rel, int L, long long P, float* pe, hipStream_t st);
+                               const float* vox_center, int pos_rel, int L, long long P, float* pe, hipStream_t st,
+                               const int* n_dev = nullptr, long long row0 = 0);
 hipError_t lidf_launch_seg_sum_ray(const float* S, int F, const int* pair_off, long long R, float* out,
                                    hipStream_t st);
 size_t lidf_seg_sum_idx_ws_bytes(long long P, long long V);
@@ -203,7 +204,8 @@ void lidf_sort_idx_layout(long long P, long long V, size_t* scanned_off, int* nb
 hipError_t lidf_launch_sort_idx(const int* idx, long long P, const int* n_dev, long long V, void* ws,
                                 const int** perm_out, const int** n_perm_out, hipStream_t st);
 hipError_t lidf_launch_pair_pos(const float* off, const int* pair_ray, const float* pair_t, const float* ray_dir,
-                                long long P, float r0, float rs, float sqrt3, float part, float* out, hipStream_t st);
+                                long long P, float r0, float rs, float sqrt3, float part, float* out, hipStream_t st,
+                                const int* n_dev = nullptr);
 hipError_t lidf_launch_ray_select(const float* pos, const long long* id, long long R, long long P, float* pred_pos,
                                   hipStream_t st);
 hipError_t lidf_launch_pair_pos_backward(const float* g_pos, const float* g_pred, const long long* id,
@@ -320,4 +322,6 @@ hipError_t lidf_launch_ief16(const Ief16Args& a, int cus, hipStream_t st);
 
 // ---- lidf_chain16.hip
 hipError_t lidf_launch_chain16(int gf, const Chain16Args& a, int cus, hipStream_t st);
+hipError_t lidf_launch_chain16_bias_row(const float* b1, const float* w1enc, int ld1, const float* benc, int nout,
+                                        float* out, hipStream_t st);
 }  // extern "C"

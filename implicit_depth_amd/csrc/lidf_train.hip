@@ -1275,7 +1275,15 @@ extern "C" hipError_t lidf_launch_rayfeat_backward(const float* d_rayfeat, int l
 __global__ void __launch_bounds__(256) lidf_pe_rows_kernel(
     const int* __restrict__ pair_ray, const int* __restrict__ pair_vox, const float* __restrict__ pair_t,
     const float* __restrict__ ray_dir, const float* __restrict__ vox_center, int pos_rel, int L,
-    long long P, float* __restrict__ pe) {
+    long long P, float* __restrict__ pe, const int* __restrict__ n_dev, long long row0) {
+    // device-side pair count (the any-width frame route; P = the slab's capacity, the list pointers start at pair
+    // row0): rows = clamp(*n_dev - row0, 0, P). No element of pair_ray / pair_vox / pair_t at or beyond the count is
+    // dereferenced — the loads below are predicated on p < P.
+    if (n_dev) {
+        const long long m = (long long)*n_dev - row0;
+        P = m < P ? (m > 0 ? m : 0) : P;
+    }
+    if ((long long)blockIdx.x * 32 >= P) return;
     // the 32 rows of a workgroup are one contiguous run of memory: built in LDS (a lane's entries lie 3 floats apart),
     // written out as whole 16-byte pieces by all 256 threads (the direct 4-byte stores ran at 2.2 TB/s)
     __shared__ __attribute__((aligned(16))) float s_rows[32 * 2 * (3 + 6 * 16)];
@@ -1355,11 +1363,11 @@ __global__ void __launch_bounds__(256) lidf_seg_sum_idx_kernel(const float* __re
 extern "C" hipError_t lidf_launch_pe_rows(const int* pair_ray, const int* pair_vox,
                                           const float* pair_t, const float* ray_dir,
                                           const float* vox_center, int pos_rel, int L, long long P,
-                                          float* pe, hipStream_t st) {
+                                          float* pe, hipStream_t st, const int* n_dev, long long row0) {
     if (P <= 0) return hipSuccess;
     if (L < 0 || L > 16) return hipErrorInvalidValue;
     hipLaunchKernelGGL(lidf_pe_rows_kernel, dim3((unsigned)((P + 31) / 32)), dim3(256), 0, st,
-                       pair_ray, pair_vox, pair_t, ray_dir, vox_center, pos_rel, L, P, pe);
+                       pair_ray, pair_vox, pair_t, ray_dir, vox_center, pos_rel, L, P, pe, n_dev, row0);
     return hipGetLastError();
 }
 extern "C" hipError_t lidf_launch_seg_sum_ray(const float* S, int F, const int* pair_off,
@@ -1625,7 +1633,10 @@ extern "C" hipError_t lidf_launch_sort_idx(const int* idx, long long P, const in
 __global__ void lidf_pair_pos_kernel(const float* __restrict__ off, const int* __restrict__ pair_ray,
                                      const float* __restrict__ pair_t,
                                      const float* __restrict__ ray_dir, long long P, float r0,
-                                     float rs, float sqrt3, float part, float* __restrict__ out) {
+                                     float rs, float sqrt3, float part, float* __restrict__ out,
+                                     const int* __restrict__ n_dev) {
+    // device-side pair count (P = the launch's capacity): pair_ray at or beyond it is never dereferenced
+    if (n_dev) P = *n_dev < P ? *n_dev : P;
     const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= P) return;
     const size_t r = (size_t)pair_ray[p];
@@ -1674,10 +1685,11 @@ __global__ void lidf_pair_pos_backward_kernel(const float* __restrict__ g_pos,
 
 extern "C" hipError_t lidf_launch_pair_pos(const float* off, const int* pair_ray, const float* pair_t,
                                            const float* ray_dir, long long P, float r0, float rs,
-                                           float sqrt3, float part, float* out, hipStream_t st) {
+                                           float sqrt3, float part, float* out, hipStream_t st,
+                                           const int* n_dev) {
     if (P <= 0) return hipSuccess;
     hipLaunchKernelGGL(lidf_pair_pos_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, off,
-                       pair_ray, pair_t, ray_dir, P, r0, rs, sqrt3, part, out);
+                       pair_ray, pair_t, ray_dir, P, r0, rs, sqrt3, part, out, n_dev);
     return hipGetLastError();
 }
 extern "C" hipError_t lidf_launch_ray_select(const float* pos, const long long* id, long long R,

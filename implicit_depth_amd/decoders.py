@@ -186,7 +186,8 @@ def is_shipped(mod):
 
 
 def _check_supported(mod, what="this entry"):
-    """Entries without a layer-by-layer counterpart (training, the fused query, stage 2, the frame call)."""
+    """Entries without a layer-by-layer counterpart (training, the fused query, stage 2). (The frame call takes gf_dim
+    32 / 64 / 128 and states its own refusals: pipeline.FrameRunner.)"""
     if not is_shipped(mod):
         raise RuntimeError("lidf_hip: %s is built for gf_dim=64, out_dim=1 (every shipped config); got "
                            "gf_dim=%d out_dim=%d. Inference at other widths runs layer by layer "

@@ -450,6 +450,17 @@ class FrameRunner:
     only — pred_pos, the depth maps, stage 2 and the statistics are bit-identical, pred_offset / pair_pred_pos
     are meaningful at the selected pairs only (other rows: NaN, or a previous frame's selected values).
 
+    Decoder widths: prob_dec / offset_dec / offset_dec_refine of gf_dim 64 (every shipped config) run lidf_frame_f32.
+    As soon as one of them has another width — each gf_dim 32, 64 or 128 with the reference's layers 4 gf -> 2 gf ->
+    gf -> 1 (generic.chain_ok), IMNet or IEF, any n_iter, the three may differ — the frame runs
+    lidf_frame_widths_f32: the same call, counts, graph capture and buffers, every decoder ONE register-chained
+    launch per slab of pe_slab pairs (default generic.QUERY_SLAB; slab boundaries do not change a bit) / per refine
+    iteration. Stage 1 equals lidf_forward at the same widths bit for bit, stage 2 within float rounding (its layer 1
+    is factorised). That route is f32, offsets='all', one stream: precision="f16x3", offsets="selected" and
+    side_stream=True are refused there, as is any other gf_dim / out_dim and LIDF_CHAIN16=0. The feature widths stay
+    the shipped ones (rgb_out 32, roi_out_bbox 2, PointNet 6 -> 32 -> 128). chain_route=True sends gf_dim 64 decoders
+    through that route as well (the A/B of the two routes at one width, scripts/frame_widths_time.py).
+
     Weight streams: the runner owns ONE blob with the packed streams of all its modules and the
     device-side fingerprints they were built from (nothing of it lives in the per-module caches, so a
     captured graph never references memory another call can free). Every frame re-validates them with one
@@ -462,10 +473,12 @@ class FrameRunner:
 
     def __init__(self, bs, h, w, device, pnet_model, prob_dec, offset_dec, opt=None, pnet_model_refine=None,
                  offset_dec_refine=None, max_pairs=None, lds_voxels=None,
-                 precision="f32", guard_every=1, offsets="all", side_stream=None, sampler_state=None):
+                 precision="f32", guard_every=1, offsets="all", side_stream=None, sampler_state=None, pe_slab=None,
+                 chain_route=False):
         import ctypes as C
         import math
-        from .decoders import _check_supported
+        from .decoders import is_shipped
+        from .generic import chain_ok
         from .pointnet import check_pointnet
         self.C = C
         self.opt = opt = opt or LidfOptions()
@@ -482,12 +495,38 @@ class FrameRunner:
         self.bs, self.h, self.w, self.dev = bs, h, w, torch.device(device)
         self.mods = (pnet_model, prob_dec, offset_dec, pnet_model_refine, offset_dec_refine)
         what = "FrameRunner (use lidf_forward / refine_forward, which run other widths layer by layer)"
-        _check_supported(prob_dec, what), _check_supported(offset_dec, what), check_pointnet(pnet_model, what)
+        check_pointnet(pnet_model, what)
         if opt.roi_out_bbox != 2:
             raise RuntimeError("lidf_hip: %s is built for roi_out_bbox = 2" % what)
         self.refine = pnet_model_refine is not None
         if self.refine:
-            _check_supported(offset_dec_refine, what), check_pointnet(pnet_model_refine, what)
+            check_pointnet(pnet_model_refine, what)
+        # the decoders: the shipped gf_dim 64 (lidf_frame_f32), or gf_dim 32 / 64 / 128 each, one register-chained
+        # launch per decoder (lidf_frame_widths_f32) as soon as one of them is not the shipped width
+        decs = [prob_dec, offset_dec] + ([offset_dec_refine] if self.refine else [])
+        self.widths = bool(chain_route) or not all(is_shipped(m) for m in decs)
+        if self.widths:
+            for m in decs:
+                if not chain_ok(m):
+                    raise RuntimeError(
+                        "lidf_hip: FrameRunner takes decoders of gf_dim 32, 64 or 128 with the reference's layers "
+                        "4 gf -> 2 gf -> gf -> 1 (out_dim 1; LIDF_CHAIN16=0 switches their one-launch kernel off); got "
+                        "gf_dim=%d out_dim=%d. Use lidf_forward / refine_forward, which run other widths layer by layer"
+                        % (m.gf_dim, m.linear_4.out_features))
+            for bad, why in ((precision != "f32", "precision %r" % precision),
+                             (offsets != "all", "offsets=%r" % offsets), (bool(side_stream), "side_stream=True")):
+                if bad:
+                    raise RuntimeError("lidf_hip: FrameRunner: %s is built for the shipped widths (gf_dim 64 in all "
+                                       "three decoders); at gf_dim %s the frame runs f32, offsets='all', on the "
+                                       "caller's stream alone" % (why, "/".join(str(m.gf_dim) for m in decs)))
+            E = 3 + 6 * opt.multires
+            D1, D2 = 256 + 2 * E + 3 + 6 * opt.multires_views, 256 + E + 3 + 6 * opt.multires_views
+            for m, d in zip(decs, (D1, D1, D2)):
+                if m.inp_dim != d:
+                    raise RuntimeError("lidf_hip: FrameRunner: decoder inp_dim must be %d for this configuration "
+                                       "(got %d)" % (d, m.inp_dim))
+        if pe_slab is not None and int(pe_slab) < 1:
+            raise ValueError("pe_slab must be a positive number of pairs")
         # the widened grid of LIDF.get_occ_vox_bound (models/pipeline.py:167-173), in the reference's f32
         t32 = lambda v: torch.tensor(v, dtype=torch.float32)  # noqa: E731
         lo, hi = t32(opt.xmin), t32(opt.xmax)
@@ -565,6 +604,33 @@ class FrameRunner:
         self.profile_events = None                 # benchmarks: six hipEvent_t recorded around the matrix launches
         self.pack_blob = torch.empty((L.lidf_frame_pack_bytes(),), dtype=torch.uint8, device=dev)
         self.pack_guard = torch.zeros((L.lidf_frame_pack_guard_bytes(),), dtype=torch.uint8, device=dev)
+        self.wd = None
+        if self.widths:
+            # LidfFrameWidths: the runner's second workspace (layer-1 tables, the slab of embedding rows), the three
+            # chain streams and their fingerprints — owned here like pack_blob / pack_guard above. The bias rows
+            # (b1 + an IEF's W1[:, enc] benc) are formed by generic._bias_row inside every frame — captured with it —
+            # so that a row's bits are the stepwise path's
+            wd = _lib.LidfFrameWidths()
+            wd.prob_gf, wd.off_gf = int(prob_dec.gf_dim), int(offset_dec.gf_dim)
+            wd.refine_gf = int(offset_dec_refine.gf_dim) if self.refine else 0
+            wd.pe_slab_pairs = int(pe_slab) if pe_slab else 0
+            wwb = L.lidf_frame_widths_workspace_bytes(bs, h, w, res, self.max_pairs, self.times, opt.multires,
+                                                      opt.multires_views, C.byref(wd))
+            wpb = L.lidf_frame_widths_pack_bytes(opt.multires, opt.multires_views, C.byref(wd))
+            if not wwb or not wpb:
+                raise RuntimeError("lidf_hip: FrameRunner: multires %d / multires_views %d outside the frame's range"
+                                   % (opt.multires, opt.multires_views))
+            self.ws_widths = torch.empty((wwb,), dtype=torch.uint8, device=dev)
+            self.pack_blob_widths = torch.empty((wpb,), dtype=torch.uint8, device=dev)
+            self.pack_guard_widths = torch.zeros((L.lidf_frame_widths_pack_guard_bytes(),), dtype=torch.uint8,
+                                                 device=dev)
+            self.bias_rows = [torch.empty((4 * int(m.gf_dim),), **f32) for m in decs]
+            wd.workspace, wd.workspace_bytes = self.ws_widths.data_ptr(), wwb
+            wd.pack_blob, wd.pack_blob_bytes = self.pack_blob_widths.data_ptr(), wpb
+            wd.pack_guard = self.pack_guard_widths.data_ptr()
+            for name, t in zip(("prob_bias", "off_bias", "refine_bias"), self.bias_rows):
+                setattr(wd, name, t.data_ptr())
+            self.wd = wd
         self.vidx, self.n_valid_idx = None, 0      # explicit valid points (load(valid_idx=))
         # opt.valid_sample_num > 0: every frame starts with query.sample_valid_launch on the frame's valid mask,
         # straight into vidx (no sync; part of the captured graph) unless load() was handed an explicit valid_idx
@@ -720,7 +786,12 @@ class FrameRunner:
         a.pack_guard = self.pack_guard.data_ptr()
         a.pack_mode = 1 if guard else 2
         a.offsets_selected = int(self.offsets == "selected")
-        if self.side_mode or (self.side_mode is None and not torch.cuda.is_current_stream_capturing()):
+        if self.widths:   # the any-width route runs on the caller's stream alone; its bias rows are part of the frame
+            from .generic import _bias_row
+            if guard:   # (a trusted frame keeps the rows of the last validated one, as it keeps the streams)
+                for t, m in zip(self.bias_rows, (prob, off, off_r)):
+                    t.copy_(_bias_row(m))
+        elif self.side_mode or (self.side_mode is None and not torch.cuda.is_current_stream_capturing()):
             if self.side is None:   # the side stream and its two events exist only for runners that fork
                 with torch.cuda.device(self.dev):
                     self.side = (torch.cuda.Stream(self.dev), _lib.hip_event(), _lib.hip_event())
@@ -732,7 +803,11 @@ class FrameRunner:
             a.profile_events = C.cast(self._pev, C.POINTER(C.c_void_p))
         try:
             with torch.cuda.device(self.dev):
-                _lib.check(_lib.lib().lidf_frame_f32(C.byref(a), _lib.current_stream(self.dev)))
+                if self.widths:
+                    _lib.check(_lib.lib().lidf_frame_widths_f32(C.byref(a), C.byref(self.wd),
+                                                                _lib.current_stream(self.dev)))
+                else:
+                    _lib.check(_lib.lib().lidf_frame_f32(C.byref(a), _lib.current_stream(self.dev)))
         except RuntimeError:
             self._frames_since_guard = None   # (the library reset the fingerprints; validate again)
             raise

@@ -40,7 +40,8 @@ enum lidf_status {
  * lidf_topk_mean_f32 / lidf_stage1_hard_neg_f32 / lidf_refine_hard_neg_f32 with struct LidfTopkJob, and after
  * those the evaluation losses (struct LidfEvalLossArgs, lidf_stage1_eval_loss_f32 / lidf_refine_eval_loss_f32, their
  * workspace-size functions and lidf_stage1_eval_hard_neg_f32 / lidf_refine_eval_hard_neg_f32), and after those
- * lidf_miss_window_workspace_bytes / lidf_miss_ray_window_f32, were added
+ * lidf_miss_window_workspace_bytes / lidf_miss_ray_window_f32, and after those struct LidfFrameWidths with
+ * lidf_frame_widths_workspace_bytes / _pack_bytes / _pack_guard_bytes / lidf_frame_widths_f32, were added
  * WITHOUT a bump: they are purely additive (no signature or struct layout changed), so the number stays 14; a
  * binding that needs them looks the symbols up and asks for a rebuild when an ABI-14 library lacks them
  * (implicit_depth_amd/_lib.py does). */
@@ -54,7 +55,7 @@ const char* lidf_strerror(int status);
  * Weights are nn.Linear storage, row-major [out,in], borrowed (never cached across calls:
  * parameters change every optimizer step). Hidden widths are fixed to gf_dim=64
  * (256 -> 128 -> 64 -> 1), the value of every shipped config, for every entry point but
- * lidf_decoder_chain_f32 (gf_dim 32 / 64 / 128: the array shapes below scale with gf_dim); any
+ * lidf_decoder_chain_f32 and lidf_frame_widths_f32 (gf_dim 32 / 64 / 128: the array shapes below scale with gf_dim); any
  * other width runs layer by layer through lidf_linear_f32 (below).
  */
 typedef struct LidfDecoder {
@@ -682,6 +683,67 @@ int lidf_frame_f32(const LidfFrameArgs* args, lidf_stream_t stream);
 int lidf_event_create(void** out);
 int lidf_event_destroy(void* event);
 
+/* ---- The same frame with decoders of gf_dim 32 / 64 / 128 (entries added under ABI 14) -----------------------
+ * lidf_frame_widths_f32 runs the frame of lidf_frame_f32 — valid points, occupied voxels, PointNet, miss rays,
+ * pairs, query, refine_times x refine, depth maps; device-side list lengths, no host round trip, capturable —
+ * when prob / off / off_refine are IMNet or IEF decoders of gf_dim 32, 64 or 128 each (layers 4 gf -> 2 gf -> gf
+ * -> 1, any n_iter, either output activation; the three may differ): every decoder is ONE register-chained
+ * launch (lidf_decoder_chain_f32's kernel) per slab of pairs / per refine iteration. The feature widths are the
+ * shipped ones (feat_grid 32 channels, RoI 2 x 2, PointNet 6 -> 32 -> 128). 64 / 64 / 64 is accepted and runs the
+ * chain route too (the A/B of the two routes at one width).
+ *
+ * LidfFrameArgs keeps its meaning. Not read on this route: packed_query, packed_refine and the decoder parts of
+ * its pack_blob. Its PointNet streams (pnet->packed / the PointNet slots of pack_blob with guards 1 and 2 of
+ * pack_guard), pack_mode, fail_after, max_pairs, lds_voxels, valid_idx_*, both position types and
+ * refine_use_all_pix behave as in lidf_frame_f32. LIDF_ERR_UNSUPPORTED: precision != LIDF_PRECISION_F32,
+ * offsets_selected != 0, a side stream (aux_stream / ev_fork / ev_join non-NULL: this route runs on `stream`
+ * alone), a gf other than 32 / 64 / 128.
+ *
+ * Sequence behind the PointNet (steps 0-4 are lidf_frame_f32's): per-ray features (RoIAlign samples summed in the
+ * reference's order, without the box-sum image — the bits of lidf_roi_align_f32 / lidf_embed_f32); per decoder
+ * the three layer-1 table launches of the stepwise path (voxpart [C, 4 gf] with b1 (+ the IEF constant), the ROI
+ * columns, the direction columns added onto them: raypart [N, 4 gf]); then ceil(max_pairs / slab) slabs of
+ * [one position-embedding launch into a [slab, 2E] buffer + one chain launch per decoder, straight into
+ * pred_prob / pred_offset], each reading counts[LIDF_FC_PAIRS] and working on clamp(P - p0, 0, slab) rows; pair
+ * positions; per-ray softmax / arg-max / select / depth. Stage 2 per iteration: the per-ray launch, the PointNet
+ * (four launches), voxpart_r [C, 4 gf] (one linear launch), one chain launch on the embed(pos) columns with
+ * end_voxel_id as the voxel index and the per-frame raypart_r [N, 4 gf] row r. No element of an index array
+ * (pair_ray, pair_vox, end_voxel_id, ...) at or beyond its device-side count is dereferenced; rows beyond a
+ * count may be left unwritten.
+ *
+ *   prob_gf / off_gf / refine_gf  gf_dim of prob / off / off_refine (refine_gf ignored when refine_times == 0)
+ *   pe_slab_pairs   pairs per slab of embedding rows; 0 = LIDF_FRAME_PE_SLAB. Slab boundaries do not change a bit.
+ *   workspace       lidf_frame_widths_workspace_bytes(...) bytes beside LidfFrameArgs.workspace; any contents
+ *   pack_blob       lidf_frame_widths_pack_bytes(...) bytes: the three chain streams. pack_mode GUARDED: one more
+ *                   fingerprint launch over the three decoders' parameters into pack_guard
+ *                   (lidf_frame_widths_pack_guard_bytes() bytes, zero-filled by the caller once) + three early-exit
+ *                   packs; TRUSTED: as the last GUARDED call left it; CALLER: packed by every call, unchecked.
+ *   prob_bias / off_bias / refine_bias   optional [4 gf] each: the decoder's layer-1 bias row b1 (+ an IEF's
+ *                   W1[:, enc columns] benc) formed by the caller — a binding that wants the row's bits to equal
+ *                   its own stepwise path's (torch's matrix-vector product) passes it; NULL: the library forms it
+ *                   (one small launch per IEF, summed j = 0..15 with fused multiply-adds).                         */
+#define LIDF_FRAME_PE_SLAB 614400
+typedef struct LidfFrameWidths {
+    int32_t prob_gf, off_gf, refine_gf;
+    int64_t pe_slab_pairs;
+    void* workspace;
+    size_t workspace_bytes;
+    void* pack_blob;
+    size_t pack_blob_bytes;
+    void* pack_guard;
+    const float* prob_bias;
+    const float* off_bias;
+    const float* refine_bias;
+} LidfFrameWidths;
+/* 0 for arguments the entry would refuse (a gf outside 32 / 64 / 128, non-positive sizes, multires outside the
+ * frame's range). */
+size_t lidf_frame_widths_workspace_bytes(int32_t batch, int32_t height, int32_t width, const int32_t* res,
+                                         int64_t max_pairs, int32_t refine_times, int32_t multires,
+                                         int32_t multires_views, const LidfFrameWidths* wd);
+size_t lidf_frame_widths_pack_bytes(int32_t multires, int32_t multires_views, const LidfFrameWidths* wd);
+size_t lidf_frame_widths_pack_guard_bytes(void);
+int lidf_frame_widths_f32(const LidfFrameArgs* args, const LidfFrameWidths* wd, lidf_stream_t stream);
+
 /* ---- One linear layer of any width ------------------------------------------------------------
  * out[r, 0:nout] = act( x[r, 0:k] . w[0:nout, 0:k]^T + b  (+ addrows[addidx[r], 0:nout]) ), torch.nn.Linear's
  * weight layout ([nout, k], row stride ldw), through the same f32 matrix-instruction kernel the fixed-width
@@ -808,6 +870,8 @@ int lidf_depth_metrics_f32(const float* pred_depth, const float* gt_depth, const
  * x must be readable up to column 16 ceil(k / 16) of its LAST row (the kernel reads whole 16-column groups and
  * masks what lies beyond k). prepacked != 0: the workspace still holds the weight stream an earlier call packed
  * for this decoder, k and w1_col0 (the slabs of one query; parameters unchanged in between) — no pack launch.
+ * voxpart and raypart must be 16-byte aligned (their rows are loaded as aligned 16-byte pieces; a row is a
+ * multiple of 16 bytes): LIDF_ERR_BAD_ARG otherwise, before any HIP call.
  * Other widths: LIDF_ERR_UNSUPPORTED (the layers run one by one, lidf_linear_f32).                             */
 size_t lidf_decoder_chain_workspace_bytes(int32_t gf_dim, int32_t k);
 int lidf_decoder_chain_f32(const LidfDecoder* dec, int32_t gf_dim, int32_t inp_dim, const float* x, int64_t ldx,
