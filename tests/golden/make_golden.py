@@ -48,8 +48,8 @@ from util import closed_form, closed_form_params, closed_form_pointnet  # noqa: 
 
 
 def _stub(name, **attrs):
-    m = types.ModuleType(name)
-    m.__dict__.update(attrs)
+    m = sys.modules.get(name) or types.ModuleType(name)   # (installed twice: the same module objects, which the
+    m.__dict__.update(attrs)                              # reference's modules already hold, get the stubs again)
     sys.modules[name] = m
     return m
 
@@ -215,6 +215,13 @@ def g3_pipeline():
     D = lidf.prob_dec.inp_dim
     lidf.prob_dec.load_state_dict(closed_form_params("IMNET", D, seed=21))
     lidf.offset_dec.load_state_dict(closed_form_params("IEF", D, seed=22))
+    batch, (B, h, w) = g3_batch()
+    g3_trace(lidf, opt, batch, B, h, w, dev, pl, Params, cfg)
+
+
+def g3_batch():
+    """The two-frame 16 x 24 batch of g3 / g4 / g7 (and of g14, make_golden_widths.py): two slanted planes seen by two
+    pinhole cameras, a rectangular hole in each frame."""
     B, h, w = 2, 16, 24
     fx = torch.tensor([21.6, 20.0], dtype=torch.float64)
     fy = torch.tensor([21.6, 22.0], dtype=torch.float64)
@@ -235,6 +242,10 @@ def g3_pipeline():
         "corrupt_mask": hole.clone(), "valid_mask": 1 - hole,
         "fx": fx, "fy": fy, "cx": cx, "cy": cy, "item_path": ["a", "b"],
     }
+    return batch, (B, h, w)
+
+
+def g3_trace(lidf, opt, batch, B, h, w, dev, pl, Params, cfg):
     cap = {}
     hk = lidf.pnet_model.register_forward_hook(lambda m, i, o: cap.__setitem__("occ_voxel_feat", o.detach().clone()))
     with torch.no_grad():

@@ -42,8 +42,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
 from make_golden import REF, closed_form_params, closed_form_pointnet, install_stubs, orc  # noqa: E402
-from make_golden_train import (FixedFeatures, MISS_SAMPLE_NUM, PARAM_STRIDE, find_face, make_batch, save_npz,  # noqa: E402
-                               strided, topk_gap)
+from make_golden_train import (FixedFeatures, MISS_SAMPLE_NUM, PARAM_STRIDE, apply_overrides,  # noqa: E402
+                               differentiable_roi_align, find_face, load_stage1, make_batch, save_npz, strided, topk_gap)
 
 EPOCH = 0
 PNET_REFINE_SEED = 43
@@ -56,8 +56,17 @@ LOSS_KEYS = ("pos_loss", "prob_loss", "surf_norm_loss", "smooth_loss", "loss_net
 REFINE_LOSS_KEYS = ("pos_loss", "surf_norm_loss", "smooth_loss", "loss_net", "err", "angle_err")
 
 
-def build(stage1_seeds, refine_seed, loss):
-    """The reference's LIDF and RefineNet with train_refine.yaml and closed-form weights; stage 1 frozen."""
+def load_refine(refine, seeds, factor=1.0):
+    """Closed-form weights at the widths the options give the two stage-2 modules; seeds = (offset_dec, pnet_model)."""
+    r = refine.opt.refine
+    refine.offset_dec.load_state_dict(closed_form_params(r.offdec_type, refine.offset_dec.inp_dim, seed=seeds[0],
+                                                         gf=r.imnet_gf, factor=factor))
+    refine.pnet_model.load_state_dict(closed_form_pointnet(seeds[1], cin=r.pnet_in, out=r.pnet_out, gf=r.pnet_gf))
+
+
+def build(stage1_seeds, refine_seed, loss, overrides=None):
+    """The reference's LIDF and RefineNet with train_refine.yaml (+ overrides: make_golden_train.apply_overrides) and
+    closed-form weights; stage 1 frozen."""
     import models.pipeline as pl
     from opt import Params
     cfg = os.path.join(REF, "experiments", "implicit_depth")
@@ -69,19 +78,16 @@ def build(stage1_seeds, refine_seed, loss):
     opt.grid.miss_sample_num = MISS_SAMPLE_NUM
     for k, v in loss.items():
         setattr(opt.loss, k, v)
+    apply_overrides(opt, overrides)
     assert opt.model.maxpool_label_epo == 0 and opt.refine.perturb and opt.refine.perturb_prob == 0.8
     torch.manual_seed(1234)
     dev = torch.device("cpu")
     lidf = pl.LIDF(opt, dev).eval()
-    D = lidf.prob_dec.inp_dim
-    lidf.prob_dec.load_state_dict(closed_form_params("IMNET", D, seed=stage1_seeds[0]))
-    lidf.offset_dec.load_state_dict(closed_form_params("IEF", D, seed=stage1_seeds[1]))
-    lidf.pnet_model.load_state_dict(closed_form_pointnet(stage1_seeds[2]))
+    load_stage1(lidf, stage1_seeds)
     for p in lidf.parameters():   # trainers/train_refine.py:71-73
         p.requires_grad = False
     refine = pl.RefineNet(opt, dev).eval()
-    refine.offset_dec.load_state_dict(closed_form_params("IEF", refine.offset_dec.inp_dim, seed=refine_seed))
-    refine.pnet_model.load_state_dict(closed_form_pointnet(PNET_REFINE_SEED))
+    load_refine(refine, (refine_seed, PNET_REFINE_SEED))
     return pl, lidf, refine, opt
 
 
@@ -219,38 +225,43 @@ def np_seeds(lidf, batch, feat):
     raise SystemExit("g10: no numpy seed pair")
 
 
-def generate(verbose=True):
+def g9_sources(g9, overrides=None):
+    """Stage-1 settings (shift, face, full_rgb_feat, (prob_dec, offset_dec, pnet_model) seeds) to try: the stored
+    stage-1 fixture's own first, then its weights and features on other depth shifts."""
+    s1 = tuple(int(v) for v in g9["seeds"])
+    feat = torch.from_numpy(np.asarray(g9["full_rgb_feat"])).clone()
+    f = g9["face_ray"]
+    yield float(g9["depth_shift"]), (int(f[0]), int(f[1]), int(f[2]), int(f[3]), float(f[4])), feat, s1
+    for shift in (0.0, 0.003, 0.007, -0.004, 0.011, -0.009, 0.014, -0.013):
+        if abs(shift - float(g9["depth_shift"])) > 1e-9:
+            face = find_face(build(s1, 31, {}, overrides)[1], shift)
+            if face is not None:
+                yield shift, face, feat, s1
+
+
+def generate(verbose=True, overrides=None, cases=CASES, sources=None, tag="g10"):
+    """sources: an iterable like g9_sources' (default: from g9_train_step.npz)."""
     torch.set_num_threads(1)
     torch.use_deterministic_algorithms(True)
     install_stubs()
-    sys.modules["torchvision.ops"].roi_align = \
-        lambda inp, boxes, output_size, spatial_scale=1.0, sampling_ratio=-1, aligned=False: orc.roi_align_fast(inp, boxes)
-    g9 = np.load(os.path.join(HERE, "g9_train_step.npz"))
-    s1 = tuple(int(v) for v in g9["seeds"])
-    shifts = [float(g9["depth_shift"])] + [v for v in (0.0, 0.003, 0.007, -0.004, 0.011, -0.009, 0.014, -0.013)
-                                            if abs(v - float(g9["depth_shift"])) > 1e-9]
-    for shift in shifts:
-        pl, lidf, _, _ = build(s1, 31, {})
-        if shift == float(g9["depth_shift"]):
-            f = g9["face_ray"]
-            face = (int(f[0]), int(f[1]), int(f[2]), int(f[3]), float(f[4]))
-        else:
-            face = find_face(lidf, shift)
-            if face is None:
-                continue
+    differentiable_roi_align()
+    if sources is None:
+        sources = g9_sources(np.load(os.path.join(HERE, "g9_train_step.npz")))
+    for shift, face, feat, s1 in sources:
+        pl, lidf, _, _ = build(s1, 31, {}, overrides)
         batch = make_batch(shift, face)
-        feat = torch.from_numpy(g9["full_rgb_feat"]).clone()
         seed_p, seed_n = np_seeds(lidf, batch, feat)
         if verbose:
-            print("g10: shift %g: numpy seeds %d (perturbed) / %d (not)" % (shift, seed_p, seed_n))
+            print("%s: shift %g: numpy seeds %d (perturbed) / %d (not)" % (tag, shift, seed_p, seed_n))
         why = {}
-        pl, lidf, refine, _ = build(s1, 31, {})
+        pl, lidf, refine, _ = build(s1, 31, {}, overrides)
         starts = []
-        for perturbed, np_seed in ((True, seed_p), (False, seed_n)):   # (stage 1 does not depend on the stage-2 seed)
+        wanted = sorted({c[1] for c in cases}, reverse=True)   # (the starts the cases use: perturbed, unperturbed)
+        for perturbed, np_seed in ((p, seed_p if p else seed_n) for p in wanted):   # (stage 1 does not depend on the stage-2 seed)
             dd, _ = stage1(lidf, batch, feat, np_seed)
             starts.append((perturbed, dd, np.random.get_state()))
         for rseed in range(31, 6000):
-            refine.offset_dec.load_state_dict(closed_form_params("IEF", refine.offset_dec.inp_dim, seed=rseed))
+            load_refine(refine, (rseed, PNET_REFINE_SEED))
             ok = True
             for perturbed, dd, state in starts:
                 np.random.set_state(state)
@@ -266,10 +277,10 @@ def generate(verbose=True):
                 break
         else:
             if verbose:
-                print("g10: shift %g rejected: %s" % (shift, why))
+                print("%s: shift %g rejected: %s" % (tag, shift, why))
             continue
         if verbose:
-            print("g10: stage-2 decoder seed %d (rejections on the way: %s)" % (rseed, why))
+            print("%s: stage-2 decoder seed %d (rejections on the way: %s)" % (tag, rseed, why))
         main = {"seeds_stage1": np.array(s1), "seeds_refine": np.array((rseed, PNET_REFINE_SEED)),
                 "np_seed_perturbed": np.int64(seed_p), "np_seed_unperturbed": np.int64(seed_n),
                 "depth_shift": np.float32(shift), "miss_sample_num": np.int64(MISS_SAMPLE_NUM),
@@ -278,8 +289,8 @@ def generate(verbose=True):
             main["batch_" + k] = batch[k].numpy()
         main["intr"] = torch.stack([batch[k].float() for k in ("fx", "fy", "cx", "cy")], 1).numpy()
         params = {}
-        for name, perturbed, loss_kw in CASES:
-            pl, lidf, refine, opt = build(s1, rseed, loss_kw)
+        for name, perturbed, loss_kw in cases:
+            pl, lidf, refine, opt = build(s1, rseed, loss_kw, overrides)
             np_seed = seed_p if perturbed else seed_n
             dd, loss1 = stage1(lidf, batch, feat, np_seed)
             checks = {}
@@ -303,11 +314,11 @@ def generate(verbose=True):
                 for k, p in getattr(refine, mod).named_parameters():
                     params["%s_g_%s.%s" % (name, mod, k)] = strided(p.grad).numpy().copy()
             if verbose:
-                print("g10 %s: R=%d P=%d noise=%s loss_net=%.6f min|preact|=%.3g (PointNet %.3g)" % (
-                    name, dd["total_miss_sample_num"], dd["miss_ray_intersect_idx"].shape[0], checks["noise"],
+                print("%s %s: R=%d P=%d noise=%s loss_net=%.6f min|preact|=%.3g (PointNet %.3g)" % (
+                    tag, name, dd["total_miss_sample_num"], dd["miss_ray_intersect_idx"].shape[0], checks["noise"],
                     float(loss["loss_net"].detach()), checks["min_preact"], checks["min_preact_pnet"]))
         return main, params
-    raise SystemExit("g10: no configuration satisfies the conditions")
+    raise SystemExit("%s: no configuration satisfies the conditions" % tag)
 
 
 def write(main, params):

@@ -90,8 +90,33 @@ class FixedFeatures(torch.nn.Module):
 PNET_SEED = 41
 
 
-def build(seeds, hard_neg):
-    """The reference's LIDF with train_lidf.yaml and closed-form weights; seeds = (prob_dec, offset_dec)."""
+def apply_overrides(opt, overrides):
+    """overrides: {"model.imnet_gf": 32, "refine.pnet_pos_type": "abs", ...} set on the reference's Params (a
+    stage-1 yaml has no refine section: those entries do not apply to it)."""
+    for path, value in (overrides or {}).items():
+        node = opt
+        *parents, leaf = path.split(".")
+        if not hasattr(opt, parents[0]):
+            continue
+        for name in parents:
+            node = getattr(node, name)
+        assert hasattr(node, leaf), path
+        setattr(node, leaf, value)
+
+
+def load_stage1(lidf, seeds, factor=1.0):
+    """Closed-form weights at the widths the options give the three stage-1 modules; seeds = (prob_dec, offset_dec,
+    pnet_model). factor: closed_form_params' factor for the two decoders."""
+    m = lidf.opt.model
+    D = lidf.prob_dec.inp_dim
+    lidf.prob_dec.load_state_dict(closed_form_params("IMNET", D, seed=seeds[0], gf=m.imnet_gf, factor=factor))
+    lidf.offset_dec.load_state_dict(closed_form_params(m.offdec_type, D, seed=seeds[1], gf=m.imnet_gf, factor=factor))
+    lidf.pnet_model.load_state_dict(closed_form_pointnet(seeds[2], cin=m.pnet_in, out=m.pnet_out, gf=m.pnet_gf))
+
+
+def build(seeds, hard_neg, overrides=None):
+    """The reference's LIDF with train_lidf.yaml (+ overrides, see apply_overrides) and closed-form weights;
+    seeds = (prob_dec, offset_dec)."""
     import models.pipeline as pl
     from opt import Params
     cfg = os.path.join(REF, "experiments", "implicit_depth")
@@ -101,12 +126,10 @@ def build(seeds, hard_neg):
     opt.grid.valid_sample_num = -1
     opt.grid.miss_sample_num = MISS_SAMPLE_NUM
     opt.loss.hard_neg, opt.loss.hard_neg_ratio = hard_neg, 0.1
+    apply_overrides(opt, overrides)
     torch.manual_seed(1234)
     lidf = pl.LIDF(opt, torch.device("cpu")).eval()
-    D = lidf.prob_dec.inp_dim
-    lidf.prob_dec.load_state_dict(closed_form_params("IMNET", D, seed=seeds[0]))
-    lidf.offset_dec.load_state_dict(closed_form_params("IEF", D, seed=seeds[1]))
-    lidf.pnet_model.load_state_dict(closed_form_pointnet(PNET_SEED))
+    load_stage1(lidf, (seeds[0], seeds[1], PNET_SEED))
     return lidf, opt
 
 
@@ -272,12 +295,12 @@ def decoder_seeds(lidf, batch, feat):
     ray, R = dd["miss_ray_intersect_idx"], dd["total_miss_sample_num"]
     D = lidf.prob_dec.inp_dim
     found = []
-    for net, kind in ((lidf.prob_dec, "IMNET"), (lidf.offset_dec, "IEF")):
+    for net, kind in ((lidf.prob_dec, "IMNET"), (lidf.offset_dec, lidf.opt.model.offdec_type)):
         pre = []
         hooks = [m.register_forward_hook(lambda mod, i, o: pre.append(o.abs().min().item()))
                  for m in (net.linear_1, net.linear_2, net.linear_3)]
         for seed in range(21, 6000):
-            net.load_state_dict(closed_form_params(kind, D, seed=seed))
+            net.load_state_dict(closed_form_params(kind, D, seed=seed, gf=lidf.opt.model.imnet_gf))
             del pre[:]
             with torch.no_grad():
                 out = net(rows)
@@ -302,16 +325,22 @@ def strided(t):
     return t[::PARAM_STRIDE] if t.numel() > 4096 else t
 
 
-def generate(verbose=True):
-    torch.set_num_threads(1)   # (the scatter-adds of the backward sum in thread order: one thread, one order)
-    torch.use_deterministic_algorithms(True)
-    install_stubs()
-    # the stub RoIAlign of make_golden.py is a numpy loop without a graph: the oracle's torch form of the same
-    # operator (equal to float rounding, tests/test_oracle_props.py) lets the gradient reach full_rgb_feat
-    sys.modules["torchvision.ops"].roi_align = \
-        lambda inp, boxes, output_size, spatial_scale=1.0, sampling_ratio=-1, aligned=False: orc.roi_align_fast(inp, boxes)
+def differentiable_roi_align():
+    """The stub RoIAlign of make_golden.py is a numpy loop without a graph: the oracle's torch form of the same
+    operator (equal to float rounding, tests/test_oracle_props.py) lets the gradient reach full_rgb_feat. That form
+    is built for 2 x 2 bins; another roi_out_bbox takes its any-size counterpart, tests/roi_ref.py."""
+    from roi_ref import roi_align_torch
+
+    def roi_align(inp, boxes, output_size, spatial_scale=1.0, sampling_ratio=-1, aligned=False):
+        return orc.roi_align_fast(inp, boxes) if output_size == 2 else roi_align_torch(inp, boxes, output_size)
+    sys.modules["torchvision.ops"].roi_align = roi_align
+
+
+def candidates(overrides=None, verbose=True, tag="g9"):
+    """(shift, face, batch, full_rgb_feat, decoder seeds) per depth shift for which a face ray exists: the geometry
+    and the decoder weights of a stage-1 step at the widths of `overrides`, before the step's own conditions."""
     for shift in (0.0, 0.003, 0.007, -0.004, 0.011, -0.009, 0.014, -0.013, 0.018, 0.021):
-        probe = build((21, 22), False)[0]
+        probe = build((21, 22), False, overrides)[0]
         face = find_face(probe, shift)
         if face is None:
             continue
@@ -320,7 +349,20 @@ def generate(verbose=True):
             feat = probe.resnet_model(batch["rgb"]).detach().clone()
         seeds = decoder_seeds(probe, batch, feat)
         if verbose:
-            print("g9: shift %g: face ray (frame, y, x, axis, value) = %s, decoder seeds %s" % (shift, face, seeds))
+            print("%s: shift %g: face ray (frame, y, x, axis, value) = %s, decoder seeds %s" % (tag, shift, face, seeds))
+        yield shift, face, batch, feat, seeds
+
+
+def setup():
+    torch.set_num_threads(1)   # (the scatter-adds of the backward sum in thread order: one thread, one order)
+    torch.use_deterministic_algorithms(True)
+    install_stubs()
+    differentiable_roi_align()
+
+
+def generate(verbose=True, overrides=None, cases=CASES, tag="g9"):
+    setup()
+    for shift, face, batch, feat, seeds in candidates(overrides, verbose, tag):
         main = {"seeds": np.array(seeds + (PNET_SEED,)), "np_seed": np.int64(NP_SEED),
                 "depth_shift": np.float32(shift), "miss_sample_num": np.int64(MISS_SAMPLE_NUM),
                 "face_ray": np.array(face, dtype=np.float64), "param_stride": np.int64(PARAM_STRIDE),
@@ -329,8 +371,8 @@ def generate(verbose=True):
             main["batch_" + k] = batch[k].numpy()
         main["intr"] = torch.stack([batch[k].float() for k in ("fx", "fy", "cx", "cy")], 1).numpy()
         params, bad = {}, []
-        for name, epoch, hard_neg in CASES:
-            lidf, opt = build(seeds, hard_neg)
+        for name, epoch, hard_neg in cases:
+            lidf, opt = build(seeds, hard_neg, overrides)
             checks = {"face": face}
             dd, loss, g_feat = run_case(lidf, batch, feat, epoch, checks)
             bad += ["%s: %s" % (name, b) for b in conditions(dd, opt, epoch, hard_neg, checks)]
@@ -352,14 +394,14 @@ def generate(verbose=True):
                 for k, p in getattr(lidf, mod).named_parameters():
                     params["%s_g_%s.%s" % (name, mod, k)] = strided(p.grad).numpy().copy()
             if verbose:
-                print("g9 %s: R=%d P=%d labels=%d loss_net=%.6f min|preact|=%.3g (PointNet %.3g)" % (
-                    name, dd["total_miss_sample_num"], dd["pcl_label"].shape[0], int(dd["pcl_label"].sum()),
+                print("%s %s: R=%d P=%d labels=%d loss_net=%.6f min|preact|=%.3g (PointNet %.3g)" % (
+                    tag, name, dd["total_miss_sample_num"], dd["pcl_label"].shape[0], int(dd["pcl_label"].sum()),
                     float(loss["loss_net"]), checks["min_preact"], checks["min_preact_pnet"]))
         if not bad:
             return main, params
         if verbose:
-            print("g9: shift %g rejected: %s" % (shift, "; ".join(bad[:4])))
-    raise SystemExit("g9: no configuration satisfies the conditions")
+            print("%s: shift %g rejected: %s" % (tag, shift, "; ".join(bad[:4])))
+    raise SystemExit("%s: no configuration satisfies the conditions" % tag)
 
 
 def save_npz(path, arrays):

@@ -13,13 +13,13 @@ from oracle import lidf_oracle as orc  # noqa: E402  (the checker; never used by
 TOL = 1e-4  # north_star: outputs within 1e-4 fp32 of the reference decoder
 
 
-def make_module(kind, params, inp_dim, device, n_iter=2, use_sigmoid=False):
+def make_module(kind, params, inp_dim, device, n_iter=2, use_sigmoid=False, gf=64):
     """Product module (implicit_depth_amd.decoders) carrying the oracle's parameters."""
     from implicit_depth_amd import IEF, IMNet
     if kind == "IEF":
-        m = IEF(device, inp_dim, 1, 64, n_iter=n_iter, use_sigmoid=use_sigmoid)
+        m = IEF(device, inp_dim, 1, gf, n_iter=n_iter, use_sigmoid=use_sigmoid)
     else:
-        m = IMNet(inp_dim, 1, 64, use_sigmoid=use_sigmoid)
+        m = IMNet(inp_dim, 1, gf, use_sigmoid=use_sigmoid)
     m.load_state_dict({k: v.clone() for k, v in params.items()})
     return m.to(device).eval()
 
@@ -63,8 +63,10 @@ def closed_form(shape, a, b, amp):
     return (amp * torch.sin(i * a + b)).float().reshape(shape)
 
 
-def closed_form_params(kind, inp_dim, seed, gf=64):
-    """State dict with reference parameter names, weights ~ amplitude 0.14 (std 0.1), biases 0.05."""
+def closed_form_params(kind, inp_dim, seed, gf=64, factor=1.0):
+    """State dict with reference parameter names, weights ~ amplitude 0.14 (std 0.1), biases 0.05. factor: the
+    linear_* weights (not the biases, not offset_enc) times it, in float32 — at amplitude 0.14 the decoders' outputs
+    stay on one branch of the output clamp (tests/golden/make_golden_widths.py searches a factor per case)."""
     dims = [("linear_1", inp_dim + (16 if kind == "IEF" else 0), 4 * gf), ("linear_2", 4 * gf, 2 * gf),
             ("linear_3", 2 * gf, gf), ("linear_4", gf, 1)]
     p = {}
@@ -73,14 +75,16 @@ def closed_form_params(kind, inp_dim, seed, gf=64):
         p["offset_enc.bias"] = closed_form((16,), 1.3, seed + 0.7, 0.1)
     for j, (name, din, dout) in enumerate(dims):
         p[name + ".weight"] = closed_form((dout, din), 0.6180339887 + 0.01 * j, seed + j, 0.14)
+        if factor != 1.0:
+            p[name + ".weight"] = p[name + ".weight"] * torch.tensor(factor, dtype=torch.float32)
         p[name + ".bias"] = closed_form((dout,), 0.7236067977, seed + 10 + j, 0.05)
     return p
 
 
-def closed_form_pointnet(seed):
-    """PointNet2Stage(6, 128, 32) state dict from the closed-form filler."""
-    shapes = {"point_lin1": (32, 6), "point_lin2": (64, 32), "vox_lin1": (64, 64),
-              "point_lin3": (128, 128), "point_lin4": (128, 128), "vox_lin2": (128, 128)}
+def closed_form_pointnet(seed, cin=6, out=128, gf=32):
+    """PointNet2Stage(cin, out, gf) state dict from the closed-form filler (default: the shipped 6 / 128 / 32)."""
+    shapes = {"point_lin1": (gf, cin), "point_lin2": (out // 2, gf), "vox_lin1": (out // 2, out // 2),
+              "point_lin3": (out, out), "point_lin4": (out, out), "vox_lin2": (out, out)}
     p = {}
     for j, (name, (dout, din)) in enumerate(shapes.items()):
         amp = 1.4 / (din ** 0.5)
@@ -89,9 +93,9 @@ def closed_form_pointnet(seed):
     return p
 
 
-def make_pointnet(params, device):
+def make_pointnet(params, device, out=128, gf=32):
     from implicit_depth_amd import PointNet2Stage
-    m = PointNet2Stage(input_channels=6, output_channels=128, gf_dim=32)
+    m = PointNet2Stage(input_channels=params["point_lin1.weight"].shape[1], output_channels=out, gf_dim=gf)
     m.load_state_dict({k: v.clone() for k, v in params.items()})
     return m.to(device).eval()
 
