@@ -2270,16 +2270,28 @@ static size_t chain16_stream_bytes(int gf, int k) {
     const int G = gf / 16;
     return (size_t)(((k + 15) / 16) * 4 * G + lidf_chain16_pass_quads(G)) * 1024;
 }
-LIDF_API size_t lidf_decoder_chain_workspace_bytes(int32_t gf_dim, int32_t k) {
+// (split: the f16x3 form — lidf_chain16_h.hip's stream, padded to that kernel's ring)
+static size_t chain16_any_stream_bytes(int gf, int k, bool split) {
+    if (!split) return chain16_stream_bytes(gf, k);
+    const int G = gf / 16;
+    return (size_t)(lidf_chain16h_l1_quads(G, k) + lidf_chain16h_pass_quads(G)) * 1024;
+}
+static size_t decoder_chain_workspace_bytes(int32_t gf_dim, int32_t k, bool split) {
     if ((gf_dim != 32 && gf_dim != 64 && gf_dim != 128) || k <= 0 || k > (1 << 16)) return 0;
-    return align_up(chain16_stream_bytes(gf_dim, k), 256) + align_up((size_t)lidf_chain16_aux_floats(gf_dim / 16) * 4, 256);
+    return align_up(chain16_any_stream_bytes(gf_dim, k, split), 256) +
+           align_up((size_t)lidf_chain16_aux_floats(gf_dim / 16) * 4, 256);
+}
+LIDF_API size_t lidf_decoder_chain_workspace_bytes(int32_t gf_dim, int32_t k) {
+    return decoder_chain_workspace_bytes(gf_dim, k, false);
+}
+LIDF_API size_t lidf_decoder_chain_split_workspace_bytes(int32_t gf_dim, int32_t k) {
+    return decoder_chain_workspace_bytes(gf_dim, k, true);
 }
 
-LIDF_API int lidf_decoder_chain_f32(const LidfDecoder* dec, int32_t gf_dim, int32_t inp_dim, const float* x,
-                                      int64_t ldx, int32_t k, int32_t w1_col0, int64_t n, const float* voxpart,
-                                      const int32_t* vox_idx, const float* raypart, const int32_t* ray_idx,
-                                      float* out, int32_t prepacked, void* workspace, size_t workspace_bytes,
-                                      lidf_stream_t stream) {
+static int decoder_chain_impl(const LidfDecoder* dec, int32_t gf_dim, int32_t inp_dim, const float* x, int64_t ldx,
+                              int32_t k, int32_t w1_col0, int64_t n, const float* voxpart, const int32_t* vox_idx,
+                              const float* raypart, const int32_t* ray_idx, float* out, int32_t prepacked,
+                              void* workspace, size_t workspace_bytes, lidf_stream_t stream, bool split) {
     if (!dec || n < 0 || k <= 0 || ldx < k || inp_dim <= 0 || w1_col0 < 0 || w1_col0 + k > inp_dim)
         return LIDF_ERR_BAD_ARG;
     if (gf_dim != 32 && gf_dim != 64 && gf_dim != 128) return LIDF_ERR_UNSUPPORTED;
@@ -2290,17 +2302,18 @@ LIDF_API int lidf_decoder_chain_f32(const LidfDecoder* dec, int32_t gf_dim, int3
     // (the kernel loads the table rows as aligned 16-byte pieces; a row is 256 gf_dim / 16 bytes)
     if (((uintptr_t)voxpart | (uintptr_t)raypart) & 15) return LIDF_ERR_BAD_ARG;
     if (k > (1 << 16)) return LIDF_ERR_UNSUPPORTED;
-    const size_t need = lidf_decoder_chain_workspace_bytes(gf_dim, k);
+    const size_t need = decoder_chain_workspace_bytes(gf_dim, k, split);
     if (!workspace || workspace_bytes < need) return LIDF_ERR_WORKSPACE;
     int rc, cus;
     if ((rc = cu_count(&cus))) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int G = gf_dim / 16;
+    const size_t sbytes = chain16_any_stream_bytes(gf_dim, k, split);
     float* sbuf = (float*)workspace;
-    float* aux = (float*)((char*)workspace + align_up(chain16_stream_bytes(gf_dim, k), 256));
+    float* aux = (float*)((char*)workspace + align_up(sbytes, 256));
     StreamLayout lay = {};
-    lay.nets = 1; lay.mode = LIDF_MODE_CHAIN16;
-    lay.total = (int)(chain16_stream_bytes(gf_dim, k) / 4);
+    lay.nets = 1; lay.mode = split ? LIDF_MODE_CHAIN16_H : LIDF_MODE_CHAIN16;
+    lay.total = (int)(sbytes / 4);
     L1Map m = {};
     m.n0 = k; m.c0 = w1_col0; m.nt = G;
     const NetW nw = to_netw(dec, inp_dim);
@@ -2314,8 +2327,26 @@ LIDF_API int lidf_decoder_chain_f32(const LidfDecoder* dec, int32_t gf_dim, int3
     a.init = dec->is_ief ? dec->init_offset : 0.f;
     a.sigmoid = dec->use_sigmoid;
     a.out = out;
-    CHECK_HIP(lidf_launch_chain16(gf_dim, a, cus, st));
+    CHECK_HIP(split ? lidf_launch_chain16h(gf_dim, a, cus, st) : lidf_launch_chain16(gf_dim, a, cus, st));
     return LIDF_OK;
+}
+
+LIDF_API int lidf_decoder_chain_f32(const LidfDecoder* dec, int32_t gf_dim, int32_t inp_dim, const float* x,
+                                      int64_t ldx, int32_t k, int32_t w1_col0, int64_t n, const float* voxpart,
+                                      const int32_t* vox_idx, const float* raypart, const int32_t* ray_idx,
+                                      float* out, int32_t prepacked, void* workspace, size_t workspace_bytes,
+                                      lidf_stream_t stream) {
+    return decoder_chain_impl(dec, gf_dim, inp_dim, x, ldx, k, w1_col0, n, voxpart, vox_idx, raypart, ray_idx, out,
+                              prepacked, workspace, workspace_bytes, stream, false);
+}
+
+LIDF_API int lidf_decoder_chain_split_f32(const LidfDecoder* dec, int32_t gf_dim, int32_t inp_dim, const float* x,
+                                            int64_t ldx, int32_t k, int32_t w1_col0, int64_t n, const float* voxpart,
+                                            const int32_t* vox_idx, const float* raypart, const int32_t* ray_idx,
+                                            float* out, int32_t prepacked, void* workspace, size_t workspace_bytes,
+                                            lidf_stream_t stream) {
+    return decoder_chain_impl(dec, gf_dim, inp_dim, x, ldx, k, w1_col0, n, voxpart, vox_idx, raypart, ray_idx, out,
+                              prepacked, workspace, workspace_bytes, stream, true);
 }
 
 // ---- the frame with decoders of gf_dim 32 / 64 / 128 (lidf_frame_widths_f32) ---------------------------------

@@ -77,7 +77,8 @@ enum { LIDF_MODE_FUSED = 0, LIDF_MODE_ROWS = 1, LIDF_MODE_L1ONLY = 2, LIDF_MODE_
        LIDF_MODE_PNET_CHAIN = 7,     // pack jobs only: the per-point chain stream of a PointNet2Stage (PN_* below)
        LIDF_MODE_IEF16 = 8,          // pack jobs only: the stage-2 decoder's 16 x 16 x 4 stream (lidf_ief16.hip)
        LIDF_MODE_PNET_BWD = 9,       // pack jobs only: the backward chains' stream of a PointNet2Stage (PNB_* below)
-       LIDF_MODE_CHAIN16 = 10 };     // the any-width decoder chain's stream (lidf_chain16.hip; L1Map.nt = gf / 16)
+       LIDF_MODE_CHAIN16 = 10,       // the any-width decoder chain's stream (lidf_chain16.hip; L1Map.nt = gf / 16)
+       LIDF_MODE_CHAIN16_H = 11 };   // its split-f16 form (lidf_chain16_h.hip): every weight as its two f16 pieces
 #define IEF16_PASS_QUADS 168   // 2 + 1 bias quads, 4 u quads, 128 layer-2 quads, 32 layer-3 quads, 1 padding quad
 #define IEF16_AUX_FLOATS 72    // w4 [64] | b4 [1] (+ padding)
 
@@ -508,6 +509,15 @@ static inline int lidf_chain16_pass_quads(int G) {
     return (raw + 7) / 8 * 8;
 }
 static inline int lidf_chain16_aux_floats(int G) { return 16 * G + 8; }
+// the split-f16 chain (lidf_chain16_h.hip): weight quads in flight per wavefront (a divisor of 8 G), the pass
+// section padded to it, and the layer-1 section of k columns (pairs of 16-column groups, two quads per output tile)
+static inline int lidf_chain16h_ring(int G) { return G >= 4 ? 16 : 8; }
+static inline int lidf_chain16h_l1_quads(int G, int k) { return ((k + 15) / 16 + 1) / 2 * 8 * G; }
+static inline int lidf_chain16h_pass_quads(int G) {
+    const int T1 = 4 * G, T2 = 2 * G, T3 = G, ring = lidf_chain16h_ring(G);
+    const int raw = (T2 + 3) / 4 + T1 * T2 + T1 / 4 + (T3 + 3) / 4 + T2 * T3;
+    return (raw + ring - 1) / ring * ring;
+}
 
 // Arguments of the two-layer per-voxel kernel (lidf_linear.hip: lidf_vox2_kernel).
 struct Vox2Args {

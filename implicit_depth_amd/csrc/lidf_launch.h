@@ -322,6 +322,7 @@ hipError_t lidf_launch_ief16(const Ief16Args& a, int cus, hipStream_t st);
 
 // ---- lidf_chain16.hip
 hipError_t lidf_launch_chain16(int gf, const Chain16Args& a, int cus, hipStream_t st);
+hipError_t lidf_launch_chain16h(int gf, const Chain16Args& a, int cus, hipStream_t st);   // lidf_chain16_h.hip
 hipError_t lidf_launch_chain16_bias_row(const float* b1, const float* w1enc, int ld1, const float* benc, int nout,
                                         float* out, hipStream_t st);
 }  // extern "C"

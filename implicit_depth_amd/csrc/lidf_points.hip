@@ -212,6 +212,58 @@ __device__ float chain16_stream_value(const NetW& n, const L1Map& m, int e) {
     return 0.f;
 }
 
+// element e of the split-f16 chain's stream (layout: lidf_chain16_h.hip): the sections of chain16_stream_value, the
+// weights as f16 pieces for the 16 x 16 x 32 instruction. Input tiles (layer 1: 16-column k-groups) go in pairs
+// (T, T + 1); per pair and output tile To two quads, the high pieces and the low pieces; dword c of lane (j, g) holds
+// the weights of row 16 To + j at features 4 g + 2 (c & 1) + {0, 1} of tile T + (c >> 1). wh = f16(w) (round to
+// nearest even), wl = f16(w - wh) (w - wh is exact in f32), subnormal pieces kept. Bias, u and padding quads are f32.
+__device__ float chain16h_pieces(float w0, float w1, int lo) {
+    typedef _Float16 h2p __attribute__((ext_vector_type(2)));
+    const _Float16 h0 = (_Float16)w0, h1 = (_Float16)w1;
+    const h2p pk = {lo ? (_Float16)(w0 - (float)h0) : h0, lo ? (_Float16)(w1 - (float)h1) : h1};
+    return __builtin_bit_cast(float, pk);
+}
+__device__ float chain16h_stream_value(const NetW& n, const L1Map& m, int e) {
+    const int G = m.nt, T1 = 4 * G, T2 = 2 * G, T3 = G;
+    const int KP = ((m.n0 + 15) / 16 + 1) / 2;
+    int quad = e / 256;
+    const int lane = (e % 256) / 4, c = e & 3;
+    const int j = lane & 15, g = lane >> 4;
+    const int f0 = 16 * (c >> 1) + 4 * g + 2 * (c & 1);   // first of the dword's two features, from the pair's tile 0
+    if (quad < KP * 2 * T1) {
+        const int kp = quad / (2 * T1), To = (quad % (2 * T1)) / 2, x = 32 * kp + f0;
+        const float* w = n.w1 + (size_t)(16 * To + j) * n.ld1 + m.c0;
+        return chain16h_pieces(x < m.n0 ? w[x] : 0.f, x + 1 < m.n0 ? w[x + 1] : 0.f, quad & 1);
+    }
+    quad -= KP * 2 * T1;
+    const int NB2 = (T2 + 3) / 4, NB3 = (T3 + 3) / 4;
+    if (quad < NB2) {
+        const int tile = 4 * quad + c;
+        return (g == 0 && tile < T2) ? n.b2[16 * tile + j] : 0.f;
+    }
+    quad -= NB2;
+    const int blk_len = 1 + 4 * T2;   // a u quad in front of every fourth input tile, 2 T2 quads per input-tile pair
+    if (quad < (T1 / 4) * blk_len) {
+        const int blk = quad / blk_len, in = quad % blk_len;
+        if (in == 0) return (g == 0 && n.is_ief) ? ief_u(n, 16 * (4 * blk + c) + j) : 0.f;
+        const int pair = (in - 1) / (2 * T2), To = ((in - 1) % (2 * T2)) / 2;
+        const float* w = n.w2 + (size_t)(16 * To + j) * (64 * G) + 16 * (4 * blk + 2 * pair) + f0;
+        return chain16h_pieces(w[0], w[1], (in - 1) & 1);
+    }
+    quad -= (T1 / 4) * blk_len;
+    if (quad < NB3) {
+        const int tile = 4 * quad + c;
+        return (g == 0 && tile < T3) ? n.b3[16 * tile + j] : 0.f;
+    }
+    quad -= NB3;
+    if (quad < T2 * T3) {
+        const int pair = quad / (2 * T3), To = (quad % (2 * T3)) / 2;
+        const float* w = n.w3 + (size_t)(16 * To + j) * (32 * G) + 32 * pair + f0;
+        return chain16h_pieces(w[0], w[1], quad & 1);
+    }
+    return 0.f;
+}
+
 __device__ __forceinline__ void pack_body(const StreamLayout& lay, const NetW& net0, const NetW& net1,
                                           const L1Map& m, float* stream, float* aux) {
     if (lay.guard && lay.guard->dirty == 0) return;   // guarded packing: fingerprint unchanged
@@ -233,9 +285,10 @@ __device__ __forceinline__ void pack_body(const StreamLayout& lay, const NetW& n
             aux[e] = e < 64 ? net0.w4[e] : (e == 64 ? net0.b4[0] : 0.f);
         return;
     }
-    if (lay.mode == LIDF_MODE_CHAIN16) {
+    if (lay.mode == LIDF_MODE_CHAIN16 || lay.mode == LIDF_MODE_CHAIN16_H) {
         const int gf = 16 * m.nt;
-        if (e < lay.total) stream[e] = chain16_stream_value(net0, m, e);
+        if (e < lay.total)
+            stream[e] = lay.mode == LIDF_MODE_CHAIN16 ? chain16_stream_value(net0, m, e) : chain16h_stream_value(net0, m, e);
         if (e < gf + 8) aux[e] = e < gf ? net0.w4[e] : (e == gf ? net0.b4[0] : 0.f);
         return;
     }

@@ -198,7 +198,7 @@ def _check_supported(mod, what="this entry"):
 def decoders_forward(inp_feat, prob_dec=None, offset_dec=None, precision="f32"):
     """Run one or both decoders on a materialised [n, D] input through liblidf_hip
     (lidf_decoders_f32; precision="f16x3": lidf_decoders_split_f32, the split-f16 products of
-    lidf_query). Returns (pred_prob or None, pred_offset or None), each [n,1]."""
+    lidf_query; decoders of gf_dim 32 / 128: lidf_decoder_chain_split_f32). Returns (pred_prob or None, pred_offset or None), each [n,1]."""
     if precision not in ("f32", "f16x3"):
         raise ValueError("precision must be 'f32' or 'f16x3'")
     if prob_dec is None and offset_dec is None:
@@ -215,12 +215,11 @@ def decoders_forward(inp_feat, prob_dec=None, offset_dec=None, precision="f32"):
         if m is not None and m.inp_dim != d:
             raise RuntimeError("decoder inp_dim %d != input width %d" % (m.inp_dim, d))
     if any(m is not None and not is_shipped(m) for m in (prob_dec, offset_dec)):
-        # widths other than the shipped ones: layer by layer (generic.py), f32 only
-        if precision != "f32":
-            raise RuntimeError("precision %r is built for gf_dim=64, out_dim=1" % precision)
+        # widths other than the shipped ones: generic.py — the one-launch chain (either precision) or layer by layer
+        # (f32 only; generic.split_refusal states why)
         from . import generic
-        return (generic.decoder_forward(prob_dec, x) if prob_dec is not None else None,
-                generic.decoder_forward(offset_dec, x) if offset_dec is not None else None)
+        return (generic.decoder_forward(prob_dec, x, precision) if prob_dec is not None else None,
+                generic.decoder_forward(offset_dec, x, precision) if offset_dec is not None else None)
     if prob_dec is not None:
         dp = _decoder_struct(prob_dec, keep)
     if offset_dec is not None:

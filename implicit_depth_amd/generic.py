@@ -22,6 +22,9 @@ Round 6: a decoder of gf_dim 32, 64 or 128 with a 1-wide head runs its inference
 (lidf_decoder_chain_f32, csrc/lidf_chain16.hip: 16-row sub-tiles of the 16 x 16 x 4 matrix instruction, activations
 in registers from layer 1 to the output) instead of one launch per layer and pass — the query and decoder_forward
 take it; LIDF_CHAIN16=0 keeps the layer-by-layer path (A/B, and the definition the chain is tested against).
+precision="f16x3" exists in that launch only (lidf_decoder_chain_split_f32, csrc/lidf_chain16_h.hip: the products of
+layers 1-3 on f16 pieces): decoder_chain, decoder_forward, query and refine take it and refuse, with the reason, a
+decoder the chain is not built for (split_refusal).
 
 Nothing here is used when the widths are the shipped ones.
 """
@@ -42,6 +45,31 @@ def chain_ok(mod):
             and mod.linear_3.out_features == gf and mod.linear_4.out_features == 1)
 
 
+def split_refusal(mod):
+    """Why precision "f16x3" does not take this decoder at a configuration other than the shipped one (the split-f16
+    products exist in the one-launch chain only: lidf_decoder_chain_split_f32), or None when it does."""
+    if chain_ok(mod):
+        return None
+    if os.environ.get("LIDF_CHAIN16", "1") == "0":
+        return ("LIDF_CHAIN16=0 switches the one-launch decoder chain off, and precision 'f16x3' at other widths "
+                "exists in that chain only (there is no layer-by-layer split path)")
+    if mod.linear_4.out_features != 1:
+        return ("precision 'f16x3' takes decoders with a 1-wide head (the chain's 4 gf -> 2 gf -> gf -> 1); got "
+                "out_dim=%d" % mod.linear_4.out_features)
+    return ("precision 'f16x3' is built for gf_dim 32 / 64 / 128 (the one-launch decoder chain; there is no "
+            "layer-by-layer split path); got gf_dim=%d" % int(mod.gf_dim))
+
+
+def _check_precision(precision, *mods):
+    if precision not in ("f32", "f16x3"):
+        raise ValueError("precision must be 'f32' or 'f16x3'")
+    if precision == "f16x3":
+        for mod in mods:
+            why = split_refusal(mod)
+            if why:
+                raise RuntimeError(why)
+
+
 def _bias_row(mod):
     """b1 (+ the IEF's constant W1[:, enc columns] benc) as the one-row voxpart table of a chain launch."""
     from .decoders import IEF
@@ -53,14 +81,18 @@ def _bias_row(mod):
 
 
 def decoder_chain(mod, x, k, w1_col0=0, voxpart=None, vox_idx=None, raypart=None, ray_idx=None, out=None,
-                  padded=False, packed=None):
+                  padded=False, packed=None, precision="f32"):
     """The whole decoder on per-row operand columns x[:, :k] (they multiply W1[:, w1_col0 : w1_col0 + k]) plus two
     gathered table rows — lidf_decoder_chain_f32. voxpart must carry b1 (+ the IEF constant: _bias_row). padded: x's
     buffer is readable up to column 16 ceil(k / 16) of its last row (otherwise the trailing rows go through a
     padded copy). packed: a dict the caller keeps over the slabs of one query — the first call leaves its workspace
-    (the packed weight stream) there, the later ones skip the pack launch. Returns [n, 1]."""
+    (the packed weight stream) there, the later ones skip the pack launch; the state is kept per precision (the two
+    streams differ). precision "f16x3": lidf_decoder_chain_split_f32 — the products of layers 1-3 on f16 pieces, the
+    tables, biases, the IEF's rank-1 term and layer 4 in f32. Returns [n, 1]."""
     from .decoders import _decoder_struct
     import ctypes as C
+    _check_precision(precision, mod)
+    split = precision == "f16x3"
     n = x.shape[0]
     dev = x.device
     if out is None:
@@ -73,8 +105,9 @@ def decoder_chain(mod, x, k, w1_col0=0, voxpart=None, vox_idx=None, raypart=None
     kq16 = (k + 15) // 16 * 16
     L = _lib.lib()
     gf = int(mod.gf_dim)
-    wsb = L.lidf_decoder_chain_workspace_bytes(gf, k)
-    state = packed if packed is not None else {}
+    wsb = (L.lidf_decoder_chain_split_workspace_bytes if split else L.lidf_decoder_chain_workspace_bytes)(gf, k)
+    entry = L.lidf_decoder_chain_split_f32 if split else L.lidf_decoder_chain_f32
+    state = packed.setdefault(precision, {}) if packed is not None else {}
     ws = state.get("ws")
     if ws is None:
         ws = state["ws"] = _lib.workspace(wsb, dev)
@@ -84,7 +117,7 @@ def decoder_chain(mod, x, k, w1_col0=0, voxpart=None, vox_idx=None, raypart=None
 
     def run(xs, ld, rows, o, vi, ri, rp):
         with torch.cuda.device(dev):
-            _lib.check(L.lidf_decoder_chain_f32(
+            _lib.check(entry(
                 C.byref(dec), gf, int(mod.inp_dim), _lib.ptr(xs), ld, k, w1_col0, rows, _lib.ptr(voxpart), _lib.ptr(vi),
                 _lib.ptr(rp), _lib.ptr(ri), _lib.ptr(o), state["ready"], _lib.ptr(ws), wsb,
                 _lib.current_stream(dev)))
@@ -189,16 +222,17 @@ def _decoder_from_layer1(mod, n, dev, layer1):
     return _out_act(mod, off)
 
 
-def decoder_forward(mod, x):
+def decoder_forward(mod, x, precision="f32"):
     """IMNet.forward / IEF.forward (models/implicit_net.py:81-98 / :131-152) at any gf_dim / out_dim
-    on [n, inp_dim] rows."""
+    on [n, inp_dim] rows. precision "f16x3": the split chain (chain_ok decoders only)."""
+    _check_precision(precision, mod)
     x = x.detach()
     n, d = x.shape
     if d != mod.inp_dim:
         raise RuntimeError("decoder inp_dim %d != input width %d" % (mod.inp_dim, d))
     l1 = mod.linear_1
     if chain_ok(mod):   # one launch: every input column is a per-row operand, the bias a one-row table
-        return decoder_chain(mod, x, d, voxpart=_bias_row(mod).reshape(1, -1).contiguous())
+        return decoder_chain(mod, x, d, voxpart=_bias_row(mod).reshape(1, -1).contiguous(), precision=precision)
     return _decoder_from_layer1(
         mod, n, x.device,
         lambda act: linear_hip(x, l1.weight, l1.bias, act=1 if act else 0, slope=0.02 if act else 0.0, k=d))
@@ -248,13 +282,15 @@ CHAIN_SLAB_FACTOR = 16
 
 def query(ray_dir, ray_pix, ray_bid, pair_off, pair_ray, pair_vox, pair_t, feat_grid, vox_feat, prob_dec,
           offset_dec, multires, multires_views, roi_inp_bbox, roi_out_bbox, offset_range, part_size,
-          vox_center, pos_rel, ray_flat, depth, want_rayfeat):
+          vox_center, pos_rel, ray_flat, depth, want_rayfeat, precision="f32"):
     """get_embedding + get_pred (models/pipeline.py:338-466) at widths other than the shipped ones:
     the decoder input rows are materialised as the reference does ([P, pnet_out + rgb_out * roi^2 +
     2E + Ed]) and the decoders run layer by layer. The pieces: lidf_roi_align_f32, lidf_embed_f32,
     lidf_pe_rows_f32, lidf_linear_f32 per layer, lidf_query_tail_f32 (pair positions, per-ray softmax /
-    arg-max, select); gathers and the concat are torch indexing on the device."""
+    arg-max, select); gathers and the concat are torch indexing on the device. precision "f16x3": the slabs run the
+    split chain (lidf_decoder_chain_split_f32, both decoders chain_ok); the layer-1 tables stay exact f32."""
     from .decoders import get_embedder
+    _check_precision(precision, prob_dec, offset_dec)
     dev = ray_dir.device
     R, P = ray_dir.shape[0], pair_ray.shape[0]
     E = 3 + 6 * multires
@@ -315,7 +351,7 @@ def query(ray_dir, ray_pix, ray_bid, pair_off, pair_ray, pair_vox, pair_t, feat_
             w1 = dec.linear_1.weight
             if chained:   # the whole decoder in one launch, straight into its slab of the output
                 decoder_chain(dec, pe, 2 * E, w1_col0=Cv + Cr, voxpart=voxpart, vox_idx=pv_i, raypart=raypart,
-                              ray_idx=pr_i, out=dst[p0:p1], padded=True, packed=pk)
+                              ray_idx=pr_i, out=dst[p0:p1], padded=True, packed=pk, precision=precision)
                 continue
 
             def layer1(act, w1=w1, voxpart=voxpart, raypart=raypart):
@@ -344,14 +380,17 @@ def query(ray_dir, ray_pix, ray_bid, pair_off, pair_ray, pair_vox, pair_t, feat_
 
 def refine(ray_dir, ray_pix, ray_bid, ray_flat, pred_pos, max_pair_id, pair_vox, voxel_bound, voxel_bid, rgb_img,
            feat_grid, valid_inp, valid_vox, pnet_model, offset_dec, forward_times, multires, multires_views,
-           roi_inp_bbox, roi_out_bbox, offset_range, pos_rel, pnet_pos_rel, ray_rgb, pnet_select):
+           roi_inp_bbox, roi_out_bbox, offset_range, pos_rel, pnet_pos_rel, ray_rgb, pnet_select, precision="f32"):
     """forward_times x RefineNet.get_pred_refine (models/pipeline.py:922-1030, eval flavour) at widths other
     than the shipped ones, step by step as the reference writes it: the end voxel of every ray
     (lidf_pcl_aabb_last_f32 over the arg-max pair's voxel), the PointNet over valid + predicted points,
     the decoder rows [R, pnet_out + rgb_out * roi^2 + E + Ed], the decoder, the offset along the ray. The
-    modules run through their own forward (layer by layer where a width differs)."""
-    from .decoders import get_embedder
+    modules run through their own forward (layer by layer where a width differs). precision "f16x3": the decoder
+    goes through decoders_forward(rows, offset_dec=..., precision=...), the PointNet stays f32."""
+    from .decoders import decoders_forward, get_embedder
     from .extensions import pcl_aabb
+    if precision not in ("f32", "f16x3"):
+        raise ValueError("precision must be 'f32' or 'f16x3'")
     dev = ray_dir.device
     R, P, V = ray_dir.shape[0], pair_vox.shape[0], voxel_bound.shape[0]
     hw = rgb_img.shape[2] * rgb_img.shape[3]
@@ -381,7 +420,8 @@ def refine(ray_dir, ray_pix, ray_bid, ray_flat, pred_pos, max_pair_id, pair_vox,
         occ = pnet_model(pn_inp.contiguous(), pn_vox.int(), n_vox=V)
         enter = (cur - center) if pos_rel else cur
         rows = torch.cat((occ[end], ray_rgb, embed(enter.contiguous()), edir), 1)
-        off = offset_dec(rows)
+        off = offset_dec(rows) if precision == "f32" else decoders_forward(rows, offset_dec=offset_dec,
+                                                                           precision=precision)[1]
         cur = (cur + (off * (offset_range[1] - offset_range[0]) + offset_range[0]) * ray_dir).contiguous()
     return cur, end_voxel
 

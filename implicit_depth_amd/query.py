@@ -489,8 +489,8 @@ def lidf_query(ray_dir, ray_pix, ray_bid, pair_off, pair_ray, pair_vox, pair_t, 
     as NaN); about half the matrix work on a real frame.
 
     Widths other than the shipped configuration (feat_grid channels != 32, roi_out_bbox != 2, vox_feat
-    width != 128, decoders with gf_dim != 64): the same function layer by layer on materialised rows
-    (generic.query; f32 only).
+    width != 128, decoders with gf_dim != 64): generic.query — the one-launch decoder chain at gf_dim 32 / 64 /
+    128 (either precision), layer by layer otherwise (f32 only).
 
     precision: "f32" (default) or "f16x3" — the decoders' matrix products evaluated as three
     f16-piece products per term with f32 accumulation (f32-level accuracy, see lidf_hip.h).
@@ -546,14 +546,15 @@ def lidf_query(ray_dir, ray_pix, ray_bid, pair_off, pair_ray, pair_vox, pair_t, 
         raise RuntimeError("pair_ray / pair_vox / pair_t must be [P] / [P] / [P,2]")
 
     if not shipped:
-        if precision != "f32":
-            raise RuntimeError("precision %r is built for the shipped widths" % precision)
+        # (precision "f16x3": the one-launch decoder chain of gf_dim 32 / 64 / 128 in its split-f16 form;
+        # generic.query refuses any other decoder with the reason)
         if offsets != "all":
             raise RuntimeError("offsets='selected' is built for the shipped widths")
         from . import generic
         return generic.query(ray_dir, ray_pix, ray_bid, pair_off, pair_ray, pair_vox, pair_t, feat_grid, vox_feat,
                              prob_dec, offset_dec, multires, multires_views, roi_inp_bbox, roi_out_bbox,
-                             offset_range, part_size, vox_center, pos_rel, ray_flat, depth, want_rayfeat)
+                             offset_range, part_size, vox_center, pos_rel, ray_flat, depth, want_rayfeat,
+                             precision=precision)
     f32 = dict(dtype=torch.float32, device=dev)
     out = {
         "pred_offset": torch.empty((P, 1), **f32),
@@ -686,9 +687,8 @@ def lidf_refine(ray_dir, ray_pix, ray_bid, ray_flat, pred_pos, max_pair_id, pair
     if offset_dec.inp_dim != D:
         raise RuntimeError("refine offset_dec inp_dim must be %d" % D)
     if not (is_shipped(offset_dec) and pnet_shipped(pnet_model) and feat_grid.shape[1] == 32 and roi_out_bbox == 2):
-        # widths other than the shipped ones: step by step through the modules (generic.refine), f32 only
-        if precision != "f32":
-            raise RuntimeError("precision %r is built for the shipped widths" % precision)
+        # widths other than the shipped ones: step by step through the modules (generic.refine); precision "f16x3"
+        # runs the decoder through decoders_forward's split routes, the PointNet stays f32
         if valid_inp.dim() != 2 or valid_inp.shape[1] != pnet_model.input_channels:
             raise RuntimeError("valid_inp must be [Nv,%d]" % pnet_model.input_channels)
         from . import generic
@@ -700,7 +700,8 @@ def lidf_refine(ray_dir, ray_pix, ray_bid, ray_flat, pred_pos, max_pair_id, pair
         return generic.refine(ray_dir, _as_i32(ray_pix, "ray_pix"), ray_bid, ray_flat, pred_pos, max_pair_id,
                               pair_vox, voxel_bound, voxel_bid, rgb_img, feat_grid, valid_inp, valid_vox,
                               pnet_model, offset_dec, forward_times, multires, multires_views, roi_inp_bbox,
-                              roi_out_bbox, offset_range, pos_rel, pnet_pos_rel, ray_rgb, pnet_select)
+                              roi_out_bbox, offset_range, pos_rel, pnet_pos_rel, ray_rgb, pnet_select,
+                              precision=precision)
     dev = ray_dir.device
     R, P, V, Nv = ray_dir.shape[0], pair_vox.shape[0], voxel_bound.shape[0], valid_inp.shape[0]
     B, _, h, w = rgb_img.shape

@@ -41,7 +41,8 @@ enum lidf_status {
  * those the evaluation losses (struct LidfEvalLossArgs, lidf_stage1_eval_loss_f32 / lidf_refine_eval_loss_f32, their
  * workspace-size functions and lidf_stage1_eval_hard_neg_f32 / lidf_refine_eval_hard_neg_f32), and after those
  * lidf_miss_window_workspace_bytes / lidf_miss_ray_window_f32, and after those struct LidfFrameWidths with
- * lidf_frame_widths_workspace_bytes / _pack_bytes / _pack_guard_bytes / lidf_frame_widths_f32, were added
+ * lidf_frame_widths_workspace_bytes / _pack_bytes / _pack_guard_bytes / lidf_frame_widths_f32, and after those
+ * lidf_decoder_chain_split_workspace_bytes / lidf_decoder_chain_split_f32, were added
  * WITHOUT a bump: they are purely additive (no signature or struct layout changed), so the number stays 14; a
  * binding that needs them looks the symbols up and asks for a rebuild when an ABI-14 library lacks them
  * (implicit_depth_amd/_lib.py does). */
@@ -878,6 +879,22 @@ int lidf_decoder_chain_f32(const LidfDecoder* dec, int32_t gf_dim, int32_t inp_d
                            int32_t k, int32_t w1_col0, int64_t n, const float* voxpart, const int32_t* vox_idx,
                            const float* raypart, const int32_t* ray_idx, float* out, int32_t prepacked,
                            void* workspace, size_t workspace_bytes, lidf_stream_t stream);
+
+/* ---- The same launch in split-f16 precision ("f16x3"; added under ABI 14 without a bump) ------------------------
+ * lidf_decoder_chain_f32's arguments, checks, error codes, prepacked semantics and workspace layout (its own size
+ * function: the stream's padding differs; a workspace packed by one entry is not the other's). Every product of
+ * layer 1 (the per-row columns x W1[:, w1_col0 : w1_col0 + k]^T), layer 2 and layer 3 is evaluated as
+ *     wh * xh + wh * xl + wl * xh      with  wh = f16(w), wl = f16(w - wh), xh = f16(x), xl = f16(x - xh)
+ * on the f16 matrix instruction with f32 accumulation; wl * xl is dropped, f16 subnormal pieces are kept.
+ * Accuracy contract: the relative error of a product is <= 2^-22 as long as |x| and every activation stay below
+ * the f16 range, |value| < 65504 (beyond it a high piece is infinite). What stays f32: the voxpart / raypart rows
+ * and their sum, the biases of layers 2 and 3, the IEF's rank-1 term u * offset (u = W1[:, enc columns] wenc),
+ * layer 4, the running offset and the output activation.                                                        */
+size_t lidf_decoder_chain_split_workspace_bytes(int32_t gf_dim, int32_t k);
+int lidf_decoder_chain_split_f32(const LidfDecoder* dec, int32_t gf_dim, int32_t inp_dim, const float* x,
+                                 int64_t ldx, int32_t k, int32_t w1_col0, int64_t n, const float* voxpart,
+                                 const int32_t* vox_idx, const float* raypart, const int32_t* ray_idx, float* out,
+                                 int32_t prepacked, void* workspace, size_t workspace_bytes, lidf_stream_t stream);
 
 /* ---- Decoders, training path (first step) -------------------------------------
  * What autograd does for models/implicit_net.py IMNet / IEF on [n, d] rows: a forward that keeps
