@@ -329,7 +329,7 @@ static QueryWs query_ws(int64_t R, int64_t V, int L, int Lv, int64_t grid_floats
     w.stream_vox = o; o += align_up((size_t)f32.lv.total * 4, 256);
     w.stream_ray = o; o += align_up(ray, 256);
     w.packed_end = o;
-    w.counter = o;    o += 256;  // tile hand-out counter of the split-f16 kernel
+    w.counter = o;    o += 256;  // tile hand-out counters of the split-f16 kernel ([1]: its launch on the selected list)
     w.voxpart = o;    o += align_up((size_t)(V > 0 ? V : 1) * 512 * 4, 256);
     w.raypart = o;    o += align_up((size_t)(R > 0 ? R : 1) * 512 * 4, 256);
     w.rayfeat = o;    o += align_up((size_t)(R > 0 ? R : 1) * (128 + f32.Ed) * 4, 256);
@@ -529,7 +529,8 @@ static SelList sel_list(char* sb, int64_t R) {
     return {(int*)sb, (int*)(sb + Rc * 4), (float*)(sb + Rc * 8), (float*)(sb + Rc * 16), (float*)(sb + Rc * 20)};
 }
 // offset_dec on that list: the second net of the two-net stream and tables `base` launches, over R points
-// (static split: R / 32 wave-tiles). base's n_dev and kept activations are the caller's to replace.
+// (f32: static split, R / 32 wave-tiles; split-f16: the caller gives the launch a counter of its own). base's
+// n_dev and kept activations are the caller's to replace.
 static PointsArgs offset_on_list(const PointsArgs& base, const QueryPlan& p, const LidfDecoder* off,
                                  const SelList& s, int64_t R) {
     PointsArgs ao = base;
@@ -570,7 +571,6 @@ static int query_impl(const LidfQueryArgs* q, void* ev_points_begin, void* ev_po
     hipStream_t st = (hipStream_t)stream;
     const int L = q->multires, Lv = q->multires_views;
 
-    if (q->offsets_selected && q->precision != LIDF_PRECISION_F32) return LIDF_ERR_UNSUPPORTED;
     if (R == 0) return LIDF_OK;  // nothing to write (pipeline.py:686-687 early exit)
     if (!q->ray_dir || !q->ray_pix || !q->ray_bid || !q->pair_off) return LIDF_ERR_BAD_ARG;
     if (q->depth && !q->ray_flat) return LIDF_ERR_BAD_ARG;
@@ -635,26 +635,34 @@ static int query_impl(const LidfQueryArgs* q, void* ev_points_begin, void* ev_po
             a.pair_pred_pos = q->pair_pred_pos;
             a.tile_counter = (int*)(ws + w.counter);   // dynamic tile hand-out of both kernels
             // (the frame path zeroes the counter with its other scratch, in one launch up front)
-            if (!dims) CHECK_HIP(hipMemsetAsync(a.tile_counter, 0, 4, st));
+            // ([1]: the split-f16 launch on the selected list)
+            if (!dims) CHECK_HIP(hipMemsetAsync(a.tile_counter, 0, 8, st));
 #ifdef LIDF_PROFILE
             a.out_base = rayfeat;  // development only: phase timers land in the rayfeat scratch
 #endif
             long long nt = (P + 127) / 128;
             if (ev_points_begin) CHECK_HIP(hipEventRecord((hipEvent_t)ev_points_begin, st));
-            if (p.split) {
-                CHECK_HIP(lidf_launch_points_h(a, cus, st));
-            } else if (!q->offsets_selected) {
-                CHECK_HIP(lidf_launch_points(LIDF_MODE_FUSED, a, (int)(nt < cus ? nt : cus), st));
+            if (!q->offsets_selected) {
+                if (p.split)
+                    CHECK_HIP(lidf_launch_points_h(a, cus, st));
+                else
+                    CHECK_HIP(lidf_launch_points(LIDF_MODE_FUSED, a, (int)(nt < cus ? nt : cus), st));
             } else {
                 // Offsets for the selected pairs only (LidfQueryArgs.offsets_selected): prob_dec on every pair
                 // (ONE net of the two-net stream and tables), the per-ray softmax / arg-max — which also leaves
                 // the selected pair of every ray as a one-pair-per-ray list —, offset_dec on that list (R
                 // points instead of P), then positions / depth / the selected pairs' slots of the per-pair arrays.
+                // Split-f16: the same sequence on lidf_points_h_kernel — its one-net form, whose prob bits are the
+                // two-net launch's (a net's arithmetic does not see the other net), then its list form, where every
+                // row gathers its own ray's row and so depends on no neighbour.
                 if (!q->max_pair_id) return LIDF_ERR_BAD_ARG;
                 PointsArgs ap = a;
                 ap.nets = 1; ap.part_ld = 512; ap.part_off = 0;
                 ap.out[1] = nullptr; ap.is_offset[0] = 0; ap.pair_pred_pos = nullptr;
-                CHECK_HIP(lidf_launch_points(LIDF_MODE_FUSED, ap, (int)(nt < cus ? nt : cus), st));
+                if (p.split)
+                    CHECK_HIP(lidf_launch_points_h(ap, cus, st));
+                else
+                    CHECK_HIP(lidf_launch_points(LIDF_MODE_FUSED, ap, (int)(nt < cus ? nt : cus), st));
                 const SelList s = sel_list(ws + w.sel, R);
                 CHECK_HIP(lidf_launch_ray_reduce_dev(q->pred_prob, nullptr, q->pair_off, R, P, dims,
                                                      dims ? dims + 1 : nullptr, q->ray_bid, q->ray_flat,
@@ -664,7 +672,12 @@ static int query_impl(const LidfQueryArgs* q, void* ev_points_begin, void* ev_po
                 PointsArgs ao = offset_on_list(a, p, q->off, s, R);
                 ao.n_dev = dims;   // (dims[0] = R)
                 const long long ntr = (R + 127) / 128;
-                CHECK_HIP(lidf_launch_points(LIDF_MODE_FUSED, ao, (int)(ntr < cus ? ntr : cus), st));
+                if (p.split) {
+                    ao.tile_counter = a.tile_counter + 1;
+                    CHECK_HIP(lidf_launch_points_h_list(ao, cus, st));
+                } else {
+                    CHECK_HIP(lidf_launch_points(LIDF_MODE_FUSED, ao, (int)(ntr < cus ? ntr : cus), st));
+                }
                 CHECK_HIP(lidf_launch_selected_finish((const long long*)q->max_pair_id, s.off, s.pos, R, P, dims,
                                                       dims ? dims + 1 : nullptr, q->ray_bid, q->ray_flat,
                                                       (long long)q->height * q->width, q->pred_offset,
@@ -1752,7 +1765,7 @@ static int frame_impl(const LidfFrameArgs* a_in, lidf_stream_t stream, ForkState
 
     // 0. every zero-initialised scratch of stage 1 in ONE launch: the look-back tickets / status words
     //    and the voxel marks (adjacent), the max-pool tables of the PointNet, the clamped-box list length
-    //    and the tile counter of the query
+    //    and the tile counters of the query (two: the split-f16 kernel's launch on the selected list has its own)
     const int64_t sort_cap = B >= 2 ? 2 * N : 0;   // several frames: the voxel table outgrows the LDS pooling
     const PnetFrameWs pf = pnet_frame_ws(C, v_lds, sort_cap);
     float* pool1 = (float*)(ws + f.pnet + pf.pool1);
@@ -1761,7 +1774,7 @@ static int frame_impl(const LidfFrameArgs* a_in, lidf_stream_t stream, ForkState
         float* zp[6] = {(float*)(ws + f.lb_head), pool1, pool2, (float*)(ws + f.query + qw.counter),
                         (float*)(ws + f.query + qw.box) + grid_floats, (float*)(ws + f.pnet + pf.sort)};
         const long long zc[6] = {(long long)(f.lb_bytes / 4) + (long long)C, (long long)C * 64,
-                                 (long long)C * 128, 1, 1, sort_cap > 0 ? (long long)C : 0};
+                                 (long long)C * 128, 2, 1, sort_cap > 0 ? (long long)C : 0};
         CHECK_HIP(lidf_launch_zero_segments(zp, zc, 6, st));
     }
     // the query of step 5 (its per-ray launches go to the side stream when there is one)

@@ -21,6 +21,7 @@ hipError_t lidf_launch_points(int mode, const PointsArgs& a, int grid, hipStream
 hipError_t lidf_launch_pack_h(const StreamLayout& lay, const NetW& n0, const NetW& n1, const L1Map& m, float* stream,
                               float* aux, hipStream_t st);
 hipError_t lidf_launch_points_h(const PointsArgs& a, int cus, hipStream_t st);
+hipError_t lidf_launch_points_h_list(const PointsArgs& a, int cus, hipStream_t st);
 
 // ---- lidf_rows_h.hip
 StreamLayout lidf_make_layout_rows_h(int nets, int D, int l1only);

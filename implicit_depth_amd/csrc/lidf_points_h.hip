@@ -30,6 +30,10 @@
 // per workgroup through LDS in chunks of 16 quads (3 rotating buffers, one s_barrier per chunk,
 // global loads issued one chunk ahead), and each wavefront keeps a 4-quad register ring of
 // ds_read_b128 in flight.
+//
+// Three instantiations of one body (PointsForm): the two-net launch over all pairs, one net of the
+// two-net stream and tables over all pairs (offsets for the selected pairs only: prob_dec), and the
+// list form of that (offset_dec on the one-pair-per-ray list, where every row is its own ray).
 #include "lidf_launch.h"
 #include <stdio.h>
 #include <stdlib.h>
@@ -367,10 +371,20 @@ __device__ __forceinline__ f32x4 feed_take(Feed& f, const FeedCfg& c, f32x4* sb,
     return a;
 }
 
+// FORM_ALL: both nets of the stream, tables of nets * 256 floats per row (the default launch).
+// FORM_PART: the launch's nets are columns part_off.. of tables with part_ld floats per row (one net of
+//            the two-net tables; the host points stream / aux at that net's section).
+// FORM_LIST: FORM_PART on a one-pair-per-ray list. A 32-point tile has 32 rays there, which the rank-1
+//            ray rounds would cover two at a time (16 instructions per layer-1 tile and pass), so the
+//            ray row is gathered per lane like the voxel row: layer 1 starts from the f32 sum
+//            voxpart[vid] + raypart[ray], no ray round runs, and a row's result depends on that row alone.
+enum PointsForm { FORM_ALL = 0, FORM_PART = 1, FORM_LIST = 2 };
+
 // What one pass needs to know about the points of this wavefront.
 struct TileCtx {
     const float* vp;     // voxpart row of this lane's point (+ net, + 4*half)
-    const float* rp;     // raypart row of this half's ray of round 0 (+ net, + lane&31)
+    const float* rp;     // raypart row of this half's ray of round 0 (+ net, + lane&31);
+                         // list form: of this lane's own ray (+ net, + 4*half)
     float rayB;          // packed (1,1) if this lane's point belongs to this half's ray
     int ray;             // this lane's ray (for the extra rounds)
     unsigned todo;       // points not covered by round 0 (0 in the common case)
@@ -388,6 +402,7 @@ __device__ long long g_chunk_ticks[32];
 #else
 #define CHUNK_PROF(q, s_)
 #endif
+template <int FORM>
 __device__ __forceinline__ float decoder_pass_h(Feed& f, const FeedCfg& c, f32x4* sb,
                                                 const TileCtx& tc, const f32x4 (&pbh)[NK1],
                                                 const f32x4 xaB, const float xyB, const _Float16 zh,
@@ -430,10 +445,32 @@ __device__ __forceinline__ float decoder_pass_h(Feed& f, const FeedCfg& c, f32x4
 #pragma unroll
             for (int i = 0; i < 4; ++i) a1[T & 1][4 * g + i] = v[i];
         }
-        rpv[T & 1] = tc.rp[T * 32];
+        if (FORM != FORM_LIST) rpv[T & 1] = tc.rp[T * 32];
+    };
+    // list form: the lane's own ray row, loaded with the voxel row and added to it (one f32 sum per
+    // feature) before the tile's first matrix instruction; the loads have a layer-2 segment to land
+    f32x4 rr[4];
+    auto gather_ray = [&](const int T) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) rr[g] = *(const f32x4*)(tc.rp + T * 32 + 8 * g);
+    };
+    auto add_ray = [&](const int T) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) a1[T & 1][4 * g + i] = __fadd_rn(a1[T & 1][4 * g + i], rr[g][i]);
+        }
     };
     gather(0);
+    if (FORM == FORM_LIST) {
+        gather_ray(0);
+        add_ray(0);
+    }
     gather(1);
+    if (FORM == FORM_LIST) {
+        gather_ray(1);
+        add_ray(1);
+    }
     pl_cur = sb[tc.pl];
 #ifdef LIDF_PROFILE_CHUNKS
     long long chunk_t = clock64();
@@ -468,11 +505,13 @@ __device__ __forceinline__ float decoder_pass_h(Feed& f, const FeedCfg& c, f32x4
             // ray: the ray part of layer 1 is a rank-1 update, two rays per instruction. Tiles that
             // straddle more than two rays (ragged scenes) take extra rounds.
             f32x16& acc = a1[d.T & 1];
+            // (list form: the ray row is in the accumulator already; elements 4, 5 stay the packer's
+            // zeros against rayB = 0)
             f32x4 Ar = A;
-            Ar[2] = split1(rpv[d.T & 1]);
+            if (FORM != FORM_LIST) Ar[2] = split1(rpv[d.T & 1]);
             acc = MFMAH(Ar, xbB, acc);
             if (d.T >= 1) prep_pairs(NK1 + 1, 8, a1[(d.T - 1) & 1], bh, bl);
-            if (tc.todo) {
+            if (FORM != FORM_LIST && tc.todo) {
                 unsigned todo = tc.todo;
                 while (todo) {
                     const int p0 = __builtin_ctz(todo);
@@ -498,7 +537,11 @@ __device__ __forceinline__ float decoder_pass_h(Feed& f, const FeedCfg& c, f32x4
             if (!d.lo) {
                 // the tile after next can start loading: its accumulator is free once the split
                 // of tile T (same parity) is done
-                if (d.j == 0 && d.T + 2 < 8) gather(d.T + 2);
+                if (d.j == 0 && d.T + 2 < 8) {
+                    gather(d.T + 2);
+                    if (FORM == FORM_LIST) gather_ray(d.T + 2);
+                }
+                if (FORM == FORM_LIST && d.j == 7 && d.T + 2 < 8) add_ray(d.T + 2);
                 // tile 7 has no layer-1 segment after it to hide its split behind, and a second
                 // operand buffer just for it would push the kernel into spilling
                 if (d.T == 7 && d.j == 0) prep_pairs(0, 8, a1[1], bh, bl);
@@ -565,6 +608,7 @@ struct GeoH {
     float te, tl, dx, dy, dz;
 };
 
+template <int FORM>
 __global__ void __launch_bounds__(256, 2) lidf_points_h_kernel(PointsArgs a) {
     extern __shared__ f32x4 sb[];  // [NBUF chunks of the stream][per wavefront: NK1 operand quads]
     const int lane = threadIdx.x & 63;
@@ -634,9 +678,12 @@ __global__ void __launch_bounds__(256, 2) lidf_points_h_kernel(PointsArgs a) {
     };
     GeoH cur = {}, nxt = {}, nx2 = {};
 
+    // floats per row of the two tables / first column of this launch's nets
+    const int part_ld = FORM == FORM_ALL ? a.nets * 256 : a.part_ld;
+    const int part_off = FORM == FORM_ALL ? 0 : a.part_off;
     TileCtx tc;
     tc.pl = LDS_STREAM_ELEMS + wave * NK1 * 64 + lane;
-    tc.ray_stride = a.nets * 256;
+    tc.ray_stride = part_ld;
 
     PROF_DECL
     for (;;) {
@@ -646,14 +693,19 @@ __global__ void __launch_bounds__(256, 2) lidf_points_h_kernel(PointsArgs a) {
     if (tb >= ntile) break;
     const long long te_ = tb + LIDF_H_GRAB < ntile ? tb + LIDF_H_GRAB : ntile;
     load_idx(tb, cur);
-    load_idx(tb + 1, nxt);
+    if (FORM != FORM_LIST) load_idx(tb + 1, nxt);
     load_dir(cur);
     for (long long tile = tb; tile < te_; ++tile) {
         PROF(0)
         const long long p = tile * 128 + wave * 32 + col;
         const bool valid = p < AN;
-        load_dir(nxt);
-        load_idx(tile + 2, nx2);
+        // (list form: no prefetch. The next tile's geometry is loaded after this tile's passes, at the foot of
+        // the loop, so that nothing of it occupies registers through them; that load is exposed, once per
+        // tile of n_iter passes)
+        if (FORM != FORM_LIST) {
+            load_dir(nxt);
+            load_idx(tile + 2, nx2);
+        }
         // this half's embedding input: lanes 0..31 embed the enter position, lanes 32..63 the leave
         // position (pipeline.py:349-360; 'rel' subtracts the voxel centre)
         const float tt = h ? cur.tl : cur.te;
@@ -669,9 +721,11 @@ __global__ void __launch_bounds__(256, 2) lidf_points_h_kernel(PointsArgs a) {
         stash[1 * 64] = cur.dx;
         stash[2 * 64] = cur.dy;
         stash[3 * 64] = cur.dz;
-        stash[4 * 64] = nxt.te;
-        stash[5 * 64] = nxt.tl;
-        stash[6 * 64] = __int_as_float(nxt.vid);
+        if (FORM != FORM_LIST) {
+            stash[4 * 64] = nxt.te;
+            stash[5 * 64] = nxt.tl;
+            stash[6 * 64] = __int_as_float(nxt.vid);
+        }
         // operands of the layer-1 k-steps, shared by all passes of this tile: high pieces in
         // registers, low pieces in this wavefront's LDS rows
         f32x4 pbh[NK1];
@@ -708,8 +762,13 @@ __global__ void __launch_bounds__(256, 2) lidf_points_h_kernel(PointsArgs a) {
             xyB = pack2(xh, yh);
         }
         // rays of this wavefront's 32 points: round 0 covers the first two distinct rays
-        int my_ray;
-        {
+        // (list form: every lane gathers the row of its own ray, there are no rounds)
+        int my_ray = cur.ray;
+        if (FORM == FORM_LIST) {
+            tc.rayB = 0.f;
+            tc.todo = 0;
+            tc.ray = cur.ray;
+        } else {
             unsigned todo = (unsigned)__ballot(h == 0);
             const int p0 = __builtin_ctz(todo);
             const int r0 = __builtin_amdgcn_readlane(cur.ray, p0);
@@ -731,14 +790,21 @@ __global__ void __launch_bounds__(256, 2) lidf_points_h_kernel(PointsArgs a) {
         PROF(1)
 
         for (int net = 0; net < a.nets; ++net) {
-            tc.vp = a.voxpart + ((size_t)cur.vid * a.nets + net) * 256 + 4 * h;
-            tc.rp = a.raypart + ((size_t)my_ray * a.nets + net) * 256 + col;
-            tc.rbase = a.raypart + net * 256 + col;
+            if (FORM == FORM_ALL) {
+                tc.vp = a.voxpart + ((size_t)cur.vid * a.nets + net) * 256 + 4 * h;
+                tc.rp = a.raypart + ((size_t)my_ray * a.nets + net) * 256 + col;
+                tc.rbase = a.raypart + net * 256 + col;
+            } else {
+                tc.vp = a.voxpart + (size_t)cur.vid * part_ld + part_off + net * 256 + 4 * h;
+                tc.rp = a.raypart + (size_t)my_ray * part_ld + part_off + net * 256 +
+                        (FORM == FORM_LIST ? 4 * h : col);
+                tc.rbase = a.raypart + part_off + net * 256 + col;
+            }
             float val = a.init[net];
             const float* ax = a.aux + net * LIDF_AUX_FLOATS;
             const int npass = a.npass[net];
             for (int pass = 0; pass < npass; ++pass)
-                val += decoder_pass_h(f, c, sb, tc, pbh, xaB, xyB, zh, val, h, col, ax);
+                val += decoder_pass_h<FORM>(f, c, sb, tc, pbh, xaB, xyB, zh, val, h, col, ax);
             PROF(2 + net)
 
             // ---------------- outputs ----------------
@@ -760,6 +826,11 @@ __global__ void __launch_bounds__(256, 2) lidf_points_h_kernel(PointsArgs a) {
                 }
             }
         }
+        if (FORM == FORM_LIST) {
+            load_idx(tile + 1, cur);
+            load_dir(cur);
+            continue;
+        }
         cur.ray = nxt.ray;
         cur.dx = nxt.dx;
         cur.dy = nxt.dy;
@@ -776,21 +847,26 @@ __global__ void __launch_bounds__(256, 2) lidf_points_h_kernel(PointsArgs a) {
     PROF_DUMP
 }
 
-extern "C" hipError_t lidf_launch_points_h(const PointsArgs& a, int cus, hipStream_t st) {
+// form: a PointsForm. FORM_ALL ignores part_ld / part_off (tables of nets * 256 floats per row); the other two
+// need part_ld > 0. FORM_LIST: a.pair_* are a one-pair-per-ray list.
+static hipError_t launch_points_h_form(const PointsArgs& a, int form, int cus, hipStream_t st) {
     if (a.n <= 0) return hipSuccess;
-    // > 64 KiB of dynamic LDS needs the opt-in once per device (one process may drive several)
-    static bool configured[64] = {};
+    if (form != FORM_ALL && a.part_ld <= 0) return hipErrorInvalidValue;
+    const void* const kern = form == FORM_ALL    ? (const void*)lidf_points_h_kernel<FORM_ALL>
+                             : form == FORM_PART ? (const void*)lidf_points_h_kernel<FORM_PART>
+                                                 : (const void*)lidf_points_h_kernel<FORM_LIST>;
+    // > 64 KiB of dynamic LDS needs the opt-in once per device and kernel (one process may drive several)
+    static bool configured[3][64] = {};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!configured[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)lidf_points_h_kernel,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+    if (!configured[form][dev]) {
+        hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
         if (e != hipSuccess) return e;
-        configured[dev] = true;
+        configured[form][dev] = true;
 #ifdef LIDF_PROFILE
         for (int lds = 32768; lds <= LDS_BYTES + 8192; lds += 4096) {
             int nb = -1;
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)lidf_points_h_kernel, 256, lds);
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, lds);
             fprintf(stderr, "occupancy with %d B of LDS per workgroup: %d workgroups per CU\n", lds, nb);
         }
 #endif
@@ -805,7 +881,12 @@ extern "C" hipError_t lidf_launch_points_h(const PointsArgs& a, int cus, hipStre
     static long long zero_[32] = {0};
     hipMemcpyToSymbolAsync(HIP_SYMBOL(g_chunk_ticks), zero_, sizeof(zero_), 0, hipMemcpyHostToDevice, st);
 #endif
-    hipLaunchKernelGGL(lidf_points_h_kernel, dim3(grid), dim3(256), LDS_BYTES, st, a);
+    if (form == FORM_ALL)
+        hipLaunchKernelGGL(lidf_points_h_kernel<FORM_ALL>, dim3(grid), dim3(256), LDS_BYTES, st, a);
+    else if (form == FORM_PART)
+        hipLaunchKernelGGL(lidf_points_h_kernel<FORM_PART>, dim3(grid), dim3(256), LDS_BYTES, st, a);
+    else
+        hipLaunchKernelGGL(lidf_points_h_kernel<FORM_LIST>, dim3(grid), dim3(256), LDS_BYTES, st, a);
 #ifdef LIDF_PROFILE_CHUNKS
     {
         long long t_[32];
@@ -816,4 +897,18 @@ extern "C" hipError_t lidf_launch_points_h(const PointsArgs& a, int cus, hipStre
     }
 #endif
     return hipGetLastError();
+}
+
+// all pairs: both nets (part_ld == 0) or the launch's nets inside wider tables (part_ld > 0)
+extern "C" hipError_t lidf_launch_points_h(const PointsArgs& a, int cus, hipStream_t st) {
+    return launch_points_h_form(a, a.part_ld > 0 ? FORM_PART : FORM_ALL, cus, st);
+}
+
+// a one-pair-per-ray list (offsets for the selected pairs only)
+extern "C" hipError_t lidf_launch_points_h_list(const PointsArgs& a, int cus, hipStream_t st) {
+#ifdef LIDF_H_LIST_ROUNDS   // development only (A/B): the list through the rank-1 ray rounds
+    return launch_points_h_form(a, FORM_PART, cus, st);
+#else
+    return launch_points_h_form(a, FORM_LIST, cus, st);
+#endif
 }

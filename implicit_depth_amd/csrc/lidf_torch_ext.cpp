@@ -11,6 +11,7 @@
 #include <c10/hip/HIPStream.h>
 #include <torch/extension.h>
 
+#include <limits>
 #include <vector>
 
 #include "lidf_hip.h"
@@ -186,6 +187,8 @@ std::vector<Tensor> forward_decoders(Tensor inp, std::vector<Tensor> prob_w, std
 // ---- get_embedding + get_pred (+ depth write-back), models/pipeline.py:338-466, :593-596 ----------
 // Returns [pred_offset [P,1], pred_prob_end [P,1], pair_pred_pos [P,3], pred_prob_end_softmax [P],
 //          max_pair_id [R] i64, pred_pos [R,3]]; `depth` [B,h,w] (optional) is updated in place.
+// offsets_selected (either precision): LidfQueryArgs.offsets_selected — pred_offset / pair_pred_pos hold values at
+// the selected pair of every ray only, their other rows are NaN.
 std::vector<Tensor> forward_query(Tensor ray_dir, Tensor ray_pix, Tensor ray_bid,
                                   c10::optional<Tensor> ray_flat, Tensor pair_off, Tensor pair_ray,
                                   Tensor pair_vox, Tensor pair_t, Tensor feat_grid, Tensor vox_feat,
@@ -194,7 +197,7 @@ std::vector<Tensor> forward_query(Tensor ray_dir, Tensor ray_pix, Tensor ray_bid
                                   bool use_sigmoid, int64_t multires, int64_t multires_views,
                                   int64_t roi_inp_bbox, bool pos_rel, double offset_range0,
                                   double offset_range1, double part_size, c10::optional<Tensor> depth,
-                                  int64_t precision) {
+                                  int64_t precision, bool offsets_selected) {
     CHECK_IN(ray_dir); CHECK_IN(pair_off); CHECK_IN(pair_ray); CHECK_IN(pair_vox); CHECK_IN(pair_t);
     CHECK_IN(feat_grid); CHECK_IN(vox_feat);
     CHECK_F32(ray_dir); CHECK_F32(pair_t); CHECK_F32(feat_grid); CHECK_F32(vox_feat);
@@ -264,6 +267,11 @@ std::vector<Tensor> forward_query(Tensor ray_dir, Tensor ray_pix, Tensor ray_bid
     }
     q.workspace = ws.data_ptr(); q.workspace_bytes = wsb;
     q.precision = (int32_t)precision;
+    if (offsets_selected) {
+        q.offsets_selected = 1;
+        pred_offset.fill_(std::numeric_limits<float>::quiet_NaN());
+        pair_pred_pos.fill_(std::numeric_limits<float>::quiet_NaN());
+    }
     check_rc(lidf_query_f32(&q, current_stream(ray_dir)));
     return {pred_offset, pred_prob, pair_pred_pos, softmax, max_pair_id, pred_pos};
 }
@@ -281,5 +289,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("pcl_aabb", &pcl_aabb, "dense point/voxel inside test: mask (extensions/pcl_aabb forward)");
     m.def("compute_ray_aabb", &compute_ray_aabb, "compact ray-major pairs: [pair_off, pair_ray, pair_vox, pair_t]");
     m.def("forward_decoders", &forward_decoders, "IMNet / IEF forward on [n, D] rows: [prob, offset]");
-    m.def("forward_query", &forward_query, "fused get_embedding + get_pred (+ depth)");
+    // (named arguments so that the trailing flag can default: the 25 positional arguments of earlier callers still bind)
+    namespace py = pybind11;
+    m.def("forward_query", &forward_query, "fused get_embedding + get_pred (+ depth)", py::arg("ray_dir"),
+          py::arg("ray_pix"), py::arg("ray_bid"), py::arg("ray_flat"), py::arg("pair_off"), py::arg("pair_ray"),
+          py::arg("pair_vox"), py::arg("pair_t"), py::arg("feat_grid"), py::arg("vox_feat"), py::arg("vox_center"),
+          py::arg("prob_w"), py::arg("off_w"), py::arg("off_n_iter"), py::arg("off_init"), py::arg("use_sigmoid"),
+          py::arg("multires"), py::arg("multires_views"), py::arg("roi_inp_bbox"), py::arg("pos_rel"),
+          py::arg("offset_range0"), py::arg("offset_range1"), py::arg("part_size"), py::arg("depth"),
+          py::arg("precision"), py::arg("offsets_selected") = false);
 }

@@ -448,7 +448,10 @@ class FrameRunner:
     capacity bounds, stays below (25.2 and 8.8 there); pass max_pairs for a finer grid that is densely occupied.
     offsets="selected" (opt-in; see query.lidf_query): the offset decoder runs on the arg-max pair of every ray
     only — pred_pos, the depth maps, stage 2 and the statistics are bit-identical, pred_offset / pair_pred_pos
-    are meaningful at the selected pairs only (other rows: NaN, or a previous frame's selected values).
+    are meaningful at the selected pairs only (other rows: NaN, or a previous frame's selected values). With
+    precision="f16x3" the statement holds for counts, voxel and ray features, pred_prob_end, the softmax and
+    max_pair_id against the f16x3 frame with offsets="all"; positions and what follows from them are held to
+    float64 by the split criterion instead (query.lidf_query).
 
     Decoder widths: prob_dec / offset_dec / offset_dec_refine of gf_dim 64 (every shipped config) run lidf_frame_f32.
     As soon as one of them has another width — each gf_dim 32, 64 or 128 with the reference's layers 4 gf -> 2 gf ->
@@ -489,8 +492,8 @@ class FrameRunner:
         if precision not in Q.PRECISIONS:
             raise ValueError("precision must be one of %s" % sorted(Q.PRECISIONS))
         self.precision = precision
-        if offsets not in ("all", "selected") or (offsets == "selected" and precision != "f32"):
-            raise ValueError("offsets must be 'all' or 'selected' (f32)")
+        if offsets not in ("all", "selected"):
+            raise ValueError("offsets must be 'all' or 'selected'")
         self.offsets = offsets      # 'selected': offset_dec on the arg-max pair of every ray only (lidf_query)
         self.bs, self.h, self.w, self.dev = bs, h, w, torch.device(device)
         self.mods = (pnet_model, prob_dec, offset_dec, pnet_model_refine, offset_dec_refine)

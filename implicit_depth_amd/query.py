@@ -482,11 +482,14 @@ def lidf_query(ray_dir, ray_pix, ray_bid, pair_off, pair_ray, pair_vox, pair_t, 
                want_rayfeat=False, precision="f32", roi_out_bbox=2, offsets="all"):
     """Fused get_embedding + get_pred (+ depth write-back) through lidf_query_f32.
 
-    offsets="selected" (opt-in, f32, shipped widths): offset_dec runs on the arg-max pair of every ray only —
+    offsets="selected" (opt-in, shipped widths): offset_dec runs on the arg-max pair of every ray only —
     everything downstream of get_pred reads pair_pred_pos through max_pair_id alone (models/pipeline.py:
     453-454), so pred_prob_end, the softmax, max_pair_id, pred_pos and the depth map are bit-identical to the
     default while pred_offset / pair_pred_pos are written ONLY at the selected pairs (the other rows are left
-    as NaN); about half the matrix work on a real frame.
+    as NaN); about half the matrix work on a real frame. With precision="f16x3" pred_prob_end, the softmax and
+    max_pair_id are bit-identical to the f16x3 call with offsets="all"; the selected pairs' offsets, pred_pos
+    and the depth map are held to float64 by the split criterion but not bit-identical to that call (there a
+    row's layer-1 ray term depends on which rays share its 32-point tile, here on the row alone).
 
     Widths other than the shipped configuration (feat_grid channels != 32, roi_out_bbox != 2, vox_feat
     width != 128, decoders with gf_dim != 64): generic.query — the one-launch decoder chain at gf_dim 32 / 64 /
@@ -601,8 +604,6 @@ def lidf_query(ray_dir, ray_pix, ray_bid, pair_off, pair_ray, pair_vox, pair_t, 
     if offsets not in ("all", "selected"):
         raise ValueError("offsets must be 'all' or 'selected'")
     if offsets == "selected":
-        if precision != "f32":
-            raise RuntimeError("offsets='selected' runs the f32 kernels")
         q.offsets_selected = 1
         out["pred_offset"].fill_(float("nan"))      # rows that are not written must not look like results
         out["pair_pred_pos"].fill_(float("nan"))

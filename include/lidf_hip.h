@@ -162,14 +162,19 @@ typedef struct LidfQueryArgs {
      * (3 small launches); eval loops pack once per checkpoint, training loops once per optimizer
      * step. The LidfDecoder pointers are then only consulted for n_iter / init_offset / sigmoid. */
     const void* packed;
-    /* Opt-in (0 = off, the reference's data flow; f32 only): run the offset decoder on the SELECTED pair
+    /* Opt-in (0 = off, the reference's data flow; either precision): run the offset decoder on the SELECTED pair
      * of every ray only. get_pred (models/pipeline.py:427-466) evaluates offset_dec on every pair but
      * everything downstream — pred_pos (:453-454), the depth map, the losses and statistics of
      * compute_loss, stage 2 — reads pair_pred_pos through max_pair_id alone. With this flag prob_dec runs
      * on all pairs, the per-ray softmax / arg-max follows, and offset_dec (two of the three decoder passes)
      * runs on one pair per ray: pred_prob, softmax, max_pair_id, pred_pos and depth are bit-identical to
      * the default; pred_offset / pair_pred_pos hold values ONLY at the selected pairs (other entries are
-     * not written). About half the matrix work on a real frame (3.6 pairs per ray). (ABI 7)            */
+     * not written). About half the matrix work on a real frame (3.6 pairs per ray). (ABI 7)
+     * With LIDF_PRECISION_F16X3 the same sequence runs on the split-f16 kernel: pred_prob, softmax and
+     * max_pair_id are bit-identical to the f16x3 call without this flag; the selected pairs' offsets and
+     * what follows from them (pred_pos, depth) are held to float64 by the split criterion but are NOT
+     * bit-identical to that call, whose layer-1 ray term depends on which rays share a 32-point tile —
+     * here a row's result depends on that row alone.                                                  */
     int32_t offsets_selected;
 } LidfQueryArgs;
 
@@ -635,7 +640,7 @@ typedef struct LidfFrameArgs {
     size_t pack_blob_bytes;
     void* pack_guard;
     int32_t pack_mode;
-    int32_t offsets_selected;   /* as LidfQueryArgs.offsets_selected (opt-in; f32) */
+    int32_t offsets_selected;   /* as LidfQueryArgs.offsets_selected (opt-in; either precision) */
     /* optional second stream (ABI 7): launches of a frame that fill a fraction of the device each run side by
      * side. On `aux_stream`: the weight-stream guard (pack_mode GUARDED: fingerprint + early-exit packs), the
      * box sums of the feature map, then — once the rays exist — the per-ray RoIAlign features; on `stream`

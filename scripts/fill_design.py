@@ -84,6 +84,23 @@ def main():
              e2e_ief_frac=f(ie.get("frac") or 0.0, 3), e2e_ief_frac_rp=f(ie.get("frac_rocprof") or 0.0, 3),
              e2e_rccl_ms=f(rec("e2e_rccl_n1")["ms_per_frame"], 3), e2e_graph_ms=f(rec("e2e_graph_f1")["ms_per_frame"], 3),
              e2e_launches=f((e1o.get("profile") or {}).get("launches_per_step_steady") or 0.0, 0))
+    # precision f16x3 with offsets selected (scripts/selected_split_time.py; not a bench.py record)
+    ss = json.load(open(os.path.join(ROOT, "profiles", "selected_split_time.json")))
+    legs = ("f32/all", "f32/selected", "f16x3/all", "f16x3/selected")
+    med = lambda xs: sorted(xs)[len(xs) // 2] if len(xs) % 2 else sum(sorted(xs)[len(xs) // 2 - 1:len(xs) // 2 + 1]) / 2  # noqa: E731
+    for key, row, field, nd in (("h", ss["query"][0], "mpoints_per_s", 0), ("b", ss["query"][1], "mpoints_per_s", 0),
+                                ("e", ss["frame"][0], "ms", 2), ("g", ss["frame"][1], "ms", 2)):
+        for i, leg in enumerate(legs):
+            v["ss_%s_%d" % (key, i)] = f(row["legs"][leg][field], nd)
+    v["ss_h_ms"] = f(ss["query"][0]["legs"]["f16x3/selected"]["ms"], 2)
+    v["ss_spread"] = f(100 * max(leg["repeat_spread"] for r in ss["query"] + ss["frame"] for leg in r["legs"].values()), 2)
+    ab = ss["library_ab"]
+    for i, leg in enumerate(legs):
+        v["ss_l_%d" % i] = "%d" % [r for r in ab if r["tag"] == "frame-" + leg][0]["frame_launches"]["launches_per_frame"]
+    v["ss_list_us"] = f(med([r["trace"]["list launch"]["median_us"] for r in ab if r["tag"] == "list-tree" and "trace" in r]), 0)
+    v["ss_rounds_us"] = f(med([r["trace"]["list launch"]["median_us"] for r in ab if r["tag"] == "list-rounds" and "trace" in r]), 0)
+    v["ss_tree_ms"] = f(med([r["ms"] for r in ab if r["tag"] == "headline-tree"]), 3)
+    v["ss_parent_ms"] = f(med([r["ms"] for r in ab if r["tag"] == "headline-parent"]), 3)
     p = os.path.join(ROOT, "DESIGN.md")
     s = open(os.path.join(ROOT, "docs", "DESIGN.in.md")).read()
     missing = sorted(set(re.findall(r"@@(\w+)@@", s)) - set(v))
