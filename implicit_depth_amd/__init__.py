@@ -14,7 +14,10 @@ Host-side mirror of the reference interface for this path (names follow the refe
                                                 models/pipeline.py:298-336, 468-650
   losses.refine_loss                         <- RefineNet.compute_loss ('train', 'valid', 'test'), models/pipeline.py:760-919
   pipeline.eval_loss / FrameRunner.loss_dict <- loss_dict of LIDF.forward / RefineNet.forward for 'valid' / 'test'
-                                                (what trainers' validate() / test() read)
+                                                (what trainers' validate() / test() read); per_frame=True: the
+                                                loss_dict of test() at bs == 1 for every frame of a batch
+  losses.frame_slice                         the bs == 1 data_dict of one frame of a batch
+  query.depth_metrics_frames                 <- the nine statistics of :577-627 for every frame of a batch
   losses.topk_mean                           <- torch.topk + mean of hard-negative mining, :475-490, 767-770
   torch_ext.ext()                            <- the pybind11 operator module (extensions/*/jit.py)
 All compute goes through csrc/liblidf_hip.so (C ABI in include/lidf_hip.h).
@@ -23,12 +26,12 @@ from . import _lib  # noqa: F401
 from .decoders import (IEF, IMNet, Embedder, decoders_forward, decoders_forward_train,  # noqa: F401
                        get_embedder)
 from .pointnet import PointNet2Stage  # noqa: F401
-from .losses import (LidfLossOptions, compute_gt, lidf_loss, lidf_loss_composite, refine_loss,  # noqa: F401
-                     refine_loss_composite, topk_mean)
+from .losses import (LidfLossOptions, compute_gt, frame_slice, lidf_loss, lidf_loss_composite,  # noqa: F401
+                     refine_loss, refine_loss_composite, topk_mean)
 from .pipeline import (LidfOptions, eval_loss, lidf_forward_train, refine_forward_train,  # noqa: F401
                        train_refine_step)
 
 __all__ = ["IEF", "IMNet", "Embedder", "PointNet2Stage", "decoders_forward", "decoders_forward_train",
            "get_embedder", "LidfLossOptions", "LidfOptions", "compute_gt", "lidf_loss", "lidf_loss_composite",
            "lidf_forward_train", "refine_loss", "refine_loss_composite", "topk_mean", "refine_forward_train", "train_refine_step",
-           "eval_loss"]
+           "eval_loss", "frame_slice"]

@@ -285,6 +285,8 @@ SIGNATURES = {
     "lidf_frame_pack_guard_bytes": (_SZ, []),
     "lidf_depth_metrics_workspace_bytes": (_SZ, []),
     "lidf_depth_metrics_f32": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _SZ, _P]),
+    "lidf_depth_metrics_frames_workspace_bytes": (_SZ, [C.c_int32]),
+    "lidf_depth_metrics_frames_f32": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _SZ, _P]),
     "lidf_build_rows_f32": (C.c_int, [_P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I64, _P, _P]),
     "lidf_rows_backward_f32": (C.c_int, [_P, _P, _P, _I64, _I64, _I64, _I, _I, _P, _P, _P]),
     "lidf_ray_features_backward_f32": (C.c_int, [_P, _P, _P, _I64, _I, _I, _I, _I, _I, _P, _P, C.c_size_t, _P]),
@@ -371,6 +373,10 @@ SIGNATURES = {
     "lidf_refine_eval_loss_workspace_bytes": (_SZ, [_I64, _I64]),
     "lidf_stage1_eval_loss_f32": (C.c_int, [C.POINTER(LidfEvalLossArgs), _P]),
     "lidf_refine_eval_loss_f32": (C.c_int, [C.POINTER(LidfEvalLossArgs), _P]),
+    "lidf_stage1_eval_loss_frames_workspace_bytes": (_SZ, [C.c_int32, C.c_int32, C.c_int32]),
+    "lidf_refine_eval_loss_frames_workspace_bytes": (_SZ, [C.c_int32, C.c_int32, C.c_int32]),
+    "lidf_stage1_eval_loss_frames_f32": (C.c_int, [C.POINTER(LidfEvalLossArgs), _P]),
+    "lidf_refine_eval_loss_frames_f32": (C.c_int, [C.POINTER(LidfEvalLossArgs), _P]),
     "lidf_stage1_eval_hard_neg_f32": (C.c_int, [C.POINTER(LidfEvalLossArgs), C.c_double, _P, _SZ, _P]),
     "lidf_refine_eval_hard_neg_f32": (C.c_int, [C.POINTER(LidfEvalLossArgs), C.c_double, _P, _SZ, _P]),
 }

@@ -2048,6 +2048,29 @@ LIDF_API int lidf_depth_metrics_f32(const float* pred_depth, const float* gt_dep
     return LIDF_OK;
 }
 
+// Every frame of a batch in one launch: the one-frame workspace per frame (its own ticket, its own partials).
+static const int FRAMES_MAX_BATCH = 65535;   // (the frame is the launch's second grid dimension)
+
+LIDF_API size_t lidf_depth_metrics_frames_workspace_bytes(int32_t batch) {
+    return batch > 0 ? (size_t)batch * lidf_depth_metrics_ws_bytes() : 0;
+}
+
+LIDF_API int lidf_depth_metrics_frames_f32(const float* pred_depth, const float* gt_depth, const void* seg_mask,
+                                           int32_t seg_dtype, int32_t batch, int32_t src_h, int32_t src_w,
+                                           int32_t dst_h, int32_t dst_w, float* out, void* workspace,
+                                           size_t workspace_bytes, lidf_stream_t stream) {
+    if (batch < 0 || src_h <= 0 || src_w <= 0 || dst_h <= 0 || dst_w <= 0) return LIDF_ERR_BAD_ARG;
+    if (batch == 0) return LIDF_OK;
+    if (!pred_depth || !gt_depth || !out) return LIDF_ERR_BAD_ARG;
+    if (seg_dtype < 0 || seg_dtype > 2 || (seg_dtype != 0 && !seg_mask)) return LIDF_ERR_BAD_ARG;
+    if ((int64_t)dst_h * dst_w > 0x7fffffffLL || batch > FRAMES_MAX_BATCH) return LIDF_ERR_UNSUPPORTED;
+    if ((uintptr_t)workspace & 7) return LIDF_ERR_BAD_ARG;
+    if (!workspace || workspace_bytes < lidf_depth_metrics_frames_workspace_bytes(batch)) return LIDF_ERR_WORKSPACE;
+    CHECK_HIP(lidf_launch_depth_metrics_frames(pred_depth, gt_depth, seg_mask, seg_mask ? seg_dtype : 0, batch, src_h,
+                                               src_w, dst_h, dst_w, out, workspace, (hipStream_t)stream));
+    return LIDF_OK;
+}
+
 // ---- decoders, training path (forward with kept activations + backward) ---------------------------
 // One linear layer through lidf_linear_kernel with the training epilogues.
 struct LinEx {
@@ -4155,7 +4178,8 @@ LIDF_API size_t lidf_refine_eval_loss_workspace_bytes(int64_t n_rays, int64_t re
     return eval_loss_ws_bytes(n_rays, resize_pixels);
 }
 
-static int eval_loss_args(const LidfEvalLossArgs* a, bool pairs, LossArgs* k) {
+// frames: the per-frame form (lidf_*_eval_loss_frames_f32) — resize_metrics and n_label are not read, xyz_gt is.
+static int eval_loss_args(const LidfEvalLossArgs* a, bool pairs, LossArgs* k, bool frames = false) {
     if (!a || a->n_rays < 0 || a->batch < 0 || a->height < 0 || a->width < 0 || (pairs && a->n_pairs < 0))
         return LIDF_ERR_BAD_ARG;
     const long long npix = (long long)a->batch * a->height * a->width;
@@ -4164,10 +4188,12 @@ static int eval_loss_args(const LidfEvalLossArgs* a, bool pairs, LossArgs* k) {
     if (a->n_rays > 0 && (!a->xyz_base || !a->ray_bid || !a->ray_flat || !a->pix2ray || !a->gt_pos || !a->pred_pos ||
                           npix == 0))
         return LIDF_ERR_BAD_ARG;
-    if (pairs && a->n_rays > 0 && (!a->pair_off || !a->gt_max_pair_id || !a->n_label)) return LIDF_ERR_BAD_ARG;
+    if (pairs && a->n_rays > 0 && (!a->pair_off || !a->gt_max_pair_id || (!frames && !a->n_label)))
+        return LIDF_ERR_BAD_ARG;
     if (pairs && a->n_pairs > 0 && (!a->pcl_label || !a->pred_prob)) return LIDF_ERR_BAD_ARG;
-    if (a->n_rays > 0 && a->resize_metrics &&
-        (a->batch != 1 || !a->xyz_gt || a->seg_dtype < 0 || a->seg_dtype > 2 || (a->seg_dtype != 0 && !a->seg_mask)))
+    if (a->n_rays > 0 && (frames || a->resize_metrics) &&
+        ((!frames && a->batch != 1) || !a->xyz_gt || a->seg_dtype < 0 || a->seg_dtype > 2 ||
+         (a->seg_dtype != 0 && !a->seg_mask)))
         return LIDF_ERR_BAD_ARG;
     memset(k, 0, sizeof(*k));
     k->R = a->n_rays, k->P = pairs ? a->n_pairs : 0, k->hw = (long long)a->height * a->width;
@@ -4220,6 +4246,66 @@ LIDF_API int lidf_stage1_eval_loss_f32(const LidfEvalLossArgs* args, lidf_stream
 
 LIDF_API int lidf_refine_eval_loss_f32(const LidfEvalLossArgs* args, lidf_stream_t stream) {
     return eval_loss_run(args, false, (hipStream_t)stream);
+}
+
+// ---- The same per frame of a batch: row b of loss [B, 17 | 15] is the bs == 1 call on frame b alone ----
+// Workspace: the double partial sums (ceil(hw / 256) rows per frame) | the per-frame depth-metrics workspaces | their
+// outputs [B, 10] (padded to 64 bytes) | the two depth images [B, hw].
+static size_t eval_frames_mout_bytes(int64_t batch) { return ((size_t)batch * 10 * sizeof(float) + 63) & ~(size_t)63; }
+
+static size_t eval_loss_frames_ws_bytes(int32_t batch, int32_t height, int32_t width, bool pairs) {
+    if (batch <= 0 || height <= 0 || width <= 0) return 0;
+    const long long hw = (long long)height * width;
+    return lidf_eval_loss_frames_partial_bytes(batch, hw, pairs ? 1 : 0) +
+           lidf_depth_metrics_frames_workspace_bytes(batch) + eval_frames_mout_bytes(batch) +
+           2 * (size_t)batch * hw * sizeof(float);
+}
+LIDF_API size_t lidf_stage1_eval_loss_frames_workspace_bytes(int32_t batch, int32_t height, int32_t width) {
+    return eval_loss_frames_ws_bytes(batch, height, width, true);
+}
+LIDF_API size_t lidf_refine_eval_loss_frames_workspace_bytes(int32_t batch, int32_t height, int32_t width) {
+    return eval_loss_frames_ws_bytes(batch, height, width, false);
+}
+
+static int eval_loss_frames_run(const LidfEvalLossArgs* args, bool pairs, hipStream_t st) {
+    LossArgs k;
+    int rc = eval_loss_args(args, pairs, &k, true);
+    if (rc) return rc;
+    if (k.B > FRAMES_MAX_BATCH) return LIDF_ERR_UNSUPPORTED;
+    // (there is no per-frame hard-negative select: the unreduced terms have no reader here)
+    if (args->pos_unreduced || args->surf_norm_dist || args->dx_dist || args->dy_dist || args->prob_unreduced)
+        return LIDF_ERR_BAD_ARG;
+    if (k.B == 0) return LIDF_OK;
+    if (!k.loss) return LIDF_ERR_BAD_ARG;
+    const size_t row = (pairs ? 17 : 15) * sizeof(float);
+    if (k.R == 0) {   // no frame has a ray, hence none a loss_dict: every row is NaN (all bits set)
+        CHECK_HIP(hipMemsetAsync(k.loss, 0xFF, (size_t)k.B * row, st));
+        return LIDF_OK;
+    }
+    if ((uintptr_t)args->workspace & 7) return LIDF_ERR_BAD_ARG;
+    if (!args->workspace || args->workspace_bytes < eval_loss_frames_ws_bytes(k.B, k.H, k.W, pairs))
+        return LIDF_ERR_WORKSPACE;
+    char* ws = (char*)args->workspace;
+    k.partial = (double*)ws;
+    char* mws = ws + lidf_eval_loss_frames_partial_bytes(k.B, k.hw, pairs ? 1 : 0);
+    float* mout = (float*)(mws + lidf_depth_metrics_frames_workspace_bytes(k.B));
+    float* pred_img = (float*)((char*)mout + eval_frames_mout_bytes(k.B));
+    float* gt_img = pred_img + (size_t)k.B * k.hw;
+    CHECK_HIP(hipMemsetAsync(mws, 0, lidf_depth_metrics_frames_workspace_bytes(k.B), st));
+    CHECK_HIP(lidf_launch_eval_depth_images_frames(k, args->xyz_gt, pred_img, gt_img, st));
+    CHECK_HIP(lidf_launch_depth_metrics_frames(pred_img, gt_img, args->seg_mask, args->seg_mask ? args->seg_dtype : 0,
+                                               k.B, k.H, k.W, EVAL_DST_H, EVAL_DST_W, mout, mws, st));
+    k.metrics = mout;
+    CHECK_HIP(lidf_launch_eval_loss_frames(k, pairs ? 1 : 0, st));
+    return LIDF_OK;
+}
+
+LIDF_API int lidf_stage1_eval_loss_frames_f32(const LidfEvalLossArgs* args, lidf_stream_t stream) {
+    return eval_loss_frames_run(args, true, (hipStream_t)stream);
+}
+
+LIDF_API int lidf_refine_eval_loss_frames_f32(const LidfEvalLossArgs* args, lidf_stream_t stream) {
+    return eval_loss_frames_run(args, false, (hipStream_t)stream);
 }
 
 LIDF_API int lidf_stage1_eval_hard_neg_f32(const LidfEvalLossArgs* args, double ratio, void* workspace,

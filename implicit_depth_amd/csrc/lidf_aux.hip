@@ -1569,10 +1569,25 @@ __device__ __forceinline__ bool metric_mask(const void* seg, int dtype, size_t i
 // 36 us; here every workgroup of 1024 threads sums its share in the strided order of the one-workgroup
 // kernel, leaves ten partial sums, and the workgroup that arrives last adds the partials in workgroup
 // order (a fixed order: run-to-run identical) and forms the statistics.
+// FRAMES: blockIdx.y is the frame of a [B, src_h, src_w] batch. Every frame has its own images, its own row of
+// out [B, 10] and its own section of the workspace — a ticket word and METRIC_MAX_WGS x METRIC_SUMS partials, the
+// one-frame layout repeated — so a frame's workgroups count and add among themselves in the one-frame launch's
+// order: row b is bit for bit the one-frame call on frame b. (A ticket shared between frames would let one
+// frame's last arriver add partials that another frame is still writing.)
+template <bool FRAMES>
 __global__ void __launch_bounds__(1024) lidf_depth_metrics_kernel(
     const float* __restrict__ pred, const float* __restrict__ gt, const void* __restrict__ seg, int seg_dtype,
     int src_h, int src_w, int dst_h, int dst_w, float* __restrict__ out, unsigned* __restrict__ ticket,
     unsigned long long* __restrict__ partial) {
+    if constexpr (FRAMES) {
+        const size_t f = blockIdx.y, npix = (size_t)src_h * src_w;
+        pred += f * npix, gt += f * npix;
+        if (seg_dtype != 0) seg = (const char*)seg + f * npix * (seg_dtype == 2 ? sizeof(float) : 1);
+        out += f * METRIC_SUMS;
+        constexpr size_t WS = 64 + (size_t)METRIC_MAX_WGS * METRIC_SUMS * 8;
+        ticket = (unsigned*)((char*)ticket + f * WS);
+        partial = (unsigned long long*)((char*)partial + f * WS);
+    }
     __shared__ double red[METRIC_SUMS][16];
     __shared__ bool s_last;
     double acc[METRIC_SUMS];
@@ -1666,8 +1681,22 @@ extern "C" hipError_t lidf_launch_depth_metrics(const float* pred, const float* 
     long long g = ((long long)dst_h * dst_w + 1023) / 1024;
     if (g > METRIC_MAX_WGS) g = METRIC_MAX_WGS;
     if (g < 1) g = 1;
-    hipLaunchKernelGGL(lidf_depth_metrics_kernel, dim3((unsigned)g), dim3(1024), 0, st, pred, gt, seg, seg_dtype,
-                       src_h, src_w, dst_h, dst_w, out, (unsigned*)ws, (unsigned long long*)((char*)ws + 64));
+    hipLaunchKernelGGL(lidf_depth_metrics_kernel<false>, dim3((unsigned)g), dim3(1024), 0, st, pred, gt, seg,
+                       seg_dtype, src_h, src_w, dst_h, dst_w, out, (unsigned*)ws,
+                       (unsigned long long*)((char*)ws + 64));
+    return hipGetLastError();
+}
+// Every frame of pred / gt / seg [B, src_h, src_w] -> out [B, 10]; ws: B x lidf_depth_metrics_ws_bytes(), all zero.
+extern "C" hipError_t lidf_launch_depth_metrics_frames(const float* pred, const float* gt, const void* seg,
+                                                       int seg_dtype, int B, int src_h, int src_w, int dst_h,
+                                                       int dst_w, float* out, void* ws, hipStream_t st) {
+    if (B <= 0) return hipSuccess;
+    long long g = ((long long)dst_h * dst_w + 1023) / 1024;
+    if (g > METRIC_MAX_WGS) g = METRIC_MAX_WGS;
+    if (g < 1) g = 1;
+    hipLaunchKernelGGL(lidf_depth_metrics_kernel<true>, dim3((unsigned)g, (unsigned)B), dim3(1024), 0, st, pred, gt,
+                       seg, seg_dtype, src_h, src_w, dst_h, dst_w, out, (unsigned*)ws,
+                       (unsigned long long*)((char*)ws + 64));
     return hipGetLastError();
 }
 

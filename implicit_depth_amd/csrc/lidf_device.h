@@ -391,7 +391,8 @@ struct LossArgs {
     float *g_pred_pos, *g_logit;
     // evaluation flavour (LidfEvalLossArgs): xyz is the base cloud xyz_corrupt_flat, loss has 17 (stage 2: 15)
     // entries, the unreduced vectors may be NULL (written for hard-negative mining only), ray_lse is not written
-    const float* metrics;         // [9] statistics of the resized frame (bs == 1), NULL = taken over the rays
+    const float* metrics;         // [9] statistics of the resized frame (bs == 1), NULL = taken over the rays;
+                                  // the per-frame form: [B, 10] rows, loss [B, 17 | 15], partial [B, blocks, 18 | 19]
 };
 
 // One top-k mean of lidf_select.hip (LidfTopkJob of the C ABI) and what its last kernel makes of the means.

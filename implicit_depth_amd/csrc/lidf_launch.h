@@ -102,6 +102,9 @@ hipError_t lidf_launch_vox_points(const float* xyz, const int* pt_key, const int
 size_t lidf_depth_metrics_ws_bytes(void);
 hipError_t lidf_launch_depth_metrics(const float* pred, const float* gt, const void* seg, int seg_dtype, int src_h,
                                      int src_w, int dst_h, int dst_w, float* out, void* ws, hipStream_t st);
+hipError_t lidf_launch_depth_metrics_frames(const float* pred, const float* gt, const void* seg, int seg_dtype, int B,
+                                            int src_h, int src_w, int dst_h, int dst_w, float* out, void* ws,
+                                            hipStream_t st);
 hipError_t lidf_launch_miss_block_count(const void* mask, int dtype, long long n, int* block_cnt, hipStream_t st);
 hipError_t lidf_launch_miss_count(const void* mask, int dtype, long long n, int* block_cnt, int* block_off, int* sums,
                                   int* n_rays, hipStream_t st);
@@ -300,6 +303,10 @@ size_t lidf_eval_loss_partial_bytes(long long R);
 hipError_t lidf_launch_eval_loss(const LossArgs& a, int pairs, hipStream_t st);
 hipError_t lidf_launch_eval_depth_images(const LossArgs& a, const float* xyz_gt, float* pred_img, float* gt_img,
                                          hipStream_t st);
+size_t lidf_eval_loss_frames_partial_bytes(int B, long long hw, int pairs);
+hipError_t lidf_launch_eval_loss_frames(const LossArgs& a, int pairs, hipStream_t st);
+hipError_t lidf_launch_eval_depth_images_frames(const LossArgs& a, const float* xyz_gt, float* pred_img,
+                                                float* gt_img, hipStream_t st);
 
 // ---- lidf_select.hip
 size_t lidf_select_workspace_bytes(int n_jobs, long long n_max);

@@ -9,6 +9,10 @@
 //   <.., EVAL = true> of the two    the evaluation flavour ('valid' / 'test', :571-650, :843-919): xyz_corrupt_flat as
 //                                  the base cloud, no stored terms unless asked for, the nine ClearGrasp statistics
 //                                  -> 17 (stage 2: 15) scalars; lidf_eval_depth_images_kernel feeds the bs == 1 branch
+//   <.., EVAL = true, FRAMES = true> the same per frame of a batch (lidf_*_eval_loss_frames_f32): frame b owns the
+//                                  rays [s_b, s_{b+1}) of the grouped ray list (a lower bound over ray_bid, taken on
+//                                  the device), its blocks of 256 rays count from s_b, and row b of loss [B, 17 | 15]
+//                                  is what the bs == 1 call on that frame alone gives, bit for bit
 //   lidf_loss_backward_kernel      per ray: d loss_net / d pred_pos (a gather over its own, its left and its
 //                                  upper pixel's normals) and d loss_net / d logits of its pairs (closed form)
 // The three loss kernels are templates on PAIRS: <true> is stage 1 (lidf_stage1_loss_*), <false> is stage 2
@@ -133,18 +137,45 @@ __device__ __forceinline__ float cosine(const float* a, const float* b, float& n
     return c;
 }
 
+// First ray of frame b in the grouped ray list: the lowest i in [0, R] with ray_bid[i] >= b (b = B gives R). On a
+// list that is not grouped the answer is still an index in [0, R].
+__device__ __forceinline__ long long frame_start(const int* __restrict__ ray_bid, long long R, int b) {
+    long long lo = 0, hi = R;
+    while (lo < hi) {
+        const long long mid = (lo + hi) >> 1;
+        if (ray_bid[mid] < b) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
 // EVAL: the exp_type != 'train' flavour (:571-618, :843-889). A.xyz is then xyz_corrupt_flat (:497), the unreduced
 // terms are stored only where their pointer is set (hard-negative mining), ray_lse is not stored (no backward), and
 // the terms of the nine statistics over the rays with nonzero ground truth (the bs != 1 branch: pred = pred_pos z,
 // gt = gt_pos z) join the partial sums.
-template <bool PAIRS, bool EVAL>
+// FRAMES (with EVAL): grid (ceil(hw / 256), B) — a ray is a distinct pixel, so no frame has more than hw rays.
+// Block j of frame b takes the rays s_b + 256 j ... of that frame and writes partial row (b, j); a block at or
+// beyond the frame's ceil(R_b / 256) leaves without touching memory. Stage 1 carries one more sum, the number of
+// labelled pairs of the ray (integer-valued, exact in double): the frame's own n_label.
+template <bool PAIRS, bool EVAL, bool FRAMES = false>
 __global__ __launch_bounds__(LOSS_BLOCK) void lidf_loss_kernel(const LossArgs A) {
+    static_assert(EVAL || !FRAMES, "the per-frame form is the evaluation flavour's");
     constexpr int NS = EVAL ? NSUM + NMET : NSUM;
-    const long long r = (long long)blockIdx.x * LOSS_BLOCK + threadIdx.x;
-    double v[NS];
+    constexpr int NP = NS + (FRAMES && PAIRS ? 1 : 0);
+    long long r = (long long)blockIdx.x * LOSS_BLOCK + threadIdx.x;
+    long long r_end = A.R;
+    if constexpr (FRAMES) {
+        __shared__ long long s_range[2];
+        if (threadIdx.x < 2) s_range[threadIdx.x] = frame_start(A.ray_bid, A.R, (int)blockIdx.y + (int)threadIdx.x);
+        __syncthreads();
+        r_end = s_range[1];
+        if (s_range[0] + (long long)blockIdx.x * LOSS_BLOCK >= r_end) return;   // (the whole block)
+        r += s_range[0];
+    }
+    double v[NP];
 #pragma unroll
-    for (int k = 0; k < NS; ++k) v[k] = 0.0;
-    if (r < A.R) {
+    for (int k = 0; k < NP; ++k) v[k] = 0.0;
+    if (r < r_end) {
         // position term and the L2 error over rays whose ground truth is not the zero-depth point (:560-566)
         float g[3], d[3];
         float pz = 0.f;
@@ -181,6 +212,7 @@ __global__ __launch_bounds__(LOSS_BLOCK) void lidf_loss_kernel(const LossArgs A)
                 if (A.label[i] != 0) {
                     l = -(z - ls);
                     psum += l;
+                    if constexpr (FRAMES) v[NS] += 1.0;
                 }
                 if (!EVAL || A.prob_un) A.prob_un[i] = l;
             }
@@ -205,19 +237,20 @@ __global__ __launch_bounds__(LOSS_BLOCK) void lidf_loss_kernel(const LossArgs A)
         v[S_SURF] = dist, v[S_DX] = dxd, v[S_DY] = dyd, v[S_ANGLE] = acosf(cc);
     }
     // stage 1 of the means: the block's sums (wavefront butterflies, then the four wavefronts in order)
-    __shared__ double part[LOSS_BLOCK / 64][NS];
+    __shared__ double part[LOSS_BLOCK / 64][NP];
     const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
 #pragma unroll
-    for (int k = 0; k < NS; ++k) {
+    for (int k = 0; k < NP; ++k) {
         const double t = wave_sum(v[k]);
         if (ln == 0) part[wv][k] = t;
     }
     __syncthreads();
-    if (threadIdx.x < NS) {
+    if (threadIdx.x < NP) {
         double t = 0.0;
 #pragma unroll
         for (int i = 0; i < LOSS_BLOCK / 64; ++i) t += part[i][threadIdx.x];
-        A.partial[(size_t)blockIdx.x * NS + threadIdx.x] = t;
+        const size_t row = FRAMES ? (size_t)blockIdx.y * gridDim.x + blockIdx.x : (size_t)blockIdx.x;
+        A.partial[row * NP + threadIdx.x] = t;
     }
 }
 
@@ -226,48 +259,78 @@ __global__ __launch_bounds__(LOSS_BLOCK) void lidf_loss_kernel(const LossArgs A)
 // stage 2: {pos_loss, surf_norm_loss, smooth_loss, loss_net, err, angle_err} (:823-840, :898-905).
 // EVAL: every wavefront takes a second quantity, and the nine statistics follow in loss_dict's order (:639-649,
 // :906-917) — from the rays' sums, or copied from A.metrics (the resized frame of the bs == 1 branch).
-template <bool PAIRS, bool EVAL>
+// FRAMES: one workgroup per frame; nblk arrives as the partial rows per frame (the launch's ceil(hw / 256)) and
+// becomes the frame's own ceil(R_b / 256), R its R_b, the label count its own sum, A.metrics / A.loss its rows of
+// [B, 10] / [B, 17 | 15]. A frame without a ray has no loss_dict (the reference returns early): its row is NaN.
+template <bool PAIRS, bool EVAL, bool FRAMES = false>
 __global__ __launch_bounds__(64 * NSUM) void lidf_loss_final_kernel(const LossArgs A, int nblk) {
     constexpr int NS = EVAL ? NSUM + NMET : NSUM;
-    __shared__ double tot[NS];
+    constexpr int NP = NS + (FRAMES && PAIRS ? 1 : 0);
+    __shared__ double tot[NP];
     const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
+    const double* partial = A.partial;
+    long long n_rays = A.R;
+    float* loss = A.loss;
+    const float* metrics = A.metrics;
+    if constexpr (FRAMES) {
+        __shared__ long long s_range[2];
+        if (threadIdx.x < 2) s_range[threadIdx.x] = frame_start(A.ray_bid, A.R, (int)blockIdx.x + (int)threadIdx.x);
+        __syncthreads();
+        n_rays = s_range[1] - s_range[0];
+        constexpr int NL = (PAIRS ? 8 : 6) + NMET;
+        loss += (size_t)blockIdx.x * NL;
+        if (n_rays <= 0) {
+            if (threadIdx.x < NL) loss[threadIdx.x] = __builtin_nanf("");
+            return;
+        }
+        partial += (size_t)blockIdx.x * nblk * NP;
+        metrics += (size_t)blockIdx.x * 10;
+        // (a grouped list has R_b <= hw; the clamp keeps an ungrouped one inside the frame's partial rows)
+        const long long own = (n_rays + LOSS_BLOCK - 1) / LOSS_BLOCK;
+        nblk = own < nblk ? (int)own : nblk;
+    }
     auto total = [&](int k) {
         double t = 0.0;
-        for (int i = ln; i < nblk; i += 64) t += A.partial[(size_t)i * NS + k];
+        for (int i = ln; i < nblk; i += 64) t += partial[(size_t)i * NP + k];
         t = wave_sum(t);
         if (ln == 0) tot[k] = t;
     };
     total(wv);
     if constexpr (EVAL) total(wv + NSUM);
+    if constexpr (FRAMES && PAIRS) {
+        if (wv == 0) total(NS);
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const double R = (double)A.R;
+        const double R = (double)n_rays;
         const float pos = (float)(tot[S_POS] / (3.0 * R));
         const float surf = (float)(tot[S_SURF] / R);
         const float smooth = (float)(tot[S_DX] / R) + (float)(tot[S_DY] / R);
         const float err = tot[S_ELEM] == 0.0 ? 0.f : (float)(tot[S_ERR] / tot[S_ELEM]);
         const float angle = (float)(tot[S_ANGLE] / R) / 3.14159265358979323846f * 180.f;
         if constexpr (PAIRS) {
-            const double L = (double)*A.n_label;
+            double L;
+            if constexpr (FRAMES) L = tot[NS];
+            else L = (double)*A.n_label;
             const float prob = (float)(tot[S_PROB] / L);   // L == 0: 0 / 0 = NaN, torch.mean of an empty tensor
             float net = A.pos_w * pos + A.prob_w * prob;
             if (A.surf_on) net += A.surf_w * surf;
             if (A.smooth_on) net += A.smooth_w * smooth;
-            A.loss[0] = pos, A.loss[1] = prob, A.loss[2] = surf, A.loss[3] = smooth, A.loss[4] = net;
-            A.loss[5] = (float)(tot[S_ACC] / R);
-            A.loss[6] = err;
-            A.loss[7] = angle;
+            loss[0] = pos, loss[1] = prob, loss[2] = surf, loss[3] = smooth, loss[4] = net;
+            loss[5] = (float)(tot[S_ACC] / R);
+            loss[6] = err;
+            loss[7] = angle;
         } else {
             float net = A.pos_w * pos;
             if (A.surf_on) net += A.surf_w * surf;
             if (A.smooth_on) net += A.smooth_w * smooth;
-            A.loss[0] = pos, A.loss[1] = surf, A.loss[2] = smooth, A.loss[3] = net, A.loss[4] = err, A.loss[5] = angle;
+            loss[0] = pos, loss[1] = surf, loss[2] = smooth, loss[3] = net, loss[4] = err, loss[5] = angle;
         }
         if constexpr (EVAL) {
-            float* out = A.loss + (PAIRS ? 8 : 6);
-            if (A.metrics) {
+            float* out = loss + (PAIRS ? 8 : 6);
+            if (metrics) {
 #pragma unroll
-                for (int i = 0; i < NMET; ++i) out[i] = A.metrics[i];
+                for (int i = 0; i < NMET; ++i) out[i] = metrics[i];
             } else {
                 depth_metric_stats(tot + NSUM, tot[S_ELEM], out);
             }
@@ -281,6 +344,16 @@ __global__ void lidf_eval_depth_images_kernel(const LossArgs A, const float* __r
                                               float* __restrict__ pred_img, float* __restrict__ gt_img) {
     const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= A.hw) return;
+    const int t = A.pix2ray[q];
+    pred_img[q] = t >= 0 ? A.pred_pos[3 * (size_t)t + 2] : A.xyz[3 * (size_t)q + 2];
+    gt_img[q] = xyz_gt[3 * (size_t)q + 2];
+}
+
+// The same two images for every frame of a batch ([B, hw] each): pix2ray holds the batch's ray numbers.
+__global__ void lidf_eval_depth_images_frames_kernel(const LossArgs A, const float* __restrict__ xyz_gt,
+                                                     float* __restrict__ pred_img, float* __restrict__ gt_img) {
+    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= (long long)A.B * A.hw) return;
     const int t = A.pix2ray[q];
     pred_img[q] = t >= 0 ? A.pred_pos[3 * (size_t)t + 2] : A.xyz[3 * (size_t)q + 2];
     gt_img[q] = xyz_gt[3 * (size_t)q + 2];
@@ -470,6 +543,38 @@ extern "C" hipError_t lidf_launch_eval_depth_images(const LossArgs& a, const flo
     if (a.hw <= 0) return hipSuccess;
     hipLaunchKernelGGL(lidf_eval_depth_images_kernel, dim3((unsigned)((a.hw + 255) / 256)), dim3(256), 0, st, a, xyz_gt,
                        pred_img, gt_img);
+    return hipGetLastError();
+}
+
+// The per-frame form: ceil(hw / 256) partial rows of 18 (stage 1: 19) doubles per frame, two launches.
+extern "C" size_t lidf_eval_loss_frames_partial_bytes(int B, long long hw, int pairs) {
+    if (B <= 0 || hw <= 0) return 0;
+    const long long blocks = (hw + LOSS_BLOCK - 1) / LOSS_BLOCK;
+    return (size_t)B * blocks * (NSUM + NMET + (pairs ? 1 : 0)) * sizeof(double);
+}
+
+extern "C" hipError_t lidf_launch_eval_loss_frames(const LossArgs& a, int pairs, hipStream_t st) {
+    if (a.R <= 0 || a.B <= 0 || a.hw <= 0) return hipSuccess;
+    const int blocks = (int)((a.hw + LOSS_BLOCK - 1) / LOSS_BLOCK);
+    const dim3 grid((unsigned)blocks, (unsigned)a.B);
+    if (pairs) {
+        hipLaunchKernelGGL((lidf_loss_kernel<true, true, true>), grid, dim3(LOSS_BLOCK), 0, st, a);
+        hipLaunchKernelGGL((lidf_loss_final_kernel<true, true, true>), dim3((unsigned)a.B), dim3(64 * NSUM), 0, st, a,
+                           blocks);
+    } else {
+        hipLaunchKernelGGL((lidf_loss_kernel<false, true, true>), grid, dim3(LOSS_BLOCK), 0, st, a);
+        hipLaunchKernelGGL((lidf_loss_final_kernel<false, true, true>), dim3((unsigned)a.B), dim3(64 * NSUM), 0, st, a,
+                           blocks);
+    }
+    return hipGetLastError();
+}
+
+extern "C" hipError_t lidf_launch_eval_depth_images_frames(const LossArgs& a, const float* xyz_gt, float* pred_img,
+                                                           float* gt_img, hipStream_t st) {
+    const long long n = (long long)a.B * a.hw;
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(lidf_eval_depth_images_frames_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a,
+                       xyz_gt, pred_img, gt_img);
     return hipGetLastError();
 }
 

@@ -10,6 +10,9 @@ Reference counterparts (paths relative to /root/reference/src):
   refine_loss          <- RefineNet.compute_loss                models/pipeline.py:760-919, the same three flavours
   refine_loss_composite  the same in plain torch ops
   LidfLossOptions      <- the loss.* keys of experiments/implicit_depth/default_config.yaml:97-107
+  per_frame=True       of the four losses: every frame of a batch gets the loss_dict test() reports at bs == 1
+                       (lidf_stage1_eval_loss_frames_f32 / lidf_refine_eval_loss_frames_f32), as [bs] tensors
+  frame_slice          the bs == 1 data_dict of one frame of a batch: what a per-frame row means
 
 compute_gt and lidf_loss run in liblidf_hip.so (csrc/lidf_loss.hip): one launch for the labels, two for the
 loss, one for its backward; no ray x voxel mask and no image-sized normal map is built, and nothing here
@@ -303,15 +306,135 @@ def _cfg(dd, opt, epoch):
             "hard_neg_ratio": opt.hard_neg_ratio, "hard_neg_select": opt.hard_neg_select}
 
 
-def _eval_loss(dd, opt, epoch, pairs, t):
+_PER_FRAME_TRAIN = ("%s: per_frame is the evaluation flavour's ('valid' / 'test': the loss_dict the reference's test() "
+                    "reports per frame at bs == 1); the training loss is one mean over the batch's rays and carries "
+                    "a backward — there is no per-frame training loss")
+_PER_FRAME_HARD_NEG = ("%s: per_frame with loss.hard_neg — there is no per-frame hard-negative select (the top-k of "
+                       "every term would be taken per frame); evaluate such frames one by one: "
+                       "losses.frame_slice(dd, b) and the bs == 1 call")
+
+
+def _refuse_per_frame(who, opt, exp_type):
+    if exp_type == "train":
+        raise NotImplementedError(_PER_FRAME_TRAIN % who)
+    if opt.hard_neg:
+        raise NotImplementedError(_PER_FRAME_HARD_NEG % who)
+
+
+def _nan_rows(keys, bs, dtype, device):
+    """The per-frame dict of a batch without a ray: no frame has a loss_dict (models/pipeline.py:686)."""
+    return {k: torch.full((bs,), float("nan"), dtype=dtype, device=device) for k in keys}
+
+
+def _frame_ends(bid, b):
+    """Device tensor [2]: first ray of frame b and of frame b + 1 in the grouped (non-decreasing) ray_bid."""
+    return torch.searchsorted(bid.contiguous(), torch.tensor([b, b + 1], dtype=bid.dtype, device=bid.device))
+
+
+_SLICE_FRAME_KEYS = ("xyz_flat", "xyz_corrupt_flat", "pred_depth", "pred_depth_refine")
+_SLICE_RAY_KEYS = ("ray_flat", "miss_flat_img_id", "gt_pos", "pred_pos", "pred_pos_refine")
+_SLICE_PAIR_KEYS = ("pcl_label", "pcl_label_float", "pred_prob_end", "pair_vox", "pair_t")
+
+
+def _n_pairs(dd):
+    """P of a data_dict, from any of its [P] lists."""
+    for k in ("pcl_label", "pair_vox", "pred_prob_end", "pair_ray"):
+        if k in dd:
+            return dd[k].shape[0]
+    raise KeyError("frame_slice: gt_max_pair_id without a pair list")
+
+
+def frame_slice(dd, b):
+    """The bs == 1 data_dict of frame b of a batch dict (lidf_forward's / FrameRunner.result()'s with the entries
+    loss_dict adds, compute_gt's entries where present), on any device: what lidf_loss / refine_loss / the composites /
+    pipeline.eval_metrics read, cut to the frame —
+      the frame's rows of xyz_flat / xyz_corrupt_flat / corrupt_mask / pred_depth / pred_depth_refine;
+      its rays (ray_flat, gt_pos, pred_pos, pred_pos_refine) with ray_bid 0;
+      its pairs (pcl_label, pred_prob_end, pair_vox, pair_t; pair_ray in the slice's ray numbers) with pair_off and
+      gt_max_pair_id re-based (a ray without pairs gets the slice's own P); voxel_bound stays whole (pair_vox indexes it);
+      pix2ray of the frame re-based to the slice's ray numbers; n_label, its own count of labelled pairs.
+    The rays must be grouped by frame (ray_bid non-decreasing, as every list of this package is). The two range ends
+    (and with pair_off the two pair ends) are read on the host in one copy. Row b of a per_frame=True loss is, bit for
+    bit, the bs == 1 loss of this dict; with loss.hard_neg it is the only route to a frame's numbers."""
+    bs, h, w = dd["bs"], dd["h"], dd["w"]
+    if not 0 <= b < bs:
+        raise IndexError("frame_slice: frame %d of a batch of %d" % (b, bs))
+    bid_key = "ray_bid" if "ray_bid" in dd else "miss_bid"
+    bid = dd[bid_key]
+    ends = _frame_ends(bid, b)
+    off = dd.get("pair_off")
+    if off is not None:
+        s, e, p0, p1 = torch.cat((ends.long(), off[ends].long())).tolist()
+    else:
+        s, e = ends.tolist()
+    out = {"bs": 1, "h": h, "w": w}
+    for k in _SLICE_FRAME_KEYS:
+        if k in dd:
+            out[k] = dd[k][b:b + 1]
+    if "corrupt_mask" in dd:
+        out["corrupt_mask"] = dd["corrupt_mask"].reshape(bs, h, w)[b:b + 1]
+    for k in ("ray_bid", "miss_bid"):
+        if k in dd:
+            out[k] = torch.zeros_like(dd[k][s:e])
+    for k in _SLICE_RAY_KEYS:
+        if k in dd:
+            out[k] = dd[k][s:e]
+    P = None
+    if off is not None:
+        P = p1 - p0
+        out["pair_off"] = off[s:e + 1] - p0
+        for k in _SLICE_PAIR_KEYS:
+            if k in dd:
+                out[k] = dd[k][p0:p1]
+        if "pair_ray" in dd:
+            out["pair_ray"] = dd["pair_ray"][p0:p1] - s
+    elif "pair_ray" in dd:   # (pairs in any order, the reference's voxel-major one included: a mask, not a range)
+        ray = dd["pair_ray"]
+        keep = (ray >= s) & (ray < e)
+        out["pair_ray"] = ray[keep] - s
+        P = int(out["pair_ray"].shape[0])
+        for k in _SLICE_PAIR_KEYS:
+            if k in dd:
+                out[k] = dd[k][keep]
+    if "voxel_bound" in dd:
+        out["voxel_bound"] = dd["voxel_bound"]
+    if "gt_max_pair_id" in dd and off is not None:
+        gm = dd["gt_max_pair_id"][s:e]
+        out["gt_max_pair_id"] = torch.where(gm >= _n_pairs(dd), torch.full_like(gm, P), gm - p0)
+    if "pcl_label" in out and ("n_label" in dd or "gt_max_pair_id" in out):
+        out["n_label"] = (out["pcl_label"] != 0).sum().to(torch.int32)
+    if "pix2ray" in dd:
+        t = dd["pix2ray"][b * h * w:(b + 1) * h * w]
+        out["pix2ray"] = torch.where(t >= 0, t - s, t)
+    return out
+
+
+def _per_frame_composite(fn, keys, who, dd, opt, exp_type, epoch, pred_key):
+    """per_frame=True of a composite: fn on frame_slice(dd, b) for every frame, stacked to [bs] tensors in the dtype
+    and on the device of dd[pred_key]; a frame without a ray gives NaN entries."""
+    _refuse_per_frame(who, opt, exp_type)
+    pred = dd[pred_key]
+    nan = torch.full((), float("nan"), dtype=pred.dtype, device=pred.device)
+    rows = []
+    for b in range(dd["bs"]):
+        fd = frame_slice(dd, b)
+        rows.append(fn(fd, opt, exp_type, epoch) if fd[pred_key].shape[0] else {k: nan for k in keys})
+    return {k: torch.stack([r[k].reshape(()) for r in rows]) for k in keys}
+
+
+def _eval_loss(dd, opt, epoch, pairs, t, per_frame=False):
     """The evaluation flavour (exp_type 'valid' / 'test', models/pipeline.py:468-650, 760-919) of either stage over
     the checked tensors `t` (LidfEvalLossArgs' names): lidf_stage1_eval_loss_f32 / lidf_refine_eval_loss_f32, two
     launches (bs == 1, the resized-frame statistics: a memset and four). Forward only: every entry is detached, no
     autograd node is made, and the unreduced [R] / [P] terms are allocated under hard_neg alone. Nothing is read
-    back, except the label count of stage 1 under hard_neg with hard_neg_select "torch"."""
+    back, except the label count of stage 1 under hard_neg with hard_neg_select "torch".
+    per_frame: lidf_stage1_eval_loss_frames_f32 / lidf_refine_eval_loss_frames_f32 — the resized-frame branch for
+    every frame of the batch (a memset and four launches), [bs] tensors; at bs == 1 the plain call, reshaped."""
     from .query import _seg_mask_arg
     who = "lidf_loss" if pairs else "refine_loss"
     bs, h, w = dd["bs"], dd["h"], dd["w"]
+    if per_frame and bs == 1:
+        return {k: v.reshape(1) for k, v in _eval_loss(dd, opt, epoch, pairs, t).items()}
     base, xyz = dd["xyz_corrupt_flat"], dd["xyz_flat"]
     _lib.require_cuda(base, names=["xyz_corrupt_flat"])
     _f32(base, "xyz_corrupt_flat")
@@ -320,7 +443,7 @@ def _eval_loss(dd, opt, epoch, pairs, t):
     dev = xyz.device
     R, P = t["gt_pos"].shape[0], (t["pcl_label"].shape[0] if pairs else 0)
     cfg = _cfg(dd, opt, epoch)
-    resize = bs == 1   # (the reference's branch, models/pipeline.py:572, 844)
+    resize = bs == 1 or per_frame   # (the reference's branch, models/pipeline.py:572, 844)
     t = dict(t, xyz_base=base)
     seg_dtype = 0
     if resize:
@@ -328,12 +451,34 @@ def _eval_loss(dd, opt, epoch, pairs, t):
             raise RuntimeError("%s: at bs == 1 the statistics are masked by dd['corrupt_mask'] "
                                "(models/pipeline.py:587-590), which dd lacks" % who)
         mask = dd["corrupt_mask"]
-        if mask.numel() != h * w:
+        if mask.numel() != bs * h * w:
             raise RuntimeError("%s: corrupt_mask must hold bs*h*w elements" % who)
         t["xyz_gt"] = xyz
-        t["seg_mask"], seg_dtype = _seg_mask_arg(mask.reshape(h, w))
+        t["seg_mask"], seg_dtype = _seg_mask_arg(mask.reshape(bs, h, w))
     f32 = dict(dtype=torch.float32, device=dev)
-    out = {"loss": torch.empty((len(EVAL_LOSS_KEYS if pairs else REFINE_EVAL_LOSS_KEYS),), **f32)}
+    keys = EVAL_LOSS_KEYS if pairs else REFINE_EVAL_LOSS_KEYS
+    if per_frame:
+        L = _lib.lib()
+        size_fn, loss_fn = (
+            (L.lidf_stage1_eval_loss_frames_workspace_bytes, L.lidf_stage1_eval_loss_frames_f32) if pairs else
+            (L.lidf_refine_eval_loss_frames_workspace_bytes, L.lidf_refine_eval_loss_frames_f32))
+        loss = torch.empty((bs, len(keys)), **f32)
+        wsb = size_fn(bs, h, w)
+        ws = _lib.workspace(wsb, dev)
+        a = _lib.LidfEvalLossArgs()
+        a.n_rays, a.n_pairs = R, P
+        a.batch, a.height, a.width, a.resize_metrics, a.seg_dtype = bs, h, w, 1, seg_dtype
+        a.pos_w, a.prob_w = cfg["pos_w"], cfg["prob_w"]
+        a.surf_norm_w, a.smooth_w = cfg["surf_norm_w"], cfg["smooth_w"]
+        a.surf_norm_on, a.smooth_on = int(cfg["surf_on"]), int(cfg["smooth_on"])
+        for k, v in t.items():
+            if v is not None and k != "n_label":   # (every frame counts its own labelled pairs)
+                setattr(a, k, v.data_ptr())
+        a.loss, a.workspace, a.workspace_bytes = loss.data_ptr(), ws.data_ptr(), wsb
+        with torch.no_grad(), torch.cuda.device(dev):
+            _lib.check(loss_fn(C.byref(a), _lib.current_stream(dev)))
+        return {k: loss[:, i] for i, k in enumerate(keys)}
+    out = {"loss": torch.empty((len(keys),), **f32)}
     if cfg["hard_neg"]:
         out.update({k: torch.empty((R,), **f32) for k in ("pos_unreduced", "surf_norm_dist", "dx_dist", "dy_dist")})
         if pairs:
@@ -368,7 +513,7 @@ def _eval_loss(dd, opt, epoch, pairs, t):
     return {k: loss[i] for i, k in enumerate(EVAL_LOSS_KEYS if pairs else REFINE_EVAL_LOSS_KEYS)}
 
 
-def lidf_loss(dd, loss_opt=None, exp_type="train", epoch=0, normal_maps=False):
+def lidf_loss(dd, loss_opt=None, exp_type="train", epoch=0, normal_maps=False, per_frame=False):
     """LIDF.compute_loss for exp_type == 'train' (models/pipeline.py:468-566) on lidf_forward_train's data_dict
     (compute_gt's entries + pred_pos [R,3] and pred_prob_end [P,1] of lidf_query_train): the reference's loss_dict
     — pos_loss, prob_loss, surf_norm_loss, smooth_loss, loss_net, acc, err, angle_err — as 0-dim device tensors.
@@ -385,10 +530,19 @@ def lidf_loss(dd, loss_opt=None, exp_type="train", epoch=0, normal_maps=False):
     gt_pos when dd['bs'] != 1, over the 144 x 256 resize of the frame masked by gt > 0 and dd['corrupt_mask'] when
     dd['bs'] == 1 (bit-equal to pipeline.eval_metrics on the same depth image). A dict without xyz_corrupt_flat (the
     training step's own) has no evaluation flavour: NotImplementedError. hard_neg applies as in training, by
-    either hard_neg_select route; without it no [R] / [P] term buffer is allocated."""
+    either hard_neg_select route; without it no [R] / [P] term buffer is allocated.
+
+    per_frame=True ('valid' / 'test' only): the same keys in the same order, each a detached float32 [bs] device
+    tensor — entry b is what this call returns for frame b alone at bs == 1 (frame_slice(dd, b)), bit for bit: the
+    loss_dict the reference's test() reports per frame, the nine statistics over that frame's 144 x 256 resize. One
+    call (lidf_stage1_eval_loss_frames_f32: a memset and four launches), no host read; the rays must be grouped by
+    frame. A frame without a ray has no loss_dict in the reference: its entries are NaN (a batch without any ray:
+    all NaN, no error). 'train' and loss.hard_neg raise NotImplementedError; bs == 1 is the plain call as [1]."""
     opt = loss_opt or LidfLossOptions()
     _base_cloud(dd, exp_type, "lidf_loss")
     _check_types(opt)
+    if per_frame:
+        _refuse_per_frame("lidf_loss", opt, exp_type)
     pred_pos, pred_prob = dd["pred_pos"], dd["pred_prob_end"]
     _lib.require_cuda(pred_pos, pred_prob, dd["xyz_flat"], names=["pred_pos", "pred_prob_end", "xyz_flat"])
     _f32(pred_pos, "pred_pos"), _f32(pred_prob, "pred_prob_end")
@@ -415,6 +569,8 @@ def lidf_loss(dd, loss_opt=None, exp_type="train", epoch=0, normal_maps=False):
                            "belong to one frame batch and ray set: [bs,h*w,3] / [R+1] int32 / [bs*h*w] int32 / [R] "
                            "/ gt_pos [R,3], pcl_label [P] and gt_max_pair_id [R] int64, n_label int32 — run "
                            "compute_gt(dd) again")
+    if R == 0 and per_frame:
+        return _nan_rows(EVAL_LOSS_KEYS, dd["bs"], torch.float32, xyz.device)
     if R == 0:
         raise RuntimeError("lidf_loss: no ray (the reference returns before compute_loss, models/pipeline.py:686)")
     if exp_type != "train":
@@ -423,7 +579,7 @@ def lidf_loss(dd, loss_opt=None, exp_type="train", epoch=0, normal_maps=False):
         t = {"ray_bid": ray_bid, "ray_flat": ray_flat, "pair_off": pair_off, "pix2ray": pix2ray, "gt_pos": gt[0],
              "pcl_label": gt[1], "gt_max_pair_id": gt[2], "n_label": gt[3].reshape(1),
              "pred_pos": pred_pos.detach().contiguous(), "pred_prob": pred_prob.detach().reshape(-1).contiguous()}
-        return _eval_loss(dd, opt, epoch, True, t)
+        return _eval_loss(dd, opt, epoch, True, t, per_frame)
     maps = None
     if normal_maps:
         shape = (dd["bs"], 3, dd["h"], dd["w"])
@@ -554,16 +710,21 @@ def _composite_terms(dd, pred_pos, gt_pos, opt, base="xyz_flat"):
     return reduce, pos_loss, surf_norm_loss, smooth_loss, angle_err, err
 
 
-def lidf_loss_composite(dd, loss_opt=None, exp_type="train", epoch=0):
+def lidf_loss_composite(dd, loss_opt=None, exp_type="train", epoch=0, per_frame=False):
     """lidf_loss written in differentiable torch ops, in the dtype of pred_pos, on any device: per-ray
     log-softmax by scatter reductions, the normals by gathering each sampled pixel's right and lower neighbour.
     Needs gt_pos and pcl_label in dd (compute_gt's, or a caller's own); every entry of the returned loss_dict
     carries its graph. It takes many small launches where lidf_loss takes three.
     exp_type 'valid' / 'test': the evaluation flavour (dd['xyz_corrupt_flat'] as the base cloud; the nine statistics
-    appended, and dd['corrupt_mask'] read, as lidf_loss describes); its entries are detached."""
+    appended, and dd['corrupt_mask'] read, as lidf_loss describes); its entries are detached.
+    per_frame=True ('valid' / 'test', no hard_neg): this function on frame_slice(dd, b) for every frame, as [bs]
+    tensors; a frame without a ray gives NaN entries."""
     opt = loss_opt or LidfLossOptions()
     base = _base_cloud(dd, exp_type, "lidf_loss_composite")
     _check_types(opt)
+    if per_frame:
+        return _per_frame_composite(lidf_loss_composite, EVAL_LOSS_KEYS, "lidf_loss_composite", dd, opt, exp_type,
+                                    epoch, "pred_pos")
     pred_pos, logit = dd["pred_pos"], dd["pred_prob_end"].reshape(-1)
     dt, dev = pred_pos.dtype, pred_pos.device
     gt_pos, label = dd["gt_pos"].to(dt), dd["pcl_label"].long()
@@ -671,7 +832,7 @@ class _RefineLossFn(torch.autograd.Function):
         return (t["g_pred_pos"].reshape(ctx.shape),) + (None,) * 7
 
 
-def refine_loss(dd, loss_opt=None, exp_type="train", epoch=0, normal_maps=False):
+def refine_loss(dd, loss_opt=None, exp_type="train", epoch=0, normal_maps=False, per_frame=False):
     """RefineNet.compute_loss for exp_type == 'train' (models/pipeline.py:760-840) on the data_dict of the stage-2
     training step (pred_pos_refine [R,3], xyz_flat, the sampled rays): the reference's loss_dict — pos_loss,
     surf_norm_loss, smooth_loss, loss_net, err, angle_err — as 0-dim device tensors. loss_net carries the graph (one
@@ -685,10 +846,14 @@ def refine_loss(dd, loss_opt=None, exp_type="train", epoch=0, normal_maps=False)
     train_refine_hardneg.yaml is LidfLossOptions(hard_neg=True, hard_neg_ratio=0.1, pos_w=20.0, surf_norm_w=2.0).
     normal_maps=True adds pred_surf_norm_img_refine [bs,3,h,w] to dd (:894, visualisation only).
     exp_type 'valid' / 'test' (:760-919): the evaluation flavour as in lidf_loss — REFINE_EVAL_LOSS_KEYS, detached,
-    dd['xyz_corrupt_flat'] as the base cloud, the nine statistics by dd['bs'] == 1 or not."""
+    dd['xyz_corrupt_flat'] as the base cloud, the nine statistics by dd['bs'] == 1 or not.
+    per_frame=True: as lidf_loss's — [bs] tensors, entry b the bs == 1 call on frame_slice(dd, b) bit for bit
+    (lidf_refine_eval_loss_frames_f32), NaN for a frame without a ray; 'train' and hard_neg are refused."""
     opt = loss_opt or LidfLossOptions()
     _base_cloud(dd, exp_type, "refine_loss")
     _check_types(opt, prob=False)
+    if per_frame:
+        _refuse_per_frame("refine_loss", opt, exp_type)
     pred = dd["pred_pos_refine"]
     _lib.require_cuda(pred, dd["xyz_flat"], names=["pred_pos_refine", "xyz_flat"])
     _f32(pred, "pred_pos_refine")
@@ -707,6 +872,8 @@ def refine_loss(dd, loss_opt=None, exp_type="train", epoch=0, normal_maps=False)
         raise RuntimeError("refine_loss: pred_pos_refine / gt_pos / xyz_flat / pix2ray / ray index do not belong to "
                            "one frame batch and ray set: [R,3] / [R,3] / [bs,h*w,3] / [bs*h*w] int32 / [R] — run "
                            "compute_gt(dd) again")
+    if R == 0 and per_frame:
+        return _nan_rows(REFINE_EVAL_LOSS_KEYS, bs, torch.float32, xyz.device)
     if R == 0:
         raise RuntimeError("refine_loss: no ray (the reference returns before stage 2, models/pipeline.py:686)")
     if exp_type != "train":
@@ -714,7 +881,7 @@ def refine_loss(dd, loss_opt=None, exp_type="train", epoch=0, normal_maps=False)
             raise NotImplementedError("refine_loss: normal_maps is the training flavour's")
         t = {"ray_bid": ray_bid, "ray_flat": ray_flat, "pix2ray": pix2ray, "gt_pos": gt_pos,
              "pred_pos": pred.detach().contiguous()}
-        return _eval_loss(dd, opt, epoch, False, t)
+        return _eval_loss(dd, opt, epoch, False, t, per_frame)
     img = None
     if normal_maps:
         img = torch.empty((bs, 3, h, w), dtype=torch.float32, device=pred.device)
@@ -727,13 +894,17 @@ def refine_loss(dd, loss_opt=None, exp_type="train", epoch=0, normal_maps=False)
     return out
 
 
-def refine_loss_composite(dd, loss_opt=None, exp_type="train", epoch=0):
+def refine_loss_composite(dd, loss_opt=None, exp_type="train", epoch=0, per_frame=False):
     """refine_loss written in differentiable torch ops, in the dtype of pred_pos_refine, on any device (the A/B
     partner of refine_loss and the route for CPU callers). Needs gt_pos in dd; every entry of the returned loss_dict
-    carries its graph. exp_type 'valid' / 'test': the evaluation flavour, as lidf_loss_composite's."""
+    carries its graph. exp_type 'valid' / 'test': the evaluation flavour, as lidf_loss_composite's; per_frame=True
+    as there."""
     opt = loss_opt or LidfLossOptions()
     base = _base_cloud(dd, exp_type, "refine_loss_composite")
     _check_types(opt, prob=False)
+    if per_frame:
+        return _per_frame_composite(refine_loss_composite, REFINE_EVAL_LOSS_KEYS, "refine_loss_composite", dd, opt,
+                                    exp_type, epoch, "pred_pos_refine")
     pred = dd["pred_pos_refine"]
     gt_pos = dd["gt_pos"].to(pred.dtype)
     _, pos_loss, surf_norm_loss, smooth_loss, angle_err, err = _composite_terms(dd, pred, gt_pos, opt, base)

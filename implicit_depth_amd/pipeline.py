@@ -394,23 +394,30 @@ def refine_forward(dd, pnet_model_refine, offset_dec_refine, opt=None, precision
 
 def eval_metrics(dd, key="pred_depth", frame=0):
     """The nine ClearGrasp statistics of LIDF.compute_loss's bs == 1 branch
-    (models/pipeline.py:577-627) for one frame, on the device."""
+    (models/pipeline.py:577-627) for one frame, on the device. frame=None: every frame of the batch in one call
+    (query.depth_metrics_frames), [bs] tensors whose entry b is the frame=b call's, bit for bit."""
     h, w = dd["h"], dd["w"]
+    if frame is None:
+        bs = dd["bs"]
+        gt = dd["xyz_flat"][:, :, 2].reshape(bs, h, w).contiguous()
+        return Q.depth_metrics_frames(dd[key].contiguous(), gt, dd["corrupt_mask"].reshape(bs, h, w))
     gt = dd["xyz_flat"][frame, :, 2].reshape(h, w).contiguous()
     return Q.depth_metrics(dd[key][frame].contiguous(), gt, dd["corrupt_mask"][frame])
 
 
-def eval_loss(dd, loss_opt=None, exp_type="valid", epoch=0, stage=1):
+def eval_loss(dd, loss_opt=None, exp_type="valid", epoch=0, stage=1, per_frame=False):
     """loss_dict of LIDF.forward(batch, 'valid' | 'test', epoch) (stage=1, models/pipeline.py:704-710) or of
     RefineNet.forward (stage=2, :1032-1041) on the data_dict of lidf_forward / refine_forward: compute_gt where its
     entries are missing, then losses.lidf_loss / losses.refine_loss in the evaluation flavour — the number a
-    trainer's validate() picks its best checkpoint by. Every entry is a detached 0-dim device tensor."""
+    trainer's validate() picks its best checkpoint by. Every entry is a detached 0-dim device tensor.
+    per_frame=True: every entry a [bs] tensor, entry b the loss_dict of frame b alone at bs == 1 — what the
+    reference's test() reports per frame (losses.lidf_loss; losses.frame_slice(dd, b) is that frame's dict)."""
     from .losses import lidf_loss, refine_loss
     if stage not in (1, 2):
         raise ValueError("stage must be 1 or 2, not %r" % (stage,))
     if exp_type not in ("valid", "test"):
         raise ValueError("eval_loss is the evaluation flavour: exp_type 'valid' or 'test', not %r" % (exp_type,))
-    return (lidf_loss if stage == 1 else refine_loss)(dd, loss_opt, exp_type, epoch)
+    return (lidf_loss if stage == 1 else refine_loss)(dd, loss_opt, exp_type, epoch, per_frame=per_frame)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -920,12 +927,13 @@ class FrameRunner:
             dd["pred_depth_refine"] = b["pred_depth_refine"]
         return ok, dd
 
-    def loss_dict(self, batch, loss_opt=None, exp_type="valid", epoch=0):
+    def loss_dict(self, batch, loss_opt=None, exp_type="valid", epoch=0, per_frame=False):
         """What a trainer's validate() / test() reads after a frame: eval_loss on result()'s data_dict plus what it
         lacks — xyz_flat, xyz_corrupt_flat and corrupt_mask of `batch`. Returns (success, loss_dict of stage 1,
         loss_dict of stage 2 — {} without refinement); success False (an early exit of the frame): two empty dicts.
         It reads the frame's counts as result() does and touches neither the frame call, its graph nor its
-        workspace."""
+        workspace. per_frame=True: [bs] tensors, entry b the bs == 1 loss_dict of frame b (eval_loss), with no host
+        read beyond the counts."""
         ok, dd = self.result()
         if not ok:
             return False, {}, {}
@@ -933,13 +941,19 @@ class FrameRunner:
         dd["xyz_flat"] = batch["xyz"].permute(0, 2, 3, 1).contiguous().reshape(bs, -1, 3)
         dd["xyz_corrupt_flat"] = batch["xyz_corrupt"].permute(0, 2, 3, 1).contiguous().reshape(bs, -1, 3)
         dd["corrupt_mask"] = batch["corrupt_mask"].reshape(bs, self.h, self.w)
-        loss1 = eval_loss(dd, loss_opt, exp_type, epoch, stage=1)
-        return True, loss1, (eval_loss(dd, loss_opt, exp_type, epoch, stage=2) if self.refine else {})
+        loss1 = eval_loss(dd, loss_opt, exp_type, epoch, stage=1, per_frame=per_frame)
+        return True, loss1, (eval_loss(dd, loss_opt, exp_type, epoch, stage=2, per_frame=per_frame)
+                             if self.refine else {})
 
     def metrics(self, batch, key=None, frame=0):
         """The nine ClearGrasp statistics (models/pipeline.py:577-627) of frame `frame` on the device:
-        xyz[frame, 2] of the NCHW batch is the ground-truth depth map as it lies (no copy)."""
+        xyz[frame, 2] of the NCHW batch is the ground-truth depth map as it lies (no copy). frame=None: every frame
+        in one call (query.depth_metrics_frames; the depth planes are gathered into one [bs,h,w] tensor), [bs]
+        tensors whose entry b is the frame=b call's, bit for bit."""
         key = key or ("pred_depth_refine" if self.refine else "pred_depth")
+        if frame is None:
+            return Q.depth_metrics_frames(self.buf[key], batch["xyz"][:, 2].contiguous(),
+                                          batch["corrupt_mask"].reshape(self.bs, self.h, self.w))
         seg = batch["corrupt_mask"].reshape(self.bs, self.h, self.w)[frame]
         return Q.depth_metrics(self.buf[key][frame], batch["xyz"][frame, 2], seg)
 
@@ -963,9 +977,11 @@ class FramePipeline:
 
     data_dict holds views of a runner's buffers, valid until the submit() that reuses the runner (the one
     after S - 1 further submits). A runner's stream waits for the caller's current stream before it starts
-    a frame: inputs produced there and reads of the previous result enqueued there are ordered before it."""
+    a frame: inputs produced there and reads of the previous result enqueued there are ordered before it.
+    metrics_frame: the frame whose statistics submit() records (FrameRunner.metrics' `frame`; default 0); None
+    records every frame of the batch in one call, [bs] tensors."""
 
-    def __init__(self, streams, bs, h, w, device, *models, with_metrics=True, **kw):
+    def __init__(self, streams, bs, h, w, device, *models, with_metrics=True, metrics_frame=0, **kw):
         if streams < 1:
             raise ValueError("streams must be >= 1")
         self.dev = torch.device(device)
@@ -984,6 +1000,7 @@ class FramePipeline:
         self.runners = [FrameRunner(bs, h, w, device, *models, sampler_state=states[k], **kw) for k in range(streams)]
         self.lanes = [torch.cuda.Stream(self.dev) for _ in range(streams)]
         self.with_metrics = with_metrics
+        self.metrics_frame = metrics_frame   # FrameRunner.metrics' frame: None records every frame ([bs] tensors)
         self.pending = []          # [(slot, metrics)] in submission order
         self.n = 0
 
@@ -1007,7 +1024,7 @@ class FramePipeline:
                 t.record_stream(lane)
         with torch.cuda.stream(lane), torch.no_grad():
             self.runners[slot].run(batch, full_rgb_feat, pred_mask, valid_idx=valid_idx)
-            m = self.runners[slot].metrics(batch) if self.with_metrics else None
+            m = self.runners[slot].metrics(batch, frame=self.metrics_frame) if self.with_metrics else None
         self.pending.append((slot, m))
 
     def collect(self):

@@ -943,6 +943,42 @@ def depth_metrics(pred_depth, gt_depth, seg_mask=None, out_size=(144, 256)):
     return res
 
 
+_METRICS_FRAMES_WS = {}   # (device index, stream, batch) -> zeroed workspace of lidf_depth_metrics_frames_f32
+
+
+def depth_metrics_frames(pred_depth, gt_depth, seg_mask=None, out_size=(144, 256)):
+    """depth_metrics for every frame of a batch in one launch (lidf_depth_metrics_frames_f32): pred_depth / gt_depth
+    [B,h,w] f32, seg_mask [B,h,w] float32 / bool / uint8 or None. Returns METRIC_NAMES + "count", each a [B] device
+    tensor; entry b is bit for bit what depth_metrics gives for frame b (NaN with count 0 for a frame without a valid
+    pixel). Every frame has its own arrival ticket and partial sums in the workspace, which is zero-filled once per
+    (device, stream, B) and left zero by every call."""
+    _lib.require_cuda(pred_depth, gt_depth, names=["pred_depth", "gt_depth"])
+    _f32(pred_depth, "pred_depth"), _f32(gt_depth, "gt_depth")
+    if pred_depth.dim() != 3 or pred_depth.shape != gt_depth.shape:
+        raise RuntimeError("pred_depth and gt_depth must be [B,h,w] tensors of the same shape")
+    B, h, w = pred_depth.shape
+    if seg_mask is not None and seg_mask.shape != pred_depth.shape:
+        raise RuntimeError("seg_mask must have the shape of the depth maps")
+    seg_mask, seg_dtype = _seg_mask_arg(seg_mask)
+    dh, dw = (h, w) if out_size is None else out_size
+    dev = pred_depth.device
+    out = torch.empty((B, 10), dtype=torch.float32, device=dev)
+    if B:
+        L = _lib.lib()
+        key = (dev.index, torch.cuda.current_stream(dev).cuda_stream, B)
+        ws = _METRICS_FRAMES_WS.get(key)
+        if ws is None:
+            ws = _METRICS_FRAMES_WS[key] = torch.zeros((L.lidf_depth_metrics_frames_workspace_bytes(B),),
+                                                       dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.lidf_depth_metrics_frames_f32(
+                _lib.ptr(pred_depth), _lib.ptr(gt_depth), _lib.ptr(seg_mask) if seg_mask is not None else None,
+                seg_dtype, B, h, w, dh, dw, _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)))
+    res = {k: out[:, i] for i, k in enumerate(METRIC_NAMES)}
+    res["count"] = out[:, 9]
+    return res
+
+
 # ------------------------------------------------------------------------------------------------
 # Training path of the query (gradients to vox_feat, feat_grid and the decoders' parameters)
 # ------------------------------------------------------------------------------------------------

@@ -42,7 +42,9 @@ enum lidf_status {
  * workspace-size functions and lidf_stage1_eval_hard_neg_f32 / lidf_refine_eval_hard_neg_f32), and after those
  * lidf_miss_window_workspace_bytes / lidf_miss_ray_window_f32, and after those struct LidfFrameWidths with
  * lidf_frame_widths_workspace_bytes / _pack_bytes / _pack_guard_bytes / lidf_frame_widths_f32, and after those
- * lidf_decoder_chain_split_workspace_bytes / lidf_decoder_chain_split_f32, were added
+ * lidf_decoder_chain_split_workspace_bytes / lidf_decoder_chain_split_f32, and after those the per-frame
+ * evaluation entries lidf_depth_metrics_frames_workspace_bytes / lidf_depth_metrics_frames_f32 and
+ * lidf_stage1_eval_loss_frames_f32 / lidf_refine_eval_loss_frames_f32 with their workspace-size functions, were added
  * WITHOUT a bump: they are purely additive (no signature or struct layout changed), so the number stays 14; a
  * binding that needs them looks the symbols up and asks for a rebuild when an ABI-14 library lacks them
  * (implicit_depth_amd/_lib.py does). */
@@ -866,6 +868,19 @@ int lidf_depth_metrics_f32(const float* pred_depth, const float* gt_depth, const
                            int32_t seg_dtype, int32_t src_h, int32_t src_w, int32_t dst_h, int32_t dst_w,
                            float* out, void* workspace, size_t workspace_bytes, lidf_stream_t stream);
 
+/* The same for every frame of a batch in ONE launch (added without a bump of ABI 14: purely additive).
+ * pred_depth / gt_depth [batch, src_h, src_w], seg_mask [batch, src_h, src_w] in seg_dtype's element type or NULL,
+ * out [batch, 10]: row b is bit for bit what lidf_depth_metrics_f32 writes for frame b alone — every frame is
+ * summed by its own workgroups in that call's pixel order, counted by its own ticket word and added in its own
+ * workgroup order. workspace: lidf_depth_metrics_frames_workspace_bytes(batch) bytes (batch times the one-frame
+ * size), 8-byte aligned, ZERO-FILLED ONCE by the caller; a call leaves it all zero. batch == 0 returns LIDF_OK
+ * without a launch; batch > 65535 is LIDF_ERR_UNSUPPORTED.                                                       */
+size_t lidf_depth_metrics_frames_workspace_bytes(int32_t batch);
+int lidf_depth_metrics_frames_f32(const float* pred_depth, const float* gt_depth, const void* seg_mask,
+                                  int32_t seg_dtype, int32_t batch, int32_t src_h, int32_t src_w, int32_t dst_h,
+                                  int32_t dst_w, float* out, void* workspace, size_t workspace_bytes,
+                                  lidf_stream_t stream);
+
 /* ---- A whole decoder at gf_dim 32 / 64 / 128 as ONE launch (ABI 12) ------------------------------------------
  * IMNet / IEF (models/implicit_net.py:60-152: gf_dim is a constructor argument) with layer 1 factorised as the
  * fixed-width kernels have it: x [n, k] (row stride ldx) are the per-row operand columns — they multiply
@@ -1361,7 +1376,8 @@ typedef struct LidfEvalLossArgs {
     int32_t resize_metrics;         /* 0: statistics over the rays; else over the resized frame (batch 1) */
     const float* xyz_base;          /* [B, h*w, 3] xyz_corrupt_flat */
     const float* xyz_gt;            /* [B, h*w, 3] xyz_flat: read under resize_metrics only */
-    const void* seg_mask;           /* [h, w] corrupt_mask of the frame, or NULL: resize_metrics only */
+    const void* seg_mask;           /* [h, w] corrupt_mask of the frame, or NULL: resize_metrics only
+                                       (lidf_*_eval_loss_frames_f32: [B, h, w]) */
     int32_t seg_dtype;
     const int32_t* ray_bid;         /* [R] */
     const int32_t* ray_flat;        /* [R] */
@@ -1392,6 +1408,42 @@ int lidf_stage1_eval_hard_neg_f32(const LidfEvalLossArgs* args, double ratio, vo
                                   size_t workspace_bytes, lidf_stream_t stream);
 int lidf_refine_eval_hard_neg_f32(const LidfEvalLossArgs* args, double ratio, void* workspace,
                                   size_t workspace_bytes, lidf_stream_t stream);
+
+/* ---- The evaluation losses PER FRAME of a batch (added without a bump of ABI 14: purely additive) -------------
+ * The reference reports its evaluation numbers from test() at bs == 1: one loss_dict per frame, the nine
+ * statistics over the 144 x 256 resize of that frame. These two entries give every frame of a batch that
+ * loss_dict in one call: loss is [batch, 17] (stage 2: [batch, 15]), and ROW b IS, BIT FOR BIT, what
+ * lidf_stage1_eval_loss_f32 / lidf_refine_eval_loss_f32 write at batch == 1 with resize_metrics != 0 for frame b
+ * cut out of the batch (its rows of xyz_base / xyz_gt / seg_mask, its rays with ray_bid 0, its pairs with pair_off
+ * and gt_max_pair_id re-based — a ray without pairs holding that frame's own n_pairs —, pix2ray re-based to its
+ * ray numbers, n_label its own count of labelled pairs). NaN entries included: prob_loss and loss_net of a frame
+ * whose pairs carry no label, the nine statistics of a frame without a valid pixel (err stays 0).
+ * A frame WITHOUT A RAY has no loss_dict in the reference (it returns early, :686): its row is all NaN.
+ *   grouping     the rays of a batch must be grouped by frame: ray_bid non-decreasing, as every list this library
+ *                produces is (torch.nonzero's order, lidf_miss_ray_fill_f32, lidf_miss_ray_window_f32). Frame b
+ *                owns the rays [s_b, s_(b+1)), s_b = the first index with ray_bid >= b, found on the device — no
+ *                size is read on the host. With a ray_bid that is NOT grouped the numbers are unspecified; no
+ *                index leaves its array even then (the ranges lie in [0, n_rays], a frame's partial rows are
+ *                clamped to its own, and every ray still reads its own pixel and its own pairs).
+ *   the struct   is taken as it is: batch, height, width, the inputs and the weights as for lidf_*_eval_loss_f32,
+ *                ray and pair indices the batch's global ones. xyz_gt is required, seg_mask is [batch, h, w] (or
+ *                NULL), resize_metrics is not read (the resized-frame branch is taken for every frame) and n_label
+ *                is not read (each frame counts its own labelled pairs). pos_unreduced / surf_norm_dist / dx_dist /
+ *                dy_dist / prob_unreduced must be NULL — LIDF_ERR_BAD_ARG otherwise: there is no per-frame
+ *                hard-negative select (evaluate such frames one by one).
+ *   launches     a memset of the statistics' workspace and four launches: the depth images of every frame, the
+ *                statistics of every frame (lidf_depth_metrics_frames_f32's kernel), the per-ray terms in blocks
+ *                of 256 rays counted from each frame's first ray (ceil(h * w / 256) blocks per frame — a ray is a
+ *                distinct pixel, so no frame has more; blocks beyond a frame's rays leave at once), one workgroup
+ *                per frame for the means. Double partial sums in a fixed order, no float atomics: bit-identical
+ *                from run to run. Everything is enqueued on `stream`.
+ * batch == 0 or n_rays == 0 returns LIDF_OK after filling loss with NaN (a memset on `stream`, no launch).
+ * batch > 65535 is LIDF_ERR_UNSUPPORTED.
+ * Workspace: lidf_*_eval_loss_frames_workspace_bytes(batch, height, width), 8-byte aligned, any contents.   */
+size_t lidf_stage1_eval_loss_frames_workspace_bytes(int32_t batch, int32_t height, int32_t width);
+size_t lidf_refine_eval_loss_frames_workspace_bytes(int32_t batch, int32_t height, int32_t width);
+int lidf_stage1_eval_loss_frames_f32(const LidfEvalLossArgs* args, lidf_stream_t stream);
+int lidf_refine_eval_loss_frames_f32(const LidfEvalLossArgs* args, lidf_stream_t stream);
 
 #ifdef __cplusplus
 }
