@@ -27,14 +27,10 @@ __global__ void __launch_bounds__(256) lidf_embed_kernel(const float* __restrict
             const float v = x[3 * (row0 + r) + c];
             float* w = tile + r * E;
             w[c] = v;
-            const float C_HI = 0.15915493667125702f, C_LO = 6.4206383e-09f;  // 1/(2 pi) = hi + lo
-            const float hi = v * C_HI;
-            const float lo = fmaf(v, C_HI, -hi) + v * C_LO;
+            const Rev rv = to_rev(v);
             float sc = 1.f;
             for (int o = 0; o < L; ++o) {
-                const float rev = __builtin_amdgcn_fractf(hi * sc) + lo * sc;
-                w[3 + 6 * o + c] = __builtin_amdgcn_sinf(rev);
-                w[6 + 6 * o + c] = __builtin_amdgcn_cosf(rev);
+                rev_sincos(rv, sc, w[3 + 6 * o + c], w[6 + 6 * o + c]);
                 sc *= 2.f;
             }
         }

@@ -1,20 +1,8 @@
 // lidf_chain16.h — what the any-width decoder chain's two kernels share (lidf_chain16.hip: exact f32;
-// lidf_chain16_h.hip: split f16): the buffer-load and matrix-instruction shorthands, the leaky ReLU on a tile's four
-// registers, the request of a sub-tile's gathered rows and prefetched operands, and a wavefront's range of sub-tiles.
+// lidf_chain16_h.hip: split f16): the request of a sub-tile's gathered rows and prefetched operands, and a wavefront's
+// range of sub-tiles. (The shorthands, the leaky ReLU and the output activation: lidf_mma.h.)
 #pragma once
-#include "lidf_launch.h"
-
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
-#define SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
-#define LDQ(rs, voff, soff) \
-    __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128((rs), (voff), (soff), 0))
-
-// leaky_relu(0.02) on the four registers of a tile (see lidf_ief16.hip: packed multiply + v_med3_f32)
-__device__ __forceinline__ void c16_lrelu4(f32x4& v) {
-    const f32x4 t = v * 0.02f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = __builtin_amdgcn_fmed3f(v[i], t[i], __builtin_inff());
-}
+#include "lidf_mma.h"
 
 #define C16_XPRE 7   // layer-1 k-quads whose operands are requested with the gathered rows (E <= 112: all of them)
 

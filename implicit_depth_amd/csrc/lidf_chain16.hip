@@ -125,7 +125,7 @@ __device__ __forceinline__ void c16_tiles(const Chain16Args& a, const long long 
 #pragma unroll
             for (int s = 0; s < NT; ++s) h[s] = MFMA16(uq[T % 4], val[s], base[T][s]);   // base + u * offset (group 0)
 #pragma unroll
-            for (int s = 0; s < NT; ++s) c16_lrelu4(h[s]);
+            for (int s = 0; s < NT; ++s) lrelu4(h[s]);
 #pragma unroll
             for (int To = 0; To < T2; To += 2) {
                 f32x4 q[2];
@@ -158,7 +158,7 @@ __device__ __forceinline__ void c16_tiles(const Chain16Args& a, const long long 
 #pragma unroll
         for (int T = 0; T < T2; ++T) {
 #pragma unroll
-            for (int s = 0; s < NT; ++s) c16_lrelu4(acc2[T][s]);
+            for (int s = 0; s < NT; ++s) lrelu4(acc2[T][s]);
 #pragma unroll
             for (int To = 0; To < T3; To += 2) {
                 f32x4 q[2];
@@ -188,7 +188,7 @@ __device__ __forceinline__ void c16_tiles(const Chain16Args& a, const long long 
             float y = 0.f;
 #pragma unroll
             for (int T = 0; T < T3; ++T) {
-                c16_lrelu4(acc3[T][s]);
+                lrelu4(acc3[T][s]);
                 const f32x4 w = w4v[T];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) y += w[r] * acc3[T][s][r];
@@ -201,10 +201,7 @@ __device__ __forceinline__ void c16_tiles(const Chain16Args& a, const long long 
 #pragma unroll
     for (int s = 0; s < NT; ++s) {
         const long long r = (half0 + s) * 16 + j;
-        if (r < AN && g == 0) {
-            const float y = val[s];
-            a.out[r] = a.sigmoid ? 1.f / (1.f + expf(-y)) : fmaxf(fminf(y, y * 0.01f + 0.99f), y * 0.01f);
-        }
+        if (r < AN && g == 0) a.out[r] = out_act(val[s], a.sigmoid);
     }
 }
 

@@ -28,11 +28,6 @@
 #include "lidf_launch.h"
 #include "lidf_chain16.h"
 
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-
-#define MFMA32H(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
-
 // the lane's quads of two input tiles -> the f16 high pieces (round to nearest even) and the f16 residuals as the
 // instruction's B operands; x - hi is exact in f32
 __device__ __forceinline__ void c16h_split8(const f32x4& x0, const f32x4& x1, h8& hi, h8& lo) {
@@ -180,8 +175,8 @@ __device__ __forceinline__ void c16h_tiles(const Chain16Args& a, const long long
             for (int s = 0; s < NT; ++s) {
                 f32x4 h0 = MFMA16(uq[T % 4], val[s], base[T][s]);   // base + u * offset (group 0), f32
                 f32x4 h1 = MFMA16(uq[T % 4 + 1], val[s], base[T + 1][s]);
-                c16_lrelu4(h0);
-                c16_lrelu4(h1);
+                lrelu4(h0);
+                lrelu4(h1);
                 c16h_split8(h0, h1, hh[s], hl[s]);
             }
 #pragma unroll
@@ -211,8 +206,8 @@ __device__ __forceinline__ void c16h_tiles(const Chain16Args& a, const long long
             h8 hh[NT], hl[NT];
 #pragma unroll
             for (int s = 0; s < NT; ++s) {
-                c16_lrelu4(acc2[T][s]);
-                c16_lrelu4(acc2[T + 1][s]);
+                lrelu4(acc2[T][s]);
+                lrelu4(acc2[T + 1][s]);
                 c16h_split8(acc2[T][s], acc2[T + 1][s], hh[s], hl[s]);
             }
 #pragma unroll
@@ -237,7 +232,7 @@ __device__ __forceinline__ void c16h_tiles(const Chain16Args& a, const long long
             float y = 0.f;
 #pragma unroll
             for (int T = 0; T < T3; ++T) {
-                c16_lrelu4(acc3[T][s]);
+                lrelu4(acc3[T][s]);
                 const f32x4 w = w4v[T];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) y += w[r] * acc3[T][s][r];
@@ -250,10 +245,7 @@ __device__ __forceinline__ void c16h_tiles(const Chain16Args& a, const long long
 #pragma unroll
     for (int s = 0; s < NT; ++s) {
         const long long r = (half0 + s) * 16 + j;
-        if (r < AN && g == 0) {
-            const float y = val[s];
-            a.out[r] = a.sigmoid ? 1.f / (1.f + expf(-y)) : fmaxf(fminf(y, y * 0.01f + 0.99f), y * 0.01f);
-        }
+        if (r < AN && g == 0) a.out[r] = out_act(val[s], a.sigmoid);
     }
 }
 

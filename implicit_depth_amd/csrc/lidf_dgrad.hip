@@ -20,11 +20,7 @@
 // masked, stored — while the next pair multiplies. Per 32 rows: 640 matrix instructions, 1.8 KB of
 // HBM traffic per row (dZ3 and the sign words in; dZ2, dZ1 out; ACC: + 1 KB, the running sum).
 #include "lidf_launch.h"
-
-#define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
-#define SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
-#define LDQ(rs, voff, soff) \
-    __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128((rs), (voff), (soff), 0))
+#include "lidf_mma.h"
 
 #define DG_A_QUADS 32
 #define DG_B_QUADS 128

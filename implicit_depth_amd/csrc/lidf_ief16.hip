@@ -28,24 +28,10 @@
 //   a pass waits behind the ring's requests and the ring behind it — measured 10 % of the launch)
 // aux: w4 [64] | b4 [1] (read once per wavefront).
 #include "lidf_launch.h"
+#include "lidf_mma.h"
 
 // (a ring of 16 quads — a lone sub-tile consumes a quad in 128 cycles — measured no faster than 8)
 #define IEF16_RING 8
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
-#define SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
-#define LDQ(rs, voff, soff) \
-    __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128((rs), (voff), (soff), 0))
-
-// leaky_relu(0.02) on the four registers of a tile: packed multiplies + one v_med3_f32 per register —
-// max(x, 0.02 x) = med3(x, 0.02 x, +inf). fmaxf would add a canonicalising v_max per input under the IEEE
-// mode (on gfx950 every vector instruction of the wavefront delays its f32 matrix instructions); inline
-// assembly instead hides the operands from the compiler's matrix-result hazard tracking (measured: wrong
-// values).
-__device__ __forceinline__ void lrelu4(f32x4& v) {
-    const f32x4 t = v * 0.02f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = __builtin_amdgcn_fmed3f(v[i], t[i], __builtin_inff());
-}
 
 #define IEF16_XPRE 4   // layer-1 k-quads whose operands are requested a tile ahead (E = 51: all four)
 
@@ -268,10 +254,7 @@ __device__ __forceinline__ void ief16_tiles(const Ief16Args& a, const long long 
 #pragma unroll
     for (int s = 0; s < NT; ++s) {
         const long long r = (half0 + s) * 16 + j;
-        if (r < AN && g == 0) {
-            const float y = val[s];
-            a.out[r] = a.sigmoid ? 1.f / (1.f + expf(-y)) : fmaxf(fminf(y, y * 0.01f + 0.99f), y * 0.01f);
-        }
+        if (r < AN && g == 0) a.out[r] = out_act(val[s], a.sigmoid);
     }
 }
 

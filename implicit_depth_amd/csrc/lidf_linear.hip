@@ -13,6 +13,7 @@
 // (>= 0), so integer atomicMax on the bit pattern is an exact, order-independent float max, and a
 // zero-initialised pool reproduces torch_scatter's 0 for a voxel without points.
 #include "lidf_launch.h"
+#include "lidf_mma.h"
 #include <cstdlib>
 
 #include "lidf_linear_kernel.inc"

@@ -1,10 +1,6 @@
 // lidf_linear_kernel.inc — the kernel template of lidf_linear.hip, shared with lidf_linear_s / _x / _sx.hip (the SPLIT / XCOL
 // instantiations live in translation units of their own: 32 instantiations in one file compiled for two minutes).
-#define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
-#define SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-#define LDQ(rs, voff, soff) \
-    __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128((rs), (voff), (soff), 0))
+#include "lidf_mma.h"
 
 // SPLIT: the operand rows come from TWO buffers — k-quads [0, kq_split) from X, the ones behind them from X2 (the
 // joint input gradient of the two decoders on materialised rows: d rows = [S_prob | S_off] [W1_prob ; W1_off], one

@@ -31,11 +31,7 @@
 //  * otherwise as in lidf_linear.hip: the wave reduces per distinct voxel of its 32 rows, one lane
 //    issues global integer atomic maxima where a plain read does not already prove them unnecessary.
 #include "lidf_launch.h"
-
-#define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
-#define SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
-#define LDQ(rs, voff, soff) \
-    __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128((rs), (voff), (soff), 0))
+#include "lidf_mma.h"
 
 static_assert(PN_P1 + PN_P2 <= PN_S1_QUADS && PN_P1 + PN_P2 + PN_P3 + PN_P4 <= PN_S2_QUADS, "stream");
 static_assert(PN_S1_QUADS % LIDF_RING == 0 && PN_S2_QUADS % LIDF_RING == 0, "ring phase");

@@ -26,11 +26,7 @@
 // launches of lidf_wgrad2_kernel: their contraction runs over the points, which the chains hold in the lane
 // dimension.
 #include "lidf_launch.h"
-
-#define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
-#define SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
-#define LDQ(rs, voff, soff) \
-    __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128((rs), (voff), (soff), 0))
+#include "lidf_mma.h"
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned long long u64;

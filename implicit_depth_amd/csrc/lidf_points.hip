@@ -24,9 +24,7 @@
 // behind an exact range reduction in revolutions, the per-ray layer-1 partial added by a rank-1
 // MFMA instead of 128 v_add per net, no staging through LDS.
 #include "lidf_launch.h"
-
-#define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
-#define SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
+#include "lidf_mma.h"
 
 // Development-only phase timers (-DLIDF_PROFILE): wave 0 of block 0 accumulates s_memtime deltas
 // per phase into a.out_base[0..7] (as integers); every wavefront leaves its start / end wall clock
@@ -42,13 +40,6 @@
 #define PROF(i)
 #define PROF_DUMP
 #endif
-
-// Weight-stream loads go through a buffer descriptor: the (wave-uniform) stream position lives in
-// an SGPR and the lane offset is one constant VGPR, so the unrolled layers need no per-load
-// 64-bit address registers (with flat pointers hipcc materialises and spills hundreds of them).
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-#define LDQ(rs, voff, soff) \
-    __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128((rs), (voff), (soff), 0))
 
 // ------------------------------------------------------------------------------------------------
 // Packer: one thread per stream float.
@@ -218,9 +209,8 @@ __device__ float chain16_stream_value(const NetW& n, const L1Map& m, int e) {
 // the weights of row 16 To + j at features 4 g + 2 (c & 1) + {0, 1} of tile T + (c >> 1). wh = f16(w) (round to
 // nearest even), wl = f16(w - wh) (w - wh is exact in f32), subnormal pieces kept. Bias, u and padding quads are f32.
 __device__ float chain16h_pieces(float w0, float w1, int lo) {
-    typedef _Float16 h2p __attribute__((ext_vector_type(2)));
     const _Float16 h0 = (_Float16)w0, h1 = (_Float16)w1;
-    const h2p pk = {lo ? (_Float16)(w0 - (float)h0) : h0, lo ? (_Float16)(w1 - (float)h1) : h1};
+    const h2 pk = {lo ? (_Float16)(w0 - (float)h0) : h0, lo ? (_Float16)(w1 - (float)h1) : h1};
     return __builtin_bit_cast(float, pk);
 }
 __device__ float chain16h_stream_value(const NetW& n, const L1Map& m, int e) {
@@ -294,6 +284,8 @@ __device__ __forceinline__ void pack_body(const StreamLayout& lay, const NetW& n
     }
     if (e < lay.total) stream[e] = stream_value(lay, net0, net1, m, e);
     if (lay.mode != LIDF_MODE_L1ONLY && lay.mode != LIDF_MODE_LINEAR && e < lay.nets * LIDF_AUX_FLOATS) {
+        // (the section pack_aux_h of lidf_mma.h writes, same feature order; kept apart: this packer has two
+        // references and no array of nets, and a helper both could call changed the code of all three)
         int sec = e / LIDF_AUX_FLOATS, i = e % LIDF_AUX_FLOATS;
         const NetW& n = sec ? net1 : net0;
         float v = 0.f;
@@ -364,12 +356,6 @@ __device__ __forceinline__ void lrelu_part(f32x16& v) {
         v[i] = r0;
         v[i + 1] = r1;
     }
-}
-
-__device__ __forceinline__ float out_act(float y, int use_sigmoid) {
-    // implicit_net.py:93-96 / :148-151
-    if (use_sigmoid) return 1.f / (1.f + expf(-y));
-    return fmaxf(fminf(y, y * 0.01f + 0.99f), y * 0.01f);
 }
 
 // One decoder pass on the 32 points of this wavefront:

@@ -35,17 +35,9 @@
 // two-net stream and tables over all pairs (offsets for the selected pairs only: prob_dec), and the
 // list form of that (offset_dec on the one-pair-per-ray list, where every row is its own ray).
 #include "lidf_launch.h"
+#include "lidf_mma.h"
 #include <stdio.h>
 #include <stdlib.h>
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-
-#define MFMAH(a, b, c) \
-    __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, (a)), __builtin_bit_cast(h8, (b)), (c), 0, 0, 0)
-#define SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
-#define LDQ(rs, voff, soff) \
-    __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128((rs), (voff), (soff), 0))
 
 // development only: per-phase cycle counters of wavefront 0 of workgroup 0, written to a.out_base
 #ifdef LIDF_PROFILE
@@ -60,9 +52,6 @@ typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 #endif
 
 
-#define CH_QUADS 16
-#define CH_ELEMS (CH_QUADS * 64)  // f32x4 elements per chunk buffer
-#define NBUF 3
 #ifndef RING_D
 #define RING_D 4  // quads of the stream in flight between LDS and the matrix instructions
 #endif
@@ -124,22 +113,9 @@ static_assert(4 + 8 * (2 * NK1 + 2) + 8 * 16 + 2 + 32 <= PASS_QUADS, "section si
 static_assert(PASS_QUADS % CH_QUADS == 0, "sections are whole chunks");
 static_assert(PASS_QUADS % RING_D == 0 && CH_QUADS - RING_D > 6, "ring slots are static; ring reads of the next chunk start after the barrier");
 
-__host__ __device__ constexpr int tile_feature(int r, int half) {
-    return (r & 3) + 8 * (r >> 2) + 4 * half;
-}
-
 // ------------------------------------------------------------------------------------------------
 // Packer: one thread per f16 element.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ _Float16 hpiece(float w, int part) {
-    const _Float16 hi = (_Float16)w;
-    if (part == 0) return hi;
-    const float r = w - (float)hi;
-    const _Float16 lo = (_Float16)r;
-    if (part == 1) return lo;
-    return (_Float16)(r - (float)lo);
-}
-
 __device__ _Float16 stream_value_h(const StreamLayout& lay, const NetW* nets, const L1Map& m,
                                    long long e) {
     const int per_net = lay.net_quads * 512;
@@ -200,18 +176,7 @@ __global__ void lidf_pack_h_kernel(StreamLayout lay, NetW net0, NetW net1, L1Map
     NetW nets[2] = {net0, net1};
     const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (e < (long long)lay.total * 2) stream[e] = stream_value_h(lay, nets, m, e);
-    if (e < lay.nets * LIDF_AUX_FLOATS) {
-        const int sec = (int)e / LIDF_AUX_FLOATS, i = (int)e % LIDF_AUX_FLOATS;
-        const NetW& n = nets[sec];
-        float v = 0.f;
-        if (i < 64) {
-            const int half = i / 32, s = i % 32;
-            v = n.w4[32 * (s >> 4) + tile_feature(s & 15, half)];
-        } else if (i == 64) {
-            v = n.b4[0];
-        }
-        aux[e] = v;
-    }
+    if (e < lay.nets * LIDF_AUX_FLOATS) pack_aux_h(nets, e, aux);
     if (e == 0) ((int*)aux)[lay.nets * LIDF_AUX_FLOATS] = 0;  // tile counter of lidf_points_h_kernel
 }
 
@@ -223,88 +188,6 @@ extern "C" hipError_t lidf_launch_pack_h(const StreamLayout& lay, const NetW& n0
     hipLaunchKernelGGL(lidf_pack_h_kernel, dim3(blocks), dim3(256), 0, st, lay, n0, n1, m,
                        (_Float16*)stream, aux);
     return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------------------
-// Kernel helpers
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float pack2(const _Float16 a, const _Float16 b) {
-    h2 v;
-    v[0] = a;
-    v[1] = b;
-    return __builtin_bit_cast(float, v);
-}
-
-// (x0, x1) -> packed f16 high pieces (round to nearest) and packed f16 residuals. x - hi is exact
-// in f32; v_fma_mix_f32 reads the f16 half directly (1 instruction per residual).
-__device__ __forceinline__ void split2(const float x0, const float x1, float& hi, float& lo) {
-    h2 hh;
-    hh[0] = (_Float16)x0;
-    hh[1] = (_Float16)x1;
-    const float hw = __builtin_bit_cast(float, hh);
-    float r0, r1;
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hw), "v"(x0));
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-        : "=v"(r1)
-        : "v"(hw), "v"(x1));
-    h2 ll;
-    ll[0] = (_Float16)r0;
-    ll[1] = (_Float16)r1;
-    hi = hw;
-    lo = __builtin_bit_cast(float, ll);
-}
-
-// x -> one word holding (hi piece, lo piece) of x
-__device__ __forceinline__ float split1(const float x) {
-    const _Float16 hi = (_Float16)x;
-    const _Float16 lo = (_Float16)(x - (float)hi);
-    return pack2(hi, lo);
-}
-
-__device__ __forceinline__ float lrelu1(const float x) {
-    const float t = x * 0.02f;
-    float r;
-    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(t));
-    return r;
-}
-
-// pairs [p0, p1) of a result tile: leaky-relu, split, store into the two k-sub-step fragments
-// (p0, p1 are compile-time constants after unrolling)
-__device__ __forceinline__ void prep_pairs(const int p0, const int p1, const f32x16& pre,
-                                           f32x4 (&bh)[2], f32x4 (&bl)[2]) {
-#pragma unroll
-    for (int p = 0; p < 8; ++p) {
-        if (p >= p0 && p < p1) {
-            float hi, lo;
-            split2(lrelu1(pre[2 * p]), lrelu1(pre[2 * p + 1]), hi, lo);
-            bh[p >> 2][p & 3] = hi;
-            bl[p >> 2][p & 3] = lo;
-        }
-    }
-}
-
-__device__ __forceinline__ float out_act_h(float y, int use_sigmoid) {
-    // implicit_net.py:93-96 / :148-151
-    if (use_sigmoid) return 1.f / (1.f + expf(-y));
-    return fmaxf(fminf(y, y * 0.01f + 0.99f), y * 0.01f);
-}
-
-// sin/cos of x*2^o in revolutions, see lidf_points.hip
-struct RevH {
-    float hi, lo;
-};
-__device__ __forceinline__ RevH to_rev_h(float x) {
-    const float C_HI = 0.15915493667125702f;
-    const float C_LO = 6.4206383e-09f;
-    RevH r;
-    r.hi = x * C_HI;
-    r.lo = fmaf(x, C_HI, -r.hi) + x * C_LO;
-    return r;
-}
-__device__ __forceinline__ void rev_sincos_h(const RevH& r, float sc, float& s, float& c) {
-    const float t = __builtin_amdgcn_fractf(r.hi * sc) + r.lo * sc;
-    s = __builtin_amdgcn_sinf(t);
-    c = __builtin_amdgcn_cosf(t);
 }
 
 // The stream feed of one wavefront.
@@ -730,7 +613,7 @@ __global__ void __launch_bounds__(256, 2) lidf_points_h_kernel(PointsArgs a) {
         // registers, low pieces in this wavefront's LDS rows
         f32x4 pbh[NK1];
         {
-            const RevH rv[3] = {to_rev_h(px), to_rev_h(py), to_rev_h(pz)};
+            const Rev rv[3] = {to_rev(px), to_rev(py), to_rev(pz)};
 #pragma unroll
             for (int ks = 0; ks < NK1; ++ks) {
                 f32x4 lo4;
@@ -738,7 +621,7 @@ __global__ void __launch_bounds__(256, 2) lidf_points_h_kernel(PointsArgs a) {
                 for (int i = 0; i < 4; ++i) {
                     const int idx = 4 * ks + i;  // combo: octave idx/3, coordinate idx%3
                     float sv, cv, hi, lo;
-                    rev_sincos_h(rv[idx % 3], (float)(1 << (idx / 3)), sv, cv);
+                    rev_sincos(rv[idx % 3], (float)(1 << (idx / 3)), sv, cv);
                     split2(sv, cv, hi, lo);
                     pbh[ks][i] = hi;
                     lo4[i] = lo;
@@ -809,7 +692,7 @@ __global__ void __launch_bounds__(256, 2) lidf_points_h_kernel(PointsArgs a) {
 
             // ---------------- outputs ----------------
             if (valid && h == 0) {
-                const float o = out_act_h(val, a.sigmoid[net]);
+                const float o = out_act(val, a.sigmoid[net]);
                 if (a.out[net]) a.out[net][p] = o;
                 if (a.is_offset[net]) {
                     // pipeline.py:437-439, same operation order in f32

@@ -12,21 +12,10 @@
 //
 // Stream per decoder: [layer 1: NKS k-steps x (8 tiles x (hi, lo))] [pass: 176 quads, pass_desc()].
 #include "lidf_launch.h"
+#include "lidf_mma.h"
 
 namespace rowsh {
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-
-#define MFMAH(a, b, c) \
-    __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, (a)), __builtin_bit_cast(h8, (b)), (c), 0, 0, 0)
-#define SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
-#define LDQ(rs, voff, soff) \
-    __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128((rs), (voff), (soff), 0))
-
 #define RPASS_QUADS 176
-#define CH_QUADS 16
-#define CH_ELEMS (CH_QUADS * 64)  // f32x4 elements per chunk buffer
-#define NBUF 3
 
 // ------------------------------------------------------------------------------------------------
 // Order of the pass section (shared by the packer and the kernel)
@@ -66,22 +55,9 @@ __host__ __device__ constexpr QD pass_desc(int s) {
     return {K_PAD, 0, 0, 0, 0, 0};
 }
 
-__host__ __device__ constexpr int tile_feature(int r, int half) {
-    return (r & 3) + 8 * (r >> 2) + 4 * half;
-}
-
 // ------------------------------------------------------------------------------------------------
 // Packer: one thread per f16 element.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ _Float16 hpiece(float w, int part) {
-    const _Float16 hi = (_Float16)w;
-    if (part == 0) return hi;
-    const float r = w - (float)hi;
-    const _Float16 lo = (_Float16)r;
-    if (part == 1) return lo;
-    return (_Float16)(r - (float)lo);
-}
-
 __device__ _Float16 stream_value_r(const StreamLayout& lay, const NetW* nets, const L1Map& m,
                                    long long e) {
     const int per_net = lay.net_quads * 512;
@@ -137,85 +113,7 @@ __global__ void lidf_pack_r_kernel(StreamLayout lay, NetW net0, NetW net1, L1Map
     NetW nets[2] = {net0, net1};
     const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (e < (long long)lay.total * 2) stream[e] = stream_value_r(lay, nets, m, e);
-    if (aux && e < lay.nets * LIDF_AUX_FLOATS) {
-        const int sec = (int)e / LIDF_AUX_FLOATS, i = (int)e % LIDF_AUX_FLOATS;
-        const NetW& n = nets[sec];
-        float v = 0.f;
-        if (i < 64) {
-            const int half = i / 32, s = i % 32;
-            v = n.w4[32 * (s >> 4) + tile_feature(s & 15, half)];
-        } else if (i == 64) {
-            v = n.b4[0];
-        }
-        aux[e] = v;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Kernel helpers
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float pack2(const _Float16 a, const _Float16 b) {
-    h2 v;
-    v[0] = a;
-    v[1] = b;
-    return __builtin_bit_cast(float, v);
-}
-
-// (x0, x1) -> packed f16 high pieces (round to nearest) and packed f16 residuals. x - hi is exact
-// in f32; v_fma_mix_f32 reads the f16 half directly (1 instruction per residual).
-__device__ __forceinline__ void split2(const float x0, const float x1, float& hi, float& lo) {
-    h2 hh;
-    hh[0] = (_Float16)x0;
-    hh[1] = (_Float16)x1;
-    const float hw = __builtin_bit_cast(float, hh);
-    float r0, r1;
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hw), "v"(x0));
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-        : "=v"(r1)
-        : "v"(hw), "v"(x1));
-    h2 ll;
-    ll[0] = (_Float16)r0;
-    ll[1] = (_Float16)r1;
-    hi = hw;
-    lo = __builtin_bit_cast(float, ll);
-}
-
-__device__ __forceinline__ float lrelu1(const float x) {
-    const float t = x * 0.02f;
-    float r;
-    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(t));
-    return r;
-}
-
-// pairs [P0, P1) of a result tile: leaky-relu, split, store into the two k-sub-step fragments
-template <int P0, int P1>
-__device__ __forceinline__ void prep_pairs(const f32x16& pre, f32x4 (&bh)[2], f32x4 (&bl)[2]) {
-#pragma unroll
-    for (int p = P0; p < P1; ++p) {
-        float hi, lo;
-        split2(lrelu1(pre[2 * p]), lrelu1(pre[2 * p + 1]), hi, lo);
-        bh[p >> 2][p & 3] = hi;
-        bl[p >> 2][p & 3] = lo;
-    }
-}
-__device__ __forceinline__ void prep_pairs_dyn(const int p0, const int p1, const f32x16& pre,
-                                               f32x4 (&bh)[2], f32x4 (&bl)[2]) {
-    // p0, p1 are compile-time constants after unrolling
-#pragma unroll
-    for (int p = 0; p < 8; ++p) {
-        if (p >= p0 && p < p1) {
-            float hi, lo;
-            split2(lrelu1(pre[2 * p]), lrelu1(pre[2 * p + 1]), hi, lo);
-            bh[p >> 2][p & 3] = hi;
-            bl[p >> 2][p & 3] = lo;
-        }
-    }
-}
-
-__device__ __forceinline__ float out_act_r(float y, int use_sigmoid) {
-    // implicit_net.py:93-96 / :148-151
-    if (use_sigmoid) return 1.f / (1.f + expf(-y));
-    return fmaxf(fminf(y, y * 0.01f + 0.99f), y * 0.01f);
+    if (aux && e < lay.nets * LIDF_AUX_FLOATS) pack_aux_h(nets, e, aux);
 }
 
 // The stream feed of one wavefront.
@@ -309,7 +207,7 @@ __device__ __forceinline__ float decoder_pass_h(Feed& f, const FeedCfg& c, f32x4
             acc2[d.t] = MFMAH(A, onesB, zero16);
         } else if (d.kind == K_U) {
             pre = MFMAH(A, offB, base[d.T]);
-            if (d.T == 0) prep_pairs<0, 8>(pre, bh[0], bl[0]);
+            if (d.T == 0) prep_pairs(0, 8, pre, bh[0], bl[0]);
         } else if (d.kind == K_L2) {
             const int par = d.T & 1;
             if (!d.lo) {
@@ -317,11 +215,11 @@ __device__ __forceinline__ float decoder_pass_h(Feed& f, const FeedCfg& c, f32x4
                 acc2[d.t] = MFMAH(A, bl[par][d.sub], acc2[d.t]);
                 if (d.T < 7) {
                     // split pair j of the next H1 tile behind these matrix instructions
-                    prep_pairs_dyn(d.j, d.j + 1, pre, bh[par ^ 1], bl[par ^ 1]);
+                    prep_pairs(d.j, d.j + 1, pre, bh[par ^ 1], bl[par ^ 1]);
                 } else {
                     // last segment (tile-major): output tiles complete one by one
-                    if (d.j >= 2 && d.j < 6) prep_pairs_dyn(2 * (d.j - 2), 2 * (d.j - 2) + 2, acc2[0], gh[0], gl[0]);
-                    if (d.j >= 6) prep_pairs_dyn(2 * (d.j - 6), 2 * (d.j - 6) + 2, acc2[1], gh[1], gl[1]);
+                    if (d.j >= 2 && d.j < 6) prep_pairs(2 * (d.j - 2), 2 * (d.j - 2) + 2, acc2[0], gh[0], gl[0]);
+                    if (d.j >= 6) prep_pairs(2 * (d.j - 6), 2 * (d.j - 6) + 2, acc2[1], gh[1], gl[1]);
                 }
             } else {
                 acc2[d.t] = MFMAH(A, bh[par][d.sub], acc2[d.t]);
@@ -340,8 +238,8 @@ __device__ __forceinline__ float decoder_pass_h(Feed& f, const FeedCfg& c, f32x4
                 acc3[d.t] = MFMAH(A, gl[d.T][d.sub], acc3[d.t]);
                 // pending splits: segment T handles the second half of H2[T+1] (first two pairs)
                 // and the first half of H2[T+2] (last two pairs)
-                if (d.T < 3 && d.j < 2) prep_pairs_dyn(4 + 2 * d.j, 6 + 2 * d.j, acc2[d.T + 1], gh[d.T + 1], gl[d.T + 1]);
-                if (d.T < 2 && d.j >= 2) prep_pairs_dyn(2 * (d.j - 2), 2 * (d.j - 2) + 2, acc2[d.T + 2], gh[d.T + 2], gl[d.T + 2]);
+                if (d.T < 3 && d.j < 2) prep_pairs(4 + 2 * d.j, 6 + 2 * d.j, acc2[d.T + 1], gh[d.T + 1], gl[d.T + 1]);
+                if (d.T < 2 && d.j >= 2) prep_pairs(2 * (d.j - 2), 2 * (d.j - 2) + 2, acc2[d.T + 2], gh[d.T + 2], gl[d.T + 2]);
                 if (d.T == 3 && d.j >= 2) {
                     // acc3[0] is complete: its half of layer 4 runs behind acc3[1]'s last steps
 #pragma unroll
@@ -509,7 +407,7 @@ __global__ void __launch_bounds__(256) lidf_rows_h_kernel(PointsArgs a) {
             const int npass = a.npass[net];
             for (int pass = 0; pass < npass; ++pass) val += decoder_pass_h(f, c, sb, base, val, h, ax);
 
-            if (valid && h == 0 && a.out[net]) a.out[net][p] = out_act_r(val, a.sigmoid[net]);
+            if (valid && h == 0 && a.out[net]) a.out[net][p] = out_act(val, a.sigmoid[net]);
         }
     }
 }

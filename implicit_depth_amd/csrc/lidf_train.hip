@@ -4,9 +4,8 @@
 // (lidf_decoder_backward_f32) runs the input-gradient chain through lidf_linear_kernel with the
 // transposed weights and the leaky-ReLU mask as epilogue, and reduces the weight gradients here.
 #include "lidf_launch.h"
+#include "lidf_mma.h"
 #include <stdlib.h>
-
-#define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 
 // C[m, j] += sum over rows r of A[r, m] * B[r, j]   (m < M, j < N), db[m] += sum_r A[r, m].
 // One wavefront per (64x64 tile of C, slice of rows): lane (c, h) feeds A[r+h, 64mt+32t+c] and
@@ -580,11 +579,10 @@ __global__ void lidf_out_act_kernel(const float* pre, long long n, int use_sigmo
     const float y = pre[i];
     float o, d;
     if (use_sigmoid) {
-        o = 1.f / (1.f + expf(-y));
+        o = out_act(y, 1);
         d = o * (1.f - o);
     } else {
-        // max(min(y, 0.01 y + 0.99), 0.01 y): identity on [0, 1], slope 0.01 outside
-        o = fmaxf(fminf(y, y * 0.01f + 0.99f), y * 0.01f);
+        o = out_act(y, 0);   // identity on [0, 1], slope 0.01 outside
         d = (y >= 0.f && y <= 1.f) ? 1.f : 0.01f;
     }
     if (out) out[i] = o;

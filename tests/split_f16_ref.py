@@ -4,8 +4,8 @@ precision="f16x3" evaluates every product of decoder layers 1-3 as  wh*xh + wh*x
 accumulation. The float32 oracle's error alone is no unit for that path: the scheme carries a representation error
 of its own (the dropped wl*xl term, the 22 bits of a two-piece operand, f16 subnormal low pieces at small weights)
 which an exact-f32 evaluation does not have. The twin restates the scheme with plain torch ops, on CPU or GPU
-tensors: every operand is rounded to f16 pieces where the kernels and their packers do (hpiece, split1, split2,
-stream_value_h, stream_value_r, decoder_pass_h) and nowhere else, exactly the three products are kept, products and
+tensors: every operand is rounded to f16 pieces where the kernels and their packers do (lidf_mma.h: hpiece, split1,
+split2; stream_value_h, stream_value_r, decoder_pass_h) and nowhere else, exactly the three products are kept, products and
 sums are float64, and a value is rounded to f32 only where the kernel holds an f32 value (layer outputs, the voxpart /
 raypart tables, u, the running offset). Layer 4 and the output activation are float64. What remains between the twin
 and the kernel is f32 accumulation, which is what the float32 oracle has: assert_split_close takes the sum of both
@@ -31,7 +31,7 @@ ROW_DEFECTS = ("act2", "act3", "wlo", "emb", "ulvh", "flush")     # "ray" exists
 
 
 def tile_feature(r, half):
-    """Feature of result register r of a 32x32 tile in lane half `half` (lidf_points_h.hip:tile_feature)."""
+    """Feature of result register r of a 32x32 tile in lane half `half` (lidf_mma.h:tile_feature)."""
     return (r & 3) + 8 * (r >> 2) + 4 * half
 
 
@@ -44,7 +44,7 @@ EMB_KSTEP = 2
 
 
 def pieces(x, n=2, flush=False):
-    """x -> its n f16 pieces (hpiece / split1 / split2), as float64 tensors. The operand is an f32 value in the
+    """x -> its n f16 pieces (lidf_mma.h: hpiece / split1 / split2), as float64 tensors. The operand is an f32 value in the
     kernel, the residual x - hi is exact in f32. flush: pieces below the f16 normal range read as zero."""
     r = x.float()
     out = []

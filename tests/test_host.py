@@ -136,6 +136,53 @@ def test_launchers_are_declared_once_in_lidf_launch_h():
     assert len(called) >= 80 and called <= declared, sorted(called - declared)
 
 
+def test_matrix_shorthands_and_split_f16_pieces_have_one_copy():
+    """The matrix-instruction shorthands, the output activation, the leaky ReLUs and the split-f16 pieces
+    are numerical contracts (the float64 tests pin their arithmetic): csrc/lidf_mma.h holds the only
+    definition of each, lidf_device.h the only revolution-reduced sin/cos, and every kernel file that
+    uses a shorthand includes the header (directly or through lidf_chain16.h)."""
+    import glob
+    csrc = os.path.join(ROOT, "implicit_depth_amd", "csrc")
+
+    def code(path):   # without comments
+        s = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+        return re.sub(r"//[^\n]*", "", s)
+
+    files = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.inc")) +
+                   glob.glob(os.path.join(csrc, "*.h")))
+    assert len(files) >= 28
+    macros = r"(?:MFMA|MFMA16|MFMAH|MFMA32H|SCHED_FENCE|LDQ)"
+    owned = {"lidf_mma.h": r"out_act\w*|lrelu1|lrelu4|hpiece|pack2|split1|split2|tile_feature|prep_pairs\w*",
+             "lidf_device.h": r"to_rev\w*|rev_sincos\w*"}
+    n_defs = {"lidf_mma.h": 9, "lidf_device.h": 2}
+    literals = {"0.99f": [], "0.15915493667125702f": []}
+    dup, bare = [], []
+    for p in files:
+        s, name = code(p), os.path.basename(p)
+        defines = re.findall(r"^[ \t]*#[ \t]*define[ \t]+(%s)\b" % macros, s, flags=re.M)
+        if name == "lidf_mma.h":
+            assert sorted(defines) == ["LDQ", "MFMA", "MFMA16", "MFMA32H", "MFMAH", "SCHED_FENCE"], defines
+        else:
+            dup += ["%s: #define %s" % (name, d) for d in defines]
+        for home, names in owned.items():   # a definition: a type in front, a body behind the parameter list
+            fns = re.findall(r"[\w&*>]\s+(%s)\s*\([^;{}]*\)\s*\{" % names, s)
+            if name == home:
+                assert len(fns) == len(set(fns)) == n_defs[home], (name, fns)
+            else:
+                dup += ["%s: %s()" % (name, f) for f in fns]
+        for lit in literals:
+            if lit in open(p).read():
+                literals[lit].append(name)
+        if p.endswith(".hip") and re.search(r"\b%s\s*\(" % macros, s):
+            if not re.search(r'#include "lidf_(?:mma|chain16)\.h"', s):
+                bare.append(name)
+    assert not dup, dup
+    assert os.path.join(csrc, "lidf_mma.h") in files and not bare, bare   # a shorthand used without the header
+    assert literals == {"0.99f": ["lidf_mma.h"], "0.15915493667125702f": ["lidf_device.h"]}, literals
+    assert '#include "lidf_mma.h"' in code(os.path.join(csrc, "lidf_chain16.h"))
+    assert '#include "lidf_launch.h"' in code(os.path.join(csrc, "lidf_mma.h"))
+
+
 def test_torch_extension_shim_loads():
     """The pybind11 shim over the C ABI is built in-tree and imports without a GPU."""
     from implicit_depth_amd import torch_ext
