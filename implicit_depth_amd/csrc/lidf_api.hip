@@ -3203,6 +3203,39 @@ LIDF_API int lidf_ray_features_backward_f32(const float* d_rayfeat, const int32_
     return LIDF_OK;
 }
 
+// ---- the same adjoint without a float atomic on the image (lidf_rayfeat_border_gather_kernel) ----
+LIDF_API size_t lidf_ray_features_backward_ordered_workspace_bytes(int32_t batch, int32_t height, int32_t width) {
+    if (batch <= 0 || height <= 0 || width <= 0) return 0;
+    return (size_t)batch * 129 * height * width * 4;   // parked-gradient image + rays-per-pixel table
+}
+
+LIDF_API int lidf_ray_features_backward_ordered_f32(const float* d_rayfeat, const int32_t* ray_pix,
+                                                      const int32_t* ray_bid, int64_t n_rays, int32_t batch,
+                                                      int32_t height, int32_t width, int32_t roi_inp_bbox,
+                                                      int32_t multires_views, float* d_feat_grid,
+                                                      void* workspace, size_t workspace_bytes,
+                                                      lidf_stream_t stream) {
+    if (n_rays < 0 || batch <= 0 || height <= 0 || width <= 0 || !d_feat_grid || multires_views < 0 ||
+        multires_views > 16)
+        return LIDF_ERR_BAD_ARG;
+    if (n_rays > 0 && (!d_rayfeat || !ray_pix || !ray_bid)) return LIDF_ERR_BAD_ARG;
+    const int half = roi_inp_bbox / 2;
+    if (half < 1 || half > 16 || batch > 2047 || (int64_t)batch * height * width > 0x3fffffffLL)
+        return LIDF_ERR_UNSUPPORTED;
+    if (n_rays > 0 && (!workspace || workspace_bytes < lidf_ray_features_backward_ordered_workspace_bytes(
+                                                           batch, height, width)))
+        return LIDF_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    CHECK_HIP(hipMemsetAsync(d_feat_grid, 0, (size_t)batch * 32 * height * width * 4, st));
+    if (n_rays == 0) return LIDF_OK;
+    float* gimg = (float*)workspace;
+    int* pix_rays = (int*)((char*)workspace + (size_t)batch * 128 * height * width * 4);
+    CHECK_HIP(lidf_launch_rayfeat_backward_ordered(d_rayfeat, 128 + 3 + 6 * multires_views, ray_pix, ray_bid,
+                                                   n_rays, half, batch, height, width, d_feat_grid, gimg,
+                                                   pix_rays, st));
+    return LIDF_OK;
+}
+
 // ---- query decoders, factorised training path -------------------------------------------------------
 LIDF_API int lidf_pe_rows_f32(const int32_t* pair_ray, const int32_t* pair_vox, const float* pair_t,
                                 const float* ray_dir, const float* vox_center, int32_t pos_rel,

@@ -195,6 +195,9 @@ hipError_t lidf_launch_rows_backward(const float* d_rows, int D, int E2, const i
 hipError_t lidf_launch_rayfeat_backward(const float* d_rayfeat, int ld_rf, const int* ray_pix, const int* ray_bid,
                                         long long R, int half, int B, int H, int W, float* d_feat, float* gimg,
                                         int* aux, hipStream_t st);
+hipError_t lidf_launch_rayfeat_backward_ordered(const float* d_rayfeat, int ld_rf, const int* ray_pix,
+                                                const int* ray_bid, long long R, int half, int B, int H, int W,
+                                                float* d_feat, float* gimg, int* aux, hipStream_t st);
 hipError_t lidf_launch_pe_rows(const int* pair_ray, const int* pair_vox, const float* pair_t, const float* ray_dir,
                                const float* vox_center, int pos_rel, int L, long long P, float* pe, hipStream_t st,
                                const int* n_dev = nullptr, long long row0 = 0);

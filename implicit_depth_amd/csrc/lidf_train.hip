@@ -6,6 +6,7 @@
 #include "lidf_launch.h"
 #include "lidf_mma.h"
 #include <stdlib.h>
+#include <algorithm>
 
 // C[m, j] += sum over rows r of A[r, m] * B[r, j]   (m < M, j < N), db[m] += sum_r A[r, m].
 // One wavefront per (64x64 tile of C, slice of rows): lane (c, h) feeds A[r+h, 64mt+32t+c] and
@@ -1255,6 +1256,185 @@ extern "C" hipError_t lidf_launch_rayfeat_backward(const float* d_rayfeat, int l
         hipLaunchKernelGGL(lidf_rayfeat_backward_ring_kernel, dim3(tiles, B * 32), dim3(256),
                            (size_t)PW * PW * 4, st, gimg, half, H, W, d_feat);
     }
+    return hipGetLastError();
+}
+
+// ---- the ordered route (lidf_ray_features_backward_ordered_f32): no float atomic on the image ----
+// Destination tiles of 16 x 16 pixels that a clamped box can reach: a source pixel of the ring of
+// clamped boxes (within `half` of a border) taps at most half + 1 pixels away, so only pixels within
+// 2 half + 1 of a border are touched. Tile rows ty < ta and ty >= tb are taken whole, of the rows
+// between them the tile columns tx < ca and tx >= cb.
+struct RoiBorderTiles { int tx_n, ta, tb, ca, cb, total; };
+static inline RoiBorderTiles roi_border_tiles(int H, int W, int half) {
+    RoiBorderTiles t;
+    const int reach = 2 * half + 1, ty_n = (H + 15) / 16;
+    t.tx_n = (W + 15) / 16;
+    t.ta = std::min((reach + 15) / 16, ty_n);
+    t.tb = std::min(std::max(t.ta, (H - reach) / 16), ty_n);
+    t.ca = std::min((reach + 15) / 16, t.tx_n);
+    t.cb = std::min(std::max(t.ca, (W - reach) / 16), t.tx_n);
+    t.total = (t.ta + ty_n - t.tb) * t.tx_n + (t.tb - t.ta) * (t.ca + t.tx_n - t.cb);
+    return t;
+}
+
+// The boxes clamped at the image border, gathered: a workgroup takes a 16 x 16 tile of DESTINATION
+// pixels, one frame and ROIB_CH channels, one after the other. In LDS it keeps
+//   gs  [4][PS][PS]  g / (gh gw) of the four bins of every clamped-box source pixel within half + 1
+//                    of the tile (PS = 18 + 2 half; 0 for every other pixel of the patch), staged
+//                    once per channel,
+//   wxt [2][PS][16]  roi_axis_weight of bin column pw of source column sx at destination column xl,
+//   wyt [2][PS][16]  the same for the rows (both once per workgroup: they depend on no channel),
+// and every destination pixel then adds its own terms onto the value the interior gather left, in
+// a fixed order and without an atomic of any kind: source pixels in raster order (row, then
+// column), bins 0..3 within a source pixel, each term (g / (gh gw)) * wy * wx rounded product by
+// product (__fmul_rn) and added on its own (__fadd_rn). Terms with a zero factor are skipped; a
+// sum never is -0 (it starts from 0 + x), so adding or skipping a zero term gives the same bits —
+// and a channel whose patch holds no gradient at all (most of them under a window of rays) is
+// left after its staging, before any weight is formed.
+// The weight tables: a thread per (axis, bin, source coordinate) walks the bin's samples in
+// roi_axis_weight's order and adds each tap to the table entry of its pixel, so every entry is
+// roi_axis_weight's sum term for term.
+// LDS: 16 PS^2 + 256 PS bytes — 17.1 KiB at half 4 (nine workgroups a CU), 51.6 KiB at half 16.
+// gs reads are one address per workgroup (broadcast), wxt reads 16 consecutive words, wyt reads 4.
+// grid.x = roi_border_tiles(...).total, grid.y = B * (32 / ROIB_CH).
+#define ROIB_CH 4
+__global__ void __launch_bounds__(256) lidf_rayfeat_border_gather_kernel(
+    const float* __restrict__ gimg, int half, int H, int W, RoiBorderTiles tl, float* __restrict__ d_feat) {
+    extern __shared__ float roib_lds[];
+    const int PS = 18 + 2 * half, PP = PS * PS;
+    float* gs = roib_lds;
+    float* wxt = gs + 4 * PP;
+    float* wyt = wxt + 2 * PS * 16;
+    int tx, ty;
+    {
+        int t = blockIdx.x;
+        const int full = (tl.ta + (H + 15) / 16 - tl.tb) * tl.tx_n;
+        if (t < full) {
+            const int row = t / tl.tx_n;
+            ty = row < tl.ta ? row : tl.tb + (row - tl.ta);
+            tx = t % tl.tx_n;
+        } else {
+            t -= full;
+            const int side = tl.ca + tl.tx_n - tl.cb;
+            ty = tl.ta + t / side;
+            const int s = t % side;
+            tx = s < tl.ca ? s : tl.cb + (s - tl.ca);
+        }
+    }
+    const int b = blockIdx.y / (32 / ROIB_CH), c0 = (blockIdx.y % (32 / ROIB_CH)) * ROIB_CH;
+    const int ox = tx * 16 - half - 1, oy = ty * 16 - half - 1;   // patch origin
+    const int xl = threadIdx.x & 15, yl = threadIdx.x >> 4;
+    const int x = tx * 16 + xl, y = ty * 16 + yl;
+    const bool inimg = x < W && y < H;
+    // the patch's rows / columns inside the image, and of those the ring's columns left and right
+    const int sy0 = max(0, -oy), sy1 = min(PS - 1, H - 1 - oy);
+    const int sx0 = max(0, -ox), sx1 = min(PS - 1, W - 1 - ox);
+    const int sxl = min(sx1, half - 1 - ox), sxr = max(sx0, W - half - ox);
+    bool tables = false;
+    for (int ch = 0; ch < ROIB_CH; ++ch) {
+        const int c = c0 + ch;
+        int nz = 0;
+        for (int i = threadIdx.x; i < PP; i += 256) {
+            const int qy = oy + i / PS, qx = ox + i % PS;
+            float v[4] = {0.f, 0.f, 0.f, 0.f};
+            if (qx >= 0 && qx < W && qy >= 0 && qy < H &&
+                (qx < half || qx > W - 1 - half || qy < half || qy > H - 1 - half)) {
+                const int u1 = min(max(qx - half, 0), W - 1), u2 = min(max(qx + half, 0), W - 1);
+                const int v1 = min(max(qy - half, 0), H - 1), v2 = min(max(qy + half, 0), H - 1);
+                const int gw = (int)ceilf((float)(u2 - u1) / 2.f), gh = (int)ceilf((float)(v2 - v1) / 2.f);
+                if (gw > 0 && gh > 0) {
+                    const float* g = gimg + (((size_t)b * 128 + c * 4) * H + qy) * W + qx;
+#pragma unroll
+                    for (int bin = 0; bin < 4; ++bin) {
+                        v[bin] = g[(size_t)bin * H * W] / (float)(gh * gw);
+                        nz |= v[bin] != 0.f;
+                    }
+                }
+            }
+#pragma unroll
+            for (int bin = 0; bin < 4; ++bin) gs[bin * PP + i] = v[bin];
+        }
+        if (__syncthreads_or(nz)) {
+            if (!tables) {
+                tables = true;
+                for (int i = threadIdx.x; i < 4 * PS; i += 256) {   // i = (axis * 2 + bin) * PS + s
+                    float* wrow = wxt + i * 16;                     // (wyt = wxt + 2 PS 16)
+#pragma unroll
+                    for (int l = 0; l < 16; ++l) wrow[l] = 0.f;
+                    const bool rows = i >= 2 * PS;
+                    const int j = rows ? i - 2 * PS : i;
+                    const int p = j / PS, LIM = rows ? H : W;
+                    const int q = (rows ? oy : ox) + j % PS, d0 = (rows ? ty : tx) * 16;
+                    if (q < 0 || q >= LIM) continue;
+                    const int c1 = min(max(q - half, 0), LIM - 1), c2 = min(max(q + half, 0), LIM - 1);
+                    const float start = (float)c1 - 0.5f, roi = ((float)c2 - 0.5f) - start;
+                    const float bin = roi / 2.f;
+                    const int n = (int)ceilf(roi / 2.f);
+                    const float bstart = start + (float)p * bin;
+                    for (int k = 0; k < n; ++k) {   // roi_axis_weight's samples, in its order
+                        int lo, hi; float l; bool ok;
+                        roi_tap(bstart + ((float)k + .5f) * bin / (float)n, LIM, lo, hi, l, ok);
+                        if (!ok) continue;
+                        if (lo >= d0 && lo < d0 + 16) wrow[lo - d0] += 1.f - l;
+                        if (hi >= d0 && hi < d0 + 16) wrow[hi - d0] += l;
+                    }
+                }
+                __syncthreads();
+            }
+            if (inimg) {
+                float* dst = d_feat + (((size_t)b * 32 + c) * H + y) * W + x;
+                float acc = *dst;
+                for (int sy = sy0; sy <= sy1; ++sy) {
+                    const float wy0 = wyt[sy * 16 + yl], wy1 = wyt[(PS + sy) * 16 + yl];
+                    if (wy0 == 0.f && wy1 == 0.f) continue;
+                    const int qy = oy + sy;
+                    const bool rowc = qy < half || qy > H - 1 - half;
+                    // a row of the ring: every column; else the ring's columns left, then right
+                    for (int part = 0; part < (rowc ? 1 : 2); ++part) {
+                        const int a = rowc || part == 0 ? sx0 : max(sxr, sxl + 1);
+                        const int e = rowc || part == 1 ? sx1 : sxl;
+                        for (int sx = a; sx <= e; ++sx) {
+                            const float wx0 = wxt[sx * 16 + xl], wx1 = wxt[(PS + sx) * 16 + xl];
+#pragma unroll
+                            for (int bin = 0; bin < 4; ++bin) {
+                                const float g = gs[bin * PP + sy * PS + sx];
+                                const float wy = (bin >> 1) ? wy1 : wy0, wx = (bin & 1) ? wx1 : wx0;
+                                if (g != 0.f && wy != 0.f && wx != 0.f)
+                                    acc = __fadd_rn(acc, __fmul_rn(__fmul_rn(g, wy), wx));
+                            }
+                        }
+                    }
+                }
+                *dst = acc;
+            }
+        }
+        __syncthreads();   // gs is staged again for the next channel
+    }
+}
+
+// d_feat (zeroed by the caller) = the interior gather + the border gather; gimg [B,128,H,W] floats and
+// aux B*H*W ints are both required. half in 1..16.
+extern "C" hipError_t lidf_launch_rayfeat_backward_ordered(const float* d_rayfeat, int ld_rf,
+                                                           const int* ray_pix, const int* ray_bid,
+                                                           long long R, int half, int B, int H, int W,
+                                                           float* d_feat, float* gimg, int* aux,
+                                                           hipStream_t st) {
+    if (R <= 0) return hipSuccess;
+    hipError_t e = hipMemsetAsync(gimg, 0, (size_t)B * 128 * H * W * 4, st);
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(aux, 0, (size_t)B * H * W * 4, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(lidf_rayfeat_count_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st,
+                       ray_pix, ray_bid, R, H, W, aux);
+    hipLaunchKernelGGL(lidf_rayfeat_backward_kernel, dim3((unsigned)((R + 63) / 64)), dim3(256), 0,
+                       st, d_rayfeat, ld_rf, ray_pix, ray_bid, R, half, H, W, d_feat, gimg, aux, 1);
+    const long long total = (long long)B * 32 * H * W;
+    hipLaunchKernelGGL(lidf_rayfeat_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256),
+                       0, st, gimg, B, H, W, half, half, d_feat);
+    const RoiBorderTiles tl = roi_border_tiles(H, W, half);
+    const int PS = 18 + 2 * half;
+    hipLaunchKernelGGL(lidf_rayfeat_border_gather_kernel, dim3(tl.total, B * (32 / ROIB_CH)), dim3(256),
+                       (size_t)(4 * PS * PS + 4 * PS * 16) * 4, st, gimg, half, H, W, tl, d_feat);
     return hipGetLastError();
 }
 

@@ -714,7 +714,8 @@ def _decoder_train_from_layer1(mod, layer1, n, dev):
 
 def query_train(ray_dir, ray_pix, ray_bid, pair_off, pair_ray, pair_vox, pair_t, feat_grid, vox_feat, prob_dec,
                 offset_dec, multires=8, multires_views=4, roi_inp_bbox=8, roi_out_bbox=2, offset_range=(0.0, 1.0),
-                part_size=0.25, vox_center=None, pos_rel=False, max_pair_id=None, offsets="all"):
+                part_size=0.25, vox_center=None, pos_rel=False, max_pair_id=None, offsets="all",
+                roi_backward="atomic"):
     """get_embedding + get_pred (models/pipeline.py:338-466) under autograd at any rgb_out / roi_out_bbox / pnet_out /
     gf_dim / multires: what query.lidf_query_train is at the shipped widths. Gradients reach feat_grid (through
     _RoiAlignFn), vox_feat and every parameter of both decoders. Layer 1 keeps the factorised form of `query` — the
@@ -726,9 +727,12 @@ def query_train(ray_dir, ray_pix, ray_bid, pair_off, pair_ray, pair_vox, pair_t,
     multires_views >= 1 (lidf_roi_align_backward_f32, lidf_gather2_backward_f32 and lidf_wgrad_f32's block path sum
     in fixed orders; a 3-column direction block or a layer of fewer than 32 outputs falls to lidf_wgrad_f32's
     atomics beyond 512 rows) and at most 16,384 voxel rows.
+    roi_backward ("atomic" / "ordered", query.lidf_query_train's argument) is checked and changes nothing here: this
+    route's adjoint to feat_grid is the ordered gather lidf_roi_align_backward_f32 already.
     Returns lidf_query_train's dict."""
     from .decoders import get_embedder
-    from .query import _QueryTailFn
+    from .query import _QueryTailFn, _roi_backward_arg
+    _roi_backward_arg(roi_backward)
     if offsets != "all":
         raise RuntimeError("offsets=%r runs inside the fixed-width training kernel only (gf_dim 64, rgb_out 32, "
                            "roi_out_bbox 2, pnet_out 128); at other widths the offset decoder runs on every pair"
@@ -965,7 +969,7 @@ class _RefineLayer1Fn(torch.autograd.Function):
 def refine_train(ray_dir, ray_pix, ray_bid, ray_flat, pred_pos, max_pair_id, pair_vox, voxel_bound, voxel_bid, rgb_img,
                  feat_grid, valid_inp, valid_vox, pnet_model, offset_dec, forward_times=2, multires=8, multires_views=4,
                  roi_inp_bbox=8, roi_out_bbox=2, offset_range=(-0.2, 0.2), pos_rel=False, pnet_pos_rel=True,
-                 perturb_noise=None, grid=None):
+                 perturb_noise=None, grid=None, roi_backward="atomic"):
     """forward_times x RefineNet.get_pred_refine (models/pipeline.py:922-1030, exp_type 'train') under autograd at any
     rgb_out / roi_out_bbox / roi_inp_bbox, PointNet2Stage(6, pnet_out, pnet_gf), IEF (any n_iter) or IMNet of any
     gf_dim with a 1-wide head, use_sigmoid on or off, multires / multires_views 0..16: what query.lidf_refine_train is
@@ -978,10 +982,12 @@ def refine_train(ray_dir, ray_pix, ray_bid, ray_flat, pred_pos, max_pair_id, pai
     d pos); the PointNet runs the module's own training path (generic.pointnet_forward_train where a width differs),
     layers 2-4 and an IEF's passes are query_train's (_decoder_train_from_layer1). Every launch goes to the caller's
     current stream. Run-to-run: as query_train — bit-identical gradients for rays on distinct pixels, gf_dim >= 32,
-    multires_views >= 1 and at most 16,384 voxels.
+    multires_views >= 1 and at most 16,384 voxels. roi_backward ("atomic" / "ordered", query.lidf_refine_train's
+    argument) is checked and changes nothing here: the adjoint to feat_grid is the ordered gather already.
     Returns pred_pos_refine [R, 3] (with grad) and the last end_voxel_id [R] i32."""
     from .decoders import get_embedder
-    from .query import _as_i32, _cell_lookup, _f32
+    from .query import _as_i32, _cell_lookup, _f32, _roi_backward_arg
+    _roi_backward_arg(roi_backward)
     if offset_dec.linear_4.out_features != 1:
         raise RuntimeError("the refine step takes a decoder with out_dim == 1 (got %d): its output is the offset "
                            "along the ray" % offset_dec.linear_4.out_features)

@@ -48,6 +48,10 @@ class LidfOptions:
         # device int32 [bs], the window starts of the 'device' route instead of a draw (None = draw)
         self.miss_sample = "numpy"
         self.miss_starts = None
+        # RoIAlign's adjoint to full_rgb_feat in the training calls: 'atomic' (default; its border boxes are summed with
+        # float atomics, equal to rounding between runs) or 'ordered' (a fixed-order gather, bit-reproducible;
+        # query.lidf_query_train). torch.use_deterministic_algorithms is not consulted
+        self.roi_backward = "atomic"
         self.maxpool_label_epo = 6
         # stage 2 (test_refine.yaml)
         self.refine_forward_times = 2
@@ -64,12 +68,19 @@ class LidfOptions:
             setattr(self, k, v)
         self.sample_num()
         self.miss_route()
+        self.roi_route()
 
     def miss_route(self):
         """miss_sample, checked: 'numpy' or 'device'."""
         if self.miss_sample not in ("numpy", "device"):
             raise ValueError("miss_sample must be 'numpy' or 'device', not %r" % (self.miss_sample,))
         return self.miss_sample
+
+    def roi_route(self):
+        """roi_backward, checked: 'atomic' or 'ordered'."""
+        if self.roi_backward not in ("atomic", "ordered"):
+            raise ValueError("roi_backward must be 'atomic' or 'ordered', not %r" % (self.roi_backward,))
+        return self.roi_backward
 
     def sample_num(self):
         """valid_sample_num as the sampler takes it: n > 0, or 0 for every valid point (None / -1)."""
@@ -286,7 +297,7 @@ def lidf_forward_train(batch, full_rgb_feat, pnet_model, prob_dec, offset_dec, o
         dd["occ_voxel_feat"], prob_dec, offset_dec, multires=opt.multires, multires_views=opt.multires_views,
         roi_inp_bbox=opt.roi_inp_bbox, roi_out_bbox=opt.roi_out_bbox, offset_range=opt.offset_range,
         part_size=dd["part_size"], vox_center=_vox_center(dd, opt), pos_rel=opt.intersect_pos_type == "rel",
-        max_pair_id=dd["gt_max_pair_id"] if epoch < opt.maxpool_label_epo else None))
+        max_pair_id=dd["gt_max_pair_id"] if epoch < opt.maxpool_label_epo else None, roi_backward=opt.roi_route()))
     return True, dd, lidf_loss(dd, loss_opt, "train", epoch)
 
 
@@ -312,7 +323,7 @@ def refine_forward_train(dd, pnet_model_refine, offset_dec_refine, opt=None, los
         forward_times=opt.refine_forward_times, multires=opt.multires, multires_views=opt.multires_views,
         roi_inp_bbox=opt.roi_inp_bbox, roi_out_bbox=opt.roi_out_bbox, offset_range=opt.refine_offset_range,
         pos_rel=opt.refine_intersect_pos_type == "rel", pnet_pos_rel=opt.refine_pnet_pos_type == "rel",
-        perturb_noise=noise,
+        perturb_noise=noise, roi_backward=opt.roi_route(),
         grid=dd if all(k in dd for k in ("voxel_coord", "grid_dims", "xmin", "part_size")) else None)
     dd["pred_pos_refine"], dd["end_voxel_id"] = pos, end_voxel
     dd["refine_perturb_noise"] = noise

@@ -983,14 +983,18 @@ def depth_metrics_frames(pred_depth, gt_depth, seg_mask=None, out_size=(144, 256
 # Training path of the query (gradients to vox_feat, feat_grid and the decoders' parameters)
 # ------------------------------------------------------------------------------------------------
 class _RayFeaturesFn(torch.autograd.Function):
-    """ray_features with RoIAlign backward to the feature map (lidf_ray_features_backward_f32)."""
+    """ray_features with RoIAlign backward to the feature map: roi_backward 'atomic' (default,
+    lidf_ray_features_backward_f32) or 'ordered' (lidf_ray_features_backward_ordered_f32: no float atomic on the
+    image, bit-reproducible for rays on distinct pixels)."""
 
     @staticmethod
-    def forward(ctx, feat_grid, ray_dir, ray_pix, ray_bid, roi_inp_bbox, multires_views):
+    def forward(ctx, feat_grid, ray_dir, ray_pix, ray_bid, roi_inp_bbox, multires_views, *roi_backward):
+        ctx.route = _roi_backward_arg(*roi_backward)
         fg = feat_grid.detach().contiguous()
         out = ray_features(fg, ray_dir, ray_pix, ray_bid, roi_inp_bbox, multires_views)
         ctx.save_for_backward(ray_pix, ray_bid)
         ctx.shape, ctx.bbox, ctx.lv = tuple(fg.shape), roi_inp_bbox, multires_views
+        ctx.n_rest = 5 + len(roi_backward)
         return out
 
     @staticmethod
@@ -999,13 +1003,25 @@ class _RayFeaturesFn(torch.autograd.Function):
         B, _, h, w = ctx.shape
         g = g.detach().contiguous().float()
         d_feat = torch.empty(ctx.shape, dtype=torch.float32, device=g.device)
-        wsb = B * 129 * h * w * 4    # scratch image of the parked gradients + rays-per-pixel table
+        L = _lib.lib()
+        if ctx.route == "ordered":
+            fn, wsb = L.lidf_ray_features_backward_ordered_f32, L.lidf_ray_features_backward_ordered_workspace_bytes(
+                B, h, w)
+        else:
+            # scratch image of the parked gradients + rays-per-pixel table
+            fn, wsb = L.lidf_ray_features_backward_f32, B * 129 * h * w * 4
         ws = _lib.workspace(wsb, g.device)
         with torch.cuda.device(g.device):
-            _lib.check(_lib.lib().lidf_ray_features_backward_f32(
-                _lib.ptr(g), _lib.ptr(ray_pix), _lib.ptr(ray_bid), g.shape[0], B, h, w, ctx.bbox,
-                ctx.lv, _lib.ptr(d_feat), _lib.ptr(ws), wsb, _lib.current_stream(g.device)))
-        return d_feat, None, None, None, None, None
+            _lib.check(fn(_lib.ptr(g), _lib.ptr(ray_pix), _lib.ptr(ray_bid), g.shape[0], B, h, w, ctx.bbox,
+                          ctx.lv, _lib.ptr(d_feat), _lib.ptr(ws), wsb, _lib.current_stream(g.device)))
+        return (d_feat,) + (None,) * ctx.n_rest
+
+
+def _roi_backward_arg(roi_backward="atomic"):
+    """roi_backward, checked: 'atomic' or 'ordered'."""
+    if roi_backward not in ("atomic", "ordered"):
+        raise ValueError("roi_backward must be 'atomic' or 'ordered', not %r" % (roi_backward,))
+    return roi_backward
 
 
 class _BuildRowsFn(torch.autograd.Function):
@@ -1266,7 +1282,7 @@ class _QueryTrainFn(torch.autograd.Function):
 def lidf_query_train(ray_dir, ray_pix, ray_bid, pair_off, pair_ray, pair_vox, pair_t, feat_grid,
                      vox_feat, prob_dec, offset_dec, multires=8, multires_views=4, roi_inp_bbox=8,
                      offset_range=(0.0, 1.0), part_size=0.25, vox_center=None, pos_rel=False,
-                     factorised=True, max_pair_id=None, offsets="all", roi_out_bbox=2):
+                     factorised=True, max_pair_id=None, offsets="all", roi_out_bbox=2, roi_backward="atomic"):
     """Differentiable get_embedding + get_pred (models/pipeline.py:338-466) for training
     (train_lidf.py:393-396): gradients reach feat_grid (through RoIAlign), vox_feat and every
     decoder parameter, all through liblidf_hip — ROI pooling, the decoder input rows, the decoders'
@@ -1287,12 +1303,19 @@ def lidf_query_train(ray_dir, ray_pix, ray_bid, pair_off, pair_ray, pair_vox, pa
     columns), decoders of another gf_dim — take generic.query_train under factorised=True: the same factorised
     layer 1, the layers behind it one autograd function each (it refuses offsets="selected" and a head wider than 1).
     factorised=False stays the shipped-feature-width rows route.
+    roi_backward: how the gradient reaches feat_grid. "atomic" (default) is lidf_ray_features_backward_f32, whose
+    border boxes are summed with float atomics (equal to rounding between runs); "ordered" (opt-in) is
+    lidf_ray_features_backward_ordered_f32, a fixed-order gather without a float atomic on the image: feat_grid's
+    gradient is then bit-reproducible for rays on distinct pixels (two rays on a pixel too; more than two are added
+    in an order that is not fixed). On the generic.query_train route "ordered" is accepted and changes nothing: its
+    adjoint (lidf_roi_align_backward_f32) is an ordered gather already. Any other value raises ValueError.
     Returns pred_offset, pred_prob_end [P,1], pair_pred_pos [P,3], pred_prob_end_softmax [P],
     max_pair_id [R] (P for an empty ray) and pred_pos [R,3]."""
     if offsets not in ("all", "selected"):
         raise ValueError("offsets must be 'all' or 'selected'")
     if offsets == "selected" and not factorised:
         raise RuntimeError("offsets='selected' needs the factorised path")
+    _roi_backward_arg(roi_backward)
     ray_pix, ray_bid = _as_i32(ray_pix, "ray_pix"), _as_i32(ray_bid, "ray_bid")   # int64 accepted
     _lib.require_cuda(ray_dir, ray_pix, ray_bid, pair_off, pair_ray, pair_vox, pair_t, feat_grid,
                       vox_feat, vox_center,
@@ -1318,7 +1341,8 @@ def lidf_query_train(ray_dir, ray_pix, ray_bid, pair_off, pair_ray, pair_vox, pa
         from . import generic
         return generic.query_train(ray_dir, ray_pix, ray_bid, pair_off, pair_ray, pair_vox, pair_t, feat_grid,
                                    vox_feat, prob_dec, offset_dec, multires, multires_views, roi_inp_bbox,
-                                   roi_out_bbox, offset_range, part_size, vox_center, pos_rel, max_pair_id, offsets)
+                                   roi_out_bbox, offset_range, part_size, vox_center, pos_rel, max_pair_id, offsets,
+                                   roi_backward)
     if feat_grid.shape[1] != 32:
         raise RuntimeError("feat_grid must be [B,32,h,w] (rgb_out=32)")
     if vox_feat.shape[1] != 128:
@@ -1342,7 +1366,8 @@ def lidf_query_train(ray_dir, ray_pix, ray_bid, pair_off, pair_ray, pair_vox, pa
                 _lib.ptr(pair_ray), _lib.ptr(pair_vox), _lib.ptr(pair_t), _lib.ptr(ray_dir),
                 _lib.ptr(vox_center) if vox_center is not None else None, 1 if pos_rel else 0,
                 multires, P, _lib.ptr(pe), _lib.current_stream(dev)))
-    rayfeat = _RayFeaturesFn.apply(feat_grid, ray_dir, ray_pix, ray_bid, roi_inp_bbox, multires_views)
+    rayfeat = _RayFeaturesFn.apply(feat_grid, ray_dir, ray_pix, ray_bid, roi_inp_bbox, multires_views,
+                                   roi_backward)
     if factorised:
         if two:
             torch.cuda.current_stream(dev).wait_stream(side)
@@ -1491,7 +1516,7 @@ def lidf_refine_train(ray_dir, ray_pix, ray_bid, ray_flat, pred_pos, max_pair_id
                       voxel_bid, rgb_img, feat_grid, valid_inp, valid_vox, pnet_model, offset_dec,
                       forward_times=2, multires=8, multires_views=4, roi_inp_bbox=8,
                       offset_range=(-0.2, 0.2), pos_rel=False, pnet_pos_rel=True, perturb_noise=None, grid=None,
-                      roi_out_bbox=2, factorised=None):
+                      roi_out_bbox=2, factorised=None, roi_backward="atomic"):
     """Differentiable RefineNet.forward (models/pipeline.py:922-1041, exp_type 'train'): the same
     arguments as lidf_refine; gradients reach every parameter of pnet_model (PointNet2Stage) and
     offset_dec (IEF / IMNet) — through the second and later iterations also via the refined position
@@ -1513,8 +1538,12 @@ def lidf_refine_train(ray_dir, ray_pix, ray_bid, ray_flat, pred_pos, max_pair_id
     with the fused node); factorised=False never does.
     perturb_noise: the scalar of refine_perturb_noise() — or None — applied in the first iteration
     (pipeline.py:937). grid: as lidf_refine (the end voxels through the cell table).
+    roi_backward: "atomic" (default) or "ordered", as in lidf_query_train — how the gradient reaches a feat_grid that
+    requires grad. On the generic.refine_train route "ordered" is accepted and changes nothing (its adjoint is the
+    ordered gather already). Any other value raises ValueError.
     Returns pred_pos_refine [R,3] (with grad) and the last end_voxel_id [R] i32."""
     from .decoders import is_shipped
+    _roi_backward_arg(roi_backward)
     from .pointnet import is_shipped as pnet_shipped, pointnet_params
     E, Ed = 3 + 6 * multires, 3 + 6 * multires_views
     # the feature widths the fused node and the composed path are built for; every other one has generic.refine_train
@@ -1525,7 +1554,7 @@ def lidf_refine_train(ray_dir, ray_pix, ray_bid, ray_flat, pred_pos, max_pair_id
         return generic.refine_train(ray_dir, ray_pix, ray_bid, ray_flat, pred_pos, max_pair_id, pair_vox, voxel_bound,
                                     voxel_bid, rgb_img, feat_grid, valid_inp, valid_vox, pnet_model, offset_dec,
                                     forward_times, multires, multires_views, roi_inp_bbox, roi_out_bbox, offset_range,
-                                    pos_rel, pnet_pos_rel, perturb_noise, grid)
+                                    pos_rel, pnet_pos_rel, perturb_noise, grid, roi_backward)
     if roi_out_bbox != 2:
         raise RuntimeError("factorised=False keeps the shipped-feature-width paths: roi_out_bbox must be 2")
     if not (is_shipped(offset_dec) and pnet_shipped(pnet_model) and feat_grid.shape[1] == 32
@@ -1533,7 +1562,8 @@ def lidf_refine_train(ray_dir, ray_pix, ray_bid, ray_flat, pred_pos, max_pair_id
         return _lidf_refine_train_composed(ray_dir, ray_pix, ray_bid, ray_flat, pred_pos, max_pair_id, pair_vox,
                                            voxel_bound, voxel_bid, rgb_img, feat_grid, valid_inp, valid_vox,
                                            pnet_model, offset_dec, forward_times, multires, multires_views,
-                                           roi_inp_bbox, offset_range, pos_rel, pnet_pos_rel, perturb_noise)
+                                           roi_inp_bbox, offset_range, pos_rel, pnet_pos_rel, perturb_noise,
+                                           roi_backward)
     ray_pix, ray_bid = _as_i32(ray_pix, "ray_pix"), _as_i32(ray_bid, "ray_bid")
     ray_flat, voxel_bid = _as_i32(ray_flat, "ray_flat"), _as_i32(voxel_bid, "voxel_bid")
     pair_vox, valid_vox = _as_i32(pair_vox, "pair_vox"), _as_i32(valid_vox, "valid_vox")
@@ -1560,7 +1590,8 @@ def lidf_refine_train(ray_dir, ray_pix, ray_bid, ray_flat, pred_pos, max_pair_id
                            "frozen stage 1, trainers/train_refine.py:73)")
     # per-ray [ROI | embed(dir)] rows: constants of the iterations (RoIAlign backward when feat_grid trains)
     if torch.is_grad_enabled() and feat_grid.requires_grad:
-        rayfeat = _RayFeaturesFn.apply(feat_grid, ray_dir, ray_pix, ray_bid, roi_inp_bbox, multires_views)
+        rayfeat = _RayFeaturesFn.apply(feat_grid, ray_dir, ray_pix, ray_bid, roi_inp_bbox, multires_views,
+                                       roi_backward)
     else:
         rayfeat = ray_features(feat_grid.detach(), ray_dir, ray_pix, ray_bid, roi_inp_bbox, multires_views)
     cur = pred_pos
@@ -1576,7 +1607,8 @@ def lidf_refine_train(ray_dir, ray_pix, ray_bid, ray_flat, pred_pos, max_pair_id
 def _lidf_refine_train_composed(ray_dir, ray_pix, ray_bid, ray_flat, pred_pos, max_pair_id, pair_vox, voxel_bound,
                       voxel_bid, rgb_img, feat_grid, valid_inp, valid_vox, pnet_model, offset_dec,
                       forward_times=2, multires=8, multires_views=4, roi_inp_bbox=8,
-                      offset_range=(-0.2, 0.2), pos_rel=False, pnet_pos_rel=True, perturb_noise=None):
+                      offset_range=(-0.2, 0.2), pos_rel=False, pnet_pos_rel=True, perturb_noise=None,
+                      roi_backward="atomic"):
     """lidf_refine_train composed from the modules' own autograd functions (rounds 3-4; the path for widths
     other than the shipped ones, and the definition tests/test_train_gpu.py compares the fused step with).
     Differentiable RefineNet.forward (models/pipeline.py:922-1041, exp_type 'train'): the same
@@ -1608,7 +1640,8 @@ def _lidf_refine_train_composed(ray_dir, ray_pix, ray_bid, ray_flat, pred_pos, m
     embed_pos, _ = get_embedder(multires) if multires > 0 else (torch.nn.Identity(), 3)
     # per-ray [ROI | embed(dir)] rows: constants of the iterations (RoIAlign backward when feat_grid trains)
     if torch.is_grad_enabled() and feat_grid.requires_grad:
-        rayfeat = _RayFeaturesFn.apply(feat_grid, ray_dir, ray_pix, ray_bid, roi_inp_bbox, multires_views)
+        rayfeat = _RayFeaturesFn.apply(feat_grid, ray_dir, ray_pix, ray_bid, roi_inp_bbox, multires_views,
+                                       roi_backward)
     else:
         rayfeat = ray_features(feat_grid.detach(), ray_dir, ray_pix, ray_bid, roi_inp_bbox, multires_views)
     roi, dir_embed = rayfeat[:, :128], rayfeat[:, 128:]

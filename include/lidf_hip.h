@@ -982,6 +982,36 @@ int lidf_ray_features_backward_f32(const float* d_rayfeat, const int32_t* ray_pi
                                    int32_t multires_views, float* d_feat_grid, void* workspace,
                                    size_t workspace_bytes, lidf_stream_t stream);
 
+/* The same adjoint, bit-reproducible: no float atomic touches d_feat_grid. Arguments as
+ * lidf_ray_features_backward_f32; roi_inp_bbox / 2 (`half`) in 1..16.
+ * Every ray is parked in the [B,128,h,w] image. Every element of d_feat_grid is written:
+ *   1. the interior value: 0 + acc / half^2, acc = the parked gradients of the unclamped boxes whose
+ *      bin covers the pixel, added one by one — bins (ph, pw) = (0,0) (0,1) (1,0) (1,1), within a bin
+ *      source rows ascending, then columns (bin ph = 0 is covered from rows y+1 .. y+half, ph = 1 from
+ *      y-half+1 .. y; columns alike);
+ *   2. onto it, one by one, the terms of the boxes clamped at the image border (a centre within `half`
+ *      of a border): source pixels in raster order (row, then column), bins 0..3 within a source
+ *      pixel, each term (g / (gh gw)) * wy * wx — gh x gw the sample grid of the CLAMPED box, wy / wx
+ *      the summed bilinear tap weights of the bin's sample rows / columns at the pixel — every product
+ *      and every sum rounded to float on its own (no fused multiply-add). Terms with a zero factor are
+ *      skipped, which changes no bit of a sum.
+ * Rays that share a (frame, pixel) are added in the parked image: two stay exact (a two-term float add
+ * is commutative), more than two are summed in an order that is not fixed. Every caller in pipeline.py
+ * names a pixel once.
+ * The result never depends on the workspace's contents at entry. n_rays == 0 writes zeros (no
+ * workspace needed). Before any HIP call: LIDF_ERR_BAD_ARG for n_rays < 0, batch / height / width < 1,
+ * multires_views outside 0..16, a NULL d_feat_grid or (n_rays > 0) a NULL d_rayfeat / ray_pix / ray_bid;
+ * LIDF_ERR_UNSUPPORTED for roi_inp_bbox / 2 outside 1..16, batch > 2047 or batch*height*width >= 2^30;
+ * LIDF_ERR_WORKSPACE (n_rays > 0) for a NULL workspace or workspace_bytes below
+ * lidf_ray_features_backward_ordered_workspace_bytes(batch, height, width) — this entry never falls
+ * back to float atomics.                                                                          */
+size_t lidf_ray_features_backward_ordered_workspace_bytes(int32_t batch, int32_t height, int32_t width);
+int lidf_ray_features_backward_ordered_f32(const float* d_rayfeat, const int32_t* ray_pix,
+                                           const int32_t* ray_bid, int64_t n_rays, int32_t batch,
+                                           int32_t height, int32_t width, int32_t roi_inp_bbox,
+                                           int32_t multires_views, float* d_feat_grid, void* workspace,
+                                           size_t workspace_bytes, lidf_stream_t stream);
+
 /* ---- Query decoders, factorised training path ------------------------------------------------
  * The layer-1 rewrite of the inference kernel carried through training: per decoder
  *   layer 1 = W1[:, enter|leave] pe[p] + voxpart[pair_vox[p]] + raypart[pair_ray[p]] (+ u*off)
