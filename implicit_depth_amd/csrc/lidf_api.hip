@@ -5,12 +5,17 @@
 
 #include "lidf_launch.h"
 #include "lidf_hip.h"
+#include "lidf_carve.h"
 
 #define LIDF_API extern "C" __attribute__((visibility("default")))
 #define CHECK_HIP(x)                       \
     do {                                   \
         if ((x) != hipSuccess) return LIDF_ERR_HIP; \
     } while (0)
+
+// a caller's workspace / blob that is NULL or short: (ptr, bytes) against a byte count, or against what `c` carved
+#define CHECK_WS(ptr, bytes, need) do { if (!lidf_covers(ptr, bytes, need)) return LIDF_ERR_WORKSPACE; } while (0)
+#define CHECK_CARVED(c, ptr, bytes) CHECK_WS(ptr, bytes, (c).used())
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static size_t linex_stream_bytes(int k);
@@ -145,14 +150,18 @@ LIDF_API int lidf_embed_f32(const float* x, int64_t n, int multires, float* out,
 }
 
 // ---- decoders on materialised rows ---------------------------------------------------------------
-LIDF_API size_t lidf_decoders_workspace_bytes(int64_t n, int d) {
-    (void)n;
+struct StreamAux { float *stream, *aux; };   // a weight stream and the layer-4 operands behind it
+static StreamAux decoders_ws(Carver& c, int d) {
+    const size_t fs = (size_t)lidf_make_layout(2, LIDF_MODE_ROWS, rows_map(d, 0, 0, 0, 1)).total;
+    const size_t hs = (size_t)lidf_make_layout_rows_h(2, d, 0).total;  // split-f16 stream
+    StreamAux w;
+    w.stream = c.take<float>(fs > hs ? fs : hs);
+    w.aux = c.take<float>(2 * LIDF_AUX_FLOATS);
+    return w;
+}
+LIDF_API size_t lidf_decoders_workspace_bytes(int64_t, int d) {
     if (d <= 0) return 0;
-    L1Map m = rows_map(d, 0, 0, 0, 1);
-    StreamLayout lay = lidf_make_layout(2, LIDF_MODE_ROWS, m);
-    const size_t hs = (size_t)lidf_make_layout_rows_h(2, d, 0).total * 4;  // split-f16 stream
-    const size_t fs = (size_t)lay.total * 4;
-    return align_up(fs > hs ? fs : hs, 256) + align_up(2 * LIDF_AUX_FLOATS * 4, 256);
+    return carved([&](Carver& c) { decoders_ws(c, d); });
 }
 
 static int decoders_impl(const float* inp, int64_t n, int d, int64_t ld_inp, const LidfDecoder* prob,
@@ -188,8 +197,9 @@ static int decoders_impl(const float* inp, int64_t n, int d, int64_t ld_inp, con
     if (n == 0) return LIDF_OK;  // empty input: nothing to write (reference returns [0,1])
     if ((prob && !out_prob) || (off && !out_off)) return LIDF_ERR_BAD_ARG;
     if (!inp) return LIDF_ERR_BAD_ARG;
-    if (!workspace || workspace_bytes < lidf_decoders_workspace_bytes(n, d))
-        return LIDF_ERR_WORKSPACE;
+    Carver c(workspace);
+    const StreamAux w = decoders_ws(c, d);
+    CHECK_CARVED(c, workspace, workspace_bytes);
     hipStream_t st = (hipStream_t)stream;
 
     const int nets = (prob ? 1 : 0) + (off ? 1 : 0);
@@ -198,9 +208,7 @@ static int decoders_impl(const float* inp, int64_t n, int d, int64_t ld_inp, con
     L1Map m = rows_map(d, 0, 0, 0, 1);
     const bool split = precision == LIDF_PRECISION_F16X3;
     StreamLayout lay = split ? lidf_make_layout_rows_h(nets, d, 0) : lidf_make_layout(nets, LIDF_MODE_ROWS, m);
-    float* stream_buf = (float*)workspace;
-    float* aux = (float*)((char*)workspace + lidf_decoders_workspace_bytes(n, d) -
-                          align_up(2 * LIDF_AUX_FLOATS * 4, 256));
+    float *stream_buf = w.stream, *aux = w.aux;
     NetW n0 = to_netw(ds[0], d);
     NetW n1 = nets == 2 ? to_netw(ds[1], d) : n0;
     if (split)
@@ -275,10 +283,14 @@ LIDF_API int lidf_ray_reduce_f32(const float* pred_prob, const float* pair_pred_
 }
 
 // ---- fused query ---------------------------------------------------------------------------------
+// the packed weights of the query (lidf_query_pack_f32's blob, and the head of the workspace)
+struct QueryPack { float *stream_pts, *aux_pts, *stream_vox, *stream_ray; };
 struct QueryWs {
-    // the first four slots hold the packed weights (lidf_query_pack_f32 writes exactly this prefix)
-    size_t stream_pts, aux_pts, stream_vox, stream_ray, packed_end, counter, voxpart, raypart, rayfeat,
-        sel, box, total;
+    QueryPack pk;
+    int* counter;    // tile hand-out counters of the split-f16 kernel ([1]: its launch on the selected list)
+    float *voxpart, *raypart, *rayfeat;
+    char* sel;       // offsets_selected: the one-pair-per-ray list (sel_list)
+    float* box;      // optional box-sum image + the list of clamped-box rays (last)
 };
 
 // Widths of the decoders' input rows: stage 1 [vox feat 128 | ROI 128 | embed(enter) | embed(leave) | embed(dir)],
@@ -317,54 +329,48 @@ static QueryPlan query_plan(int L, int Lv, int precision) {
     return p;
 }
 
-static QueryWs query_ws(int64_t R, int64_t V, int L, int Lv, int64_t grid_floats = 0) {
-    QueryWs w;
+static QueryPack query_pack_lay(Carver& c, int L, int Lv) {
     // the per-point and the per-ray slot serve either precision: sized for the larger stream
     const QueryPlan f32 = query_plan(L, Lv, LIDF_PRECISION_F32), f16 = query_plan(L, Lv, LIDF_PRECISION_F16X3);
-    const size_t pts = (size_t)(f32.lf.total > f16.lf.total ? f32.lf.total : f16.lf.total) * 4;
-    const size_t ray = (size_t)(f32.lr.total > f16.lh.total ? f32.lr.total : f16.lh.total) * 4;
-    size_t o = 0;
-    w.stream_pts = o; o += align_up(pts, 256);
-    w.aux_pts = o;    o += align_up(2 * LIDF_AUX_FLOATS * 4, 256);
-    w.stream_vox = o; o += align_up((size_t)f32.lv.total * 4, 256);
-    w.stream_ray = o; o += align_up(ray, 256);
-    w.packed_end = o;
-    w.counter = o;    o += 256;  // tile hand-out counters of the split-f16 kernel ([1]: its launch on the selected list)
-    w.voxpart = o;    o += align_up((size_t)(V > 0 ? V : 1) * 512 * 4, 256);
-    w.raypart = o;    o += align_up((size_t)(R > 0 ? R : 1) * 512 * 4, 256);
-    w.rayfeat = o;    o += align_up((size_t)(R > 0 ? R : 1) * (128 + f32.Ed) * 4, 256);
-    // offsets_selected: the one-pair-per-ray list (sel_list)
-    w.sel = o;        o += align_up((size_t)(R > 0 ? R : 1) * 32, 256);
-    // optional box-sum image + the list of clamped-box rays (last)
-    w.box = o;        o += grid_floats > 0 ? align_up((size_t)(grid_floats + R + 1) * 4, 256) : 0;
-    w.total = o;
+    QueryPack k;
+    k.stream_pts = c.take<float>(f32.lf.total > f16.lf.total ? f32.lf.total : f16.lf.total);
+    k.aux_pts = c.take<float>(2 * LIDF_AUX_FLOATS);
+    k.stream_vox = c.take<float>(f32.lv.total);
+    k.stream_ray = c.take<float>(f32.lr.total > f16.lh.total ? f32.lr.total : f16.lh.total);
+    return k;
+}
+static QueryWs query_ws(Carver& c, int64_t R, int64_t V, int L, int Lv, int64_t grid_floats = 0) {
+    const size_t Rc = (size_t)(R > 0 ? R : 1), Vc = (size_t)(V > 0 ? V : 1);
+    QueryWs w;
+    w.pk = query_pack_lay(c, L, Lv);
+    w.counter = c.take<int>(64);
+    w.voxpart = c.take<float>(Vc * 512);
+    w.raypart = c.take<float>(Rc * 512);
+    w.rayfeat = c.take<float>(Rc * (128 + 3 + 6 * Lv));
+    w.sel = c.take<char>(Rc * 32);
+    w.box = c.take_if<float>(grid_floats > 0, (size_t)(grid_floats + R + 1));
     return w;
 }
 
 LIDF_API size_t lidf_query_workspace_bytes(int64_t n_rays, int64_t n_vox, int64_t grid_floats) {
     // sized for the largest supported embedding (multires = multires_views = 16)
-    return query_ws(n_rays, n_vox, LIDF_MAX_L_FUSED, 16, grid_floats > 0 ? grid_floats : 0).total;
+    return carved([&](Carver& c) { query_ws(c, n_rays, n_vox, LIDF_MAX_L_FUSED, 16, grid_floats); });
 }
 
 // The decoders' parameters re-ordered into the streams the query kernels consume: the per-point
 // stream (+ layer-4 operands), the per-voxel and the per-ray layer-1 streams.
-static int pack_query_weights(const LidfDecoder* prob, const LidfDecoder* off, const QueryPlan& p, char* dst,
+static int pack_query_weights(const LidfDecoder* prob, const LidfDecoder* off, const QueryPlan& p, const QueryPack& k,
                               hipStream_t st) {
-    const QueryWs w = query_ws(1, 1, p.L, p.Lv);
-    float* stream_pts = (float*)(dst + w.stream_pts);
-    float* aux_pts = (float*)(dst + w.aux_pts);
-    float* stream_vox = (float*)(dst + w.stream_vox);
-    float* stream_ray = (float*)(dst + w.stream_ray);
     NetW np = to_netw(prob, p.D), no = to_netw(off, p.D);
     if (p.split)
-        CHECK_HIP(lidf_launch_pack_h(guarded(p.lf), np, no, p.mf, stream_pts, aux_pts, st));
+        CHECK_HIP(lidf_launch_pack_h(guarded(p.lf), np, no, p.mf, k.stream_pts, k.aux_pts, st));
     else
-        CHECK_HIP(pack_stream(p.lf, np, no, p.mf, stream_pts, aux_pts, st));
-    CHECK_HIP(pack_stream(p.lv, np, no, p.mv, stream_vox, aux_pts, st));
+        CHECK_HIP(pack_stream(p.lf, np, no, p.mf, k.stream_pts, k.aux_pts, st));
+    CHECK_HIP(pack_stream(p.lv, np, no, p.mv, k.stream_vox, k.aux_pts, st));
     if (p.split)
-        CHECK_HIP(lidf_launch_pack_rows_h(guarded(p.lh), np, no, p.mr, stream_ray, nullptr, st));
+        CHECK_HIP(lidf_launch_pack_rows_h(guarded(p.lh), np, no, p.mr, k.stream_ray, nullptr, st));
     else
-        CHECK_HIP(pack_stream(p.lr, np, no, p.mr, stream_ray, aux_pts, st));
+        CHECK_HIP(pack_stream(p.lr, np, no, p.mr, k.stream_ray, k.aux_pts, st));
     return LIDF_OK;
 }
 
@@ -382,7 +388,7 @@ static int check_query_model(const LidfDecoder* prob, const LidfDecoder* off, in
 }
 
 LIDF_API size_t lidf_query_pack_bytes(void) {
-    return query_ws(1, 1, LIDF_MAX_L_FUSED, 16).packed_end;
+    return carved([&](Carver& c) { query_pack_lay(c, LIDF_MAX_L_FUSED, 16); });
 }
 
 LIDF_API int lidf_query_pack_f32(const LidfDecoder* prob, const LidfDecoder* off, int multires,
@@ -390,11 +396,11 @@ LIDF_API int lidf_query_pack_f32(const LidfDecoder* prob, const LidfDecoder* off
                                    size_t packed_bytes, lidf_stream_t stream) {
     int rc = check_query_model(prob, off, multires, multires_views, precision);
     if (rc) return rc;
-    if (!packed || packed_bytes < query_ws(1, 1, multires, multires_views).packed_end)
-        return LIDF_ERR_WORKSPACE;
+    Carver c(packed);
+    const QueryPack k = query_pack_lay(c, multires, multires_views);
+    CHECK_CARVED(c, packed, packed_bytes);
     JobScope js;
-    if ((rc = pack_query_weights(prob, off, query_plan(multires, multires_views, precision), (char*)packed,
-                                 (hipStream_t)stream)))
+    if ((rc = pack_query_weights(prob, off, query_plan(multires, multires_views, precision), k, (hipStream_t)stream)))
         return rc;
     CHECK_HIP(flush_jobs(js.jobs, (hipStream_t)stream));
     return LIDF_OK;
@@ -463,8 +469,9 @@ LIDF_API int lidf_query_pack_guarded_f32(const LidfDecoder* prob, const LidfDeco
     int rc = check_query_model(prob, off, multires, multires_views, precision);
     if (rc) return rc;
     if (!guard) return LIDF_ERR_BAD_ARG;
-    if (!packed || packed_bytes < query_ws(1, 1, multires, multires_views).packed_end)
-        return LIDF_ERR_WORKSPACE;
+    Carver c(packed);
+    query_pack_lay(c, multires, multires_views);
+    CHECK_CARVED(c, packed, packed_bytes);
     const int D = query_D(multires, multires_views);
     const float* ptrs[LIDF_FP_MAX_SEGS];
     long long cnt[LIDF_FP_MAX_SEGS];
@@ -478,16 +485,16 @@ LIDF_API int lidf_query_pack_guarded_f32(const LidfDecoder* prob, const LidfDeco
 
 // The arguments of one layer-1 table launch of the query, both nets ([n, 512]):
 //   per voxel  voxpart[v] = W1[:, 0:128] vox_feat[v] + b1 (+c),   per ray  raypart[r] = W1[:, rgb | dir] rayfeat[r]
-// pk: the packed weight streams (QueryWs prefix). The split-f16 query forms the per-ray table with the rows_h kernel.
+// k: the packed weight streams. The split-f16 query forms the per-ray table with the rows_h kernel.
 enum { L1_VOX, L1_RAY };
 static PointsArgs l1_table_args(const QueryPlan& p, int table, const float* X, int64_t n, const int* n_dev,
-                                float* out, const char* pk, const QueryWs& w) {
+                                float* out, const QueryPack& k) {
     const bool vox = table == L1_VOX;
     const L1Map& m = vox ? p.mv : p.mr;
     const StreamLayout& l = vox ? p.lv : p.split ? p.lh : p.lr;
     PointsArgs a = {};
-    a.stream = (const float*)(pk + (vox ? w.stream_vox : w.stream_ray));
-    a.aux = (const float*)(pk + w.aux_pts);
+    a.stream = vox ? k.stream_vox : k.stream_ray;
+    a.aux = k.aux_pts;
     a.nets = 2; a.l1_quads = l.l1_quads; a.net_quads = l.net_quads;
     a.n = n; a.n_dev = n_dev;
     a.X = X; a.ldx = vox ? 128 : 128 + p.Ed;
@@ -499,17 +506,17 @@ static PointsArgs l1_table_args(const QueryPlan& p, int table, const float* X, i
 // The arguments of the per-point kernel that every caller sets alike: both nets of the stream over the P pairs and the
 // two tables in the workspace. The caller adds its nets' passes and outputs (fill_net_args) and what differs between
 // callers: n_dev, tile_counter, pair_pred_pos, the kept activations, a one-net launch (nets, part_ld, part_off).
-static PointsArgs points_args(const QueryPlan& p, const char* pk, char* ws, const QueryWs& w, int64_t P,
+static PointsArgs points_args(const QueryPlan& p, const QueryPack& k, const QueryWs& w, int64_t P,
                               const int* pair_ray, const int* pair_vox, const float* pair_t, const float* ray_dir,
                               const float* vox_center, int pos_rel, float range0, float range1, float part_size) {
     PointsArgs a = {};
-    a.stream = (const float*)(pk + w.stream_pts);
-    a.aux = (const float*)(pk + w.aux_pts);
+    a.stream = k.stream_pts;
+    a.aux = k.aux_pts;
     a.nets = 2; a.l1_quads = p.lf.l1_quads; a.net_quads = p.lf.net_quads;
     a.n = P;
     a.pair_ray = pair_ray; a.pair_vox = pair_vox; a.pair_t = pair_t;
     a.ray_dir = ray_dir;
-    a.voxpart = (const float*)(ws + w.voxpart); a.raypart = (const float*)(ws + w.raypart);
+    a.voxpart = w.voxpart; a.raypart = w.raypart;
     a.vox_center = vox_center; a.pos_rel = pos_rel; a.L = p.L;
     a.r0 = range0;
     a.rscale = range1 - range0;
@@ -583,32 +590,31 @@ static int query_impl(const LidfQueryArgs* q, void* ev_points_begin, void* ev_po
         if (q->batch <= 0 || q->height <= 0 || q->width <= 0) return LIDF_ERR_BAD_ARG;
         // the box-sum image (B*32*h*w floats) is used when the caller's workspace has room for it
         const int64_t grid_floats = (int64_t)q->batch * 32 * q->height * q->width;
-        QueryWs w = query_ws(R, V, L, Lv, grid_floats);
-        bool use_box = q->workspace_bytes >= w.total;
-        if (!use_box) w = query_ws(R, V, L, Lv);
-        if (!q->workspace || q->workspace_bytes < w.total) return LIDF_ERR_WORKSPACE;
-        char* ws = (char*)q->workspace;
+        Carver c(q->workspace);
+        QueryWs w = query_ws(c, R, V, L, Lv, grid_floats);
+        const bool use_box = c.covers(q->workspace, q->workspace_bytes);
+        if (!use_box) w = query_ws(c = Carver(q->workspace), R, V, L, Lv);
+        CHECK_CARVED(c, q->workspace, q->workspace_bytes);
         // 1. weight streams: the caller's packed blob (lidf_query_pack_f32, built once per
         // parameter version) or packed here, into the head of the workspace, for this call
-        const char* pk = q->packed ? (const char*)q->packed : ws;
+        Carver pc(q->packed);
+        const QueryPack k = q->packed ? query_pack_lay(pc, L, Lv) : w.pk;
         if (!q->packed && phases != QP_ALL) return LIDF_ERR_BAD_ARG;
         const QueryPlan p = query_plan(L, Lv, q->precision);
-        if (!q->packed && (rc = pack_query_weights(q->prob, q->off, p, ws, st))) return rc;
-        float* rayfeat = q->rayfeat_out ? q->rayfeat_out : (float*)(ws + w.rayfeat);
+        if (!q->packed && (rc = pack_query_weights(q->prob, q->off, p, k, st))) return rc;
+        float* rayfeat = q->rayfeat_out ? q->rayfeat_out : w.rayfeat;
         int cus;
         if ((rc = cu_count(&cus))) return rc;
 
         // 2. per-ray features [ROI 2x2 of the feature map | embed(dir)]
         if (phases & QP_RAYFEAT)
-            CHECK_HIP(lidf_launch_rayfeat_dev(q->feat_grid, use_box ? (float*)(ws + w.box) : nullptr,
-                                              q->batch, q->height, q->width, q->ray_dir, q->ray_pix,
-                                              q->ray_bid, R, dims, q->roi_inp_bbox / 2, Lv, rayfeat,
+            CHECK_HIP(lidf_launch_rayfeat_dev(q->feat_grid, w.box, q->batch, q->height, q->width, q->ray_dir,
+                                              q->ray_pix, q->ray_bid, R, dims, q->roi_inp_bbox / 2, Lv, rayfeat,
                                               128 + p.Ed, st));
         // 3. layer-1 partial products: per voxel and per ray (l1_table_args)
         {
-            const PointsArgs av = l1_table_args(p, L1_VOX, q->vox_feat, V, dims ? dims + 2 : nullptr,
-                                                (float*)(ws + w.voxpart), pk, w);
-            const PointsArgs a = l1_table_args(p, L1_RAY, rayfeat, R, dims, (float*)(ws + w.raypart), pk, w);
+            const PointsArgs av = l1_table_args(p, L1_VOX, q->vox_feat, V, dims ? dims + 2 : nullptr, w.voxpart, k);
+            const PointsArgs a = l1_table_args(p, L1_RAY, rayfeat, R, dims, w.raypart, k);
             const long long ntv = (V + 127) / 128, nt = (R + 127) / 128;
             if (extra_l1) { extra_l1->X = rayfeat; extra_l1->ldx = 128 + p.Ed; }
             if (p.split) {
@@ -627,13 +633,13 @@ static int query_impl(const LidfQueryArgs* q, void* ev_points_begin, void* ev_po
         if (!(phases & QP_MAIN)) return LIDF_OK;
         // 4. per-point kernel
         {
-            PointsArgs a = points_args(p, pk, ws, w, P, q->pair_ray, q->pair_vox, q->pair_t, q->ray_dir,
+            PointsArgs a = points_args(p, k, w, P, q->pair_ray, q->pair_vox, q->pair_t, q->ray_dir,
                                        q->vox_center, q->pos_rel, q->offset_range0, q->offset_range1, q->part_size);
             a.n_dev = dims ? dims + 1 : nullptr;
             fill_net_args(a, 0, q->prob, q->pred_prob, 0);
             fill_net_args(a, 1, q->off, q->pred_offset, 1);
             a.pair_pred_pos = q->pair_pred_pos;
-            a.tile_counter = (int*)(ws + w.counter);   // dynamic tile hand-out of both kernels
+            a.tile_counter = w.counter;   // dynamic tile hand-out of both kernels
             // (the frame path zeroes the counter with its other scratch, in one launch up front)
             // ([1]: the split-f16 launch on the selected list)
             if (!dims) CHECK_HIP(hipMemsetAsync(a.tile_counter, 0, 8, st));
@@ -663,7 +669,7 @@ static int query_impl(const LidfQueryArgs* q, void* ev_points_begin, void* ev_po
                     CHECK_HIP(lidf_launch_points_h(ap, cus, st));
                 else
                     CHECK_HIP(lidf_launch_points(LIDF_MODE_FUSED, ap, (int)(nt < cus ? nt : cus), st));
-                const SelList s = sel_list(ws + w.sel, R);
+                const SelList s = sel_list(w.sel, R);
                 CHECK_HIP(lidf_launch_ray_reduce_dev(q->pred_prob, nullptr, q->pair_off, R, P, dims,
                                                      dims ? dims + 1 : nullptr, q->ray_bid, q->ray_flat,
                                                      (long long)q->height * q->width, q->pred_prob_softmax,
@@ -719,22 +725,22 @@ LIDF_API int lidf_ray_dirs_f32(const float* intr, int batch, int height, int wid
 }
 
 // ---- get_miss_ray (mask -> compacted rays) ------------------------------------------------------
-struct MissWs {
-    size_t block_cnt, block_off, sums, total;
-};
-static MissWs miss_ws(int64_t n) {
-    if (n < 0) n = 0;
-    const size_t nb = (size_t)((n + 1023) / 1024);
+// block sums of lidf_launch_scan over n elements (lidf_exclusive_scan_i32's whole workspace)
+static int* scan_ws(Carver& c, int64_t n) { return c.take<int>((size_t)(((n > 0 ? n : 0) + 1023) / 1024 + 1)); }
+
+struct MissWs { int *block_cnt, *block_off, *sums; };
+static MissWs miss_ws(Carver& c, int64_t n) {
+    const size_t nb = (size_t)(((n > 0 ? n : 0) + 1023) / 1024);
     MissWs w;
-    size_t o = 0;
-    w.block_cnt = o; o += align_up((nb + 1) * 4, 256);
-    w.block_off = o; o += align_up((nb + 2) * 4, 256);
-    w.sums = o;      o += lidf_exclusive_scan_workspace_bytes((int64_t)nb);
-    w.total = o;
+    w.block_cnt = c.take<int>(nb + 1);
+    w.block_off = c.take<int>(nb + 2);
+    w.sums = scan_ws(c, (int64_t)nb);
     return w;
 }
 
-LIDF_API size_t lidf_miss_ray_workspace_bytes(int64_t n_pixels) { return miss_ws(n_pixels).total; }
+LIDF_API size_t lidf_miss_ray_workspace_bytes(int64_t n_pixels) {
+    return carved([&](Carver& c) { miss_ws(c, n_pixels); });
+}
 
 LIDF_API int lidf_miss_ray_count(const void* mask, int mask_dtype, int64_t n_pixels,
                                    int32_t* n_rays, void* workspace, size_t workspace_bytes,
@@ -743,11 +749,10 @@ LIDF_API int lidf_miss_ray_count(const void* mask, int mask_dtype, int64_t n_pix
     if (mask_dtype < LIDF_MASK_F32 || mask_dtype > LIDF_MASK_I64) return LIDF_ERR_BAD_ARG;
     if (n_pixels > 0x7ffffbffLL) return LIDF_ERR_UNSUPPORTED;
     if (n_pixels > 0 && !mask) return LIDF_ERR_BAD_ARG;
-    const MissWs w = miss_ws(n_pixels);
-    if (!workspace || workspace_bytes < w.total) return LIDF_ERR_WORKSPACE;
-    char* ws = (char*)workspace;
-    CHECK_HIP(lidf_launch_miss_count(mask, mask_dtype, n_pixels, (int*)(ws + w.block_cnt),
-                                     (int*)(ws + w.block_off), (int*)(ws + w.sums), n_rays,
+    Carver c(workspace);
+    const MissWs w = miss_ws(c, n_pixels);
+    CHECK_CARVED(c, workspace, workspace_bytes);
+    CHECK_HIP(lidf_launch_miss_count(mask, mask_dtype, n_pixels, w.block_cnt, w.block_off, w.sums, n_rays,
                                      (hipStream_t)stream));
     return LIDF_OK;
 }
@@ -764,10 +769,10 @@ LIDF_API int lidf_miss_ray_fill_f32(const void* mask, int mask_dtype, const floa
     if (n > 0x7ffffbffLL) return LIDF_ERR_UNSUPPORTED;
     if (n == 0) return LIDF_OK;
     if (!mask || (ray_dir && !intr)) return LIDF_ERR_BAD_ARG;
-    const MissWs w = miss_ws(n);
-    if (!workspace || workspace_bytes < w.total) return LIDF_ERR_WORKSPACE;
-    const char* ws = (const char*)workspace;
-    CHECK_HIP(lidf_launch_miss_fill(mask, mask_dtype, n, (const int*)(ws + w.block_off), intr,
+    Carver c(workspace);   // (only read here: what lidf_miss_ray_count left)
+    const MissWs w = miss_ws(c, n);
+    CHECK_CARVED(c, workspace, workspace_bytes);
+    CHECK_HIP(lidf_launch_miss_fill(mask, mask_dtype, n, w.block_off, intr,
                                     height, width, ray_bid, ray_flat, ray_pix, ray_dir,
                                     (long long*)miss_bid, (long long*)miss_flat_img_id,
                                     (long long*)miss_img_ind, (hipStream_t)stream));
@@ -797,23 +802,19 @@ LIDF_API int lidf_sample_valid_points(const void* mask, int mask_dtype, int batc
 }
 
 // ---- the random window of the miss rays (mask -> at most bs * miss_sample_num rays) -------------------------------
-struct MissWindowWs {
-    size_t block_cnt, block_off, img_off, total;
-};
-static MissWindowWs miss_window_ws(int batch, int64_t n) {
+struct MissWindowWs { int *block_cnt, *block_off, *img_off; };
+static MissWindowWs miss_window_ws(Carver& c, int batch, int64_t n) {
     const size_t nb = (size_t)((n + MISS_ITEMS - 1) / MISS_ITEMS);
     MissWindowWs w;
-    size_t o = 0;
-    w.block_cnt = o; o += align_up((nb + 1) * 4, 256);
-    w.block_off = o; o += align_up((nb + 1) * 4, 256);
-    w.img_off = o;   o += align_up(((size_t)batch + 1) * 4, 256);
-    w.total = o;
+    w.block_cnt = c.take<int>(nb + 1);
+    w.block_off = c.take<int>(nb + 1);
+    w.img_off = c.take<int>((size_t)batch + 1);
     return w;
 }
 
 LIDF_API size_t lidf_miss_window_workspace_bytes(int batch, int64_t n_pixels) {
     if (batch < 1 || n_pixels < 0) return 0;
-    return miss_window_ws(batch, n_pixels).total;
+    return carved([&](Carver& c) { miss_window_ws(c, batch, n_pixels); });
 }
 
 LIDF_API int lidf_miss_ray_window_f32(const void* mask, int mask_dtype, const float* intr, int batch, int height,
@@ -830,12 +831,12 @@ LIDF_API int lidf_miss_ray_window_f32(const void* mask, int mask_dtype, const fl
     const int64_t n = (int64_t)batch * height * width;
     if (n > 0x7ffffbffLL) return LIDF_ERR_UNSUPPORTED;                                   // (as lidf_miss_ray_count)
     if ((int64_t)batch * miss_sample_num > 0x7fffffffLL) return LIDF_ERR_UNSUPPORTED;   // rows of the outputs
-    const MissWindowWs w = miss_window_ws(batch, n);
-    if (workspace_bytes < w.total) return LIDF_ERR_WORKSPACE;
-    char* ws = (char*)workspace;
+    Carver c(workspace);
+    const MissWindowWs w = miss_window_ws(c, batch, n);
+    CHECK_CARVED(c, workspace, workspace_bytes);
     CHECK_HIP(lidf_launch_miss_window(mask, mask_dtype, intr, batch, height, width, miss_sample_num,
-                                      (const unsigned long long*)rng_state, starts, (int*)(ws + w.block_cnt),
-                                      (int*)(ws + w.block_off), (int*)(ws + w.img_off), ray_bid, ray_flat, ray_pix,
+                                      (const unsigned long long*)rng_state, starts, w.block_cnt,
+                                      w.block_off, w.img_off, ray_bid, ray_flat, ray_pix,
                                       ray_dir, (long long*)miss_bid, (long long*)miss_flat_img_id,
                                       (long long*)miss_img_ind, window, n_rays, (hipStream_t)stream));
     return LIDF_OK;
@@ -895,25 +896,22 @@ LIDF_API int lidf_ray_aabb_fill_f32(const float* ray_dir, const float* voxel_bou
 }
 
 // ---- the compact list on a regular voxel grid (lidf_aux.hip: per-axis interval tables + cell table)
-struct GridWs {
-    size_t cell, col, tab, total;
-};
+struct GridWs { int* cell; unsigned* col; float* tab; };
 static bool grid_dims_ok(int batch, int rx, int ry, int rz) {
     return batch >= 0 && rx > 0 && ry > 0 && rz > 0 && rx <= 1024 && ry <= 1024 && rz <= 1024 &&
            (long long)batch * rx * ry * rz <= 0x7fffffffLL;
 }
-static GridWs grid_ws(int batch, int rx, int ry, int rz) {
+static GridWs grid_ws(Carver& c, int batch, int rx, int ry, int rz) {
+    const size_t B = (size_t)(batch > 0 ? batch : 1);
     GridWs w;
-    size_t o = 0;
-    w.cell = o; o += align_up((size_t)(batch > 0 ? batch : 1) * rx * ry * rz * 4, 256);
-    w.col = o;  o += align_up((size_t)(batch > 0 ? batch : 1) * rx * ry * ((rz + 31) / 32) * 4, 256);
-    w.tab = o;  o += align_up((size_t)(batch > 0 ? batch : 1) * (rx + ry + rz) * 8, 256);
-    w.total = o;
+    w.cell = c.take<int>(B * rx * ry * rz);
+    w.col = c.take<unsigned>(B * rx * ry * ((rz + 31) / 32));
+    w.tab = c.take<float>(B * (rx + ry + rz) * 2);
     return w;
 }
 LIDF_API size_t lidf_ray_aabb_grid_workspace_bytes(int32_t batch, int32_t rx, int32_t ry, int32_t rz) {
     if (!grid_dims_ok(batch, rx, ry, rz)) return 0;
-    return grid_ws(batch, rx, ry, rz).total;
+    return carved([&](Carver& c) { grid_ws(c, batch, rx, ry, rz); });
 }
 
 LIDF_API int lidf_ray_aabb_grid_build_f32(const float* voxel_bound, const int32_t* voxel_bid,
@@ -923,13 +921,12 @@ LIDF_API int lidf_ray_aabb_grid_build_f32(const float* voxel_bound, const int32_
     if (n_vox < 0 || !grid_dims_ok(batch, rx, ry, rz)) return LIDF_ERR_BAD_ARG;
     if (n_vox > 0x7fffffffLL) return LIDF_ERR_UNSUPPORTED;
     if (n_vox > 0 && (!voxel_bound || !voxel_bid || !voxel_coord)) return LIDF_ERR_BAD_ARG;
-    const GridWs w = grid_ws(batch, rx, ry, rz);
-    if (!grid || grid_bytes < w.total) return LIDF_ERR_WORKSPACE;
+    Carver c(grid);
+    const GridWs w = grid_ws(c, batch, rx, ry, rz);
+    CHECK_CARVED(c, grid, grid_bytes);
     if (batch == 0) return LIDF_OK;
     CHECK_HIP(lidf_launch_ray_aabb_grid_build(voxel_bound, voxel_bid, voxel_coord, n_vox, batch, rx, ry,
-                                              rz, (int*)((char*)grid + w.cell),
-                                              (unsigned*)((char*)grid + w.col),
-                                              (float*)((char*)grid + w.tab), (hipStream_t)stream));
+                                              rz, w.cell, w.col, w.tab, (hipStream_t)stream));
     return LIDF_OK;
 }
 
@@ -941,13 +938,11 @@ static int grid_rays(bool fill, const float* ray_dir, const int32_t* ray_bid, in
     if (n_rays > 0x7fffffffLL) return LIDF_ERR_UNSUPPORTED;
     if (n_rays == 0) return LIDF_OK;
     if (!ray_dir || !ray_bid || (fill ? !pair_off : !count)) return LIDF_ERR_BAD_ARG;
-    const GridWs w = grid_ws(batch, rx, ry, rz);
-    if (!grid || grid_bytes < w.total) return LIDF_ERR_WORKSPACE;
-    CHECK_HIP(lidf_launch_ray_aabb_grid(fill, ray_dir, ray_bid, n_rays, batch, rx, ry, rz,
-                                        (const int*)((const char*)grid + w.cell),
-                                        (const unsigned*)((const char*)grid + w.col),
-                                        (const float*)((const char*)grid + w.tab), count, pair_off,
-                                        pair_ray, pair_vox, pair_t, (hipStream_t)stream));
+    Carver c(grid);   // (only read here: what lidf_ray_aabb_grid_build_f32 left)
+    const GridWs w = grid_ws(c, batch, rx, ry, rz);
+    CHECK_CARVED(c, grid, grid_bytes);
+    CHECK_HIP(lidf_launch_ray_aabb_grid(fill, ray_dir, ray_bid, n_rays, batch, rx, ry, rz, w.cell, w.col, w.tab,
+                                        count, pair_off, pair_ray, pair_vox, pair_t, (hipStream_t)stream));
     return LIDF_OK;
 }
 
@@ -968,19 +963,17 @@ LIDF_API int lidf_ray_aabb_grid_fill_f32(const float* ray_dir, const int32_t* ra
                      pair_off, pair_ray, pair_vox, pair_t, stream);
 }
 
-LIDF_API size_t lidf_exclusive_scan_workspace_bytes(int64_t n) {
-    if (n < 0) n = 0;
-    return align_up((size_t)((n + 1023) / 1024 + 1) * 4, 256);
-}
+LIDF_API size_t lidf_exclusive_scan_workspace_bytes(int64_t n) { return carved([&](Carver& c) { scan_ws(c, n); }); }
 
 LIDF_API int lidf_exclusive_scan_i32(const int32_t* in, int64_t n, int32_t* out, void* workspace,
                                        size_t workspace_bytes, lidf_stream_t stream) {
     if (n < 0 || !out) return LIDF_ERR_BAD_ARG;
     if (n > 0x7ffffffeLL) return LIDF_ERR_UNSUPPORTED;
     if (n > 0 && !in) return LIDF_ERR_BAD_ARG;
-    if (!workspace || workspace_bytes < lidf_exclusive_scan_workspace_bytes(n))
-        return LIDF_ERR_WORKSPACE;
-    CHECK_HIP(lidf_launch_scan(in, n, out, (int*)workspace, (hipStream_t)stream));
+    Carver c(workspace);
+    int* sums = scan_ws(c, n);
+    CHECK_CARVED(c, workspace, workspace_bytes);
+    CHECK_HIP(lidf_launch_scan(in, n, out, sums, (hipStream_t)stream));
     return LIDF_OK;
 }
 
@@ -1065,37 +1058,6 @@ static int run_vox2(const float* X, int k1, int64_t n, const int* n_dev, const f
     return LIDF_OK;
 }
 
-struct PnetWs {
-    size_t s[7], chain, f1, f2, pool1, g1, gpart, f4, pool2, part, part_bytes, sort, total;
-};
-static PnetWs pnet_ws(int64_t n, int64_t v) {
-    PnetWs w;
-    size_t o = 0;
-    const int ks[7] = {6, 32, 64, 64, 64, 128, 128};
-    const int nts[7] = {1, 2, 2, 4, 4, 4, 4};
-    for (int i = 0; i < 7; ++i) { w.s[i] = o; o += lin_stream_bytes(ks[i], nts[i]); }
-    w.chain = o; o += align_up(lidf_pointnet_chain_stream_bytes(), 256);
-    const size_t N = (size_t)(n > 0 ? n : 1), V = (size_t)(v > 0 ? v : 1);
-    // (no per-point intermediates: the inference chains keep them in registers; f1 marks the end of
-    // the stream slots)
-    w.f1 = o; w.f2 = o; w.f4 = o;
-    (void)N;
-    w.pool1 = o; o += align_up(V * 64 * 4, 256);
-    w.g1 = o;    o += align_up(V * 64 * 4, 256);
-    w.gpart = o; o += align_up(V * 128 * 4, 256);
-    w.pool2 = o; o += align_up(V * 128 * 4, 256);
-    w.part_bytes = lidf_pointnet_pool_scratch_bytes(v);
-    w.part = o;  o += align_up(w.part_bytes, 256);
-    // tables beyond the LDS pooling: the points are walked grouped by voxel (counting-sort scratch)
-    w.sort = o;  o += v > lidf_pointnet_lds_max_voxels() ? align_up(lidf_pointnet_sort_bytes(n, v), 256) : 0;
-    w.total = o;
-    return w;
-}
-
-LIDF_API size_t lidf_pointnet_workspace_bytes(int64_t n_pts, int64_t n_vox) {
-    return pnet_ws(n_pts, n_vox).total;
-}
-
 static int check_pointnet_w(const LidfPointNet* w) {
     if (!w || !w->w_p1 || !w->b_p1 || !w->w_p2 || !w->b_p2 || !w->w_v1 || !w->b_v1 || !w->w_p3 ||
         !w->b_p3 || !w->w_p4 || !w->b_p4 || !w->w_v2 || !w->b_v2)
@@ -1112,6 +1074,40 @@ struct PnetBufs {
     float* part;    // slabs of the LDS pooling path (NULL: global atomic maxima)
     int* sort;      // counting-sort scratch of the voxel-sorted walk (tables beyond the LDS pooling) or NULL
 };
+
+// the weight streams of the seven layers (the one copy of their contraction lengths and tile counts)
+static void pnet_streams(Carver& c, float* s[7]) {
+    static const int ks[7] = {6, 32, 64, 64, 64, 128, 128}, nts[7] = {1, 2, 2, 4, 4, 4, 4};
+    for (int i = 0; i < 7; ++i) s[i] = (float*)c.take_bytes(lin_stream_bytes(ks[i], nts[i]));
+}
+// the packed blob (lidf_pointnet_pack_f32), and the head of lidf_pointnet_f32's workspace
+static void pnet_pack_lay(Carver& c, PnetBufs& b) {
+    pnet_streams(c, b.streams);
+    b.chain = (float*)c.take_bytes(lidf_pointnet_chain_stream_bytes());
+}
+// the per-voxel tables of the inference path
+static void pnet_pool_lay(Carver& c, int64_t v, PnetBufs& b) {
+    const size_t V = (size_t)(v > 0 ? v : 1);
+    b.pool1 = c.take<float>(V * 64);
+    b.g1 = c.take<float>(V * 64);
+    b.gpart = c.take<float>(V * 128);
+    b.pool2 = c.take<float>(V * 128);
+}
+// (no per-point intermediates: the inference chains keep them in registers)
+static PnetBufs pnet_ws(Carver& c, int64_t n, int64_t v) {
+    PnetBufs b = {};
+    pnet_pack_lay(c, b);
+    pnet_pool_lay(c, v, b);
+    const size_t part_bytes = lidf_pointnet_pool_scratch_bytes(v);
+    b.part = c.take_if<float>(part_bytes > 0, part_bytes / sizeof(float));
+    // tables beyond the LDS pooling: the points are walked grouped by voxel (counting-sort scratch)
+    b.sort = c.take_if<int>(v > lidf_pointnet_lds_max_voxels(), (lidf_pointnet_sort_bytes(n, v) + 3) / sizeof(int));
+    return b;
+}
+
+LIDF_API size_t lidf_pointnet_workspace_bytes(int64_t n_pts, int64_t n_vox) {
+    return carved([&](Carver& c) { pnet_ws(c, n_pts, n_vox); });
+}
 
 // mode 0: pack the weight streams and run; 1: pack only (lidf_pointnet_pack_f32); 2: run on
 // streams packed earlier
@@ -1223,32 +1219,25 @@ LIDF_API int lidf_pointnet_f32(const LidfPointNet* w, const float* inp, const in
     if (!out || (n > 0 && (!inp || !vox))) return LIDF_ERR_BAD_ARG;
     int rc;
     if ((rc = check_pointnet_w(w))) return rc;
-    PnetWs ws = pnet_ws(n, n_vox);
-    if (!workspace || workspace_bytes < ws.total) return LIDF_ERR_WORKSPACE;
-    char* base = (char*)workspace;
-    PnetBufs b = {};
-    b.f1 = (float*)(base + ws.f1); b.f2 = (float*)(base + ws.f2);
-    b.pool1 = (float*)(base + ws.pool1); b.g1 = (float*)(base + ws.g1);
-    b.gpart = (float*)(base + ws.gpart); b.f4 = (float*)(base + ws.f4);
-    b.f5 = nullptr; b.pool2 = (float*)(base + ws.pool2);
-    for (int i = 0; i < 7; ++i)
-        b.streams[i] = w->packed ? (float*)((char*)w->packed + ws.s[i]) : (float*)(base + ws.s[i]);
-    b.chain = w->packed ? (float*)((char*)w->packed + ws.chain) : (float*)(base + ws.chain);
-    b.part = ws.part_bytes ? (float*)(base + ws.part) : nullptr;
-    b.sort = n_vox > lidf_pointnet_lds_max_voxels() ? (int*)(base + ws.sort) : nullptr;
+    Carver c(workspace);
+    PnetBufs b = pnet_ws(c, n, n_vox);   // (f5 NULL: the inference branch)
+    CHECK_CARVED(c, workspace, workspace_bytes);
+    Carver pc(w->packed);
+    if (w->packed) pnet_pack_lay(pc, b);   // the caller's streams instead of the workspace's
     int cus;
     if ((rc = cu_count(&cus))) return rc;
     return pointnet_impl(w, inp, vox, n, n_vox, out, b, cus, (hipStream_t)stream, w->packed ? 2 : 0);
 }
 
-LIDF_API size_t lidf_pointnet_pack_bytes(void) { return pnet_ws(1, 1).f1; }   // the stream slots
+LIDF_API size_t lidf_pointnet_pack_bytes(void) {
+    return carved([](Carver& c) { PnetBufs b; pnet_pack_lay(c, b); });
+}
 
 // the module's streams into `packed` as pack jobs of the caller's JobScope (or direct launches without one)
 static int pointnet_pack_into(const LidfPointNet* w, void* packed, hipStream_t st) {
-    const PnetWs ws = pnet_ws(1, 1);
+    Carver c(packed);
     PnetBufs b = {};
-    for (int i = 0; i < 7; ++i) b.streams[i] = (float*)((char*)packed + ws.s[i]);
-    b.chain = (float*)((char*)packed + ws.chain);
+    pnet_pack_lay(c, b);
     int rc, cus;
     if ((rc = cu_count(&cus))) return rc;
     return pointnet_impl(w, nullptr, nullptr, 0, 0, nullptr, b, cus, st, 1);
@@ -1258,7 +1247,7 @@ LIDF_API int lidf_pointnet_pack_f32(const LidfPointNet* w, void* packed, size_t 
                                       lidf_stream_t stream) {
     int rc;
     if ((rc = check_pointnet_w(w))) return rc;
-    if (!packed || packed_bytes < lidf_pointnet_pack_bytes()) return LIDF_ERR_WORKSPACE;
+    CHECK_WS(packed, packed_bytes, lidf_pointnet_pack_bytes());
     JobScope js;
     if ((rc = pointnet_pack_into(w, packed, (hipStream_t)stream))) return rc;
     CHECK_HIP(flush_jobs(js.jobs, (hipStream_t)stream));
@@ -1270,7 +1259,7 @@ LIDF_API int lidf_pointnet_pack_guarded_f32(const LidfPointNet* w, void* packed,
     int rc;
     if ((rc = check_pointnet_w(w))) return rc;
     if (!guard) return LIDF_ERR_BAD_ARG;
-    if (!packed || packed_bytes < lidf_pointnet_pack_bytes()) return LIDF_ERR_WORKSPACE;
+    CHECK_WS(packed, packed_bytes, lidf_pointnet_pack_bytes());
     const float* ptrs[12];
     long long cnt[12];
     const int k = pnet_segs(w, ptrs, cnt, 0);
@@ -1279,45 +1268,63 @@ LIDF_API int lidf_pointnet_pack_guarded_f32(const LidfPointNet* w, void* packed,
 }
 
 // ---- stage-2 refinement ----------------------------------------------------------------------
+// The weight streams of refine_ief_factorised (lidf_refine_pack_f32's blob): [layer-1 stream of the per-voxel launch |
+// of the per-ray launch (ROI + direction columns, sized for the widest direction embedding) | stream + aux of the
+// chain | stream | aux of the 16 x 16 x 4 decoder (lidf_ief16.hip): E <= 99 embed(pos) columns = 7 k-quads]
+struct RefineFact {
+    float *s_vox, *s_ray;
+    char* s_chain;
+    float *s16, *aux16;
+};
+static RefineFact refine_fact(Carver& c, int D);
 struct RefineWs {
-    size_t pnet_inp, pnet_vox, inp_embed, end_voxel, vox_feat, off, pnet, dec, voxpart, raypart, fact, total;
+    float* pnet_inp;
+    int* pnet_vox;
+    float* inp_embed;
+    int* end_voxel;
+    float *vox_feat, *off;
+    void *pnet, *dec;                // the workspaces of lidf_pointnet_f32 and of the split-f16 decoder
+    size_t pnet_bytes, dec_bytes;
+    float *voxpart, *raypart;
+    RefineFact fact;
 };
 // the IEF of stage 2 with the voxel-feature columns of layer 1 as a per-voxel product (defined below)
-static size_t refine_fact_bytes(int D);
 static int refine_ief_factorised(const LidfDecoder* off, int D, const float* vox_feat, int64_t V,
                                  const float* inp_embed, const int32_t* end_voxel, int64_t R,
-                                 float* out, float* voxpart, char* scratch, hipStream_t st,
+                                 float* out, float* voxpart, const RefineFact& f, hipStream_t st,
                                  int pack_mode, const int* R_dev = nullptr, const int* V_dev = nullptr,
                                  void* const* ev_rows = nullptr, const float* rayfeat = nullptr, int Ed = 0,
                                  float* raypart = nullptr, bool make_raypart = false,
                                  bool voxpart_ready = false);
 // the counterpart of pointnet_pack_into for the stage-2 decoder: refine_ief_factorised in its pack-only form
 // (pack_mode 1: no rows, no tables, nothing launched but the packs)
-static int refine_pack_into(const LidfDecoder* off, int L, int Lv, char* dst, hipStream_t st) {
-    return refine_ief_factorised(off, refine_D(L, Lv), nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, dst, st, 1,
-                                 nullptr, nullptr, nullptr, nullptr, 3 + 6 * Lv, nullptr, false);
+static int refine_pack_into(const LidfDecoder* off, int L, int Lv, void* dst, hipStream_t st) {
+    Carver c(dst);
+    return refine_ief_factorised(off, refine_D(L, Lv), nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr,
+                                 refine_fact(c, refine_D(L, Lv)), st, 1, nullptr, nullptr, nullptr, nullptr, 3 + 6 * Lv,
+                                 nullptr, false);
 }
-static RefineWs refine_ws(int64_t R, int64_t Nv, int64_t V, int D) {
+static RefineWs refine_ws(Carver& c, int64_t R, int64_t Nv, int64_t V, int D) {
     RefineWs w;
-    size_t o = 0;
-    const size_t n = (size_t)(R + Nv > 0 ? R + Nv : 1), r = (size_t)(R > 0 ? R : 1);
-    w.pnet_inp = o;  o += align_up(n * 6 * 4, 256);
-    w.pnet_vox = o;  o += align_up(n * 4, 256);
-    w.inp_embed = o; o += align_up(r * D * 4, 256);
-    w.end_voxel = o; o += align_up(r * 4, 256);
-    w.vox_feat = o;  o += align_up((size_t)(V > 0 ? V : 1) * 128 * 4, 256);
-    w.off = o;       o += align_up(r * 4, 256);
-    w.pnet = o;      o += align_up(lidf_pointnet_workspace_bytes(R + Nv, V), 256);
-    w.dec = o;       o += align_up(lidf_decoders_workspace_bytes(R, D), 256);
-    w.voxpart = o;   o += align_up((size_t)(V > 0 ? V : 1) * LIDF_H1 * 4, 256);
-    w.raypart = o;   o += align_up(r * LIDF_H1 * 4, 256);
-    w.fact = o;      o += align_up(refine_fact_bytes(D), 256);
-    w.total = o;
+    const size_t n = (size_t)(R + Nv > 0 ? R + Nv : 1), r = (size_t)(R > 0 ? R : 1), v = (size_t)(V > 0 ? V : 1);
+    w.pnet_inp = c.take<float>(n * 6);
+    w.pnet_vox = c.take<int>(n);
+    w.inp_embed = c.take<float>(r * D);
+    w.end_voxel = c.take<int>(r);
+    w.vox_feat = c.take<float>(v * 128);
+    w.off = c.take<float>(r);
+    w.pnet_bytes = lidf_pointnet_workspace_bytes(R + Nv, V);
+    w.pnet = c.take_bytes(w.pnet_bytes);
+    w.dec_bytes = lidf_decoders_workspace_bytes(R, D);
+    w.dec = c.take_bytes(w.dec_bytes);
+    w.voxpart = c.take<float>(v * LIDF_H1);
+    w.raypart = c.take<float>(r * LIDF_H1);
+    w.fact = refine_fact(c, D);
     return w;
 }
 
 LIDF_API size_t lidf_refine_workspace_bytes(int64_t n_rays, int64_t n_valid, int64_t n_vox) {
-    return refine_ws(n_rays, n_valid, n_vox, 256 + 2 * (3 + 6 * 16)).total;
+    return carved([&](Carver& c) { refine_ws(c, n_rays, n_valid, n_vox, 256 + 2 * (3 + 6 * 16)); });
 }
 
 static int refine_impl(const LidfRefineArgs* q, lidf_stream_t stream, void* const* ev) {
@@ -1337,16 +1344,13 @@ static int refine_impl(const LidfRefineArgs* q, lidf_stream_t stream, void* cons
         return LIDF_ERR_BAD_ARG;
     const int Ed = 3 + 6 * q->multires_views;
     const int D = refine_D(q->multires, q->multires_views);
-    RefineWs w = refine_ws(R, Nv, V, D);
-    if (!q->workspace || q->workspace_bytes < w.total) return LIDF_ERR_WORKSPACE;
+    Carver c(q->workspace);
+    const RefineWs w = refine_ws(c, R, Nv, V, D);
+    CHECK_CARVED(c, q->workspace, q->workspace_bytes);
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)q->workspace;
-    float* pnet_inp = (float*)(ws + w.pnet_inp);
-    int* pnet_vox = (int*)(ws + w.pnet_vox);
-    float* inp_embed = (float*)(ws + w.inp_embed);
-    int* end_voxel = q->end_voxel_id ? q->end_voxel_id : (int*)(ws + w.end_voxel);
-    float* vox_feat = (float*)(ws + w.vox_feat);
-    float* off = (float*)(ws + w.off);
+    float *pnet_inp = w.pnet_inp, *inp_embed = w.inp_embed, *vox_feat = w.vox_feat, *off = w.off;
+    int* pnet_vox = w.pnet_vox;
+    int* end_voxel = q->end_voxel_id ? q->end_voxel_id : w.end_voxel;
     // final_pnet_inp = cat(valid points, predicted points), final_revidx likewise
     // (pipeline.py:1007-1008)
     CellLookup cells = {};
@@ -1385,8 +1389,7 @@ static int refine_impl(const LidfRefineArgs* q, lidf_stream_t stream, void* cons
                                           q->multires_views, q->multires, q->pos_rel, R, nullptr, inp_embed, D,
                                           q->precision == LIDF_PRECISION_F32 ? 1 : 0, st));
     if (ev && ev[0]) CHECK_HIP(hipEventRecord((hipEvent_t)ev[0], st));
-    if ((rc = lidf_pointnet_f32(q->pnet, pnet_inp, pnet_vox, R + Nv, V, vox_feat, ws + w.pnet,
-                                lidf_pointnet_workspace_bytes(R + Nv, V), stream)))
+    if ((rc = lidf_pointnet_f32(q->pnet, pnet_inp, pnet_vox, R + Nv, V, vox_feat, w.pnet, w.pnet_bytes, stream)))
         return rc;
     if (ev && ev[1]) CHECK_HIP(hipEventRecord((hipEvent_t)ev[1], st));
     if (q->precision != LIDF_PRECISION_F32 && q->precision != LIDF_PRECISION_F16X3)
@@ -1397,17 +1400,16 @@ static int refine_impl(const LidfRefineArgs* q, lidf_stream_t stream, void* cons
         // the start of the layer-1 accumulators
         // weight streams: the caller's blob (lidf_refine_pack_f32, once per parameter version) or
         // packed here for this call
-        if ((rc = refine_ief_factorised(q->off, D, vox_feat, V, inp_embed, end_voxel, R, off,
-                                        (float*)(ws + w.voxpart),
-                                        q->packed ? (char*)q->packed : ws + w.fact, st, q->packed ? 2 : 0,
+        Carver pc(q->packed);
+        if ((rc = refine_ief_factorised(q->off, D, vox_feat, V, inp_embed, end_voxel, R, off, w.voxpart,
+                                        q->packed ? refine_fact(pc, D) : w.fact, st, q->packed ? 2 : 0,
                                         nullptr, nullptr, ev ? ev + 2 : nullptr, q->rayfeat, Ed,
-                                        q->ray_l1 ? q->ray_l1 : (float*)(ws + w.raypart),
-                                        !(q->ray_l1 && q->ray_l1_ready))))
+                                        q->ray_l1 ? q->ray_l1 : w.raypart, !(q->ray_l1 && q->ray_l1_ready))))
             return rc;
     } else {
         CHECK_HIP(lidf_launch_refine_gather(vox_feat, end_voxel, R, inp_embed, D, st));
-        if ((rc = decoders_impl(inp_embed, R, D, D, nullptr, q->off, nullptr, off, ws + w.dec,
-                                lidf_decoders_workspace_bytes(R, D), q->precision, stream)))
+        if ((rc = decoders_impl(inp_embed, R, D, D, nullptr, q->off, nullptr, off, w.dec, w.dec_bytes, q->precision,
+                                stream)))
             return rc;
     }
     CHECK_HIP(lidf_launch_refine_finish(q->pred_pos, off, q->ray_dir, q->offset_range0,
@@ -1429,91 +1431,86 @@ LIDF_API int lidf_refine_profile_f32(const LidfRefineArgs* q, void* ev_pnet_begi
 // ---- the evaluation path of a batch of frames without a host round trip (lidf_frame_f32) --------
 // PointNet2Stage with device-side counts: pointnet_impl's inference branch, every launch sized for
 // the capacities (n_cap points, V_cap voxels) and reading *n_dev / *V_dev on the device.
-struct PnetFrameWs {
-    size_t pool1, g1, gpart, pool2, sort, total;
-};
-static PnetFrameWs pnet_frame_ws(int64_t v_cap, int v_lds, int64_t n_cap = 0) {
-    (void)v_lds;
-    PnetFrameWs w;
-    size_t o = 0;
-    const size_t V = (size_t)(v_cap > 0 ? v_cap : 1);
-    w.pool1 = o; o += align_up(V * 64 * 4, 256);
-    w.g1 = o;    o += align_up(V * 64 * 4, 256);
-    w.gpart = o; o += align_up(V * 128 * 4, 256);
-    w.pool2 = o; o += align_up(V * 128 * 4, 256);
-    // (the grouping of a batch's points by voxel: its table of counts, V words at the head, starts zeroed)
-    w.sort = o;  o += n_cap > 0 ? align_up(lidf_group_idx_bytes(n_cap, v_cap), 256) : 0;
-    w.total = o;
-    return w;
+// its scratch: the per-voxel tables and, with sort_cap > 0, the grouping of a batch's points by voxel (its table of
+// counts, V words at the head, starts zeroed)
+static PnetBufs pnet_frame_ws(Carver& c, int64_t v_cap, int64_t sort_cap) {
+    PnetBufs b = {};
+    pnet_pool_lay(c, v_cap, b);
+    b.sort = sort_cap > 0 ? (int*)c.take_bytes(lidf_group_idx_bytes(sort_cap, v_cap)) : nullptr;
+    return b;
 }
-// (pool1 / pool2 of `ws` must be zero on entry: merged with the caller's other zeroed scratch)
-// sort_cap > 0 (several frames per batch: the voxel table is expected to exceed the LDS pooling): beyond
+// (pool1 / pool2 of `f` must be zero on entry: merged with the caller's other zeroed scratch)
+// f.sort (several frames per batch: the voxel table is expected to exceed the LDS pooling): beyond
 // v_lds voxels the chains walk the points grouped by voxel (the counting sort runs unconditionally).
 // Four launches: chain 1 -> [vox_lin1 | voxel half of point_lin3] -> chain 2 -> [vox_lin2 | tail].
 static int pointnet_frame(const LidfPointNet* w, const float* inp, const int32_t* vox, int64_t n_cap,
                           const int* n_dev, int64_t V_cap, int v_lds, const int* V_dev, float* out,
-                          char* ws, int cus, hipStream_t st, int64_t sort_cap = 0,
-                          const VoxTail* tail = nullptr) {
+                          PnetBufs f, int cus, hipStream_t st, const VoxTail* tail = nullptr) {
     int rc;
     if ((rc = check_pointnet_w(w))) return rc;
     if (!w->packed) return LIDF_ERR_BAD_ARG;
-    const PnetFrameWs f = pnet_frame_ws(V_cap, v_lds, sort_cap);
     const int *perm = nullptr, *n_perm = nullptr;
-    if (sort_cap > 0)
-        CHECK_HIP(lidf_launch_group_idx(vox, n_cap, n_dev, V_cap, ws + f.sort, &perm, &n_perm, st));
-    const PnetWs pw = pnet_ws(1, 1);   // offsets of the packed streams
-    float* streams[7];
-    for (int i = 0; i < 7; ++i) streams[i] = (float*)((char*)w->packed + pw.s[i]);
-    const float* chain = (const float*)((const char*)w->packed + pw.chain);
-    float* pool1 = (float*)(ws + f.pool1);
-    float* g1 = (float*)(ws + f.g1);
-    float* gpart = (float*)(ws + f.gpart);
-    float* pool2 = (float*)(ws + f.pool2);
-    CHECK_HIP(lidf_launch_pointnet_chain_dev(1, chain, inp, vox, nullptr, pool1, V_cap, v_lds, n_cap,
+    if (f.sort) CHECK_HIP(lidf_launch_group_idx(vox, n_cap, n_dev, V_cap, f.sort, &perm, &n_perm, st));
+    Carver pc(w->packed);
+    pnet_pack_lay(pc, f);   // the packed streams
+    CHECK_HIP(lidf_launch_pointnet_chain_dev(1, f.chain, inp, vox, nullptr, f.pool1, V_cap, v_lds, n_cap,
                                              n_dev, V_dev, perm, n_perm, cus, st));
-    if ((rc = run_vox2(pool1, 64, V_cap, V_dev, streams[2], 2, 1, g1, streams[3], 9, 4, 0, gpart, st)))
+    if ((rc = run_vox2(f.pool1, 64, V_cap, V_dev, f.streams[2], 2, 1, f.g1, f.streams[3], 9, 4, 0, f.gpart, st)))
         return rc;
-    CHECK_HIP(lidf_launch_pointnet_chain_dev(2, chain, inp, vox, gpart, pool2, V_cap, v_lds, n_cap,
+    CHECK_HIP(lidf_launch_pointnet_chain_dev(2, f.chain, inp, vox, f.gpart, f.pool2, V_cap, v_lds, n_cap,
                                              n_dev, V_dev, perm, n_perm, cus, st));
-    return run_vox2(pool2, 128, V_cap, V_dev, streams[6], 4, 1, out, tail ? tail->stream : nullptr,
+    return run_vox2(f.pool2, 128, V_cap, V_dev, f.streams[6], 4, 1, out, tail ? tail->stream : nullptr,
                     tail ? tail->kq : 0, tail ? tail->nt : 0, 0, tail ? tail->out : nullptr, st);
 }
 
 struct FrameWs {
-    size_t lb_head, lb_pairs, cell_flag, cell_rank, vox_bid, vox_center, pt_key, pt_rank, pnet,
-        query, inp_embed, off, vox_feat_r, voxpart_r, raypart_r, pos_a, pos_b, pnet_abs, sel, dec, total;
-    size_t lb_bytes;   // lb_head .. cell_flag: the look-back tickets / status words, zeroed with cell_flag
+    void *lb_head, *lb_pairs;   // the look-back tickets / status words, zeroed with cell_flag as one run
+    size_t lb_bytes;            // ... their bytes: cell_flag follows at once
+    int *cell_flag, *cell_rank, *vox_bid;
+    float* vox_center;
+    int *pt_key, *pt_rank;
+    PnetBufs pnet;
+    void* query;                // the query's workspace, sized for the largest embedding ...
+    size_t query_bytes;
+    QueryWs q;                  // ... and its slots at this frame's (L, Lv)
+    // stage 2 (refine_times > 0)
+    float *inp_embed, *off, *vox_feat_r, *voxpart_r, *raypart_r, *pos[2], *pnet_abs;
+    unsigned char* sel;
+    void* dec;                  // split-f16 IEF: the decoder's workspace
+    size_t dec_bytes;
 };
-static FrameWs frame_ws(int B, int h, int w, const int32_t* res, int64_t max_pairs, int v_lds,
-                        int refine_times) {
-    (void)max_pairs;
+static FrameWs frame_ws(Carver& c, int B, int h, int w, const int32_t* res, int refine_times, int L, int Lv) {
     FrameWs f;
-    size_t o = 0;
-    const size_t N = (size_t)B * h * w, C = (size_t)B * res[0] * res[1] * res[2];
-    f.lb_head = o;   o += align_up(lidf_frame_head_lb_bytes((long long)N), 256);
-    f.lb_pairs = o;  o += align_up(lidf_ray_aabb_onepass_lb_bytes((long long)N), 256);
-    f.lb_bytes = o;
-    f.cell_flag = o; o += align_up(C * 4, 256);
-    f.cell_rank = o; o += align_up((C + 1) * 4, 256);
-    f.vox_bid = o;   o += align_up((C + (size_t)B + 1) * 4, 256);   // [V] image of a voxel | [B + 1] first voxel of an image
-    f.vox_center = o; o += align_up(C * 12, 256);
-    f.pt_key = o;    o += align_up(N * 4, 256);
-    f.pt_rank = o;   o += align_up((N + 1) * 4, 256);
-    f.pnet = o;      o += align_up(pnet_frame_ws((int64_t)C, v_lds, B >= 2 ? (int64_t)(2 * N) : 0).total, 256);
-    f.query = o;     o += align_up(lidf_query_workspace_bytes((int64_t)N, (int64_t)C, (int64_t)B * 32 * h * w), 256);
+    const size_t N = (size_t)B * h * w, C = (size_t)B * res[0] * res[1] * res[2], start = c.used();
+    f.lb_head = c.take_bytes(lidf_frame_head_lb_bytes((long long)N));
+    f.lb_pairs = c.take_bytes(lidf_ray_aabb_onepass_lb_bytes((long long)N));
+    f.lb_bytes = c.used() - start;
+    f.cell_flag = c.take<int>(C);
+    f.cell_rank = c.take<int>(C + 1);
+    f.vox_bid = c.take<int>(C + (size_t)B + 1);   // [V] image of a voxel | [B + 1] first voxel of an image
+    f.vox_center = c.take<float>(C * 3);
+    f.pt_key = c.take<int>(N);
+    f.pt_rank = c.take<int>(N + 1);
+    // (several frames: the voxel table outgrows the LDS pooling, the points are grouped by voxel)
+    f.pnet = pnet_frame_ws(c, (int64_t)C, B >= 2 ? (int64_t)(2 * N) : 0);
+    const int64_t grid_floats = (int64_t)B * 32 * h * w;
+    f.query_bytes = lidf_query_workspace_bytes((int64_t)N, (int64_t)C, grid_floats);
+    f.query = c.take_bytes(f.query_bytes);
+    Carver qc(f.query);
+    f.q = query_ws(qc, (int64_t)N, (int64_t)C, L, Lv, grid_floats);
     const int Dmax = 256 + 2 * (3 + 6 * 16);
     const bool rf = refine_times > 0;
-    f.inp_embed = o;  o += rf ? align_up(N * Dmax * 4, 256) : 0;
-    f.off = o;        o += rf ? align_up(N * 4, 256) : 0;
-    f.vox_feat_r = o; o += rf ? align_up(C * 128 * 4, 256) : 0;
-    f.voxpart_r = o;  o += rf ? align_up(C * LIDF_H1 * 4, 256) : 0;
-    f.raypart_r = o;  o += rf ? align_up(N * LIDF_H1 * 4, 256) : 0;
-    f.pos_a = o;      o += rf ? align_up(N * 12, 256) : 0;
-    f.pos_b = o;      o += rf ? align_up(N * 12, 256) : 0;
-    f.pnet_abs = o;   o += rf ? align_up(2 * N * 24, 256) : 0;
-    f.sel = o;        o += rf ? align_up(N, 256) : 0;
-    f.dec = o;        o += rf ? align_up(lidf_decoders_workspace_bytes((int64_t)N, Dmax), 256) : 0;   // split-f16 IEF
-    f.total = o;
+    f.inp_embed = c.take_if<float>(rf, N * Dmax);
+    f.off = c.take_if<float>(rf, N);
+    f.vox_feat_r = c.take_if<float>(rf, C * 128);
+    f.voxpart_r = c.take_if<float>(rf, C * LIDF_H1);
+    f.raypart_r = c.take_if<float>(rf, N * LIDF_H1);
+    f.pos[0] = c.take_if<float>(rf, N * 3);
+    f.pos[1] = c.take_if<float>(rf, N * 3);
+    f.pnet_abs = c.take_if<float>(rf, 2 * N * 6);
+    f.sel = c.take_if<unsigned char>(rf, N);
+    f.dec_bytes = rf ? lidf_decoders_workspace_bytes((int64_t)N, Dmax) : 0;
+    f.dec = c.take_bytes(f.dec_bytes);
     return f;
 }
 
@@ -1526,37 +1523,33 @@ static int frame_lds_voxels(int32_t v, size_t C) {
 
 LIDF_API size_t lidf_frame_workspace_bytes(int32_t batch, int32_t height, int32_t width, const int32_t* res,
                                            int64_t max_pairs, int32_t lds_voxels, int32_t refine_times) {
+    // (the sizes depend on neither max_pairs nor lds_voxels; the slots are sized for the largest embedding)
     if (batch <= 0 || height <= 0 || width <= 0 || !res || res[0] <= 0 || res[1] <= 0 || res[2] <= 0) return 0;
-    const size_t C = (size_t)batch * res[0] * res[1] * res[2];
-    return frame_ws(batch, height, width, res, max_pairs, frame_lds_voxels(lds_voxels, C), refine_times).total;
+    return carved([&](Carver& c) { frame_ws(c, batch, height, width, res, refine_times, LIDF_MAX_L_FUSED, 16); });
 }
 
 
 // ---- the weight streams of every module of a frame in one blob, validated by ONE fingerprint launch ----
-struct FramePackLay {
-    size_t query, pnet, pnet_r, refine, total;
-};
-static FramePackLay frame_pack_lay() {
+// (each module's blob as its own pack call lays it out, in a slot sized for the largest embedding)
+struct FramePackLay { void *query, *pnet, *pnet_r, *refine; };
+static FramePackLay frame_pack_lay(Carver& c) {
     FramePackLay l;
-    size_t o = 0;
-    l.query = o;  o += align_up(lidf_query_pack_bytes(), 256);
-    l.pnet = o;   o += align_up(lidf_pointnet_pack_bytes(), 256);
-    l.pnet_r = o; o += align_up(lidf_pointnet_pack_bytes(), 256);
-    l.refine = o; o += align_up(lidf_refine_pack_bytes(16, 16), 256);
-    l.total = o;
+    l.query = c.take_bytes(lidf_query_pack_bytes());
+    l.pnet = c.take_bytes(lidf_pointnet_pack_bytes());
+    l.pnet_r = c.take_bytes(lidf_pointnet_pack_bytes());
+    l.refine = c.take_bytes(lidf_refine_pack_bytes(16, 16));
     return l;
 }
 #define FRAME_GUARD_STRIDE 64
 static_assert(sizeof(LidfPackGuardState) <= FRAME_GUARD_STRIDE, "guard stride");
-LIDF_API size_t lidf_frame_pack_bytes(void) { return frame_pack_lay().total; }
+LIDF_API size_t lidf_frame_pack_bytes(void) { return carved([&](Carver& c) { frame_pack_lay(c); }); }
 LIDF_API size_t lidf_frame_pack_guard_bytes(void) { return (size_t)LIDF_FP_GROUPS * FRAME_GUARD_STRIDE; }
 
 // groups: 0 the query's two decoders, 1 the PointNet, 2 the stage-2 PointNet, 3 the stage-2 decoder (f32)
-static int frame_pack_guarded(const LidfFrameArgs* a, char* blob, char* guards, hipStream_t st) {
+static int frame_pack_guarded(const LidfFrameArgs* a, const FramePackLay& l, char* guards, hipStream_t st) {
     const bool rf = a->refine_times > 0, split = a->precision == LIDF_PRECISION_F16X3;
     const int L = a->multires, Lv = a->multires_views;
     const int D = query_D(L, Lv);
-    const FramePackLay l = frame_pack_lay();
     const float* ptrs[LIDF_FP_MULTI_SEGS];
     long long cnt[LIDF_FP_MULTI_SEGS];
     int grp[LIDF_FP_MULTI_SEGS];
@@ -1588,19 +1581,20 @@ static int frame_pack_guarded(const LidfFrameArgs* a, char* blob, char* guards, 
     JobScope js;
     {
         GuardScope g((const LidfPackGuardState*)guards);
-        rc = pack_query_weights(a->prob, a->off, query_plan(L, Lv, a->precision), blob + l.query, st);
+        Carver qc(l.query);
+        rc = pack_query_weights(a->prob, a->off, query_plan(L, Lv, a->precision), query_pack_lay(qc, L, Lv), st);
     }
     if (!rc) {
         GuardScope g((const LidfPackGuardState*)(guards + FRAME_GUARD_STRIDE));
-        rc = pointnet_pack_into(a->pnet, blob + l.pnet, st);
+        rc = pointnet_pack_into(a->pnet, l.pnet, st);
     }
     if (!rc && rf) {
         GuardScope g((const LidfPackGuardState*)(guards + 2 * FRAME_GUARD_STRIDE));
-        rc = pointnet_pack_into(a->pnet_refine, blob + l.pnet_r, st);
+        rc = pointnet_pack_into(a->pnet_refine, l.pnet_r, st);
     }
     if (!rc && rf && !split) {
         GuardScope g((const LidfPackGuardState*)(guards + 3 * FRAME_GUARD_STRIDE));
-        rc = refine_pack_into(a->off_refine, L, Lv, blob + l.refine, st);
+        rc = refine_pack_into(a->off_refine, L, Lv, l.refine, st);
     }
     if (!rc && flush_jobs(js.jobs, st) != hipSuccess) rc = LIDF_ERR_HIP;
     return rc ? guard_fail(guards, gbytes, st, rc) : LIDF_OK;
@@ -1617,7 +1611,7 @@ static int frame_impl(const LidfFrameArgs* a_in, lidf_stream_t stream, ForkState
                       const LidfFrameWidths* wd = nullptr);
 // the any-width route of the frame (lidf_frame_widths_f32, defined behind lidf_decoder_chain_f32)
 static int frame_widths_check(const LidfFrameArgs* a, const LidfFrameWidths* wd);
-static int frame_widths_pack(const LidfFrameArgs* a, const LidfFrameWidths* wd, char* pnet_blob, char* pnet_blob_r,
+static int frame_widths_pack(const LidfFrameArgs* a, const LidfFrameWidths* wd, void* pnet_blob, void* pnet_blob_r,
                              hipStream_t st);
 static int frame_widths_query(const LidfFrameArgs* a, const LidfFrameWidths* wd, int64_t N, int64_t C,
                               const float* vox_center, int cus, hipStream_t st);
@@ -1703,15 +1697,15 @@ static int frame_impl(const LidfFrameArgs* a_in, lidf_stream_t stream, ForkState
     // launch over every module, or trusted)
     LidfPointNet pn_loc = *a->pnet, pnr_loc = {};
     if (rf) pnr_loc = *a->pnet_refine;
-    if (own_pack && (!a->pack_blob || !a->pack_guard || a->pack_blob_bytes < frame_pack_lay().total))
-        return LIDF_ERR_WORKSPACE;
+    Carver bc(a->pack_blob);
+    const FramePackLay pl = frame_pack_lay(bc);
+    if (own_pack && (!a->pack_guard || !bc.covers(a->pack_blob, a->pack_blob_bytes))) return LIDF_ERR_WORKSPACE;
     const int v_lds = frame_lds_voxels(a->lds_voxels, (size_t)C);
-    const FrameWs f = frame_ws(B, h, w, a->res, a->max_pairs, v_lds, a->refine_times);
-    if (!a->workspace || a->workspace_bytes < f.total) return LIDF_ERR_WORKSPACE;
+    Carver c(a->workspace);
+    const FrameWs f = frame_ws(c, B, h, w, a->res, a->refine_times, a->multires, a->multires_views);
+    CHECK_CARVED(c, a->workspace, a->workspace_bytes);
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)a->workspace;
     const int64_t grid_floats = (int64_t)B * 32 * h * w;
-    const QueryWs qw = query_ws(N, C, a->multires, a->multires_views, grid_floats);
     // side stream (optional): launches that fill a fraction of the device each run side by side —
     //   side: weight-stream guard (fingerprint + early-exit packs), box sums | per-ray features
     //   main: zeroed scratch, head                                           | cells, pairs, points, (guard done) PointNet
@@ -1727,36 +1721,31 @@ static int frame_impl(const LidfFrameArgs* a_in, lidf_stream_t stream, ForkState
         CHECK_HIP(hipStreamWaitEvent(sx, (hipEvent_t)a->ev_fork, 0));
     }
     if (own_pack) {
-        const FramePackLay pl = frame_pack_lay();
-        char* blob = (char*)a->pack_blob;
         if (wd) {
-            if ((rc = frame_widths_pack(a, wd, blob + pl.pnet, rf ? blob + pl.pnet_r : nullptr, st))) return rc;
+            if ((rc = frame_widths_pack(a, wd, pl.pnet, rf ? pl.pnet_r : nullptr, st))) return rc;
         } else if (a->pack_mode == LIDF_FRAME_PACK_GUARDED) {
-            rc = frame_pack_guarded(a, blob, (char*)a->pack_guard, two ? sx : st);
+            rc = frame_pack_guarded(a, pl, (char*)a->pack_guard, two ? sx : st);
             if (two && !rc) {   // (first record of ev_join: the weight streams are valid; a failure joins at the exit)
                 if (hipEventRecord((hipEvent_t)a->ev_join, sx) != hipSuccess) rc = LIDF_ERR_HIP;
                 guard_on_side = true;
             }
             if (rc) return rc;
         }
-        a->packed_query = blob + pl.query;
-        pn_loc.packed = blob + pl.pnet;
-        pnr_loc.packed = blob + pl.pnet_r;
-        a->packed_refine = blob + pl.refine;
+        a->packed_query = pl.query;
+        pn_loc.packed = pl.pnet;
+        pnr_loc.packed = pl.pnet_r;
+        a->packed_refine = pl.refine;
     } else if (wd) {
         if ((rc = frame_widths_pack(a, wd, nullptr, nullptr, st))) return rc;   // (the chain streams: every call)
     }
     if (two)
-        CHECK_HIP(lidf_launch_rayfeat_phase(a->feat_grid, (float*)(ws + f.query + qw.box), B, h, w, a->ray_dir,
+        CHECK_HIP(lidf_launch_rayfeat_phase(a->feat_grid, f.q.box, B, h, w, a->ray_dir,
                                             a->ray_pix, a->ray_bid, N, a->counts, a->roi_inp_bbox / 2,
                                             a->multires_views, a->rayfeat, 128 + Edv, 1, sx));
     a->pnet = &pn_loc;
     if (rf) a->pnet_refine = &pnr_loc;
     int* counts = a->counts;
-    int* cell_flag = (int*)(ws + f.cell_flag);
-    int* cell_rank = (int*)(ws + f.cell_rank);
-    int* pt_key = (int*)(ws + f.pt_key);
-    int* pt_rank = (int*)(ws + f.pt_rank);
+    int *cell_flag = f.cell_flag, *cell_rank = f.cell_rank, *pt_key = f.pt_key, *pt_rank = f.pt_rank;
     GridSpec g;
     for (int k = 0; k < 3; ++k) { g.xmin[k] = a->xmin[k]; g.r[k] = a->res[k]; }
     g.crop = a->part_size;
@@ -1766,15 +1755,11 @@ static int frame_impl(const LidfFrameArgs* a_in, lidf_stream_t stream, ForkState
     // 0. every zero-initialised scratch of stage 1 in ONE launch: the look-back tickets / status words
     //    and the voxel marks (adjacent), the max-pool tables of the PointNet, the clamped-box list length
     //    and the tile counters of the query (two: the split-f16 kernel's launch on the selected list has its own)
-    const int64_t sort_cap = B >= 2 ? 2 * N : 0;   // several frames: the voxel table outgrows the LDS pooling
-    const PnetFrameWs pf = pnet_frame_ws(C, v_lds, sort_cap);
-    float* pool1 = (float*)(ws + f.pnet + pf.pool1);
-    float* pool2 = (float*)(ws + f.pnet + pf.pool2);
+    float *pool1 = f.pnet.pool1, *pool2 = f.pnet.pool2;
     {
-        float* zp[6] = {(float*)(ws + f.lb_head), pool1, pool2, (float*)(ws + f.query + qw.counter),
-                        (float*)(ws + f.query + qw.box) + grid_floats, (float*)(ws + f.pnet + pf.sort)};
+        float* zp[6] = {(float*)f.lb_head, pool1, pool2, (float*)f.q.counter, f.q.box + grid_floats, (float*)f.pnet.sort};
         const long long zc[6] = {(long long)(f.lb_bytes / 4) + (long long)C, (long long)C * 64,
-                                 (long long)C * 128, 2, 1, sort_cap > 0 ? (long long)C : 0};
+                                 (long long)C * 128, 2, 1, f.pnet.sort ? (long long)C : 0};
         CHECK_HIP(lidf_launch_zero_segments(zp, zc, 6, st));
     }
     // the query of step 5 (its per-ray launches go to the side stream when there is one)
@@ -1785,7 +1770,7 @@ static int frame_impl(const LidfFrameArgs* a_in, lidf_stream_t stream, ForkState
     q.pair_vox = a->pair_vox; q.pair_t = a->pair_t;
     q.batch = B; q.height = h; q.width = w; q.feat_grid = a->feat_grid;
     q.n_vox = C; q.vox_feat = a->occ_voxel_feat;
-    q.vox_center = a->pos_rel ? (float*)(ws + f.vox_center) : nullptr;
+    q.vox_center = a->pos_rel ? f.vox_center : nullptr;
     q.prob = a->prob; q.off = a->off;
     q.multires = a->multires; q.multires_views = a->multires_views; q.roi_inp_bbox = a->roi_inp_bbox;
     q.pos_rel = a->pos_rel ? 1 : 0;
@@ -1793,29 +1778,31 @@ static int frame_impl(const LidfFrameArgs* a_in, lidf_stream_t stream, ForkState
     q.pred_offset = a->pred_offset; q.pred_prob = a->pred_prob; q.pair_pred_pos = a->pair_pred_pos;
     q.pred_prob_softmax = a->pred_prob_softmax; q.max_pair_id = a->max_pair_id; q.pred_pos = a->pred_pos;
     q.depth = a->pred_depth;
-    q.workspace = ws + f.query;
-    q.workspace_bytes = lidf_query_workspace_bytes(N, C, (int64_t)B * 32 * h * w);
+    q.workspace = f.query;
+    q.workspace_bytes = f.query_bytes;
     q.rayfeat_out = a->rayfeat;
     q.precision = a->precision;
     q.packed = a->packed_query;
     q.offsets_selected = a->offsets_selected;
     // (f32 stage 2: the per-ray part of its decoder's layer 1, W1[:, ROI | dir] rayfeat[r] — constant
     // over the refine iterations — is a third table of the query's layer-1 launch)
+    Carver rpc(a->packed_refine);   // (NULL where stage 2 does not run in f32: never read then)
+    const RefineFact rfact = refine_fact(rpc, refine_D(a->multires, a->multires_views));
     PointsArgs xr = {};
     if (rf && !split) {
         const int Edr = 3 + 6 * a->multires_views;
-        xr.stream = (const float*)((const char*)a->packed_refine + linex_stream_bytes(128));
+        xr.stream = rfact.s_ray;
         xr.nets = 1;
         xr.KQ1 = (128 + Edr + 2 + 7) / 8;
         xr.l1_quads = xr.net_quads = xr.KQ1 * 8;
         xr.n = N; xr.n_dev = counts;
         xr.D = 128 + Edr; xr.has_bias = 0;
-        xr.out_base = (float*)(ws + f.raypart_r);
+        xr.out_base = f.raypart_r;
     }
     // 1. valid points (with their rows of the PointNet input), rays, depth map, voxel marks: ONE launch
     //    over the pixels (look-back prefix over its workgroups)
     CHECK_HIP(lidf_launch_frame_head(a->valid_mask, a->miss_mask, a->xyz_corrupt, a->rgb, a->intr, B, h, w,
-                                     a->valid_stride, g, ws + f.lb_head, counts, a->valid_bid, a->valid_flat,
+                                     a->valid_stride, g, f.lb_head, counts, a->valid_bid, a->valid_flat,
                                      a->valid_xyz, a->valid_rgb, cell_flag, pt_key, pt_rank, a->ray_bid,
                                      a->ray_flat, a->ray_pix, a->ray_dir, a->pred_depth,
                                      rf ? a->pred_depth_refine : nullptr, a->valid_idx_bid, a->valid_idx_flat,
@@ -1823,7 +1810,7 @@ static int frame_impl(const LidfFrameArgs* a_in, lidf_stream_t stream, ForkState
     if (two) {
         CHECK_HIP(hipEventRecord((hipEvent_t)a->ev_fork, st));   // (a second record: the rays exist)
         CHECK_HIP(hipStreamWaitEvent(sx, (hipEvent_t)a->ev_fork, 0));
-        CHECK_HIP(lidf_launch_rayfeat_phase(a->feat_grid, (float*)(ws + f.query + qw.box), B, h, w, a->ray_dir,
+        CHECK_HIP(lidf_launch_rayfeat_phase(a->feat_grid, f.q.box, B, h, w, a->ray_dir,
                                             a->ray_pix, a->ray_bid, N, counts, a->roi_inp_bbox / 2,
                                             a->multires_views, a->rayfeat, 128 + Edv, 2, sx));
         // (the per-ray layer-1 tables stay on the main stream: a launch that fills the device starves the
@@ -1831,17 +1818,17 @@ static int frame_impl(const LidfFrameArgs* a_in, lidf_stream_t stream, ForkState
     }
     FRAME_FAIL_AFTER(1);
     // 2. occupied voxels: cells -> voxels (V) in one workgroup, points -> PointNet rows
-    int* vox_bid = (int*)(ws + f.vox_bid);   // [V] image index of every occupied voxel
-    float* vox_center = a->pos_rel ? (float*)(ws + f.vox_center) : nullptr;   // intersect_pos_type 'rel'
+    int* vox_bid = f.vox_bid;   // [V] image index of every occupied voxel
+    float* vox_center = a->pos_rel ? f.vox_center : nullptr;   // intersect_pos_type 'rel'
     int* vox_start = B > 1 ? vox_bid + C : nullptr;   // (one image: every voxel is its image's)
     CHECK_HIP(lidf_launch_frame_cells(cell_flag, C, g, cell_rank, a->occ_bid_coord, a->voxel_bound, vox_bid,
                                       vox_center, counts, vox_start, st));
     // 3. ray / voxel pairs: count, offsets (cut at max_pairs, P) and fill in ONE launch (on the main stream:
     //    behind the per-ray features it made the side branch the longer one — measured)
     CHECK_HIP(lidf_launch_ray_aabb_onepass(a->ray_dir, a->voxel_bound, a->ray_bid, vox_bid, N, counts,
-                                           ws + f.lb_pairs, a->pair_off, a->pair_ray, a->pair_vox, a->pair_t,
+                                           f.lb_pairs, a->pair_off, a->pair_ray, a->pair_vox, a->pair_t,
                                            a->max_pairs, vox_start, st));
-    float* pnet_abs = (rf && !a->refine_pnet_pos_rel) ? (float*)(ws + f.pnet_abs) : nullptr;
+    float* pnet_abs = (rf && !a->refine_pnet_pos_rel) ? f.pnet_abs : nullptr;
     CHECK_HIP(lidf_launch_frame_points(a->valid_xyz, a->valid_rgb, pt_key, pt_rank, cell_rank, g, N, counts,
                                        a->valid_v_pid, a->revidx, a->valid_v_rel_coord, a->pnet_inp,
                                        pnet_abs, st));
@@ -1850,7 +1837,7 @@ static int frame_impl(const LidfFrameArgs* a_in, lidf_stream_t stream, ForkState
     if (two) CHECK_HIP(hipEventRecord((hipEvent_t)a->ev_join, sx));   // (second record: the per-ray features)
     // 4. voxel embedding: PointNet over the in-grid valid points
     if ((rc = pointnet_frame(a->pnet, a->pnet_inp, a->revidx, N, counts + LIDF_FC_VALID_IN, C, v_lds,
-                             counts + LIDF_FC_VOX, a->occ_voxel_feat, ws + f.pnet, cus, st, sort_cap)))
+                             counts + LIDF_FC_VOX, a->occ_voxel_feat, f.pnet, cus, st)))
         return rc;
     FRAME_FAIL_AFTER(3);
     if (two) CHECK_HIP(hipStreamWaitEvent(st, (hipEvent_t)a->ev_join, 0));
@@ -1881,13 +1868,10 @@ static int frame_impl(const LidfFrameArgs* a_in, lidf_stream_t stream, ForkState
     // 6. stage 2: refine_times x get_pred_refine on the device-resident state
     const int Ed = 3 + 6 * a->multires_views;
     const int D = refine_D(a->multires, a->multires_views);
-    float* inp_embed = (float*)(ws + f.inp_embed);
-    float* offv = (float*)(ws + f.off);
-    float* vox_feat_r = (float*)(ws + f.vox_feat_r);
-    float* voxpart_r = (float*)(ws + f.voxpart_r);
+    float *inp_embed = f.inp_embed, *offv = f.off, *vox_feat_r = f.vox_feat_r, *voxpart_r = f.voxpart_r;
     unsigned char* sel = nullptr;
     if (!a->refine_use_all_pix) {
-        sel = (unsigned char*)(ws + f.sel);
+        sel = f.sel;
         CHECK_HIP(lidf_launch_frame_select(a->valid_mask, a->ray_bid, a->ray_flat, hw, N, counts, sel, st));
     }
     // the stage-2 PointNet reads [valid points | predicted points]: the predicted rows are written
@@ -1901,13 +1885,13 @@ static int frame_impl(const LidfFrameArgs* a_in, lidf_stream_t stream, ForkState
         // (its last per-voxel launch also forms the voxel columns of the decoder's layer 1), the decoder.
         // (any-width route: the PointNet without that tail — the voxel table is a launch of its own at 4 gf
         // columns —, the decoder as one chain launch)
-        const VoxTail tail = {(const float*)a->packed_refine, (128 + 2 + 7) / 8, 8, voxpart_r};
+        const VoxTail tail = {rfact.s_vox, (128 + 2 + 7) / 8, 8, voxpart_r};
         for (int it = 0; it < a->refine_times; ++it) {
             RefineStepArgs sa = {};
             sa.prev_pos = cur;
             sa.prev_off = it > 0 ? offv : nullptr;
             sa.r0 = rr0; sa.rs = rrs;
-            sa.cur_pos = it > 0 ? (float*)(ws + ((it & 1) ? f.pos_b : f.pos_a)) : nullptr;
+            sa.cur_pos = it > 0 ? f.pos[it & 1] : nullptr;
             sa.ray_dir = a->ray_dir; sa.ray_bid = a->ray_bid; sa.ray_flat = a->ray_flat;
             sa.max_pair_id = (const long long*)a->max_pair_id; sa.pair_vox = a->pair_vox;
             sa.vbound = a->voxel_bound; sa.vox_bid = vox_bid;
@@ -1922,7 +1906,7 @@ static int frame_impl(const LidfFrameArgs* a_in, lidf_stream_t stream, ForkState
             CHECK_HIP(lidf_launch_refine_step(sa, N, st));
             if (it > 0) cur = sa.cur_pos;
             if ((rc = pointnet_frame(a->pnet_refine, pn_inp, a->revidx, 2 * N, counts + LIDF_FC_PNET_REFINE, C,
-                                     v_lds, counts + LIDF_FC_VOX, vox_feat_r, ws + f.pnet, cus, st, sort_cap,
+                                     v_lds, counts + LIDF_FC_VOX, vox_feat_r, f.pnet, cus, st,
                                      wd ? nullptr : &tail)))
                 return rc;
             if (wd) {
@@ -1930,10 +1914,10 @@ static int frame_impl(const LidfFrameArgs* a_in, lidf_stream_t stream, ForkState
                 continue;
             }
             if ((rc = refine_ief_factorised(a->off_refine, D, vox_feat_r, C, inp_embed, a->end_voxel_id, N,
-                                            offv, voxpart_r, (char*)a->packed_refine, st, 2,
+                                            offv, voxpart_r, rfact, st, 2,
                                             counts + LIDF_FC_RAYS, counts + LIDF_FC_VOX,
                                             (pev && it < 2) ? pev + 2 + 2 * it : nullptr, a->rayfeat,
-                                            Ed, (float*)(ws + f.raypart_r), false, true)))
+                                            Ed, f.raypart_r, false, true)))
                 return rc;
         }
         CHECK_HIP(lidf_launch_refine_finish_dev(cur, offv, a->ray_dir, rr0, rrs, N, counts, a->pred_pos_refine,
@@ -1942,7 +1926,7 @@ static int frame_impl(const LidfFrameArgs* a_in, lidf_stream_t stream, ForkState
     }
     for (int it = 0; it < a->refine_times; ++it) {   // split-f16 products: whole decoder rows, layer by layer
         float* out = it == a->refine_times - 1 ? a->pred_pos_refine
-                                               : (float*)(ws + ((it & 1) ? f.pos_b : f.pos_a));
+                                               : f.pos[it & 1];
         {   // this iteration's zero-initialised scratch in one launch: end voxels + the max-pool tables
             float* zp[3] = {(float*)a->end_voxel_id, pool1, pool2};
             const long long zc[3] = {(long long)N, (long long)C * 64, (long long)C * 128};
@@ -1956,12 +1940,12 @@ static int frame_impl(const LidfFrameArgs* a_in, lidf_stream_t stream, ForkState
                                               a->multires_views, a->multires, a->refine_pos_rel, N, counts,
                                               inp_embed, D, 0, st));
         if ((rc = pointnet_frame(a->pnet_refine, pn_inp, a->revidx, 2 * N, counts + LIDF_FC_PNET_REFINE, C,
-                                 v_lds, counts + LIDF_FC_VOX, vox_feat_r, ws + f.pnet, cus, st, sort_cap)))
+                                 v_lds, counts + LIDF_FC_VOX, vox_feat_r, f.pnet, cus, st)))
             return rc;
         // (the voxel feature gathered into the rows, the weights packed per call)
         CHECK_HIP(lidf_launch_refine_gather_dev(vox_feat_r, a->end_voxel_id, N, counts, inp_embed, D, st));
-        if ((rc = decoders_impl(inp_embed, N, D, D, nullptr, a->off_refine, nullptr, offv, ws + f.dec,
-                                lidf_decoders_workspace_bytes(N, D), LIDF_PRECISION_F16X3, stream,
+        if ((rc = decoders_impl(inp_embed, N, D, D, nullptr, a->off_refine, nullptr, offv, f.dec,
+                                f.dec_bytes, LIDF_PRECISION_F16X3, stream,
                                 counts + LIDF_FC_RAYS)))
             return rc;
         const bool last = it == a->refine_times - 1;
@@ -1974,25 +1958,21 @@ static int frame_impl(const LidfFrameArgs* a_in, lidf_stream_t stream, ForkState
 }
 
 // ---- occupied-voxel build ----------------------------------------------------------------------
-struct VoxWs {
-    size_t cell_flag, cell_rank, pt_key, pt_valid, pt_rank, scan, total;
-};
-static VoxWs vox_ws(int64_t n, int64_t ncell) {
+struct VoxWs { int *cell_flag, *cell_rank, *pt_key, *pt_valid, *pt_rank, *scan; };
+static VoxWs vox_ws(Carver& c, int64_t n, int64_t ncell) {
     VoxWs w;
-    size_t o = 0;
     const size_t N = (size_t)(n > 0 ? n : 1), C = (size_t)(ncell > 0 ? ncell : 1);
-    w.cell_flag = o; o += align_up(C * 4, 256);
-    w.cell_rank = o; o += align_up((C + 1) * 4, 256);
-    w.pt_key = o;    o += align_up(N * 4, 256);
-    w.pt_valid = o;  o += align_up(N * 4, 256);
-    w.pt_rank = o;   o += align_up((N + 1) * 4, 256);
-    w.scan = o;      o += align_up(lidf_exclusive_scan_workspace_bytes(N > C ? (int64_t)N : (int64_t)C), 256);
-    w.total = o;
+    w.cell_flag = c.take<int>(C);
+    w.cell_rank = c.take<int>(C + 1);
+    w.pt_key = c.take<int>(N);
+    w.pt_valid = c.take<int>(N);
+    w.pt_rank = c.take<int>(N + 1);
+    w.scan = scan_ws(c, N > C ? (int64_t)N : (int64_t)C);   // (serves both scans in turn)
     return w;
 }
 
 LIDF_API size_t lidf_voxelize_workspace_bytes(int64_t n_pts, int64_t n_cells) {
-    return vox_ws(n_pts, n_cells).total;
+    return carved([&](Carver& c) { vox_ws(c, n_pts, n_cells); });
 }
 
 LIDF_API int lidf_voxelize_f32(const float* xyz, const int32_t* bid, int64_t n, int batch,
@@ -2006,23 +1986,20 @@ LIDF_API int lidf_voxelize_f32(const float* xyz, const int32_t* bid, int64_t n, 
     if (ncell > 0x7fffffffLL || n > 0x7fffffffLL) return LIDF_ERR_UNSUPPORTED;
     if (n > 0 && (!xyz || !bid || !valid_pid || !revidx || !rel_coord)) return LIDF_ERR_BAD_ARG;
     if (!occ_bid_coord || !voxel_bound) return LIDF_ERR_BAD_ARG;
-    VoxWs w = vox_ws(n, ncell);
-    if (!workspace || workspace_bytes < w.total) return LIDF_ERR_WORKSPACE;
+    Carver c(workspace);
+    const VoxWs w = vox_ws(c, n, ncell);
+    CHECK_CARVED(c, workspace, workspace_bytes);
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    int* cell_flag = (int*)(ws + w.cell_flag);
-    int* cell_rank = (int*)(ws + w.cell_rank);
-    int* pt_key = (int*)(ws + w.pt_key);
-    int* pt_valid = (int*)(ws + w.pt_valid);
-    int* pt_rank = (int*)(ws + w.pt_rank);
+    int *cell_flag = w.cell_flag, *cell_rank = w.cell_rank, *pt_key = w.pt_key, *pt_valid = w.pt_valid,
+        *pt_rank = w.pt_rank;
     GridSpec g;
     for (int a = 0; a < 3; ++a) { g.xmin[a] = xmin[a]; g.r[a] = res[a]; }
     g.crop = crop;
     g.B = batch;
     CHECK_HIP(hipMemsetAsync(cell_flag, 0, (size_t)ncell * 4, st));
     CHECK_HIP(lidf_launch_vox_mark(xyz, bid, n, g, cell_flag, pt_key, pt_valid, st));
-    CHECK_HIP(lidf_launch_scan(cell_flag, ncell, cell_rank, (int*)(ws + w.scan), st));
-    CHECK_HIP(lidf_launch_scan(pt_valid, n, pt_rank, (int*)(ws + w.scan), st));
+    CHECK_HIP(lidf_launch_scan(cell_flag, ncell, cell_rank, w.scan, st));
+    CHECK_HIP(lidf_launch_scan(pt_valid, n, pt_rank, w.scan, st));
     CHECK_HIP(lidf_launch_vox_cells(cell_flag, cell_rank, ncell, g, occ_bid_coord, voxel_bound, st));
     CHECK_HIP(lidf_launch_vox_points(xyz, pt_key, pt_rank, cell_rank, n, g, valid_pid, revidx,
                                      rel_coord, st));
@@ -2042,7 +2019,7 @@ LIDF_API int lidf_depth_metrics_f32(const float* pred_depth, const float* gt_dep
     if (!pred_depth || !gt_depth || !out) return LIDF_ERR_BAD_ARG;
     if (seg_dtype < 0 || seg_dtype > 2 || (seg_dtype != 0 && !seg_mask)) return LIDF_ERR_BAD_ARG;
     if ((int64_t)dst_h * dst_w > 0x7fffffffLL) return LIDF_ERR_UNSUPPORTED;
-    if (!workspace || workspace_bytes < lidf_depth_metrics_ws_bytes()) return LIDF_ERR_WORKSPACE;
+    CHECK_WS(workspace, workspace_bytes, lidf_depth_metrics_ws_bytes());
     CHECK_HIP(lidf_launch_depth_metrics(pred_depth, gt_depth, seg_mask, seg_mask ? seg_dtype : 0, src_h, src_w,
                                         dst_h, dst_w, out, workspace, (hipStream_t)stream));
     return LIDF_OK;
@@ -2065,7 +2042,7 @@ LIDF_API int lidf_depth_metrics_frames_f32(const float* pred_depth, const float*
     if (seg_dtype < 0 || seg_dtype > 2 || (seg_dtype != 0 && !seg_mask)) return LIDF_ERR_BAD_ARG;
     if ((int64_t)dst_h * dst_w > 0x7fffffffLL || batch > FRAMES_MAX_BATCH) return LIDF_ERR_UNSUPPORTED;
     if ((uintptr_t)workspace & 7) return LIDF_ERR_BAD_ARG;
-    if (!workspace || workspace_bytes < lidf_depth_metrics_frames_workspace_bytes(batch)) return LIDF_ERR_WORKSPACE;
+    CHECK_WS(workspace, workspace_bytes, lidf_depth_metrics_frames_workspace_bytes(batch));
     CHECK_HIP(lidf_launch_depth_metrics_frames(pred_depth, gt_depth, seg_mask, seg_mask ? seg_dtype : 0, batch, src_h,
                                                src_w, dst_h, dst_w, out, workspace, (hipStream_t)stream));
     return LIDF_OK;
@@ -2178,8 +2155,7 @@ LIDF_API int lidf_roi_align_backward_f32(const float* d_out, int64_t ld_dout, co
                        ld_dout < (int64_t)channels * roi_out_bbox * roi_out_bbox))
         return LIDF_ERR_BAD_ARG;
     if ((int64_t)batch * height * width > 0x3fffffffLL || n_rays > 0x7fffffffLL) return LIDF_ERR_UNSUPPORTED;
-    if (n_rays > 0 && (!workspace || workspace_bytes < lidf_roi_align_backward_ws_bytes(batch, height, width)))
-        return LIDF_ERR_WORKSPACE;
+    if (n_rays > 0) CHECK_WS(workspace, workspace_bytes, lidf_roi_align_backward_ws_bytes(batch, height, width));
     hipStream_t st = (hipStream_t)stream;
     if (n_rays == 0) {
         CHECK_HIP(hipMemsetAsync(d_feat_grid, 0, (size_t)nel * 4, st));
@@ -2265,7 +2241,7 @@ static int linear_impl(const float* x, int64_t ldx, int64_t n, int32_t k, const 
     if (addrows2 && (!addidx2 || ld_add2 < nout)) return LIDF_ERR_BAD_ARG;
     // the max-pool epilogue raises whole 32-column tiles of non-negative values
     if (pool && (!poolidx || ld_pool < nout || nout % 32 != 0 || !act || slope != 0.f)) return LIDF_ERR_BAD_ARG;
-    if (!workspace || workspace_bytes < linex_stream_bytes(k)) return LIDF_ERR_WORKSPACE;
+    CHECK_WS(workspace, workspace_bytes, linex_stream_bytes(k));
     int rc, cus;
     if ((rc = cu_count(&cus))) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -2312,10 +2288,16 @@ static size_t chain16_any_stream_bytes(int gf, int k, bool split) {
     const int G = gf / 16;
     return (size_t)(lidf_chain16h_l1_quads(G, k) + lidf_chain16h_pass_quads(G)) * 1024;
 }
+// one decoder's chain stream | layer-4 operands: lidf_decoder_chain_f32's workspace, a slot of the any-width pack blob
+static StreamAux chain16_ws(Carver& c, int gf, int k, bool split) {
+    StreamAux w;
+    w.stream = (float*)c.take_bytes(chain16_any_stream_bytes(gf, k, split));
+    w.aux = c.take<float>(lidf_chain16_aux_floats(gf / 16));
+    return w;
+}
 static size_t decoder_chain_workspace_bytes(int32_t gf_dim, int32_t k, bool split) {
     if ((gf_dim != 32 && gf_dim != 64 && gf_dim != 128) || k <= 0 || k > (1 << 16)) return 0;
-    return align_up(chain16_any_stream_bytes(gf_dim, k, split), 256) +
-           align_up((size_t)lidf_chain16_aux_floats(gf_dim / 16) * 4, 256);
+    return carved([&](Carver& c) { chain16_ws(c, gf_dim, k, split); });
 }
 LIDF_API size_t lidf_decoder_chain_workspace_bytes(int32_t gf_dim, int32_t k) {
     return decoder_chain_workspace_bytes(gf_dim, k, false);
@@ -2338,15 +2320,15 @@ static int decoder_chain_impl(const LidfDecoder* dec, int32_t gf_dim, int32_t in
     // (the kernel loads the table rows as aligned 16-byte pieces; a row is 256 gf_dim / 16 bytes)
     if (((uintptr_t)voxpart | (uintptr_t)raypart) & 15) return LIDF_ERR_BAD_ARG;
     if (k > (1 << 16)) return LIDF_ERR_UNSUPPORTED;
-    const size_t need = decoder_chain_workspace_bytes(gf_dim, k, split);
-    if (!workspace || workspace_bytes < need) return LIDF_ERR_WORKSPACE;
+    Carver c(workspace);
+    const StreamAux w = chain16_ws(c, gf_dim, k, split);
+    CHECK_CARVED(c, workspace, workspace_bytes);
     int rc, cus;
     if ((rc = cu_count(&cus))) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int G = gf_dim / 16;
     const size_t sbytes = chain16_any_stream_bytes(gf_dim, k, split);
-    float* sbuf = (float*)workspace;
-    float* aux = (float*)((char*)workspace + align_up(sbytes, 256));
+    float *sbuf = w.stream, *aux = w.aux;
     StreamLayout lay = {};
     lay.nets = 1; lay.mode = split ? LIDF_MODE_CHAIN16_H : LIDF_MODE_CHAIN16;
     lay.total = (int)(sbytes / 4);
@@ -2397,11 +2379,15 @@ static inline bool widths_gf_ok(int gf) { return gf == 32 || gf == 64 || gf == 1
 #define WIDTHS_GUARDS 3   // prob, off, off_refine
 
 struct WidthsWs {
-    size_t lin, iota, rp, bias, voxpart[2], raypart[2], pe, voxpart_r, raypart_r, total;
+    char* lin;      // the table launches' weight stream (k <= 128)
+    int* iota;      // row r -> r: the gathered term of the ray tables
+    float* rp;      // W1[:, ROI] roi, before the direction columns
+    float* bias;    // the bias rows the library forms itself
+    float *voxpart[2], *raypart[2], *pe, *voxpart_r, *raypart_r;
     int64_t slab;
 };
-static WidthsWs widths_ws(int B, int h, int w, const int32_t* res, int64_t max_pairs, int refine_times, int L,
-                          const LidfFrameWidths* wd) {
+static WidthsWs widths_ws(Carver& c, int B, int h, int w, const int32_t* res, int64_t max_pairs, int refine_times,
+                          int L, const LidfFrameWidths* wd) {
     WidthsWs W;
     const size_t N = (size_t)B * h * w, C = (size_t)B * res[0] * res[1] * res[2];
     const int gfs[2] = {wd->prob_gf, wd->off_gf};
@@ -2410,21 +2396,24 @@ static WidthsWs widths_ws(int B, int h, int w, const int32_t* res, int64_t max_p
     if (rf && wd->refine_gf > gmax) gmax = wd->refine_gf;
     W.slab = wd->pe_slab_pairs > 0 ? wd->pe_slab_pairs : LIDF_FRAME_PE_SLAB;
     if (W.slab > max_pairs) W.slab = max_pairs;
-    size_t o = 0;
-    W.lin = o;  o += align_up(linex_stream_bytes(128), 256);      // the table launches' weight stream (k <= 128)
-    W.iota = o; o += align_up(N * 4, 256);                        // row r -> r: the gathered term of the ray tables
-    W.rp = o;   o += align_up(N * 4 * gmax * 4, 256);             // W1[:, ROI] roi, before the direction columns
-    W.bias = o; o += align_up((size_t)3 * 512 * 4, 256);          // the bias rows the library forms itself
+    W.lin = (char*)c.take_bytes(linex_stream_bytes(128));
+    W.iota = c.take<int>(N);
+    W.rp = c.take<float>(N * 4 * gmax);
+    W.bias = c.take<float>(3 * 512);
     for (int i = 0; i < 2; ++i) {
-        W.voxpart[i] = o; o += align_up(C * 4 * gfs[i] * 4, 256);
-        W.raypart[i] = o; o += align_up(N * 4 * gfs[i] * 4, 256);
+        W.voxpart[i] = c.take<float>(C * 4 * gfs[i]);
+        W.raypart[i] = c.take<float>(N * 4 * gfs[i]);
     }
     // (16 floats of slack behind the rows: the chain launch reads whole 16-column groups of the last row)
-    W.pe = o;   o += align_up((size_t)W.slab * 2 * (3 + 6 * L) * 4 + 64, 256);
-    W.voxpart_r = o; o += rf ? align_up(C * 4 * wd->refine_gf * 4, 256) : 0;
-    W.raypart_r = o; o += rf ? align_up(N * 4 * wd->refine_gf * 4, 256) : 0;
-    W.total = o;
+    W.pe = c.take<float>((size_t)W.slab * 2 * (3 + 6 * L) + 16);
+    W.voxpart_r = c.take_if<float>(rf, C * 4 * wd->refine_gf);
+    W.raypart_r = c.take_if<float>(rf, N * 4 * wd->refine_gf);
     return W;
+}
+// ... on the workspace of a call that frame_widths_check accepted
+static WidthsWs widths_ws_of(const LidfFrameArgs* a, const LidfFrameWidths* wd) {
+    Carver c(wd->workspace);
+    return widths_ws(c, a->batch, a->height, a->width, a->res, a->max_pairs, a->refine_times, a->multires, wd);
 }
 static bool widths_args_ok(const LidfFrameWidths* wd, int refine_times, int L, int Lv) {
     return wd && widths_gf_ok(wd->prob_gf) && widths_gf_ok(wd->off_gf) &&
@@ -2438,25 +2427,23 @@ LIDF_API size_t lidf_frame_widths_workspace_bytes(int32_t batch, int32_t height,
     if (batch <= 0 || height <= 0 || width <= 0 || !res || res[0] <= 0 || res[1] <= 0 || res[2] <= 0 ||
         max_pairs <= 0 || refine_times < 0 || !widths_args_ok(wd, refine_times, multires, multires_views))
         return 0;
-    return widths_ws(batch, height, width, res, max_pairs, refine_times, multires, wd).total;
+    return carved([&](Carver& c) { widths_ws(c, batch, height, width, res, max_pairs, refine_times, multires, wd); });
 }
 
 // the three chain streams (stream | layer-4 operands each, as lidf_decoder_chain_f32's workspace)
-struct WidthsPack { size_t dec[3], total; };
-static WidthsPack widths_pack_lay(int L, bool rf, const LidfFrameWidths* wd) {
-    WidthsPack p;
+struct WidthsPack { StreamAux dec[3]; };
+static WidthsPack widths_pack_lay(Carver& c, int L, bool rf, const LidfFrameWidths* wd) {
+    WidthsPack p = {};
     const int E = 3 + 6 * L;
-    size_t o = 0;
-    p.dec[0] = o; o += align_up(lidf_decoder_chain_workspace_bytes(wd->prob_gf, 2 * E), 256);
-    p.dec[1] = o; o += align_up(lidf_decoder_chain_workspace_bytes(wd->off_gf, 2 * E), 256);
-    p.dec[2] = o; o += rf ? align_up(lidf_decoder_chain_workspace_bytes(wd->refine_gf, E), 256) : 0;
-    p.total = o;
+    p.dec[0] = chain16_ws(c, wd->prob_gf, 2 * E, false);
+    p.dec[1] = chain16_ws(c, wd->off_gf, 2 * E, false);
+    if (rf) p.dec[2] = chain16_ws(c, wd->refine_gf, E, false);
     return p;
 }
 LIDF_API size_t lidf_frame_widths_pack_bytes(int32_t multires, int32_t multires_views, const LidfFrameWidths* wd) {
     // (sized with the third stream whatever refine_times a later call passes: refine_gf outside the widths = none)
     if (!wd || !widths_args_ok(wd, widths_gf_ok(wd->refine_gf) ? 1 : 0, multires, multires_views)) return 0;
-    return widths_pack_lay(multires, widths_gf_ok(wd->refine_gf), wd).total;
+    return carved([&](Carver& c) { widths_pack_lay(c, multires, widths_gf_ok(wd->refine_gf), wd); });
 }
 LIDF_API size_t lidf_frame_widths_pack_guard_bytes(void) { return (size_t)WIDTHS_GUARDS * FRAME_GUARD_STRIDE; }
 
@@ -2472,19 +2459,19 @@ static int frame_widths_check(const LidfFrameArgs* a, const LidfFrameWidths* wd)
         return LIDF_ERR_UNSUPPORTED;
     int rc;
     if ((rc = check_decoder(a->prob)) || (rc = check_decoder(a->off))) return rc;
-    const WidthsWs W = widths_ws(a->batch, a->height, a->width, a->res, a->max_pairs, a->refine_times, a->multires, wd);
-    if (!wd->workspace || wd->workspace_bytes < W.total) return LIDF_ERR_WORKSPACE;
-    if (!wd->pack_blob || wd->pack_blob_bytes < widths_pack_lay(a->multires, rf, wd).total) return LIDF_ERR_WORKSPACE;
+    Carver cw, cp, cf, cb;   // (sizing passes: the layouts are carved where they are used)
+    widths_ws(cw, a->batch, a->height, a->width, a->res, a->max_pairs, a->refine_times, a->multires, wd);
+    CHECK_CARVED(cw, wd->workspace, wd->workspace_bytes);
+    widths_pack_lay(cp, a->multires, rf, wd);
+    CHECK_CARVED(cp, wd->pack_blob, wd->pack_blob_bytes);
     if (a->pack_mode != LIDF_FRAME_PACK_CALLER && !wd->pack_guard) return LIDF_ERR_WORKSPACE;
     if (((uintptr_t)wd->workspace | (uintptr_t)wd->pack_blob) & 15) return LIDF_ERR_BAD_ARG;
     // (LidfFrameArgs' own workspace and blob, which frame_impl checks again behind its first HIP call: here every
     // size error of this entry is reported before one)
-    const size_t Cc = (size_t)a->batch * a->res[0] * a->res[1] * a->res[2];
-    if (!a->workspace || a->workspace_bytes < frame_ws(a->batch, a->height, a->width, a->res, a->max_pairs,
-                                                       frame_lds_voxels(a->lds_voxels, Cc), a->refine_times).total)
-        return LIDF_ERR_WORKSPACE;
-    if (a->pack_mode != LIDF_FRAME_PACK_CALLER &&
-        (!a->pack_blob || !a->pack_guard || a->pack_blob_bytes < frame_pack_lay().total))
+    frame_ws(cf, a->batch, a->height, a->width, a->res, a->refine_times, a->multires, a->multires_views);
+    CHECK_CARVED(cf, a->workspace, a->workspace_bytes);
+    frame_pack_lay(cb);
+    if (a->pack_mode != LIDF_FRAME_PACK_CALLER && (!a->pack_guard || !cb.covers(a->pack_blob, a->pack_blob_bytes)))
         return LIDF_ERR_WORKSPACE;
     // stage 2 hands the chain launch the embed(pos) columns [256, 256 + E) of inp_embed (row stride D): whole
     // 16-column groups are read, so the last row must be readable up to column 256 + 16 ceil(E / 16) — inside the
@@ -2503,14 +2490,15 @@ static int widths_decoder_segs(const LidfDecoder* d, int dcore, int gf, const fl
     for (int i = 0; i < (d->is_ief ? 10 : 8); ++i) { ptrs[k] = p[i]; n[k] = c[i]; ++k; }
     return k;
 }
-static int widths_chain_pack(const LidfDecoder* dec, int gf, int inp_dim, int k, int c0, char* dst, hipStream_t st) {
+static int widths_chain_pack(const LidfDecoder* dec, int gf, int inp_dim, int k, int c0, const StreamAux& dst,
+                             hipStream_t st) {
     StreamLayout lay = {};
     lay.nets = 1; lay.mode = LIDF_MODE_CHAIN16;
     lay.total = (int)(chain16_stream_bytes(gf, k) / 4);
     L1Map m = {};
     m.n0 = k; m.c0 = c0; m.nt = gf / 16;
     const NetW nw = to_netw(dec, inp_dim);
-    CHECK_HIP(pack_stream(lay, nw, nw, m, (float*)dst, (float*)(dst + align_up(chain16_stream_bytes(gf, k), 256)), st));
+    CHECK_HIP(pack_stream(lay, nw, nw, m, dst.stream, dst.aux, st));
     return LIDF_OK;
 }
 
@@ -2518,12 +2506,13 @@ static int widths_chain_pack(const LidfDecoder* dec, int gf, int inp_dim, int k,
 // of LidfFrameArgs.pack_guard (the slots lidf_frame_f32 keeps them in), the three decoders into
 // LidfFrameWidths.pack_guard — and the early-exit packs under them; TRUSTED: nothing; CALLER (pnet_blob NULL):
 // the chain streams packed without a check, the PointNet streams are the caller's.
-static int frame_widths_pack(const LidfFrameArgs* a, const LidfFrameWidths* wd, char* pnet_blob, char* pnet_blob_r,
+static int frame_widths_pack(const LidfFrameArgs* a, const LidfFrameWidths* wd, void* pnet_blob, void* pnet_blob_r,
                              hipStream_t st) {
     if (a->pack_mode == LIDF_FRAME_PACK_TRUSTED) return LIDF_OK;
     const bool rf = a->refine_times > 0, guard = a->pack_mode == LIDF_FRAME_PACK_GUARDED;
     const int L = a->multires, Lv = a->multires_views, E = 3 + 6 * L;
-    const WidthsPack pl = widths_pack_lay(L, rf, wd);
+    Carver bc(wd->pack_blob);
+    const WidthsPack pl = widths_pack_lay(bc, L, rf, wd);
     const LidfDecoder* decs[3] = {a->prob, a->off, rf ? a->off_refine : nullptr};
     const int gfs[3] = {wd->prob_gf, wd->off_gf, wd->refine_gf};
     const int dims[3] = {query_D(L, Lv), query_D(L, Lv), refine_D(L, Lv)};
@@ -2562,7 +2551,7 @@ static int frame_widths_pack(const LidfFrameArgs* a, const LidfFrameWidths* wd, 
     for (int i = 0; i < nd && !rc; ++i) {
         GuardScope g(guard ? (const LidfPackGuardState*)(guards + (size_t)i * FRAME_GUARD_STRIDE) : nullptr);
         // (the per-row operand columns start behind [vox feat 128 | ROI 128] in both stages' rows)
-        rc = widths_chain_pack(decs[i], gfs[i], dims[i], ks[i], 256, (char*)wd->pack_blob + pl.dec[i], st);
+        rc = widths_chain_pack(decs[i], gfs[i], dims[i], ks[i], 256, pl.dec[i], st);
     }
     if (!rc && pnet_blob) {
         GuardScope g(guard ? (const LidfPackGuardState*)pguards : nullptr);
@@ -2603,9 +2592,9 @@ static int frame_widths_query(const LidfFrameArgs* a, const LidfFrameWidths* wd,
                               const float* vox_center, int cus, hipStream_t st) {
     const int L = a->multires, Lv = a->multires_views, E = 3 + 6 * L, Ed = 3 + 6 * Lv, D = query_D(L, Lv);
     const bool rf = a->refine_times > 0;
-    const WidthsWs W = widths_ws(a->batch, a->height, a->width, a->res, a->max_pairs, a->refine_times, L, wd);
-    const WidthsPack pl = widths_pack_lay(L, rf, wd);
-    char* ws = (char*)wd->workspace;
+    const WidthsWs W = widths_ws_of(a, wd);
+    Carver bc(wd->pack_blob);
+    const WidthsPack pl = widths_pack_lay(bc, L, rf, wd);
     const int* counts = a->counts;
     const int* n_rays = counts + LIDF_FC_RAYS;
     const int* n_pairs = counts + LIDF_FC_PAIRS;
@@ -2615,33 +2604,33 @@ static int frame_widths_query(const LidfFrameArgs* a, const LidfFrameWidths* wd,
     // image: every bin is summed in the reference's sample order, the bits of the stepwise path at these widths
     CHECK_HIP(lidf_launch_rayfeat_phase(a->feat_grid, nullptr, a->batch, a->height, a->width, a->ray_dir, a->ray_pix,
                                         a->ray_bid, N, n_rays, a->roi_inp_bbox / 2, Lv, a->rayfeat, 128 + Ed, 0, st));
-    int* iota = (int*)(ws + W.iota);
+    int* iota = W.iota;
     CHECK_HIP(lidf_launch_iota(iota, N, st));
     const LidfDecoder* decs[2] = {a->prob, a->off};
     const int gfs[2] = {wd->prob_gf, wd->off_gf};
     const float* given[2] = {wd->prob_bias, wd->off_bias};
-    float* rp = (float*)(ws + W.rp);
+    float* rp = W.rp;
     for (int i = 0; i < 2; ++i) {
         const LidfDecoder* d = decs[i];
         const int nout = 4 * gfs[i], ld1 = D + (d->is_ief ? 16 : 0);
         const float* bias;
-        if ((rc = widths_bias_row(d, gfs[i], D, given[i], (float*)(ws + W.bias) + 512 * i, &bias, st))) return rc;
+        if ((rc = widths_bias_row(d, gfs[i], D, given[i], W.bias + 512 * i, &bias, st))) return rc;
         // voxpart [C, 4 gf] = W1[:, 0:128] occ_voxel_feat + bias row, rows < counts[VOX]
         if ((rc = widths_linear(a->occ_voxel_feat, 128, C, n_vox, 128, d->w1, ld1, bias, nout, nullptr, nullptr,
-                                (float*)(ws + W.voxpart[i]), ws + W.lin, st)))
+                                W.voxpart[i], W.lin, st)))
             return rc;
         // rp = W1[:, ROI columns] rayfeat[:, :128]; raypart [N, 4 gf] = W1[:, dir columns] rayfeat[:, 128:] + rp
         // (rows < counts[RAYS]; the gathered term's index is the row itself: iota below the count)
         if ((rc = widths_linear(a->rayfeat, 128 + Ed, N, n_rays, 128, d->w1 + 128, ld1, nullptr, nout, nullptr,
-                                nullptr, rp, ws + W.lin, st)))
+                                nullptr, rp, W.lin, st)))
             return rc;
         if ((rc = widths_linear(a->rayfeat + 128, 128 + Ed, N, n_rays, Ed, d->w1 + 256 + 2 * E, ld1, nullptr, nout, rp,
-                                iota, (float*)(ws + W.raypart[i]), ws + W.lin, st)))
+                                iota, W.raypart[i], W.lin, st)))
             return rc;
     }
     // the slabs: every launch reads counts[PAIRS] and works on clamp(P - p0, 0, rows of the slab) rows; no
     // element of pair_ray / pair_vox / pair_t at or beyond counts[PAIRS] is dereferenced
-    float* pe = (float*)(ws + W.pe);
+    float* pe = W.pe;
     float* outs[2] = {a->pred_prob, a->pred_offset};
     for (int64_t p0 = 0; p0 < a->max_pairs; p0 += W.slab) {
         const int64_t rows = a->max_pairs - p0 < W.slab ? a->max_pairs - p0 : W.slab;
@@ -2649,14 +2638,13 @@ static int frame_widths_query(const LidfFrameArgs* a, const LidfFrameWidths* wd,
                                       a->pos_rel ? 1 : 0, L, rows, pe, st, n_pairs, p0));
         for (int i = 0; i < 2; ++i) {
             const LidfDecoder* d = decs[i];
-            const char* blob = (const char*)wd->pack_blob + pl.dec[i];
             Chain16Args c = {};
-            c.stream = (const float*)blob;
-            c.aux = (const float*)(blob + align_up(chain16_stream_bytes(gfs[i], 2 * E), 256));
+            c.stream = pl.dec[i].stream;
+            c.aux = pl.dec[i].aux;
             c.KQ = (2 * E + 15) / 16; c.E = 2 * E; c.n = rows;
             c.X = pe; c.ldx = 2 * E;
-            c.vox = a->pair_vox + p0; c.voxpart = (const float*)(ws + W.voxpart[i]);
-            c.ray = a->pair_ray + p0; c.raypart = (const float*)(ws + W.raypart[i]);
+            c.vox = a->pair_vox + p0; c.voxpart = W.voxpart[i];
+            c.ray = a->pair_ray + p0; c.raypart = W.raypart[i];
             c.npass = d->is_ief ? d->n_iter : 1;
             c.init = d->is_ief ? d->init_offset : 0.f;
             c.sigmoid = d->use_sigmoid;
@@ -2679,18 +2667,17 @@ static int frame_widths_query(const LidfFrameArgs* a, const LidfFrameWidths* wd,
 // stage 2, once per frame: raypart_r [N, 4 gf] = W1r[:, ROI | dir columns] rayfeat[r], rows < counts[RAYS]
 static int frame_widths_refine_tables(const LidfFrameArgs* a, const LidfFrameWidths* wd, int64_t N, hipStream_t st) {
     const int L = a->multires, Lv = a->multires_views, E = 3 + 6 * L, Ed = 3 + 6 * Lv, D = refine_D(L, Lv);
-    const WidthsWs W = widths_ws(a->batch, a->height, a->width, a->res, a->max_pairs, a->refine_times, L, wd);
-    char* ws = (char*)wd->workspace;
+    const WidthsWs W = widths_ws_of(a, wd);
     const LidfDecoder* d = a->off_refine;
     const int nout = 4 * wd->refine_gf, ld1 = D + (d->is_ief ? 16 : 0);
     const int* n_rays = a->counts + LIDF_FC_RAYS;
-    float* rp = (float*)(ws + W.rp);
+    float* rp = W.rp;
     int rc;
     if ((rc = widths_linear(a->rayfeat, 128 + Ed, N, n_rays, 128, d->w1 + 128, ld1, nullptr, nout, nullptr, nullptr,
-                            rp, ws + W.lin, st)))
+                            rp, W.lin, st)))
         return rc;
     return widths_linear(a->rayfeat + 128, 128 + Ed, N, n_rays, Ed, d->w1 + 256 + E, ld1, nullptr, nout, rp,
-                         (const int*)(ws + W.iota), (float*)(ws + W.raypart_r), ws + W.lin, st);
+                         W.iota, W.raypart_r, W.lin, st);
 }
 
 // stage 2, per iteration behind the PointNet: voxpart_r [C, 4 gf] (rows < counts[VOX]), then the decoder as one
@@ -2699,25 +2686,24 @@ static int frame_widths_refine_decoder(const LidfFrameArgs* a, const LidfFrameWi
                                        const float* vox_feat_r, const float* inp_embed, float* offv, int cus,
                                        hipStream_t st) {
     const int L = a->multires, Lv = a->multires_views, E = 3 + 6 * L, D = refine_D(L, Lv), gf = wd->refine_gf;
-    const WidthsWs W = widths_ws(a->batch, a->height, a->width, a->res, a->max_pairs, a->refine_times, L, wd);
-    const WidthsPack pl = widths_pack_lay(L, true, wd);
-    char* ws = (char*)wd->workspace;
+    const WidthsWs W = widths_ws_of(a, wd);
+    Carver bc(wd->pack_blob);
+    const WidthsPack pl = widths_pack_lay(bc, L, true, wd);
     const LidfDecoder* d = a->off_refine;
     const int ld1 = D + (d->is_ief ? 16 : 0);
     const float* bias;
     int rc;
-    if ((rc = widths_bias_row(d, gf, D, wd->refine_bias, (float*)(ws + W.bias) + 1024, &bias, st))) return rc;
+    if ((rc = widths_bias_row(d, gf, D, wd->refine_bias, W.bias + 1024, &bias, st))) return rc;
     if ((rc = widths_linear(vox_feat_r, 128, C, a->counts + LIDF_FC_VOX, 128, d->w1, ld1, bias, 4 * gf, nullptr, nullptr,
-                            (float*)(ws + W.voxpart_r), ws + W.lin, st)))
+                            W.voxpart_r, W.lin, st)))
         return rc;
-    const char* blob = (const char*)wd->pack_blob + pl.dec[2];
     Chain16Args c = {};
-    c.stream = (const float*)blob;
-    c.aux = (const float*)(blob + align_up(chain16_stream_bytes(gf, E), 256));
+    c.stream = pl.dec[2].stream;
+    c.aux = pl.dec[2].aux;
     c.KQ = (E + 15) / 16; c.E = E; c.n = N;
     c.X = inp_embed + 256; c.ldx = D;
-    c.vox = a->end_voxel_id; c.voxpart = (const float*)(ws + W.voxpart_r);
-    c.ray = nullptr; c.raypart = (const float*)(ws + W.raypart_r);
+    c.vox = a->end_voxel_id; c.voxpart = W.voxpart_r;
+    c.ray = nullptr; c.raypart = W.raypart_r;
     c.npass = d->is_ief ? d->n_iter : 1;
     c.init = d->is_ief ? d->init_offset : 0.f;
     c.sigmoid = d->use_sigmoid;
@@ -2795,14 +2781,16 @@ static int run_chain_train(const LidfDecoder* dec, int dcore, const L1Map& m, co
     return LIDF_OK;
 }
 
-// scratch of refine_ief_factorised: [layer-1 stream of the per-voxel launch | of the per-ray launch (ROI +
-// direction columns, sized for the widest direction embedding) | stream + aux of the chain]
 #define REFINE_RAY_K (128 + 3 + 6 * 16)
-// ... | stream + aux of the 16 x 16 x 4 decoder (lidf_ief16.hip): E <= 99 embed(pos) columns = 7 k-quads]
 static size_t ief16_stream_bytes(int E) { return (size_t)(((E + 15) / 16) * 16 + IEF16_PASS_QUADS) * 1024; }
-static size_t refine_fact_bytes(int D) {
-    return linex_stream_bytes(128) + linex_stream_bytes(REFINE_RAY_K) + chain_stream_bytes(D - 128) +
-           align_up(ief16_stream_bytes(3 + 6 * 16), 256) + align_up(IEF16_AUX_FLOATS * 4, 256);
+static RefineFact refine_fact(Carver& c, int D) {
+    RefineFact f;
+    f.s_vox = (float*)c.take_bytes(linex_stream_bytes(128));
+    f.s_ray = (float*)c.take_bytes(linex_stream_bytes(REFINE_RAY_K));
+    f.s_chain = (char*)c.take_bytes(chain_stream_bytes(D - 128));
+    f.s16 = (float*)c.take_bytes(ief16_stream_bytes(3 + 6 * 16));
+    f.aux16 = c.take<float>(IEF16_AUX_FLOATS);
+    return f;
 }
 // LIDF_IEF16=0 in the environment: the 32 x 32 rows kernel of rounds 2-3 instead (A/B measurements)
 static bool use_ief16() {
@@ -2816,7 +2804,7 @@ static bool use_ief16() {
 
 static int refine_ief_factorised(const LidfDecoder* off, int D, const float* vox_feat, int64_t V,
                                  const float* inp_embed, const int32_t* end_voxel, int64_t R,
-                                 float* out, float* voxpart, char* scratch, hipStream_t st,
+                                 float* out, float* voxpart, const RefineFact& f, hipStream_t st,
                                  int pack_mode, const int* R_dev, const int* V_dev, void* const* ev_rows,
                                  const float* rayfeat, int Ed, float* raypart, bool make_raypart,
                                  bool voxpart_ready) {
@@ -2829,9 +2817,6 @@ static int refine_ief_factorised(const LidfDecoder* off, int D, const float* vox
     const int ld1 = D + (off->is_ief ? 16 : 0);
     const int E = D - 256 - Ed;
     if (E < 0 || Ed < 0 || 128 + Ed > REFINE_RAY_K) return LIDF_ERR_UNSUPPORTED;
-    char* s_vox = scratch;
-    char* s_ray = scratch + linex_stream_bytes(128);
-    char* s_chain = s_ray + linex_stream_bytes(REFINE_RAY_K);
     LinEx L = {};
     L.w = off->w1; L.b = off->b1; L.ldw = ld1; L.nout = LIDF_H1; L.k = 128; L.dcore = D;
     L.ief = off->is_ief ? off : nullptr;   // bias += c
@@ -2839,7 +2824,7 @@ static int refine_ief_factorised(const LidfDecoder* off, int D, const float* vox
     L.n_dev = V_dev;
     // (voxpart_ready: the frame path forms the per-voxel rows in the launch of the PointNet's last
     // per-voxel layer — VoxTail, the same stream)
-    if (!(voxpart_ready && pack_mode == 2) && (rc = run_linex(L, (float*)s_vox, cus, st, pack_mode))) return rc;
+    if (!(voxpart_ready && pack_mode == 2) && (rc = run_linex(L, f.s_vox, cus, st, pack_mode))) return rc;
     if (make_raypart || pack_mode == 1) {
         LinEx Lr = {};
         Lr.w = off->w1; Lr.b = nullptr; Lr.ldw = ld1; Lr.nout = LIDF_H1;
@@ -2848,11 +2833,9 @@ static int refine_ief_factorised(const LidfDecoder* off, int D, const float* vox
         Lr.dcore = D;
         Lr.X = rayfeat; Lr.ldx = 128 + Ed; Lr.n = R; Lr.out = raypart; Lr.ld_out = LIDF_H1;
         Lr.n_dev = R_dev;
-        if ((rc = run_linex(Lr, (float*)s_ray, cus, st, pack_mode))) return rc;
+        if ((rc = run_linex(Lr, f.s_ray, cus, st, pack_mode))) return rc;
     }
     // the decoder on 16-ray sub-tiles (lidf_ief16.hip): its stream rides behind the others
-    char* s16 = s_chain + chain_stream_bytes(D - 128);
-    float* aux16 = (float*)(s16 + align_up(ief16_stream_bytes(3 + 6 * 16), 256));
     if (pack_mode != 2) {
         StreamLayout lay = {};
         lay.nets = 1; lay.mode = LIDF_MODE_IEF16;
@@ -2860,12 +2843,12 @@ static int refine_ief_factorised(const LidfDecoder* off, int D, const float* vox
         L1Map m16 = {};
         m16.n0 = E; m16.c0 = 256;
         const NetW nw = to_netw(off, D);
-        CHECK_HIP(pack_stream(lay, nw, nw, m16, (float*)s16, aux16, st));
+        CHECK_HIP(pack_stream(lay, nw, nw, m16, f.s16, f.aux16, st));
     }
     if (!use_ief16() || pack_mode == 1) {
         if (ev_rows && ev_rows[0] && pack_mode != 1) CHECK_HIP(hipEventRecord((hipEvent_t)ev_rows[0], st));
         rc = run_chain_train(off, D, rows_map(E, 256, 0, 0, 0), inp_embed ? inp_embed + 256 : nullptr, D, R,
-                             end_voxel, nullptr, voxpart, raypart, nullptr, nullptr, out, s_chain, cus, st,
+                             end_voxel, nullptr, voxpart, raypart, nullptr, nullptr, out, f.s_chain, cus, st,
                              LIDF_MODE_ROWS_GATHER, pack_mode, R_dev);
         if (!rc && ev_rows && ev_rows[1] && pack_mode != 1) CHECK_HIP(hipEventRecord((hipEvent_t)ev_rows[1], st));
         return rc;
@@ -2873,7 +2856,7 @@ static int refine_ief_factorised(const LidfDecoder* off, int D, const float* vox
     if (R <= 0) return LIDF_OK;
     if (ev_rows && ev_rows[0]) CHECK_HIP(hipEventRecord((hipEvent_t)ev_rows[0], st));   // (benchmarks only)
     Ief16Args ia = {};
-    ia.stream = (const float*)s16; ia.aux = aux16; ia.KQ = (E + 15) / 16; ia.E = E;
+    ia.stream = f.s16; ia.aux = f.aux16; ia.KQ = (E + 15) / 16; ia.E = E;
     ia.n = R; ia.n_dev = R_dev;
     ia.X = inp_embed + 256; ia.ldx = D;
     ia.vox = end_voxel; ia.voxpart = voxpart; ia.raypart = raypart;
@@ -2888,7 +2871,7 @@ static int refine_ief_factorised(const LidfDecoder* off, int D, const float* vox
 
 LIDF_API size_t lidf_refine_pack_bytes(int32_t multires, int32_t multires_views) {
     if (multires < 0 || multires > 16 || multires_views < 0 || multires_views > 16) return 0;
-    return align_up(refine_fact_bytes(refine_D(multires, multires_views)), 256);
+    return carved([&](Carver& c) { refine_fact(c, refine_D(multires, multires_views)); });
 }
 
 LIDF_API int lidf_refine_pack_f32(const LidfDecoder* off, int32_t multires, int32_t multires_views,
@@ -2898,9 +2881,9 @@ LIDF_API int lidf_refine_pack_f32(const LidfDecoder* off, int32_t multires, int3
     if ((rc = check_decoder(off))) return rc;
     const size_t need = lidf_refine_pack_bytes(multires, multires_views);
     if (!need) return LIDF_ERR_UNSUPPORTED;
-    if (!packed || packed_bytes < need) return LIDF_ERR_WORKSPACE;
+    CHECK_WS(packed, packed_bytes, need);
     JobScope js;
-    if ((rc = refine_pack_into(off, multires, multires_views, (char*)packed, (hipStream_t)stream))) return rc;
+    if ((rc = refine_pack_into(off, multires, multires_views, packed, (hipStream_t)stream))) return rc;
     CHECK_HIP(flush_jobs(js.jobs, (hipStream_t)stream));
     return LIDF_OK;
 }
@@ -2913,7 +2896,7 @@ LIDF_API int lidf_refine_pack_guarded_f32(const LidfDecoder* off, int32_t multir
     if ((rc = check_decoder(off))) return rc;
     const size_t need = lidf_refine_pack_bytes(multires, multires_views);
     if (!need) return LIDF_ERR_UNSUPPORTED;
-    if (!packed || packed_bytes < need) return LIDF_ERR_WORKSPACE;
+    CHECK_WS(packed, packed_bytes, need);
     const float* ptrs[LIDF_FP_MAX_SEGS];
     long long cnt[LIDF_FP_MAX_SEGS];
     const int k = decoder_segs(off, refine_D(multires, multires_views), ptrs, cnt, 0);
@@ -2923,26 +2906,29 @@ LIDF_API int lidf_refine_pack_guarded_f32(const LidfDecoder* off, int32_t multir
 }
 
 struct TrainWs {
-    size_t stream, dz1, dz2, dz3, S, goff, wg, chain, small, total;
+    float *stream, *dz1, *dz2, *dz3;
+    float* S;       // running sum of dZ1 over the IEF's passes
+    float *goff, *wg;
+    char* chain;
+    float* small;   // B sums of the passes (the IEF's first pass, lidf_ief_finish_kernel)
 };
-static TrainWs train_ws(int64_t n, int d) {
+static TrainWs train_ws(Carver& c, int64_t n, int d) {
     TrainWs w;
     const size_t N = (size_t)(n > 0 ? n : 1);
-    size_t o = 0;
-    const int kmax = d > 256 ? d : 256;
-    w.stream = o; o += linex_stream_bytes(kmax);
-    w.dz1 = o;    o += align_up(N * LIDF_H1 * 4, 256);
-    w.dz2 = o;    o += align_up(N * LIDF_H2 * 4, 256);
-    w.dz3 = o;    o += align_up(N * LIDF_H3 * 4, 256);
-    w.S = o;      o += align_up(N * LIDF_H1 * 4, 256);   // running sum of dZ1 over the IEF's passes
-    w.goff = o;   o += align_up(N * 4, 256);
-    w.wg = o;     o += align_up(WG_SCRATCH_FLOATS * 4, 256);
-    w.chain = o;  o += chain_stream_bytes(d);
-    w.small = o;  o += 512 * 4;   // B sums of the passes (the IEF's first pass, lidf_ief_finish_kernel)
-    w.total = o;
+    w.stream = (float*)c.take_bytes(linex_stream_bytes(d > 256 ? d : 256));
+    w.dz1 = c.take<float>(N * LIDF_H1);
+    w.dz2 = c.take<float>(N * LIDF_H2);
+    w.dz3 = c.take<float>(N * LIDF_H3);
+    w.S = c.take<float>(N * LIDF_H1);
+    w.goff = c.take<float>(N);
+    w.wg = c.take<float>(WG_SCRATCH_FLOATS);
+    w.chain = (char*)c.take_bytes(chain_stream_bytes(d));
+    w.small = c.take<float>(512);
     return w;
 }
-LIDF_API size_t lidf_decoder_train_workspace_bytes(int64_t n, int32_t d) { return train_ws(n, d).total; }
+LIDF_API size_t lidf_decoder_train_workspace_bytes(int64_t n, int32_t d) {
+    return carved([&](Carver& c) { train_ws(c, n, d); });
+}
 
 static inline const unsigned* act_m1(const float* pass, int64_t n) { return (const unsigned*)(pass + (size_t)n * LIDF_ACT_M1); }
 static inline const unsigned* act_m2(const float* pass, int64_t n) { return (const unsigned*)(pass + (size_t)n * LIDF_ACT_M2); }
@@ -2957,39 +2943,29 @@ LIDF_API int lidf_decoder_forward_train_f32(const float* inp, int64_t n, int32_t
     if ((rc = check_decoder(dec))) return rc;
     if (n == 0) return LIDF_OK;
     if (!inp || !out || !act) return LIDF_ERR_BAD_ARG;
-    const TrainWs w = train_ws(n, d);
-    if (!workspace || workspace_bytes < w.total) return LIDF_ERR_WORKSPACE;
+    Carver c(workspace);
+    const TrainWs w = train_ws(c, n, d);
+    CHECK_CARVED(c, workspace, workspace_bytes);
     hipStream_t st = (hipStream_t)stream;
-    float* sbuf = (float*)((char*)workspace + w.stream);
     int cus;
     if ((rc = cu_count(&cus))) return rc;
     const int npass = dec->is_ief ? dec->n_iter : 1;
-    const int ld1 = d + (dec->is_ief ? 16 : 0);
     float* pre = act + (size_t)npass * n * ACT_ROW_FLOATS;  // final pre-activation
-    (void)ld1; (void)sbuf;
     // [inp | enc(off)] W1^T + b1 = inp W1x^T + (b1 + c) + u * off, then the chain, in registers
-    if ((rc = run_chain_train(dec, d, rows_map(d, 0, 0, 0, 1), inp, ld_inp, n, nullptr, nullptr, nullptr,
-                              nullptr, act, pre, out, (char*)workspace + w.chain, cus, st)))
-        return rc;
-    return LIDF_OK;
+    return run_chain_train(dec, d, rows_map(d, 0, 0, 0, 1), inp, ld_inp, n, nullptr, nullptr, nullptr, nullptr, act,
+                           pre, out, w.chain, cus, st);
 }
 
 // The backward of one decoder up to (and without) the input gradient: every parameter gradient, and S = the sum
 // of dZ1 over the passes left in the workspace (*S_out) for the caller's input-gradient product.
 static int decoder_backward_core(const float* inp, int64_t n, int32_t d, int64_t ld_inp, const LidfDecoder* dec,
-                                 const float* act, const float* g_out, const LidfDecoderGrads* grads, char* ws,
+                                 const float* act, const float* g_out, const LidfDecoderGrads* grads,
                                  const TrainWs& w, int cus, hipStream_t st, float** S_out) {
     const int npass = dec->is_ief ? dec->n_iter : 1;
     const int ld1 = d + (dec->is_ief ? 16 : 0);
-    float* sbuf = (float*)(ws + w.stream);
-    float* dz1 = (float*)(ws + w.dz1);
-    float* dz2 = (float*)(ws + w.dz2);
-    float* dz3 = (float*)(ws + w.dz3);
-    float* goff = (float*)(ws + w.goff);
-    float* wgs = (float*)(ws + w.wg);
+    float *sbuf = w.stream, *dz1 = w.dz1, *dz2 = w.dz2, *dz3 = w.dz3, *goff = w.goff, *wgs = w.wg, *S = w.S,
+          *small = w.small;
     const float* pre = act + (size_t)npass * n * ACT_ROW_FLOATS;
-    float* S = (float*)(ws + w.S);
-    float* small = (float*)(ws + w.small);
     CHECK_HIP(hipMemsetAsync(small, 0, 512 * 4, st));
     // through the output activation: goff = dL/d(off_n)
     CHECK_HIP(lidf_launch_out_act(pre, n, dec->use_sigmoid, nullptr, g_out, goff, st));
@@ -3091,14 +3067,14 @@ LIDF_API int lidf_decoder_backward_f32(const float* inp, int64_t n, int32_t d, i
     CHECK_HIP(zero_decoder_grads(grads, d + (dec->is_ief ? 16 : 0), dec->is_ief, st));
     if (n == 0) return LIDF_OK;
     if (!inp || !act || !g_out) return LIDF_ERR_BAD_ARG;
-    const TrainWs w = train_ws(n, d);
-    if (!workspace || workspace_bytes < w.total) return LIDF_ERR_WORKSPACE;
-    char* ws = (char*)workspace;
+    Carver c(workspace);
+    const TrainWs w = train_ws(c, n, d);
+    CHECK_CARVED(c, workspace, workspace_bytes);
     int cus;
     if ((rc = cu_count(&cus))) return rc;
     float* S = nullptr;
-    if ((rc = decoder_backward_core(inp, n, d, ld_inp, dec, act, g_out, grads, ws, w, cus, st, &S))) return rc;
-    if (d_inp) return decoder_input_grad(S, dec, nullptr, nullptr, n, d, d_inp, ld_dinp, (float*)(ws + w.stream), cus, st);
+    if ((rc = decoder_backward_core(inp, n, d, ld_inp, dec, act, g_out, grads, w, cus, st, &S))) return rc;
+    if (d_inp) return decoder_input_grad(S, dec, nullptr, nullptr, n, d, d_inp, ld_dinp, w.stream, cus, st);
     return LIDF_OK;
 }
 
@@ -3106,11 +3082,19 @@ LIDF_API int lidf_decoder_backward_f32(const float* inp, int64_t n, int32_t d, i
 // the two input gradients are one K = 512 product over [S_prob | S_off] and the rows' gradient is stored once —
 // not two K = 256 products, two stores of [n, d] and the accumulation autograd runs when the modules are two nodes.
 // Workspace: [decoder workspace of prob | of off | stream of the K = 512 product].
+struct PairWs { TrainWs prob, off; float* stream; };
+static PairWs pair_ws(Carver& c, int64_t n, int d) {
+    PairWs w;
+    w.prob = train_ws(c, n, d);
+    w.off = train_ws(c, n, d);
+    w.stream = (float*)c.take_bytes(linex_stream_bytes(2 * LIDF_H1));
+    return w;
+}
 LIDF_API size_t lidf_decoder_pair_workspace_bytes(int64_t n, int32_t d) {
-    return 2 * align_up(train_ws(n, d).total, 256) + linex_stream_bytes(2 * LIDF_H1);
+    return carved([&](Carver& c) { pair_ws(c, n, d); });
 }
 LIDF_API size_t lidf_decoder_pair_workspace_offset(int64_t n, int32_t d, int32_t which) {
-    return (size_t)(which ? 1 : 0) * align_up(train_ws(n, d).total, 256);
+    return which ? carved([&](Carver& c) { train_ws(c, n, d); }) : 0;   // (where PairWs.off starts)
 }
 
 LIDF_API int lidf_decoder_pair_backward_f32(const float* inp, int64_t n, int32_t d, int64_t ld_inp,
@@ -3130,16 +3114,15 @@ LIDF_API int lidf_decoder_pair_backward_f32(const float* inp, int64_t n, int32_t
     CHECK_HIP(zero_decoder_grads(grads_off, d + (off->is_ief ? 16 : 0), off->is_ief, st));
     if (n == 0) return LIDF_OK;
     if (!inp || !act_prob || !act_off || !g_prob || !g_off) return LIDF_ERR_BAD_ARG;
-    const TrainWs w = train_ws(n, d);
-    const size_t one = align_up(w.total, 256);
-    if (!workspace || workspace_bytes < lidf_decoder_pair_workspace_bytes(n, d)) return LIDF_ERR_WORKSPACE;
-    char* ws = (char*)workspace;
+    Carver c(workspace);
+    const PairWs w = pair_ws(c, n, d);
+    CHECK_CARVED(c, workspace, workspace_bytes);
     int cus;
     if ((rc = cu_count(&cus))) return rc;
     float *Sp = nullptr, *So = nullptr;
-    if ((rc = decoder_backward_core(inp, n, d, ld_inp, prob, act_prob, g_prob, grads_prob, ws, w, cus, st, &Sp))) return rc;
-    if ((rc = decoder_backward_core(inp, n, d, ld_inp, off, act_off, g_off, grads_off, ws + one, w, cus, st, &So))) return rc;
-    if (d_inp) return decoder_input_grad(Sp, prob, So, off, n, d, d_inp, ld_dinp, (float*)(ws + 2 * one), cus, st);
+    if ((rc = decoder_backward_core(inp, n, d, ld_inp, prob, act_prob, g_prob, grads_prob, w.prob, cus, st, &Sp))) return rc;
+    if ((rc = decoder_backward_core(inp, n, d, ld_inp, off, act_off, g_off, grads_off, w.off, cus, st, &So))) return rc;
+    if (d_inp) return decoder_input_grad(Sp, prob, So, off, n, d, d_inp, ld_dinp, w.stream, cus, st);
     return LIDF_OK;
 }
 
@@ -3222,9 +3205,8 @@ LIDF_API int lidf_ray_features_backward_ordered_f32(const float* d_rayfeat, cons
     const int half = roi_inp_bbox / 2;
     if (half < 1 || half > 16 || batch > 2047 || (int64_t)batch * height * width > 0x3fffffffLL)
         return LIDF_ERR_UNSUPPORTED;
-    if (n_rays > 0 && (!workspace || workspace_bytes < lidf_ray_features_backward_ordered_workspace_bytes(
-                                                           batch, height, width)))
-        return LIDF_ERR_WORKSPACE;
+    if (n_rays > 0)
+        CHECK_WS(workspace, workspace_bytes, lidf_ray_features_backward_ordered_workspace_bytes(batch, height, width));
     hipStream_t st = (hipStream_t)stream;
     CHECK_HIP(hipMemsetAsync(d_feat_grid, 0, (size_t)batch * 32 * height * width * 4, st));
     if (n_rays == 0) return LIDF_OK;
@@ -3259,30 +3241,32 @@ LIDF_API size_t lidf_query_decoder_act_floats(int64_t n_pairs, int64_t n_rays, i
 }
 
 struct QTrainWs {
-    size_t stream, dz1, dz2, dz3, S, goff, dvox, dray, wg, seg, seg_bytes, chain, small, total;
+    float *stream, *dz1, *dz2, *dz3, *S, *goff, *dvox, *dray, *wg;
+    void* seg;          // scratch of the per-voxel segment sums (NULL: none needed)
+    size_t seg_bytes;
+    char* chain;
+    float* small;       // B sums of the passes | column sums of the running sum
 };
-static QTrainWs qtrain_ws(int64_t P, int64_t R, int64_t V) {
+static QTrainWs qtrain_ws(Carver& c, int64_t P, int64_t R, int64_t V) {
     QTrainWs w;
     const size_t N = (size_t)(P > 0 ? P : 1);
-    size_t o = 0;
-    w.stream = o; o += linex_stream_bytes(256);
-    w.dz1 = o;    o += align_up(N * LIDF_H1 * 4, 256);
-    w.dz2 = o;    o += align_up(N * LIDF_H2 * 4, 256);
-    w.dz3 = o;    o += align_up(N * LIDF_H3 * 4, 256);
-    w.S = o;      o += align_up(N * LIDF_H1 * 4, 256);
-    w.goff = o;   o += align_up(N * 4, 256);
-    w.dvox = o;   o += align_up((size_t)(V > 0 ? V : 1) * LIDF_H1 * 4, 256);
-    w.dray = o;   o += align_up((size_t)(R > 0 ? R : 1) * LIDF_H1 * 4, 256);
-    w.wg = o;     o += align_up(WG_SCRATCH_FLOATS * 4, 256);
+    w.stream = (float*)c.take_bytes(linex_stream_bytes(256));
+    w.dz1 = c.take<float>(N * LIDF_H1);
+    w.dz2 = c.take<float>(N * LIDF_H2);
+    w.dz3 = c.take<float>(N * LIDF_H3);
+    w.S = c.take<float>(N * LIDF_H1);
+    w.goff = c.take<float>(N);
+    w.dvox = c.take<float>((size_t)(V > 0 ? V : 1) * LIDF_H1);
+    w.dray = c.take<float>((size_t)(R > 0 ? R : 1) * LIDF_H1);
+    w.wg = c.take<float>(WG_SCRATCH_FLOATS);
     w.seg_bytes = lidf_seg_sum_idx_ws_bytes(P, V);
-    w.seg = o;    o += align_up(w.seg_bytes, 256);
-    w.chain = o;  o += chain_stream_bytes(2 * (3 + 6 * 16));
-    w.small = o;  o += 512 * 4;   // B sums of the passes | column sums of the running sum
-    w.total = o;
+    w.seg = w.seg_bytes ? c.take_bytes(w.seg_bytes) : nullptr;
+    w.chain = (char*)c.take_bytes(chain_stream_bytes(2 * (3 + 6 * 16)));
+    w.small = c.take<float>(512);
     return w;
 }
 LIDF_API size_t lidf_query_decoder_workspace_bytes(int64_t n_pairs, int64_t n_rays, int64_t n_vox) {
-    return qtrain_ws(n_pairs, n_rays, n_vox).total;
+    return carved([&](Carver& c) { qtrain_ws(c, n_pairs, n_rays, n_vox); });
 }
 
 static int check_qtrain(const LidfQueryTrainArgs* q) {
@@ -3343,10 +3327,11 @@ LIDF_API int lidf_query_decoder_forward_train_f32(const LidfQueryTrainArgs* q, f
     const int64_t P = q->n_pairs, R = q->n_rays, V = q->n_vox;
     if (P == 0) return LIDF_OK;
     if (!out || !act) return LIDF_ERR_BAD_ARG;
-    const QTrainWs w = qtrain_ws(P, R, V);
-    if (!workspace || workspace_bytes < w.total) return LIDF_ERR_WORKSPACE;
+    Carver c(workspace);
+    const QTrainWs w = qtrain_ws(c, P, R, V);
+    CHECK_CARVED(c, workspace, workspace_bytes);
     hipStream_t st = (hipStream_t)stream;
-    float* sbuf = (float*)((char*)workspace + w.stream);
+    float* sbuf = w.stream;
     int cus;
     if ((rc = cu_count(&cus))) return rc;
     const LidfDecoder* dec = q->dec;
@@ -3357,8 +3342,7 @@ LIDF_API int lidf_query_decoder_forward_train_f32(const LidfQueryTrainArgs* q, f
     float* passes = raypart + (size_t)R * LIDF_H1;
     float* pre = passes + (size_t)npass * qact_pass(P);
     // (one stream slot serves the two layer-1 launches in turn: each is consumed before the next pack)
-    return qdec_forward_impl(q, E2, out, voxpart, raypart, passes, pre, sbuf, sbuf, (char*)workspace + w.chain,
-                             cus, st);
+    return qdec_forward_impl(q, E2, out, voxpart, raypart, passes, pre, sbuf, sbuf, w.chain, cus, st);
 }
 
 LIDF_API size_t lidf_query_forward_train_workspace_bytes(int64_t n_rays, int64_t n_vox) {
@@ -3381,20 +3365,20 @@ LIDF_API int lidf_query_forward_train_f32(const LidfQueryTrainArgs* q, const Lid
     if (P == 0) return LIDF_OK;
     if (!pair_t || !ray_dir || !out_prob || !out_off || !act_prob || !act_off || (pos_rel && !vox_center))
         return LIDF_ERR_BAD_ARG;
-    const QueryWs w = query_ws(R, V, L, Lv);
-    if (!workspace || workspace_bytes < w.total) return LIDF_ERR_WORKSPACE;
+    Carver c(workspace);
+    const QueryWs w = query_ws(c, R, V, L, Lv);
+    CHECK_CARVED(c, workspace, workspace_bytes);
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
     const QueryPlan p = query_plan(L, Lv, LIDF_PRECISION_F32);
-    if ((rc = pack_query_weights(q->dec, offset_dec, p, ws, st))) return rc;
+    if ((rc = pack_query_weights(q->dec, offset_dec, p, w.pk, st))) return rc;
     int cus;
     if ((rc = cu_count(&cus))) return rc;
     // per-voxel and per-ray parts of layer 1, both nets: [V,512], [R,512]
     CHECK_HIP(lidf_launch_l1only_pair(
-        l1_table_args(p, L1_RAY, q->rayfeat, R, nullptr, (float*)(ws + w.raypart), ws, w),
-        l1_table_args(p, L1_VOX, q->vox_feat, V, nullptr, (float*)(ws + w.voxpart), ws, w), nullptr, cus, st));
+        l1_table_args(p, L1_RAY, q->rayfeat, R, nullptr, w.raypart, w.pk),
+        l1_table_args(p, L1_VOX, q->vox_feat, V, nullptr, w.voxpart, w.pk), nullptr, cus, st));
     // (pair_pred_pos stays NULL: the differentiable tail, lidf_query_tail_f32, forms it — no offset range here)
-    PointsArgs a = points_args(p, ws, ws, w, P, q->pair_ray, q->pair_vox, pair_t, ray_dir, vox_center, pos_rel,
+    PointsArgs a = points_args(p, w.pk, w, P, q->pair_ray, q->pair_vox, pair_t, ray_dir, vox_center, pos_rel,
                                0.f, 0.f, 0.f);
     fill_net_args(a, 0, q->dec, out_prob, 0);
     fill_net_args(a, 1, offset_dec, out_off, 1);
@@ -3442,18 +3426,18 @@ LIDF_API int lidf_query_forward_train_selected_f32(const LidfQueryTrainArgs* q, 
     if (!pair_t || !ray_dir || !out_prob || !softmax || !pred_offset || !pair_pred_pos || !act_prob || !act_off_rows ||
         (pos_rel && !vox_center))
         return LIDF_ERR_BAD_ARG;
-    const QueryWs w = query_ws(R, V, L, Lv);
-    if (!workspace || workspace_bytes < w.total) return LIDF_ERR_WORKSPACE;
-    char* ws = (char*)workspace;
+    Carver c(workspace);
+    const QueryWs w = query_ws(c, R, V, L, Lv);
+    CHECK_CARVED(c, workspace, workspace_bytes);
     const QueryPlan p = query_plan(L, Lv, LIDF_PRECISION_F32);
-    if ((rc = pack_query_weights(q->dec, offset_dec, p, ws, st))) return rc;
+    if ((rc = pack_query_weights(q->dec, offset_dec, p, w.pk, st))) return rc;
     int cus;
     if ((rc = cu_count(&cus))) return rc;
     // per-voxel and per-ray parts of layer 1, both nets: [V,512], [R,512]
     CHECK_HIP(lidf_launch_l1only_pair(
-        l1_table_args(p, L1_RAY, q->rayfeat, R, nullptr, (float*)(ws + w.raypart), ws, w),
-        l1_table_args(p, L1_VOX, q->vox_feat, V, nullptr, (float*)(ws + w.voxpart), ws, w), nullptr, cus, st));
-    PointsArgs a = points_args(p, ws, ws, w, P, q->pair_ray, q->pair_vox, pair_t, ray_dir, vox_center, pos_rel,
+        l1_table_args(p, L1_RAY, q->rayfeat, R, nullptr, w.raypart, w.pk),
+        l1_table_args(p, L1_VOX, q->vox_feat, V, nullptr, w.voxpart, w.pk), nullptr, cus, st));
+    PointsArgs a = points_args(p, w.pk, w, P, q->pair_ray, q->pair_vox, pair_t, ray_dir, vox_center, pos_rel,
                                offset_range0, offset_range1, part_size);
     a.nets = 1; a.part_ld = 512; a.part_off = 0;
     fill_net_args(a, 0, q->dec, out_prob, 0);
@@ -3462,7 +3446,7 @@ LIDF_API int lidf_query_forward_train_selected_f32(const LidfQueryTrainArgs* q, 
     a.tr_pass_floats = (long long)qact_pass(P);
     const long long nt = (P + 127) / 128;
     CHECK_HIP(lidf_launch_points(LIDF_MODE_FUSED, a, (int)(nt < cus ? nt : cus), st));
-    const SelList sl = sel_list(ws + w.sel, R);
+    const SelList sl = sel_list(w.sel, R);
     const bool given = max_pair_id_in != nullptr;
     CHECK_HIP(lidf_launch_ray_reduce_dev(out_prob, nullptr, q->pair_off, R, P, nullptr, nullptr, nullptr, nullptr, 0,
                                          softmax, (long long*)max_pair_id, nullptr, nullptr, st, q->pair_vox, pair_t,
@@ -3508,23 +3492,16 @@ struct QdecBwd {
 };
 static int qdec_backward_impl(const LidfQueryTrainArgs* q, const QdecBwd& o, const float* passes, const float* pre,
                               const float* g_out, float* d_vox_feat, float* d_rayfeat, int accumulate_inputs,
-                              const LidfDecoderGrads* grads, char* ws, const QTrainWs& w, int cus, hipStream_t st) {
+                              const LidfDecoderGrads* grads, const QTrainWs& w, int cus, hipStream_t st) {
     int rc;
     const LidfDecoder* dec = q->dec;
     const int64_t P = q->n_pairs, R = q->n_rays, V = q->n_vox;
     const int E2 = o.E2, Ed = 3 + 6 * q->multires_views;
     const int D = 256 + E2 + Ed, ld1 = D + (dec->is_ief ? 16 : 0);
     const int npass = dec->is_ief ? dec->n_iter : 1;
-    float* sbuf = (float*)(ws + w.stream);
-    float* dz1 = (float*)(ws + w.dz1);
-    float* dz2 = (float*)(ws + w.dz2);
-    float* dz3 = (float*)(ws + w.dz3);
-    float* S = o.S_keep ? o.S_keep : (float*)(ws + w.S);
-    float* goff = (float*)(ws + w.goff);
-    float* wgs = (float*)(ws + w.wg);
-    float* dvox = (float*)(ws + w.dvox);
-    float* dray = (float*)(ws + w.dray);
-    float* small = (float*)(ws + w.small);
+    float *sbuf = w.stream, *dz1 = w.dz1, *dz2 = w.dz2, *dz3 = w.dz3, *goff = w.goff, *wgs = w.wg, *dvox = w.dvox,
+          *dray = w.dray, *small = w.small;
+    float* S = o.S_keep ? o.S_keep : w.S;
     CHECK_HIP(hipMemsetAsync(small, 0, 512 * 4, st));
     if (!o.goff_ready) CHECK_HIP(lidf_launch_out_act(pre, P, dec->use_sigmoid, nullptr, g_out, goff, st));
     // W3^T | W2^T of the chained input-gradient launches: the same stream for every pass
@@ -3580,8 +3557,7 @@ static int qdec_backward_impl(const LidfQueryTrainArgs* q, const QdecBwd& o, con
         CHECK_HIP(lidf_launch_pnet_gather_segsum(S, o.ss_perm, o.ss_row0, o.ss_vstart, o.ss_first, V, o.ss_n,
                                                  o.ss_partial, dvox, st));
     else
-        CHECK_HIP(lidf_launch_seg_sum_idx(S, q->pair_vox, P, V, dvox, w.seg_bytes ? ws + w.seg : nullptr,
-                                          w.seg_bytes, st));
+        CHECK_HIP(lidf_launch_seg_sum_idx(S, q->pair_vox, P, V, dvox, w.seg, w.seg_bytes, st));
     // voxel part: voxpart[v] = W1[:, 0:128] vox_feat[v] + b1 (+ c)
     CHECK_HIP(lidf_launch_wgrad(dvox, LIDF_H1, LIDF_H1, q->vox_feat, 128, 128, V, grads->w1, ld1, grads->b1, wgs, WG_SCRATCH_FLOATS, st));
     if (!o.S_keep) {
@@ -3634,8 +3610,9 @@ LIDF_API int lidf_query_decoder_backward_f32(const LidfQueryTrainArgs* q, const 
     }
     if (P == 0) return LIDF_OK;
     if (!act || !g_out) return LIDF_ERR_BAD_ARG;
-    const QTrainWs w = qtrain_ws(P, R, V);
-    if (!workspace || workspace_bytes < w.total) return LIDF_ERR_WORKSPACE;
+    Carver c(workspace);
+    const QTrainWs w = qtrain_ws(c, P, R, V);
+    CHECK_CARVED(c, workspace, workspace_bytes);
     int cus;
     if ((rc = cu_count(&cus))) return rc;
     const float* voxpart = act;
@@ -3644,32 +3621,32 @@ LIDF_API int lidf_query_decoder_backward_f32(const LidfQueryTrainArgs* q, const 
     const float* pre = passes + (size_t)npass * qact_pass(P);
     QdecBwd o = {};
     o.E2 = E2; o.zero_grads = true;
-    return qdec_backward_impl(q, o, passes, pre, g_out, d_vox_feat, d_rayfeat, accumulate_inputs, grads,
-                              (char*)workspace, w, cus, st);
+    return qdec_backward_impl(q, o, passes, pre, g_out, d_vox_feat, d_rayfeat, accumulate_inputs, grads, w, cus, st);
 }
 
 // The decoder's backward from ONE pair per ray (the offset decoder under the reference's losses): see
 // lidf_gather_sel_rows_kernel. The compacted problem — R pairs, pair r on ray r — goes through the same launches
 // as the dense one.
-struct QRowsWs { size_t pvox, poff, g, pe, act, inner, total; QTrainWs w; };
-static QRowsWs qrows_ws(int64_t R, int64_t V, int E2, int npass) {
+struct QRowsWs {
+    int *pvox, *poff;
+    float *g, *pe, *act;
+    QTrainWs w;   // the compacted problem's decoder workspace
+};
+static QRowsWs qrows_ws(Carver& c, int64_t R, int64_t V, int E2, int npass) {
     QRowsWs l;
     const size_t N = (size_t)(R > 0 ? R : 1);
-    size_t o = 0;
-    l.pvox = o;  o += align_up(N * 4, 256);
-    l.poff = o;  o += align_up((N + 1) * 4, 256);
-    l.g = o;     o += align_up(N * 4, 256);
-    l.pe = o;    o += align_up(N * (size_t)E2 * 4, 256);
-    l.act = o;   o += align_up(((size_t)npass * qact_pass((int64_t)N) + N) * 4, 256);
-    l.w = qtrain_ws(R, R, V);
-    l.inner = o; o += l.w.total;
-    l.total = o;
+    l.pvox = c.take<int>(N);
+    l.poff = c.take<int>(N + 1);
+    l.g = c.take<float>(N);
+    l.pe = c.take<float>(N * (size_t)E2);
+    l.act = c.take<float>((size_t)npass * qact_pass((int64_t)N) + N);
+    l.w = qtrain_ws(c, R, R, V);
     return l;
 }
 LIDF_API size_t lidf_query_decoder_rows_workspace_bytes(int64_t n_rays, int64_t n_vox, int32_t multires,
                                                           int32_t n_pass) {
     if (n_rays < 0 || n_vox < 0 || multires < 0 || multires > 16 || n_pass <= 0) return 0;
-    return qrows_ws(n_rays, n_vox, 2 * (3 + 6 * multires), n_pass).total;
+    return carved([&](Carver& c) { qrows_ws(c, n_rays, n_vox, 2 * (3 + 6 * multires), n_pass); });
 }
 LIDF_API int lidf_query_decoder_backward_rows_f32(const LidfQueryTrainArgs* q, const float* act, int32_t act_is_rows,
                                                     const int64_t* rows, const float* g_pred_pos,
@@ -3697,28 +3674,26 @@ LIDF_API int lidf_query_decoder_backward_rows_f32(const LidfQueryTrainArgs* q, c
     }
     if (P == 0 || R == 0) return LIDF_OK;
     if (!act || !rows || !ray_dir) return LIDF_ERR_BAD_ARG;
-    const QRowsWs l = qrows_ws(R, V, E2, npass);
-    if (!workspace || workspace_bytes < l.total) return LIDF_ERR_WORKSPACE;
+    Carver c(workspace);
+    const QRowsWs l = qrows_ws(c, R, V, E2, npass);
+    CHECK_CARVED(c, workspace, workspace_bytes);
     int cus;
     if ((rc = cu_count(&cus))) return rc;
-    char* ws = (char*)workspace;
-    int* pvox = (int*)(ws + l.pvox);
-    int* poff = (int*)(ws + l.poff);
-    float* g = (float*)(ws + l.g);
-    float* pe = (float*)(ws + l.pe);
+    int *pvox = l.pvox, *poff = l.poff;
+    float *g = l.g, *pe = l.pe;
     const float* passes_src = act + (size_t)(V + R) * LIDF_H1;   // behind voxpart | raypart (lidf_query_decoder_act_floats)
     // (act_is_rows: the activations are the list's own — lidf_query_forward_train_selected_f32 — and stay where they are)
-    const float* passes = act_is_rows ? passes_src : (const float*)(ws + l.act);
+    const float* passes = act_is_rows ? passes_src : l.act;
     CHECK_HIP(lidf_launch_gather_sel_rows(act_is_rows ? nullptr : passes_src, P, npass, (const long long*)rows, R,
                                           q->pair_vox, q->pe, E2, g_pred_pos, g_offset_rows, ray_dir, scale,
-                                          (float*)(ws + l.act), pvox, pe, g, poff, st));
+                                          l.act, pvox, pe, g, poff, st));
     LidfQueryTrainArgs qc = *q;
     qc.n_pairs = R;
     qc.pair_off = poff; qc.pair_ray = poff; qc.pair_vox = pvox; qc.pe = pe;   // (pair r on ray r: pair_ray = 0..R-1 = poff)
     QdecBwd o = {};
     o.E2 = E2; o.zero_grads = true;
     return qdec_backward_impl(&qc, o, passes, passes + (size_t)npass * qact_pass(R), g, d_vox_feat, d_rayfeat,
-                              accumulate_inputs, grads, ws + l.inner, l.w, cus, st);
+                              accumulate_inputs, grads, l.w, cus, st);
 }
 
 // ---- per-pair / per-ray tail of get_pred, forward and adjoint -------------------------------------
@@ -3776,49 +3751,46 @@ LIDF_API int lidf_embed_backward_f32(const float* x, const float* g_out, int64_t
 }
 
 // ---- PointNet2Stage, training path ----------------------------------------------------------------
-struct PnetAct {   // offsets in floats into the caller's `act`
-    size_t f1, f2, f4, f5, pool1, g1, pool2, out, arg1, arg2, total;
+// What the layer-by-layer forward keeps in the caller's `act`. Its size is exported in floats, unpadded: carved at
+// alignment 4 (a Carver(act, 4), or c.here(4) inside a larger layout).
+struct PnetAct {
+    float *f1, *f2, *f4, *f5, *pool1, *g1, *pool2, *out;
+    int *arg1, *arg2;
 };
-static PnetAct pnet_act(int64_t n, int64_t v) {
+static PnetAct pnet_act(Carver& c, int64_t n, int64_t v) {
     PnetAct a;
     const size_t N = (size_t)(n > 0 ? n : 1), V = (size_t)(v > 0 ? v : 1);
-    size_t o = 0;
-    a.f1 = o; o += N * 32;
-    a.f2 = o; o += N * 64;
-    a.f4 = o; o += N * 128;
-    a.f5 = o; o += N * 128;
-    a.pool1 = o; o += V * 64;
-    a.g1 = o; o += V * 64;
-    a.pool2 = o; o += V * 128;
-    a.out = o; o += V * 128;
-    a.arg1 = o; o += V * 64;    // int32
-    a.arg2 = o; o += V * 128;   // int32
-    a.total = o;
+    a.f1 = c.take<float>(N * 32);
+    a.f2 = c.take<float>(N * 64);
+    a.f4 = c.take<float>(N * 128);
+    a.f5 = c.take<float>(N * 128);
+    a.pool1 = c.take<float>(V * 64);
+    a.g1 = c.take<float>(V * 64);
+    a.pool2 = c.take<float>(V * 128);
+    a.out = c.take<float>(V * 128);
+    a.arg1 = c.take<int>(V * 64);
+    a.arg2 = c.take<int>(V * 128);
     return a;
 }
 struct PnetTrainWs {
-    size_t s[7], gpart, stream, dz_out, dp2, dz5, dz4, s4, dg1, df2, dp1, dz1, wg, total;
+    float *s[7], *gpart, *stream, *dz_out, *dp2, *dz5, *dz4, *s4, *dg1, *df2, *dp1, *dz1, *wg;
 };
-static PnetTrainWs pnet_train_ws(int64_t n, int64_t v) {
+static PnetTrainWs pnet_train_ws(Carver& c, int64_t n, int64_t v) {
     PnetTrainWs w;
     const size_t N = (size_t)(n > 0 ? n : 1), V = (size_t)(v > 0 ? v : 1);
-    size_t o = 0;
-    const int ks[7] = {6, 32, 64, 64, 64, 128, 128};
-    const int nts[7] = {1, 2, 2, 4, 4, 4, 4};
-    for (int i = 0; i < 7; ++i) { w.s[i] = o; o += lin_stream_bytes(ks[i], nts[i]); }
-    w.gpart = o;  o += align_up(V * 128 * 4, 256);
-    w.stream = o; o += linex_stream_bytes(256);
-    w.dz_out = o; o += align_up(V * 128 * 4, 256);
-    w.dp2 = o;    o += align_up(V * 128 * 4, 256);
-    w.dz5 = o;    o += align_up(N * 128 * 4, 256);
-    w.dz4 = o;    o += align_up(N * 128 * 4, 256);
-    w.s4 = o;     o += align_up(V * 128 * 4, 256);
-    w.dg1 = o;    o += align_up(V * 64 * 4, 256);
-    w.df2 = o;    o += align_up(N * 64 * 4, 256);
-    w.dp1 = o;    o += align_up(V * 64 * 4, 256);
-    w.dz1 = o;    o += align_up(N * 32 * 4, 256);
-    w.wg = o;     o += align_up(WG_SCRATCH_FLOATS * 4, 256);
-    w.total = o;
+    pnet_streams(c, w.s);
+    w.gpart = c.take<float>(V * 128);
+    w.stream = (float*)c.take_bytes(linex_stream_bytes(256));
+    w.dz_out = c.take<float>(V * 128);
+    w.dp2 = c.take<float>(V * 128);
+    w.dz5 = c.take<float>(N * 128);
+    w.dz4 = c.take<float>(N * 128);
+    w.s4 = c.take<float>(V * 128);
+    w.dg1 = c.take<float>(V * 64);
+    w.df2 = c.take<float>(N * 64);
+    w.dp1 = c.take<float>(V * 64);
+    w.dz1 = c.take<float>(N * 32);
+    w.wg = c.take<float>(WG_SCRATCH_FLOATS);
     return w;
 }
 
@@ -3828,24 +3800,22 @@ static PnetTrainWs pnet_train_ws(int64_t n, int64_t v) {
 // forward with the rows kept: layer by layer through lidf_linear_kernel (mode 0: pack and run, 2: streams packed
 // earlier), then the arg row of every pooled entry
 static int pointnet_train_forward_impl(const LidfPointNet* w, const float* inp, const int32_t* vox, int64_t n,
-                                       int64_t n_vox, float* out, float* act, float* gpart,
+                                       int64_t n_vox, float* out, const PnetAct& a, float* gpart,
                                        float* const streams[7], int cus, hipStream_t st, int mode) {
     int rc;
-    const PnetAct a = pnet_act(n, n_vox);
     PnetBufs b = {};
-    b.f1 = act + a.f1; b.f2 = act + a.f2; b.f4 = act + a.f4; b.f5 = act + a.f5;
-    b.pool1 = act + a.pool1; b.g1 = act + a.g1; b.pool2 = act + a.pool2;
+    b.f1 = a.f1; b.f2 = a.f2; b.f4 = a.f4; b.f5 = a.f5;
+    b.pool1 = a.pool1; b.g1 = a.g1; b.pool2 = a.pool2;
     b.gpart = gpart;
     for (int i = 0; i < 7; ++i) b.streams[i] = streams[i];
     if ((rc = pointnet_impl(w, inp, vox, n, n_vox, out, b, cus, st, mode))) return rc;
     if (mode == 1) return LIDF_OK;
-    if (out != act + a.out)
-        CHECK_HIP(hipMemcpyAsync(act + a.out, out, (size_t)n_vox * 128 * 4, hipMemcpyDeviceToDevice, st));
+    if (out != a.out) CHECK_HIP(hipMemcpyAsync(a.out, out, (size_t)n_vox * 128 * 4, hipMemcpyDeviceToDevice, st));
     // arg of every pooled entry: the lowest row attaining the maximum
-    CHECK_HIP(hipMemsetAsync(act + a.arg1, 0x7f, (size_t)n_vox * 64 * 4, st));
-    CHECK_HIP(hipMemsetAsync(act + a.arg2, 0x7f, (size_t)n_vox * 128 * 4, st));
-    CHECK_HIP(lidf_launch_segmax_arg(b.f2, vox, b.pool1, n, 64, (int*)(act + a.arg1), st));
-    CHECK_HIP(lidf_launch_segmax_arg(b.f5, vox, b.pool2, n, 128, (int*)(act + a.arg2), st));
+    CHECK_HIP(hipMemsetAsync(a.arg1, 0x7f, (size_t)n_vox * 64 * 4, st));
+    CHECK_HIP(hipMemsetAsync(a.arg2, 0x7f, (size_t)n_vox * 128 * 4, st));
+    CHECK_HIP(lidf_launch_segmax_arg(b.f2, vox, b.pool1, n, 64, a.arg1, st));
+    CHECK_HIP(lidf_launch_segmax_arg(b.f5, vox, b.pool2, n, 128, a.arg2, st));
     return LIDF_OK;
 }
 
@@ -3858,14 +3828,12 @@ static int pointnet_forward_train_layers(const LidfPointNet* w, const float* inp
     if (!out || !act || (n > 0 && (!inp || !vox))) return LIDF_ERR_BAD_ARG;
     int rc;
     if ((rc = check_pointnet_w(w))) return rc;
-    const PnetTrainWs ws = pnet_train_ws(n, n_vox);
-    if (!workspace || workspace_bytes < ws.total) return LIDF_ERR_WORKSPACE;
-    char* base = (char*)workspace;
-    float* streams[7];
-    for (int i = 0; i < 7; ++i) streams[i] = (float*)(base + ws.s[i]);
+    Carver c(workspace), ca(act, 4);
+    const PnetTrainWs ws = pnet_train_ws(c, n, n_vox);
+    CHECK_CARVED(c, workspace, workspace_bytes);
     int cus;
     if ((rc = cu_count(&cus))) return rc;
-    return pointnet_train_forward_impl(w, inp, vox, n, n_vox, out, act, (float*)(base + ws.gpart), streams, cus,
+    return pointnet_train_forward_impl(w, inp, vox, n, n_vox, out, pnet_act(ca, n, n_vox), ws.gpart, ws.s, cus,
                                        (hipStream_t)stream, 0);
 }
 
@@ -3873,8 +3841,8 @@ static int pointnet_forward_train_layers(const LidfPointNet* w, const float* inp
 // them in turn), pack_mode of those launches (0 pack and run, 1 pack only, 2 packed earlier); zero_grads false:
 // the parameter gradients are accumulated into.
 static int pointnet_backward_impl(const LidfPointNet* w, const float* inp, const int32_t* vox, int64_t n,
-                                  int64_t n_vox, const float* act, const float* g_out, float* d_inp,
-                                  const LidfPointNetGrads* g, char* base, const PnetTrainWs& ws, bool zero_grads,
+                                  int64_t n_vox, const PnetAct& a, const float* g_out, float* d_inp,
+                                  const LidfPointNetGrads* g, const PnetTrainWs& ws, bool zero_grads,
                                   float* const* slots, int pack_mode, int cus, hipStream_t st) {
     int rc;
     const bool po = pack_mode == 1;
@@ -3886,21 +3854,11 @@ static int pointnet_backward_impl(const LidfPointNet* w, const float* inp, const
     }
     if (d_inp && n > 0 && !po) CHECK_HIP(hipMemsetAsync(d_inp, 0, (size_t)n * 6 * 4, st));
     if (n_vox == 0 && !po) return LIDF_OK;
-    const PnetAct a = pnet_act(n, n_vox);
-    float* sbuf = (float*)(base + ws.stream);
-    float* dz_out = (float*)(base + ws.dz_out);
-    float* dp2 = (float*)(base + ws.dp2);
-    float* dz5 = (float*)(base + ws.dz5);
-    float* dz4 = (float*)(base + ws.dz4);
-    float* s4 = (float*)(base + ws.s4);
-    float* dg1 = (float*)(base + ws.dg1);
-    float* df2 = (float*)(base + ws.df2);
-    float* dp1 = (float*)(base + ws.dp1);
-    float* dz1 = (float*)(base + ws.dz1);
-    float* wgs = (float*)(base + ws.wg);
-    const float *f1 = act + a.f1, *f2 = act + a.f2, *f4 = act + a.f4;
-    const float *pool1 = act + a.pool1, *g1 = act + a.g1, *pool2 = act + a.pool2, *outv = act + a.out;
-    const int *arg1 = (const int*)(act + a.arg1), *arg2 = (const int*)(act + a.arg2);
+    float *sbuf = ws.stream, *dz_out = ws.dz_out, *dp2 = ws.dp2, *dz5 = ws.dz5, *dz4 = ws.dz4, *s4 = ws.s4,
+          *dg1 = ws.dg1, *df2 = ws.df2, *dp1 = ws.dp1, *dz1 = ws.dz1, *wgs = ws.wg;
+    const float *f1 = a.f1, *f2 = a.f2, *f4 = a.f4;
+    const float *pool1 = a.pool1, *g1 = a.g1, *pool2 = a.pool2, *outv = a.out;
+    const int *arg1 = a.arg1, *arg2 = a.arg2;
     const int64_t V = n_vox;
     int slot = 0;
     auto lin = [&](const LinEx& L) { float* sp = slots ? slots[slot] : sbuf; ++slot; return run_linex(L, sp, cus, st, pack_mode); };
@@ -3973,12 +3931,13 @@ static int pointnet_backward_layers(const LidfPointNet* w, const float* inp, con
         return LIDF_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     if (n_vox > 0 && (!act || !g_out || (n > 0 && (!inp || !vox)))) return LIDF_ERR_BAD_ARG;
-    const PnetTrainWs ws = pnet_train_ws(n, n_vox);
-    if (n_vox > 0 && (!workspace || workspace_bytes < ws.total)) return LIDF_ERR_WORKSPACE;
+    Carver c(workspace), ca(act, 4);
+    const PnetTrainWs ws = pnet_train_ws(c, n, n_vox);
+    if (n_vox > 0) CHECK_CARVED(c, workspace, workspace_bytes);
     int cus;
     if ((rc = cu_count(&cus))) return rc;
-    return pointnet_backward_impl(w, inp, vox, n, n_vox, act, g_out, d_inp, g, (char*)workspace, ws, true, nullptr,
-                                  0, cus, st);
+    return pointnet_backward_impl(w, inp, vox, n, n_vox, pnet_act(ca, n, n_vox), g_out, d_inp, g, ws, true, nullptr, 0,
+                                  cus, st);
 }
 
 // ---- Stage-1 training step: labels and loss (lidf_loss.hip) -------------------------------------
@@ -4044,7 +4003,7 @@ LIDF_API int lidf_stage1_loss_f32(const LidfLossArgs* args, lidf_stream_t stream
     if (k.R == 0) return LIDF_OK;
     if (!k.loss || !k.pos_un || !k.surf_dist || !k.dx_dist || !k.dy_dist || !k.ray_lse || (k.P > 0 && !k.prob_un))
         return LIDF_ERR_BAD_ARG;
-    if (!args->workspace || args->workspace_bytes < lidf_stage1_loss_workspace_bytes(k.R)) return LIDF_ERR_WORKSPACE;
+    CHECK_WS(args->workspace, args->workspace_bytes, lidf_stage1_loss_workspace_bytes(k.R));
     CHECK_HIP(lidf_launch_stage1_loss(k, args->gt_surf_norm_img, args->pred_surf_norm_img, (hipStream_t)stream));
     return LIDF_OK;
 }
@@ -4092,7 +4051,7 @@ LIDF_API int lidf_refine_loss_f32(const LidfRefineLossArgs* args, lidf_stream_t 
     if (rc) return rc;
     if (k.R == 0) return LIDF_OK;
     if (!k.loss || !k.pos_un || !k.surf_dist || !k.dx_dist || !k.dy_dist) return LIDF_ERR_BAD_ARG;
-    if (!args->workspace || args->workspace_bytes < lidf_refine_loss_workspace_bytes(k.R)) return LIDF_ERR_WORKSPACE;
+    CHECK_WS(args->workspace, args->workspace_bytes, lidf_refine_loss_workspace_bytes(k.R));
     CHECK_HIP(lidf_launch_refine_loss(k, args->pred_surf_norm_img, (hipStream_t)stream));
     return LIDF_OK;
 }
@@ -4128,7 +4087,7 @@ static int select_check(const SelectJob* jobs, int n_jobs, double ratio, const v
         n_max = j.n > n_max ? j.n : n_max;
     }
     if ((uintptr_t)workspace & 7) return LIDF_ERR_BAD_ARG;
-    if (!workspace || workspace_bytes < lidf_select_workspace_bytes(n_jobs, n_max)) return LIDF_ERR_WORKSPACE;
+    CHECK_WS(workspace, workspace_bytes, lidf_select_workspace_bytes(n_jobs, n_max));
     return LIDF_OK;
 }
 
@@ -4198,11 +4157,22 @@ LIDF_API int lidf_refine_hard_neg_f32(const LidfRefineLossArgs* args, double rat
 // images of the bs == 1 branch.
 static const int EVAL_DST_H = 144, EVAL_DST_W = 256;   // cv2.resize(..., (256, 144)), models/pipeline.py:582
 
+// (both eval-loss workspaces are packed: their carver runs at alignment 1, the slot sizes keep 8-byte alignment)
+struct EvalLossWs { double* partial; void* mws; float *mout, *pred_img, *gt_img; };
+static EvalLossWs eval_loss_ws(Carver& c, int64_t n_rays, int64_t resize_pixels) {
+    EvalLossWs w = {};
+    w.partial = (double*)c.take_bytes(lidf_eval_loss_partial_bytes(n_rays));
+    if (resize_pixels <= 0) return w;
+    w.mws = c.take_bytes(lidf_depth_metrics_ws_bytes());
+    w.mout = c.take<float>(16);
+    w.pred_img = c.take<float>((size_t)resize_pixels);
+    w.gt_img = c.take<float>((size_t)resize_pixels);
+    return w;
+}
 static size_t eval_loss_ws_bytes(int64_t n_rays, int64_t resize_pixels) {
-    if (n_rays <= 0) return 0;
-    size_t n = lidf_eval_loss_partial_bytes(n_rays);
-    if (resize_pixels > 0) n += lidf_depth_metrics_ws_bytes() + 64 + 2 * (size_t)resize_pixels * sizeof(float);
-    return n;
+    Carver c(nullptr, 1);
+    if (n_rays > 0) eval_loss_ws(c, n_rays, resize_pixels);
+    return c.used();
 }
 LIDF_API size_t lidf_stage1_eval_loss_workspace_bytes(int64_t n_rays, int64_t resize_pixels) {
     return eval_loss_ws_bytes(n_rays, resize_pixels);
@@ -4255,19 +4225,16 @@ static int eval_loss_run(const LidfEvalLossArgs* args, bool pairs, hipStream_t s
     if ((k.surf_dist || k.dx_dist || k.dy_dist) && !(k.surf_dist && k.dx_dist && k.dy_dist)) return LIDF_ERR_BAD_ARG;
     const long long rpix = args->resize_metrics ? k.hw : 0;
     if ((uintptr_t)args->workspace & 7) return LIDF_ERR_BAD_ARG;
-    if (!args->workspace || args->workspace_bytes < eval_loss_ws_bytes(k.R, rpix)) return LIDF_ERR_WORKSPACE;
-    char* ws = (char*)args->workspace;
-    k.partial = (double*)ws;
+    Carver c(args->workspace, 1);
+    const EvalLossWs w = eval_loss_ws(c, k.R, rpix);
+    CHECK_CARVED(c, args->workspace, args->workspace_bytes);
+    k.partial = w.partial;
     if (rpix > 0) {
-        char* mws = ws + lidf_eval_loss_partial_bytes(k.R);
-        float* mout = (float*)(mws + lidf_depth_metrics_ws_bytes());
-        float* pred_img = mout + 16;
-        float* gt_img = pred_img + rpix;
-        CHECK_HIP(hipMemsetAsync(mws, 0, lidf_depth_metrics_ws_bytes(), st));
-        CHECK_HIP(lidf_launch_eval_depth_images(k, args->xyz_gt, pred_img, gt_img, st));
-        CHECK_HIP(lidf_launch_depth_metrics(pred_img, gt_img, args->seg_mask, args->seg_mask ? args->seg_dtype : 0,
-                                            k.H, k.W, EVAL_DST_H, EVAL_DST_W, mout, mws, st));
-        k.metrics = mout;
+        CHECK_HIP(hipMemsetAsync(w.mws, 0, lidf_depth_metrics_ws_bytes(), st));
+        CHECK_HIP(lidf_launch_eval_depth_images(k, args->xyz_gt, w.pred_img, w.gt_img, st));
+        CHECK_HIP(lidf_launch_depth_metrics(w.pred_img, w.gt_img, args->seg_mask, args->seg_mask ? args->seg_dtype : 0,
+                                            k.H, k.W, EVAL_DST_H, EVAL_DST_W, w.mout, w.mws, st));
+        k.metrics = w.mout;
     }
     CHECK_HIP(lidf_launch_eval_loss(k, pairs ? 1 : 0, st));
     return LIDF_OK;
@@ -4286,12 +4253,19 @@ LIDF_API int lidf_refine_eval_loss_f32(const LidfEvalLossArgs* args, lidf_stream
 // outputs [B, 10] (padded to 64 bytes) | the two depth images [B, hw].
 static size_t eval_frames_mout_bytes(int64_t batch) { return ((size_t)batch * 10 * sizeof(float) + 63) & ~(size_t)63; }
 
+static EvalLossWs eval_loss_frames_ws(Carver& c, int32_t batch, long long hw, bool pairs) {
+    EvalLossWs w;
+    w.partial = (double*)c.take_bytes(lidf_eval_loss_frames_partial_bytes(batch, hw, pairs ? 1 : 0));
+    w.mws = c.take_bytes(lidf_depth_metrics_frames_workspace_bytes(batch));
+    w.mout = (float*)c.take_bytes(eval_frames_mout_bytes(batch));
+    w.pred_img = c.take<float>((size_t)batch * hw);
+    w.gt_img = c.take<float>((size_t)batch * hw);
+    return w;
+}
 static size_t eval_loss_frames_ws_bytes(int32_t batch, int32_t height, int32_t width, bool pairs) {
-    if (batch <= 0 || height <= 0 || width <= 0) return 0;
-    const long long hw = (long long)height * width;
-    return lidf_eval_loss_frames_partial_bytes(batch, hw, pairs ? 1 : 0) +
-           lidf_depth_metrics_frames_workspace_bytes(batch) + eval_frames_mout_bytes(batch) +
-           2 * (size_t)batch * hw * sizeof(float);
+    Carver c(nullptr, 1);
+    if (batch > 0 && height > 0 && width > 0) eval_loss_frames_ws(c, batch, (long long)height * width, pairs);
+    return c.used();
 }
 LIDF_API size_t lidf_stage1_eval_loss_frames_workspace_bytes(int32_t batch, int32_t height, int32_t width) {
     return eval_loss_frames_ws_bytes(batch, height, width, true);
@@ -4316,19 +4290,16 @@ static int eval_loss_frames_run(const LidfEvalLossArgs* args, bool pairs, hipStr
         return LIDF_OK;
     }
     if ((uintptr_t)args->workspace & 7) return LIDF_ERR_BAD_ARG;
-    if (!args->workspace || args->workspace_bytes < eval_loss_frames_ws_bytes(k.B, k.H, k.W, pairs))
-        return LIDF_ERR_WORKSPACE;
-    char* ws = (char*)args->workspace;
-    k.partial = (double*)ws;
-    char* mws = ws + lidf_eval_loss_frames_partial_bytes(k.B, k.hw, pairs ? 1 : 0);
-    float* mout = (float*)(mws + lidf_depth_metrics_frames_workspace_bytes(k.B));
-    float* pred_img = (float*)((char*)mout + eval_frames_mout_bytes(k.B));
-    float* gt_img = pred_img + (size_t)k.B * k.hw;
-    CHECK_HIP(hipMemsetAsync(mws, 0, lidf_depth_metrics_frames_workspace_bytes(k.B), st));
-    CHECK_HIP(lidf_launch_eval_depth_images_frames(k, args->xyz_gt, pred_img, gt_img, st));
-    CHECK_HIP(lidf_launch_depth_metrics_frames(pred_img, gt_img, args->seg_mask, args->seg_mask ? args->seg_dtype : 0,
-                                               k.B, k.H, k.W, EVAL_DST_H, EVAL_DST_W, mout, mws, st));
-    k.metrics = mout;
+    Carver c(args->workspace, 1);
+    const EvalLossWs w = eval_loss_frames_ws(c, k.B, k.hw, pairs);
+    CHECK_CARVED(c, args->workspace, args->workspace_bytes);
+    k.partial = w.partial;
+    CHECK_HIP(hipMemsetAsync(w.mws, 0, lidf_depth_metrics_frames_workspace_bytes(k.B), st));
+    CHECK_HIP(lidf_launch_eval_depth_images_frames(k, args->xyz_gt, w.pred_img, w.gt_img, st));
+    CHECK_HIP(lidf_launch_depth_metrics_frames(w.pred_img, w.gt_img, args->seg_mask,
+                                               args->seg_mask ? args->seg_dtype : 0, k.B, k.H, k.W, EVAL_DST_H,
+                                               EVAL_DST_W, w.mout, w.mws, st));
+    k.metrics = w.mout;
     CHECK_HIP(lidf_launch_eval_loss_frames(k, pairs ? 1 : 0, st));
     return LIDF_OK;
 }

@@ -16,52 +16,57 @@ static bool pnetc_ok(int64_t n, int64_t V) {
            lidf_sort_idx_ws_bytes(n, V) > 0;
 }
 
-struct PnetActC {   // byte offsets into the block the forward keeps for the backward (sorted-order rows)
-    size_t inps, voxs, f1s, f2s, f4s, pool1, arg1, g1, pool2, arg2, out, vstart, first, sort, total;
+struct PnetActC {   // the block the forward keeps for the backward (sorted-order rows)
+    float* inps;
+    int* voxs;
+    float *f1s, *f2s, *f4s, *pool1;
+    int* arg1;
+    float *g1, *pool2;
+    int* arg2;
+    float* out;
+    int *vstart, *first;
+    char* sort;
 };
-static PnetActC pnetc_act(int64_t n, int64_t v) {
+static PnetActC pnetc_act(Carver& c, int64_t n, int64_t v) {
     PnetActC a;
     const size_t N = (size_t)(n > 0 ? n : 1), V = (size_t)(v > 0 ? v : 1);
-    size_t o = 0;
-    a.inps = o;   o += align_up(N * 24, 256);
-    a.voxs = o;   o += align_up(N * 4, 256);
-    a.f1s = o;    o += align_up(N * 32 * 4, 256);
-    a.f2s = o;    o += align_up(N * 64 * 4, 256);
-    a.f4s = o;    o += align_up(N * 128 * 4, 256);
-    a.pool1 = o;  o += align_up(V * 64 * 4, 256);
-    a.arg1 = o;   o += align_up(V * 64 * 4, 256);
-    a.g1 = o;     o += align_up(V * 64 * 4, 256);
-    a.pool2 = o;  o += align_up(V * 128 * 4, 256);
-    a.arg2 = o;   o += align_up(V * 128 * 4, 256);
-    a.out = o;    o += align_up(V * 128 * 4, 256);
-    a.vstart = o; o += align_up((V + 2) * 4, 256);
-    a.first = o;  o += align_up((V + 2) * 4, 256);
-    a.sort = o;   o += align_up(lidf_sort_idx_ws_bytes((long long)N, (long long)V), 256);
-    a.total = o;
+    a.inps = c.take<float>(N * 6);
+    a.voxs = c.take<int>(N);
+    a.f1s = c.take<float>(N * 32);
+    a.f2s = c.take<float>(N * 64);
+    a.f4s = c.take<float>(N * 128);
+    a.pool1 = c.take<float>(V * 64);
+    a.arg1 = c.take<int>(V * 64);
+    a.g1 = c.take<float>(V * 64);
+    a.pool2 = c.take<float>(V * 128);
+    a.arg2 = c.take<int>(V * 128);
+    a.out = c.take<float>(V * 128);
+    a.vstart = c.take<int>(V + 2);
+    a.first = c.take<int>(V + 2);
+    a.sort = (char*)c.take_bytes(lidf_sort_idx_ws_bytes((long long)N, (long long)V));
     return a;
 }
 struct PnetWsC {   // scratch of one forward / backward
-    size_t pool64, gpart, dz_out, dp2, dz4s, df2s, partial, s4, dg1, dp1, dz2s, dz1s, wg, stream, total;
+    char* pool64;
+    float *gpart, *dz_out, *dp2, *dz4s, *df2s, *partial, *s4, *dg1, *dp1, *dz2s, *dz1s, *wg, *stream;
 };
-static PnetWsC pnetc_ws(int64_t n, int64_t v) {
+static PnetWsC pnetc_ws(Carver& c, int64_t n, int64_t v) {
     PnetWsC w;
     const size_t N = (size_t)(n > 0 ? n : 1), V = (size_t)(v > 0 ? v : 1);
-    size_t o = 0;
-    w.pool64 = o;  o += align_up(V * (64 + 128) * 8, 256);
-    w.gpart = o;   o += align_up(V * 128 * 4, 256);
-    w.dz_out = o;  o += align_up(V * 128 * 4, 256);
-    w.dp2 = o;     o += align_up(V * 128 * 4, 256);
-    w.dz4s = o;    o += align_up(N * 128 * 4, 256);
-    w.df2s = o;    o += align_up(N * 64 * 4, 256);
-    w.partial = o; o += align_up((N / (size_t)lidf_pnet_chunk_rows() + V + 1) * 128 * 4, 256);
-    w.s4 = o;      o += align_up(V * 128 * 4, 256);
-    w.dg1 = o;     o += align_up(V * 64 * 4, 256);
-    w.dp1 = o;     o += align_up(V * 64 * 4, 256);
-    w.dz2s = o;    o += align_up(N * 64 * 4, 256);
-    w.dz1s = o;    o += align_up(N * 32 * 4, 256);
-    w.wg = o;      o += align_up(WG_SCRATCH_FLOATS * 4, 256);
-    w.stream = o;  o += linex_stream_bytes(256);
-    w.total = o;
+    w.pool64 = c.take<char>(V * (64 + 128) * 8);
+    w.gpart = c.take<float>(V * 128);
+    w.dz_out = c.take<float>(V * 128);
+    w.dp2 = c.take<float>(V * 128);
+    w.dz4s = c.take<float>(N * 128);
+    w.df2s = c.take<float>(N * 64);
+    w.partial = c.take<float>((N / (size_t)lidf_pnet_chunk_rows() + V + 1) * 128);
+    w.s4 = c.take<float>(V * 128);
+    w.dg1 = c.take<float>(V * 64);
+    w.dp1 = c.take<float>(V * 64);
+    w.dz2s = c.take<float>(N * 64);
+    w.dz1s = c.take<float>(N * 32);
+    w.wg = c.take<float>(WG_SCRATCH_FLOATS);
+    w.stream = (float*)c.take_bytes(linex_stream_bytes(256));
     return w;
 }
 #define PNETC_BWD_STREAM_BYTES ((size_t)(PNB_A_QUADS + PNB_B_QUADS) * 1024)
@@ -88,40 +93,33 @@ static int pnetc_pack(const LidfPointNet* w, float* chain, float* const streams[
 }
 
 // forward with what the backward needs kept in `act` (pnetc_act); streams packed by pnetc_pack
-static int pnetc_forward(const float* inp, const int32_t* vox, int64_t n, int64_t V, float* out, char* act,
-                         char* ws, const float* chain, float* const streams[7], int cus, hipStream_t st) {
+static int pnetc_forward(const float* inp, const int32_t* vox, int64_t n, int64_t V, float* out, const PnetActC& a,
+                         const PnetWsC& w, const float* chain, float* const streams[7], int cus, hipStream_t st) {
     int rc;
-    const PnetActC a = pnetc_act(n, V);
-    const PnetWsC w = pnetc_ws(n, V);
-    float* pool64 = (float*)(ws + w.pool64);
     {
-        float* zp[1] = {pool64};
+        float* zp[1] = {(float*)w.pool64};
         const long long zc[1] = {(long long)V * (64 + 128) * 2};
         CHECK_HIP(lidf_launch_zero_segments(zp, zc, 1, st));
     }
     const int *perm = nullptr, *n_perm = nullptr;
-    CHECK_HIP(lidf_launch_sort_idx(vox, n, nullptr, V, act + a.sort, &perm, &n_perm, st));
+    CHECK_HIP(lidf_launch_sort_idx(vox, n, nullptr, V, a.sort, &perm, &n_perm, st));
     size_t sc_off, perm_off;
     int nblk;
     lidf_sort_idx_layout(n, V, &sc_off, &nblk, &perm_off);
-    int* vstart = (int*)(act + a.vstart);
-    int* first = (int*)(act + a.first);
-    CHECK_HIP(lidf_launch_pnet_tables((const int*)(act + a.sort + sc_off), nblk, V, n_perm, vstart, first, st));
-    float* gpart = (float*)(ws + w.gpart);
-    float *pool1 = (float*)(act + a.pool1), *g1 = (float*)(act + a.g1), *pool2 = (float*)(act + a.pool2);
-    void* p64_1 = ws + w.pool64;
-    void* p64_2 = ws + w.pool64 + (size_t)V * 64 * 8;
-    CHECK_HIP(lidf_launch_pnet_train_fwd(1, chain, inp, vox, perm, n_perm, nullptr, (float*)(act + a.inps),
-                                         (int*)(act + a.voxs), (float*)(act + a.f1s), (float*)(act + a.f2s), nullptr,
-                                         p64_1, V, n, cus, st));
-    CHECK_HIP(lidf_launch_pnet_unpack(p64_1, V * 64, pool1, (int*)(act + a.arg1), st));
+    CHECK_HIP(lidf_launch_pnet_tables((const int*)(a.sort + sc_off), nblk, V, n_perm, a.vstart, a.first, st));
+    float *gpart = w.gpart, *pool1 = a.pool1, *g1 = a.g1, *pool2 = a.pool2;
+    void* p64_1 = w.pool64;
+    void* p64_2 = w.pool64 + (size_t)V * 64 * 8;
+    CHECK_HIP(lidf_launch_pnet_train_fwd(1, chain, inp, vox, perm, n_perm, nullptr, a.inps, a.voxs, a.f1s, a.f2s,
+                                         nullptr, p64_1, V, n, cus, st));
+    CHECK_HIP(lidf_launch_pnet_unpack(p64_1, V * 64, pool1, a.arg1, st));
     // g1 = relu(vox_lin1(pool1)); gpart[v] = W3[:, :64] g1[v] + b3: one launch over the voxels
     if ((rc = run_vox2(pool1, 64, V, nullptr, streams[2], 2, 1, g1, streams[3], 9, 4, 0, gpart, st))) return rc;
     CHECK_HIP(lidf_launch_pnet_train_fwd(2, chain, inp, vox, perm, n_perm, gpart, nullptr, nullptr, nullptr, nullptr,
-                                         (float*)(act + a.f4s), p64_2, V, n, cus, st));
-    CHECK_HIP(lidf_launch_pnet_unpack(p64_2, V * 128, pool2, (int*)(act + a.arg2), st));
+                                         a.f4s, p64_2, V, n, cus, st));
+    CHECK_HIP(lidf_launch_pnet_unpack(p64_2, V * 128, pool2, a.arg2, st));
     // out = relu(vox_lin2(pool2))
-    float* outk = (float*)(act + a.out);
+    float* outk = a.out;
     if ((rc = run_vox2(pool2, 128, V, nullptr, streams[6], 4, 1, outk, nullptr, 0, 0, 0, nullptr, st))) return rc;
     if (out && out != outk)
         CHECK_HIP(hipMemcpyAsync(out, outk, (size_t)V * 128 * 4, hipMemcpyDeviceToDevice, st));
@@ -131,36 +129,22 @@ static int pnetc_forward(const float* inp, const int32_t* vox, int64_t n, int64_
 // backward: slots = the seven transposed-launch streams of pointnet_backward_impl (0: vox_lin2^T, 3: the voxel half
 // of point_lin3^T, 4: vox_lin1^T are the ones read here), pack_mode 0 = pack and run, 2 = packed earlier (then
 // `slots` must be given); bwd = the backward chains' stream. Parameter gradients are accumulated into.
-static int pnetc_backward(const LidfPointNet* w, int64_t n, int64_t V, const char* act, const float* g_out,
-                          float* d_inp, bool zero_dinp, const LidfPointNetGrads* g, char* ws, float* const* slots,
-                          int pack_mode, const float* bwd, int cus, hipStream_t st) {
+static int pnetc_backward(const LidfPointNet* w, int64_t n, int64_t V, const PnetActC& a, const float* g_out,
+                          float* d_inp, bool zero_dinp, const LidfPointNetGrads* g, const PnetWsC& s,
+                          float* const* slots, int pack_mode, const float* bwd, int cus, hipStream_t st) {
     int rc;
-    const PnetActC a = pnetc_act(n, V);
-    const PnetWsC s = pnetc_ws(n, V);
     size_t sc_off, perm_off;
     int nblk;
     lidf_sort_idx_layout(n, V, &sc_off, &nblk, &perm_off);   // (where the forward's sort left its scan and perm)
-    const int* scanned = (const int*)(act + a.sort + sc_off);
+    const int* scanned = (const int*)(a.sort + sc_off);
     const int* n_perm = scanned + (size_t)V * nblk;
-    const int* perm = (const int*)(act + a.sort + perm_off);
-    const float *inps = (const float*)(act + a.inps), *f1s = (const float*)(act + a.f1s);
-    const float *f2s = (const float*)(act + a.f2s), *f4s = (const float*)(act + a.f4s);
-    const int* voxs = (const int*)(act + a.voxs);
-    const float *pool1 = (const float*)(act + a.pool1), *g1 = (const float*)(act + a.g1);
-    const float *pool2 = (const float*)(act + a.pool2), *outv = (const float*)(act + a.out);
-    const int *arg1 = (const int*)(act + a.arg1), *arg2 = (const int*)(act + a.arg2);
-    const int *vstart = (const int*)(act + a.vstart), *first = (const int*)(act + a.first);
-    float* dz_out = (float*)(ws + s.dz_out);
-    float* dp2 = (float*)(ws + s.dp2);
-    float* dz4s = (float*)(ws + s.dz4s);
-    float* df2s = (float*)(ws + s.df2s);
-    float* s4 = (float*)(ws + s.s4);
-    float* dg1 = (float*)(ws + s.dg1);
-    float* dp1 = (float*)(ws + s.dp1);
-    float* dz2s = (float*)(ws + s.dz2s);
-    float* dz1s = (float*)(ws + s.dz1s);
-    float* wgs = (float*)(ws + s.wg);
-    float* sbuf = (float*)(ws + s.stream);
+    const int* perm = (const int*)(a.sort + perm_off);
+    const float *inps = a.inps, *f1s = a.f1s, *f2s = a.f2s, *f4s = a.f4s;
+    const int* voxs = a.voxs;
+    const float *pool1 = a.pool1, *g1 = a.g1, *pool2 = a.pool2, *outv = a.out;
+    const int *arg1 = a.arg1, *arg2 = a.arg2, *vstart = a.vstart, *first = a.first;
+    float *dz_out = s.dz_out, *dp2 = s.dp2, *dz4s = s.dz4s, *df2s = s.df2s, *s4 = s.s4, *dg1 = s.dg1, *dp1 = s.dp1,
+          *dz2s = s.dz2s, *dz1s = s.dz1s, *wgs = s.wg, *sbuf = s.stream;
     auto lin = [&](const LinEx& L, int slot) {
         return run_linex(L, slots ? slots[slot] : sbuf, cus, st, slots ? pack_mode : 0);
     };
@@ -178,7 +162,7 @@ static int pnetc_backward(const LidfPointNet* w, int64_t n, int64_t V, const cha
     CHECK_HIP(lidf_launch_pnet_bwd_a(bwd, voxs, n_perm, dp2, arg2, f4s, dz4s, df2s, n, cus, st));
     // f4 = relu(point_lin3(cat(g1[vox], f2))): weight columns 0..63 meet g1[vox] (per-voxel row sums of dz4),
     // 64..127 meet f2
-    CHECK_HIP(lidf_launch_pnet_segsum(dz4s, vstart, first, V, n, (float*)(ws + s.partial), s4, st));
+    CHECK_HIP(lidf_launch_pnet_segsum(dz4s, vstart, first, V, n, s.partial, s4, st));
     CHECK_HIP(lidf_launch_wgrad(s4, 128, 128, g1, 64, 64, V, g->w_p3, 128, nullptr, wgs, WG_SCRATCH_FLOATS, st));
     CHECK_HIP(lidf_launch_wgrad(dz4s, 128, 128, f2s, 64, 64, n, g->w_p3 + 64, 128, g->b_p3, wgs, WG_SCRATCH_FLOATS, st));
     // g1 = relu(vox_lin1(pool1))
@@ -201,28 +185,26 @@ static int pnetc_backward(const LidfPointNet* w, int64_t n, int64_t V, const cha
 // ---- the public entry points (include/lidf_hip.h): the chains where the voxel table allows the sort, else layer by
 // layer. Workspace of the chains' form: [scratch | inference chains' stream | backward chains' stream | the seven
 // layer slots]; every call packs what it reads (the stepwise API keeps no stream between calls).
-struct PnetPubWs {
-    size_t scratch, chain, bwd, s[7], total;
-};
-static PnetPubWs pnet_pub_ws(int64_t n, int64_t v) {
+struct PnetPubWs { PnetWsC scratch; float *chain, *bwd, *s[7]; };
+static PnetPubWs pnet_pub_ws(Carver& c, int64_t n, int64_t v) {
     PnetPubWs w;
-    size_t o = 0;
-    w.scratch = o; o += align_up(pnetc_ws(n, v).total, 256);
-    w.chain = o;   o += align_up(lidf_pointnet_chain_stream_bytes(), 256);
-    w.bwd = o;     o += align_up(PNETC_BWD_STREAM_BYTES, 256);
-    const int ks[7] = {6, 32, 64, 64, 64, 128, 128};
-    const int nts[7] = {1, 2, 2, 4, 4, 4, 4};
-    for (int i = 0; i < 7; ++i) { w.s[i] = o; o += lin_stream_bytes(ks[i], nts[i]); }
-    w.total = o;
+    w.scratch = pnetc_ws(c, n, v);
+    w.chain = (float*)c.take_bytes(lidf_pointnet_chain_stream_bytes());
+    w.bwd = (float*)c.take_bytes(PNETC_BWD_STREAM_BYTES);
+    pnet_streams(c, w.s);
     return w;
 }
+// (either path's needs: which one a call takes, pnetc_ok decides)
 LIDF_API size_t lidf_pointnet_train_act_floats(int64_t n_pts, int64_t n_vox) {
-    const size_t a = pnet_act(n_pts, n_vox).total, c = (pnetc_act(n_pts, n_vox).total + 3) / 4;
-    return a > c ? a : c;
+    Carver c(nullptr, 4);
+    c.either([&](Carver& u) { pnet_act(u, n_pts, n_vox); },
+             [&](Carver& u) { Carver k; pnetc_act(k, n_pts, n_vox); u.take_bytes(k.used()); });
+    return c.used() / sizeof(float);
 }
 LIDF_API size_t lidf_pointnet_train_workspace_bytes(int64_t n_pts, int64_t n_vox) {
-    const size_t a = pnet_train_ws(n_pts, n_vox).total, c = pnet_pub_ws(n_pts, n_vox).total;
-    return a > c ? a : c;
+    Carver c;
+    c.either([&](Carver& u) { pnet_train_ws(u, n_pts, n_vox); }, [&](Carver& u) { pnet_pub_ws(u, n_pts, n_vox); });
+    return c.used();
 }
 
 LIDF_API int lidf_pointnet_forward_train_f32(const LidfPointNet* w, const float* inp, const int32_t* vox, int64_t n,
@@ -234,16 +216,13 @@ LIDF_API int lidf_pointnet_forward_train_f32(const LidfPointNet* w, const float*
     if (!out || !act || !inp || !vox) return LIDF_ERR_BAD_ARG;
     int rc, cus;
     if ((rc = check_pointnet_w(w))) return rc;
-    const PnetPubWs pw = pnet_pub_ws(n, n_vox);
-    if (!workspace || workspace_bytes < pw.total) return LIDF_ERR_WORKSPACE;
+    Carver c(workspace), ca(act);
+    const PnetPubWs pw = pnet_pub_ws(c, n, n_vox);
+    CHECK_CARVED(c, workspace, workspace_bytes);
     if ((rc = cu_count(&cus))) return rc;
-    char* ws = (char*)workspace;
-    float* streams[7];
-    for (int i = 0; i < 7; ++i) streams[i] = (float*)(ws + pw.s[i]);
     hipStream_t st = (hipStream_t)stream;
-    if ((rc = pnetc_pack(w, (float*)(ws + pw.chain), streams, (float*)(ws + pw.bwd), cus, st))) return rc;
-    return pnetc_forward(inp, vox, n, n_vox, out, (char*)act, ws + pw.scratch, (const float*)(ws + pw.chain), streams,
-                         cus, st);
+    if ((rc = pnetc_pack(w, pw.chain, pw.s, pw.bwd, cus, st))) return rc;
+    return pnetc_forward(inp, vox, n, n_vox, out, pnetc_act(ca, n, n_vox), pw.scratch, pw.chain, pw.s, cus, st);
 }
 
 LIDF_API int lidf_pointnet_backward_f32(const LidfPointNet* w, const float* inp, const int32_t* vox, int64_t n,
@@ -259,11 +238,11 @@ LIDF_API int lidf_pointnet_backward_f32(const LidfPointNet* w, const float* inp,
     if (!g->w_p1 || !g->b_p1 || !g->w_p2 || !g->b_p2 || !g->w_v1 || !g->b_v1 || !g->w_p3 || !g->b_p3 ||
         !g->w_p4 || !g->b_p4 || !g->w_v2 || !g->b_v2 || !act || !g_out)
         return LIDF_ERR_BAD_ARG;
-    const PnetPubWs pw = pnet_pub_ws(n, n_vox);
-    if (!workspace || workspace_bytes < pw.total) return LIDF_ERR_WORKSPACE;
+    Carver c(workspace), ca(act);
+    const PnetPubWs pw = pnet_pub_ws(c, n, n_vox);
+    CHECK_CARVED(c, workspace, workspace_bytes);
     if ((rc = cu_count(&cus))) return rc;
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
     {   // the gradients start at zero
         float* const zp[12] = {g->w_p1, g->b_p1, g->w_p2, g->b_p2, g->w_v1, g->b_v1, g->w_p3, g->b_p3,
                                g->w_p4, g->b_p4, g->w_v2, g->b_v2};
@@ -278,9 +257,9 @@ LIDF_API int lidf_pointnet_backward_f32(const LidfPointNet* w, const float* inp,
         nw.w1 = w->w_p1; nw.b1 = w->b_p1; nw.w2 = w->w_p2; nw.b2 = w->b_p2; nw.w3 = w->w_p3;
         nw.b3 = w->w_p4; nw.w4 = w->b_p4;
         L1Map m0 = {};
-        CHECK_HIP(pack_stream(lay, nw, nw, m0, (float*)(ws + pw.bwd), nullptr, st));
+        CHECK_HIP(pack_stream(lay, nw, nw, m0, pw.bwd, nullptr, st));
     }
     (void)inp; (void)vox;   // (the forward kept their sorted copies)
-    return pnetc_backward(w, n, n_vox, (const char*)act, g_out, d_inp, true, g, ws + pw.scratch, nullptr, 0,
-                          (const float*)(ws + pw.bwd), cus, st);
+    return pnetc_backward(w, n, n_vox, pnetc_act(ca, n, n_vox), g_out, d_inp, true, g, pw.scratch, nullptr, 0, pw.bwd,
+                          cus, st);
 }

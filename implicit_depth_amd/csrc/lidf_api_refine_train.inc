@@ -16,77 +16,87 @@
 //             after the loop the per-ray part once on the sum of S over the iterations.
 // Parameter gradients accumulate inside the call (every kernel that writes one adds into it).
 
-struct RtLay {
-    // `act`: [weight streams | raypart | ray index | per-iteration blocks]
-    size_t s_pnf[7], s_pnb[PNET_BWD_SLOTS], s_pnchain, s_pnbwd, s_vox, s_ray, s_chain, s_dvox, s_dpe, s_dgrad;
-    size_t raypart, ray_idx, iter0, iter_bytes, total;
-    // inside an iteration's block
-    size_t cur, end_voxel, pn_inp, pn_vox, pnact, pe, voxpart, passes, pre, off;
+// One iteration's block of `act`. The PointNet's forward keeps the chains' sorted rows or the layer-by-layer
+// path's activations in the same bytes (pnetc_ok decides which).
+struct RtIter {
+    float* cur;
+    int* end_voxel;
+    float* pn_inp;
+    int* pn_vox;
+    PnetAct pa;
+    PnetActC pc;
+    float* pe;          // rows [ROI | embed(pos) | embed(dir)]
+    float *voxpart, *passes, *pre, *off;
 };
-static RtLay rt_lay(int64_t R, int64_t Nv, int64_t V, int E, int npass, int T) {
-    RtLay l;
-    size_t o = 0;
-    const int ks[7] = {6, 32, 64, 64, 64, 128, 128};
-    const int nts[7] = {1, 2, 2, 4, 4, 4, 4};
-    for (int i = 0; i < 7; ++i) { l.s_pnf[i] = o; o += lin_stream_bytes(ks[i], nts[i]); }
-    for (int i = 0; i < PNET_BWD_SLOTS; ++i) { l.s_pnb[i] = o; o += linex_stream_bytes(PNET_BWD_SLOT_K[i]); }
-    l.s_pnchain = o; o += align_up(lidf_pointnet_chain_stream_bytes(), 256);   // the PointNet's chains (forward | backward)
-    l.s_pnbwd = o;   o += align_up(PNETC_BWD_STREAM_BYTES, 256);
-    l.s_vox = o;   o += linex_stream_bytes(128);
-    l.s_ray = o;   o += linex_stream_bytes(REFINE_RAY_K);
-    l.s_chain = o; o += chain_stream_bytes(3 + 6 * 16);
-    l.s_dvox = o;  o += linex_stream_bytes(256);
-    l.s_dpe = o;   o += linex_stream_bytes(256);
-    l.s_dgrad = o; o += align_up(lidf_dgrad_stream_bytes(), 256);
+static RtIter rt_iter(Carver& c, int64_t R, int64_t Nv, int64_t V, int E, int npass) {
+    RtIter l;
     const size_t r = (size_t)(R > 0 ? R : 1), n = (size_t)(R + Nv > 0 ? R + Nv : 1), v = (size_t)(V > 0 ? V : 1);
-    l.raypart = o; o += align_up(r * LIDF_H1 * 4, 256);
-    l.ray_idx = o; o += align_up(r * 4, 256);
-    l.iter0 = o;
-    size_t b = 0;
-    l.cur = b;       b += align_up(r * 12, 256);
-    l.end_voxel = b; b += align_up(r * 4, 256);
-    l.pn_inp = b;    b += align_up(n * 24, 256);
-    l.pn_vox = b;    b += align_up(n * 4, 256);
-    {   // what the PointNet's forward keeps: the chains' sorted rows, or the layer-by-layer path's
-        const size_t pa = pnet_act((int64_t)n, (int64_t)v).total * 4, pc = pnetc_act((int64_t)n, (int64_t)v).total;
-        l.pnact = b; b += align_up(pa > pc ? pa : pc, 256);
-    }
-    l.pe = b;        b += align_up(r * (size_t)(128 + E + 3 + 6 * 16) * 4, 256);   // rows [ROI | embed(pos) | embed(dir)]
-    l.voxpart = b;   b += align_up(v * LIDF_H1 * 4, 256);
-    l.passes = b;    b += align_up((size_t)npass * qact_pass((int64_t)r) * 4, 256);
-    l.pre = b;       b += align_up(r * 4, 256);
-    l.off = b;       b += align_up(r * 4, 256);
-    l.iter_bytes = b;
-    l.total = o + (size_t)(T > 0 ? T : 1) * b;
+    l.cur = c.take<float>(r * 3);
+    l.end_voxel = c.take<int>(r);
+    l.pn_inp = c.take<float>(n * 6);
+    l.pn_vox = c.take<int>(n);
+    c.either([&](Carver& u) { Carver k = u.here(4); l.pa = pnet_act(k, (int64_t)n, (int64_t)v); u.take_bytes(k.used()); },
+             [&](Carver& u) { l.pc = pnetc_act(u, (int64_t)n, (int64_t)v); });
+    l.pe = c.take<float>(r * (size_t)(128 + E + 3 + 6 * 16));
+    l.voxpart = c.take<float>(v * LIDF_H1);
+    l.passes = c.take<float>((size_t)npass * qact_pass((int64_t)r));
+    l.pre = c.take<float>(r);
+    l.off = c.take<float>(r);
+    return l;
+}
+// `act`: [weight streams | raypart | ray index | per-iteration blocks]
+struct RtLay {
+    float *s_pnf[7], *s_pnb[PNET_BWD_SLOTS], *s_pnchain, *s_pnbwd, *s_vox, *s_ray;
+    char* s_chain;
+    float *s_dvox, *s_dpe, *s_dgrad, *raypart;
+    int* ray_idx;
+    char* iter0;          // T blocks of iter_bytes each (rt_iter)
+    size_t iter_bytes;
+};
+static RtLay rt_lay(Carver& c, int64_t R, int64_t Nv, int64_t V, int E, int npass, int T) {
+    RtLay l;
+    pnet_streams(c, l.s_pnf);
+    for (int i = 0; i < PNET_BWD_SLOTS; ++i) l.s_pnb[i] = (float*)c.take_bytes(linex_stream_bytes(PNET_BWD_SLOT_K[i]));
+    l.s_pnchain = (float*)c.take_bytes(lidf_pointnet_chain_stream_bytes());   // the PointNet's chains (forward | backward)
+    l.s_pnbwd = (float*)c.take_bytes(PNETC_BWD_STREAM_BYTES);
+    l.s_vox = (float*)c.take_bytes(linex_stream_bytes(128));
+    l.s_ray = (float*)c.take_bytes(linex_stream_bytes(REFINE_RAY_K));
+    l.s_chain = (char*)c.take_bytes(chain_stream_bytes(3 + 6 * 16));
+    l.s_dvox = (float*)c.take_bytes(linex_stream_bytes(256));
+    l.s_dpe = (float*)c.take_bytes(linex_stream_bytes(256));
+    l.s_dgrad = (float*)c.take_bytes(lidf_dgrad_stream_bytes());
+    const size_t r = (size_t)(R > 0 ? R : 1);
+    l.raypart = c.take<float>(r * LIDF_H1);
+    l.ray_idx = c.take<int>(r);
+    Carver one;
+    rt_iter(one, R, Nv, V, E, npass);
+    l.iter_bytes = one.used();
+    l.iter0 = (char*)c.take_bytes((size_t)(T > 0 ? T : 1) * l.iter_bytes);
     return l;
 }
 
+// the backward's (and the PointNet forward's) scratch
 struct RtWs {
-    size_t pn, qd, ssum, s_it, dvoxfeat, d_pe, d_inp, g_a, g_b, goff_in, ss_partial, total;
-    PnetTrainWs pw;
+    PnetTrainWs pw;     // the PointNet's: layer by layer ...
+    PnetWsC pcw;        // ... or through the chains, in the same bytes
     QTrainWs qw;
+    float *ssum, *s_it, *dvoxfeat, *d_pe, *d_inp, *g[2], *ss_partial;
 };
-static RtWs rt_ws(int64_t R, int64_t Nv, int64_t V, int E) {
+static RtWs rt_ws(Carver& c, int64_t R, int64_t Nv, int64_t V, int E) {
     RtWs w;
-    size_t o = 0;
     const size_t r = (size_t)(R > 0 ? R : 1), n = (size_t)(R + Nv > 0 ? R + Nv : 1), v = (size_t)(V > 0 ? V : 1);
-    w.pw = pnet_train_ws((int64_t)n, (int64_t)v);
-    w.qw = qtrain_ws((int64_t)r, (int64_t)r, (int64_t)v);
-    {
-        const size_t pc = pnetc_ws((int64_t)n, (int64_t)v).total;
-        w.pn = o; o += align_up(w.pw.total > pc ? w.pw.total : pc, 256);
-    }
-    w.qd = o;       o += align_up(w.qw.total, 256);
-    w.ssum = o;     o += align_up(r * LIDF_H1 * 4, 256);
-    w.s_it = o;     o += align_up(r * LIDF_H1 * 4, 256);
-    w.dvoxfeat = o; o += align_up(v * 128 * 4, 256);
-    w.d_pe = o;     o += align_up(r * (size_t)E * 4, 256);
-    w.d_inp = o;    o += align_up(n * 24, 256);
-    w.g_a = o;      o += align_up(r * 12, 256);
-    w.g_b = o;      o += align_up(r * 12, 256);
-    w.goff_in = o;  o += align_up(r * 4, 256);
-    w.ss_partial = o; o += align_up((n / (size_t)lidf_pnet_chunk_rows() + v + 1) * 256 * 4, 256);
-    w.total = o;
+    c.either([&](Carver& u) { w.pw = pnet_train_ws(u, (int64_t)n, (int64_t)v); },
+             [&](Carver& u) { w.pcw = pnetc_ws(u, (int64_t)n, (int64_t)v); });
+    w.qw = qtrain_ws(c, (int64_t)r, (int64_t)r, (int64_t)v);
+    w.ssum = c.take<float>(r * LIDF_H1);
+    w.s_it = c.take<float>(r * LIDF_H1);
+    w.dvoxfeat = c.take<float>(v * 128);
+    w.d_pe = c.take<float>(r * (size_t)E);
+    w.d_inp = c.take<float>(n * 6);
+    w.g[0] = c.take<float>(r * 3);
+    w.g[1] = c.take<float>(r * 3);
+    c.take<float>(r);   // (a slot no launch uses any more: kept, the workspace's size is part of the ABI's behaviour)
+    w.ss_partial = c.take<float>((n / (size_t)lidf_pnet_chunk_rows() + v + 1) * 256);
     return w;
 }
 
@@ -95,11 +105,11 @@ LIDF_API size_t lidf_refine_train_act_bytes(int64_t n_rays, int64_t n_valid, int
     (void)multires_views;
     if (n_rays < 0 || n_valid < 0 || n_vox < 0 || multires < 0 || multires > 16 || n_pass < 1 || forward_times < 1)
         return 0;
-    return rt_lay(n_rays, n_valid, n_vox, 3 + 6 * multires, n_pass, forward_times).total;
+    return carved([&](Carver& c) { rt_lay(c, n_rays, n_valid, n_vox, 3 + 6 * multires, n_pass, forward_times); });
 }
 LIDF_API size_t lidf_refine_train_workspace_bytes(int64_t n_rays, int64_t n_valid, int64_t n_vox, int32_t multires) {
     if (n_rays < 0 || n_valid < 0 || n_vox < 0 || multires < 0 || multires > 16) return 0;
-    return rt_ws(n_rays, n_valid, n_vox, 3 + 6 * multires).total;
+    return carved([&](Carver& c) { rt_ws(c, n_rays, n_valid, n_vox, 3 + 6 * multires); });
 }
 
 static int rt_check(const LidfRefineArgs* q, int T, bool need_out = true) {
@@ -154,18 +164,16 @@ static int rt_pack_transposed(const LidfDecoder* dec, int E, int Ed, float* s_dv
     return run_linex(L, s_dpe, cus, st, 1);
 }
 
-static void rt_query_args(const LidfRefineArgs* q, const RtLay& l, char* it, char* act, LidfQueryTrainArgs* t) {
+static void rt_query_args(const LidfRefineArgs* q, const RtLay& l, const RtIter& it, LidfQueryTrainArgs* t) {
     *t = {};
     t->n_pairs = q->n_rays; t->n_rays = q->n_rays; t->n_vox = q->n_vox;
     t->pair_off = nullptr;
-    t->pair_ray = (const int32_t*)(act + l.ray_idx);
-    t->pair_vox = (const int32_t*)(it + l.end_voxel);
-    t->pe = (const float*)(it + l.pe) + 128;   // (the embed(pos) window of the iteration's layer-1 rows)
+    t->pair_ray = l.ray_idx;
+    t->pair_vox = it.end_voxel;
+    t->pe = it.pe + 128;   // (the embed(pos) window of the iteration's layer-1 rows)
     t->multires = q->multires; t->multires_views = q->multires_views;
     // (occ_voxel_feat of the iteration: where the PointNet's forward keeps its output)
-    const int64_t n = q->n_rays + q->n_valid;
-    t->vox_feat = pnetc_ok(n, q->n_vox) ? (const float*)(it + l.pnact + pnetc_act(n, q->n_vox).out)
-                                        : (const float*)(it + l.pnact) + pnet_act(n, q->n_vox).out;
+    t->vox_feat = pnetc_ok(q->n_rays + q->n_valid, q->n_vox) ? it.pc.out : it.pa.out;
     t->rayfeat = q->rayfeat;
     t->dec = q->off;
 }
@@ -180,66 +188,61 @@ LIDF_API int lidf_refine_train_forward_f32(const LidfRefineArgs* q, int32_t forw
     const LidfDecoder* dec = q->off;
     const int E = 3 + 6 * q->multires, Ed = 3 + 6 * q->multires_views;
     const int npass = dec->is_ief ? dec->n_iter : 1;
-    const RtLay l = rt_lay(R, Nv, V, E, npass, T);
-    const RtWs w = rt_ws(R, Nv, V, E);
-    if (!act_v || act_bytes < l.total) return LIDF_ERR_WORKSPACE;
-    if (!q->workspace || q->workspace_bytes < w.total) return LIDF_ERR_WORKSPACE;
+    Carver ca(act_v), cw(q->workspace);
+    const RtLay l = rt_lay(ca, R, Nv, V, E, npass, T);
+    const RtWs w = rt_ws(cw, R, Nv, V, E);
+    CHECK_CARVED(ca, act_v, act_bytes);
+    CHECK_CARVED(cw, q->workspace, q->workspace_bytes);
+    auto iter = [&](int it) {   // block `it` of the per-iteration blocks
+        Carver ci(l.iter0 + (size_t)it * l.iter_bytes);
+        return rt_iter(ci, R, Nv, V, E, npass);
+    };
     CellLookup cells;
     if ((rc = rt_cells(q, &cells))) return rc;
     if ((rc = cu_count(&cus))) return rc;
     hipStream_t st = (hipStream_t)stream;
-    char* act = (char*)act_v;
-    char* ws = (char*)q->workspace;
     const bool chain = pnetc_ok(n, V);   // PointNet2Stage through the training chains (else layer by layer)
-    float* pnf[7];
-    float* pnb[PNET_BWD_SLOTS];
-    for (int i = 0; i < 7; ++i) pnf[i] = (float*)(act + l.s_pnf[i]);
-    for (int i = 0; i < PNET_BWD_SLOTS; ++i) pnb[i] = (float*)(act + l.s_pnb[i]);
-    float* raypart = (float*)(act + l.raypart);
-    int* ray_idx = (int*)(act + l.ray_idx);
+    float* const* pnf = l.s_pnf;
+    float* const* pnb = l.s_pnb;
+    float* raypart = l.raypart;
+    const RtIter first = iter(0);
     LidfQueryTrainArgs t;
-    rt_query_args(q, l, act + l.iter0, act, &t);
+    rt_query_args(q, l, first, &t);
     {   // every weight stream of the step — the forward launches' and the backward launches' — in one multi-pack
         JobScope js;
         if (chain)
-            rc = pnetc_pack(q->pnet, (float*)(act + l.s_pnchain), pnf, (float*)(act + l.s_pnbwd), cus, st);
-        else
-            rc = pointnet_train_forward_impl(q->pnet, nullptr, nullptr, 0, 0, nullptr,
-                                             (float*)(act + l.iter0 + l.pnact), nullptr, pnf, cus, st, 1);
+            rc = pnetc_pack(q->pnet, l.s_pnchain, pnf, l.s_pnbwd, cus, st);
+        else   // (pack only: no activation is touched)
+            rc = pointnet_train_forward_impl(q->pnet, nullptr, nullptr, 0, 0, nullptr, first.pa, nullptr, pnf, cus, st, 1);
         if (!rc) {
             LidfPointNetGrads none = {};
-            rc = pointnet_backward_impl(q->pnet, nullptr, nullptr, 0, 0, (const float*)(act + l.iter0 + l.pnact),
-                                        nullptr, nullptr, &none, ws + w.pn, w.pw, false, pnb, 1, cus, st);
+            rc = pointnet_backward_impl(q->pnet, nullptr, nullptr, 0, 0, first.pa, nullptr, nullptr, &none, w.pw, false,
+                                        pnb, 1, cus, st);
         }
         if (!rc)
-            rc = qdec_forward_impl(&t, E, nullptr, nullptr, nullptr, nullptr, nullptr, (float*)(act + l.s_vox),
-                                   (float*)(act + l.s_ray), act + l.s_chain, cus, st, 1);
-        if (!rc)
-            rc = rt_pack_transposed(dec, E, Ed, (float*)(act + l.s_dvox), (float*)(act + l.s_dpe), cus, st);
+            rc = qdec_forward_impl(&t, E, nullptr, nullptr, nullptr, nullptr, nullptr, l.s_vox, l.s_ray, l.s_chain, cus,
+                                   st, 1);
+        if (!rc) rc = rt_pack_transposed(dec, E, Ed, l.s_dvox, l.s_dpe, cus, st);
         if (!rc && flush_jobs(js.jobs, st) != hipSuccess) rc = LIDF_ERR_HIP;
         if (rc) return rc;
     }
-    CHECK_HIP(lidf_launch_pack_dgrad(dec->w3, dec->w2, (float*)(act + l.s_dgrad), st));
-    CHECK_HIP(lidf_launch_iota(ray_idx, R, st));
+    CHECK_HIP(lidf_launch_pack_dgrad(dec->w3, dec->w2, l.s_dgrad, st));
+    CHECK_HIP(lidf_launch_iota(l.ray_idx, R, st));
     // the per-ray part of layer 1: the same in every iteration
-    if ((rc = qdec_forward_impl(&t, E, nullptr, nullptr, raypart, nullptr, nullptr, nullptr, (float*)(act + l.s_ray),
-                                nullptr, cus, st, 2, 2)))
+    if ((rc = qdec_forward_impl(&t, E, nullptr, nullptr, raypart, nullptr, nullptr, nullptr, l.s_ray, nullptr, cus, st,
+                                2, 2)))
         return rc;
     const float r0 = q->offset_range0, rs = q->offset_range1 - q->offset_range0;
     const float* cur = q->pred_pos;
     for (int it = 0; it < T; ++it) {
-        char* ib = act + l.iter0 + (size_t)it * l.iter_bytes;
-        float* cur_keep = (float*)(ib + l.cur);
-        int* end_voxel = (int*)(ib + l.end_voxel);
+        const RtIter ib = iter(it);
+        float* cur_keep = ib.cur;
+        int* end_voxel = ib.end_voxel;
         // (the chains keep sorted copies of what their backward reads: one [valid | predicted] buffer serves every
         // iteration, its valid rows copied once per step; the layer-by-layer path keeps a buffer per iteration)
-        char* pib = chain ? act + l.iter0 : ib;
-        float* pn_inp = (float*)(pib + l.pn_inp);
-        int* pn_vox = (int*)(pib + l.pn_vox);
-        float* pnact = (float*)(ib + l.pnact);
-        float* pe = (float*)(ib + l.pe);
-        float* off = (float*)(ib + l.off);
-        const PnetAct pa = pnet_act(n, V);
+        float* pn_inp = chain ? first.pn_inp : ib.pn_inp;
+        int* pn_vox = chain ? first.pn_vox : ib.pn_vox;
+        float *pe = ib.pe, *off = ib.off;
         if (it == 0) {   // (later iterations start from the position the one before wrote into their block)
             CHECK_HIP(hipMemcpyAsync(cur_keep, cur, (size_t)R * 12, hipMemcpyDeviceToDevice, st));
             cur = cur_keep;
@@ -262,18 +265,15 @@ LIDF_API int lidf_refine_train_forward_f32(const LidfRefineArgs* q, int32_t forw
         CHECK_HIP(lidf_launch_refine_rows_dev(cur, end_voxel, q->voxel_bound, q->rayfeat, 128 + Ed, q->multires_views,
                                               q->multires, q->pos_rel, R, nullptr, pe - 128, 128 + E + Ed, 0, st));
         if (chain)
-            rc = pnetc_forward(pn_inp, pn_vox, n, V, nullptr, (char*)pnact, ws + w.pn,
-                               (const float*)(act + l.s_pnchain), pnf, cus, st);
+            rc = pnetc_forward(pn_inp, pn_vox, n, V, nullptr, ib.pc, w.pcw, l.s_pnchain, pnf, cus, st);
         else
-            rc = pointnet_train_forward_impl(q->pnet, pn_inp, pn_vox, n, V, pnact + pa.out, pnact,
-                                             (float*)(ws + w.pn + w.pw.gpart), pnf, cus, st, 2);
+            rc = pointnet_train_forward_impl(q->pnet, pn_inp, pn_vox, n, V, ib.pa.out, ib.pa, w.pw.gpart, pnf, cus, st, 2);
         if (rc) return rc;
-        rt_query_args(q, l, ib, act, &t);
-        if ((rc = qdec_forward_impl(&t, E, off, (float*)(ib + l.voxpart), raypart, (float*)(ib + l.passes),
-                                    (float*)(ib + l.pre), (float*)(act + l.s_vox), nullptr, act + l.s_chain, cus, st,
-                                    2, 1 | 4, 128 + E + Ed)))
+        rt_query_args(q, l, ib, &t);
+        if ((rc = qdec_forward_impl(&t, E, off, ib.voxpart, raypart, ib.passes, ib.pre, l.s_vox, nullptr, l.s_chain,
+                                    cus, st, 2, 1 | 4, 128 + E + Ed)))
             return rc;
-        float* out = it == T - 1 ? q->pred_pos_out : (float*)(ib + l.iter_bytes + l.cur);
+        float* out = it == T - 1 ? q->pred_pos_out : iter(it + 1).cur;
         CHECK_HIP(lidf_launch_refine_finish(cur, off, q->ray_dir, r0, rs, R, out, st));
         if (it == T - 1 && q->end_voxel_id)
             CHECK_HIP(hipMemcpyAsync(q->end_voxel_id, end_voxel, (size_t)R * 4, hipMemcpyDeviceToDevice, st));
@@ -312,85 +312,67 @@ LIDF_API int lidf_refine_train_backward_f32(const LidfRefineArgs* q, int32_t for
     }
     if (R == 0) return LIDF_OK;
     if (!g_pos) return LIDF_ERR_BAD_ARG;
-    const RtLay l = rt_lay(R, Nv, V, E, npass, T);
-    const RtWs w = rt_ws(R, Nv, V, E);
-    if (!act_v || act_bytes < l.total) return LIDF_ERR_WORKSPACE;
-    if (!q->workspace || q->workspace_bytes < w.total) return LIDF_ERR_WORKSPACE;
+    Carver ca(act_v), cw(q->workspace);   // (the streams inside `act` are read, nothing of it is written)
+    const RtLay l = rt_lay(ca, R, Nv, V, E, npass, T);
+    const RtWs w = rt_ws(cw, R, Nv, V, E);
+    CHECK_CARVED(ca, act_v, act_bytes);
+    CHECK_CARVED(cw, q->workspace, q->workspace_bytes);
     if ((rc = cu_count(&cus))) return rc;
     const bool chain = pnetc_ok(n, V);
-    char* act = (char*)act_v;   // (the streams inside are read, nothing of it is written)
-    char* ws = (char*)q->workspace;
-    float* pnb[PNET_BWD_SLOTS];
-    for (int i = 0; i < PNET_BWD_SLOTS; ++i) pnb[i] = (float*)(act + l.s_pnb[i]);
-    float* ssum = (float*)(ws + w.ssum);
-    float* s_it = (float*)(ws + w.s_it);
-    float* dvoxfeat = (float*)(ws + w.dvoxfeat);
-    float* d_pe = (float*)(ws + w.d_pe);
-    float* d_inp = (float*)(ws + w.d_inp);
-    float* gbuf[2] = {(float*)(ws + w.g_a), (float*)(ws + w.g_b)};
-    float* goff_in = (float*)(ws + w.goff_in);
-    float* wgs = (float*)(ws + w.qd + w.qw.wg);
+    float* const* pnb = l.s_pnb;
+    float *ssum = w.ssum, *s_it = w.s_it, *dvoxfeat = w.dvoxfeat, *d_pe = w.d_pe, *d_inp = w.d_inp;
     const float rs = q->offset_range1 - q->offset_range0;
     const float* g = g_pos;
-    const PnetAct pa = pnet_act(n, V);
     for (int it = T - 1; it >= 0; --it) {
-        char* ib = act + l.iter0 + (size_t)it * l.iter_bytes;
-        const float* cur = (const float*)(ib + l.cur);
-        const int* end_voxel = (const int*)(ib + l.end_voxel);
-        const float* pnact = (const float*)(ib + l.pnact);
+        Carver ci(l.iter0 + (size_t)it * l.iter_bytes);
+        const RtIter ib = rt_iter(ci, R, Nv, V, E, npass);
+        const float* cur = ib.cur;
+        const int* end_voxel = ib.end_voxel;
         // does a gradient have to reach the position this iteration started from?
         const bool need_dcur = it > 0 || d_pred_pos != nullptr;
         // d off = rs <g, dir>, through the output activation: straight into the decoder backward's goff
-        CHECK_HIP(lidf_launch_refine_train_goff(g, q->ray_dir, rs, R, (const float*)(ib + l.pre), dec->use_sigmoid,
-                                                (float*)(ws + w.qd + w.qw.goff), st));
-        (void)goff_in;
+        CHECK_HIP(lidf_launch_refine_train_goff(g, q->ray_dir, rs, R, ib.pre, dec->use_sigmoid, w.qw.goff, st));
         LidfQueryTrainArgs t;
-        rt_query_args(q, l, ib, act, &t);
+        rt_query_args(q, l, ib, &t);
         QdecBwd o = {};
         o.E2 = E; o.zero_grads = false;
         // (the sum of S over the iterations is only needed for d_rayfeat; the last iteration's S opens it)
         o.S_keep = (d_rayfeat && it == T - 1) ? ssum : s_it;
-        o.l1rows = (const float*)(ib + l.pe); o.l1_ld = 128 + E + Ed; o.l1_cols = 128 + E + Ed; o.l1_c0 = 128;
+        o.l1rows = ib.pe; o.l1_ld = 128 + E + Ed; o.l1_cols = 128 + E + Ed; o.l1_c0 = 128;
         o.d_pe = need_dcur ? d_pe : nullptr;
-        o.s_dvox = (float*)(act + l.s_dvox); o.s_dpe = (float*)(act + l.s_dpe); o.pack_mode = 2;
-        o.s_dgrad = (const float*)(act + l.s_dgrad);
+        o.s_dvox = l.s_dvox; o.s_dpe = l.s_dpe; o.pack_mode = 2;
+        o.s_dgrad = l.s_dgrad;
         o.goff_ready = true;
         if (chain) {   // the PointNet's sort of this iteration groups the rays by end voxel already
-            const PnetActC pc = pnetc_act(n, V);
             size_t sc_off, perm_off;
             int nblk;
             lidf_sort_idx_layout(n, V, &sc_off, &nblk, &perm_off);
-            const char* pb = (const char*)pnact;
-            o.ss_perm = (const int*)(pb + pc.sort + perm_off);
-            o.ss_vstart = (const int*)(pb + pc.vstart);
-            o.ss_first = (const int*)(pb + pc.first);
+            o.ss_perm = (const int*)(ib.pc.sort + perm_off);
+            o.ss_vstart = ib.pc.vstart;
+            o.ss_first = ib.pc.first;
             o.ss_row0 = Nv; o.ss_n = n;
-            o.ss_partial = (float*)(ws + w.ss_partial);
+            o.ss_partial = w.ss_partial;
         }
-        if ((rc = qdec_backward_impl(&t, o, (const float*)(ib + l.passes), (const float*)(ib + l.pre), goff_in,
-                                     dvoxfeat, nullptr, 0, gd, ws + w.qd, w.qw, cus, st)))
+        if ((rc = qdec_backward_impl(&t, o, ib.passes, ib.pre, nullptr, dvoxfeat, nullptr, 0, gd, w.qw, cus, st)))
             return rc;
         if (d_rayfeat && it != T - 1) CHECK_HIP(lidf_launch_add_inplace(ssum, s_it, R * LIDF_H1, st));
         if (chain)
-            rc = pnetc_backward(q->pnet, n, V, (const char*)pnact, dvoxfeat, need_dcur ? d_inp : nullptr, true, gp,
-                                ws + w.pn, pnb, 2, (const float*)(act + l.s_pnbwd), cus, st);
+            rc = pnetc_backward(q->pnet, n, V, ib.pc, dvoxfeat, need_dcur ? d_inp : nullptr, true, gp, w.pcw, pnb, 2,
+                                l.s_pnbwd, cus, st);
         else
-            rc = pointnet_backward_impl(q->pnet, (const float*)(ib + l.pn_inp), (const int32_t*)(ib + l.pn_vox), n, V,
-                                        pnact, dvoxfeat, need_dcur ? d_inp : nullptr, gp, ws + w.pn, w.pw, false, pnb,
-                                        2, cus, st);
+            rc = pointnet_backward_impl(q->pnet, ib.pn_inp, ib.pn_vox, n, V, ib.pa, dvoxfeat,
+                                        need_dcur ? d_inp : nullptr, gp, w.pw, false, pnb, 2, cus, st);
         if (rc) return rc;
-        (void)pa;
         if (need_dcur) {
-            float* gn = it == 0 ? d_pred_pos : gbuf[it & 1];
+            float* gn = it == 0 ? d_pred_pos : w.g[it & 1];
             CHECK_HIP(lidf_launch_refine_train_dcur(g, cur, end_voxel, q->voxel_bound, q->pos_rel, d_pe, q->multires,
                                                     d_inp + (size_t)Nv * 6, R, gn, st));
             g = gn;
         }
     }
     // (dW1's ROI / embed(dir) columns came with every iteration's S^T [ROI | embed(pos) | embed(dir)] product)
-    (void)wgs;
     if (d_rayfeat) {   // raypart[r] = W1[:, 128:256] roi[r] + W1[:, 256 + E:] embed(dir)[r], on the sum of S
-        float* sbuf = (float*)(ws + w.qd + w.qw.stream);
+        float* sbuf = w.qw.stream;
         LinEx L = {};
         L.transposed = 1; L.ldw = ld1; L.k = LIDF_H1; L.ldx = LIDF_H1; L.X = ssum; L.n = R;
         L.w = dec->w1 + 128; L.nout = 128; L.out = d_rayfeat; L.ld_out = 128 + Ed;
@@ -443,7 +425,7 @@ LIDF_API int lidf_refine_step_forward_f32(const float* pos, const int64_t* max_p
         const long long nc = rstep_n_cells(batch, grid_res);
         if (nc == 0 || !grid_xmin || !(grid_part > 0.f)) return LIDF_ERR_BAD_ARG;
         if (nc < 0) return LIDF_ERR_UNSUPPORTED;
-        if (!workspace || workspace_bytes < (size_t)nc * 4) return LIDF_ERR_WORKSPACE;
+        CHECK_WS(workspace, workspace_bytes, (size_t)nc * 4);
         for (int k = 0; k < 3; ++k) {
             cells.g.xmin[k] = grid_xmin[k];
             cells.g.r[k] = grid_res[k];

@@ -94,6 +94,97 @@ def test_struct_layouts_match_header(tmp_path):
             assert int(seen["%s.%s" % (n, f)]) == getattr(cls, f).offset, (n, f)
 
 
+CARVER_PROBE = r"""
+#include <stdio.h>
+#include <stdint.h>
+#include "lidf_carve.h"
+#define CHECK(x) do { if (!(x)) { printf("FAILED line %d: %s\n", __LINE__, #x); return 1; } } while (0)
+struct Inner { float* a; int* b; };
+static Inner inner(Carver& c, size_t n) { Inner i; i.a = c.take<float>(n); i.b = c.take<int>(n + 1); return i; }
+struct Act { float* x; int* y; };                                   // (carved at alignment 4, sized in floats)
+static Act act(Carver& c, size_t n) { Act a; a.x = c.take<float>(n); a.y = c.take<int>(3 * n); return a; }
+struct Outer {
+    char* head; double* zero; float* opt; Inner in; Act small; Inner big; short* tail; void* sub; Inner in_sub;
+};
+static Outer outer(Carver& c, size_t n, bool with_opt) {
+    Outer o;
+    o.head = c.take<char>(n);
+    o.zero = c.take<double>(0);
+    o.opt = c.take_if<float>(with_opt, n);
+    o.in = inner(c, n);                                             // nested: the same carver
+    c.either([&](Carver& u) { Carver k = u.here(4); o.small = act(k, n); u.take_bytes(k.used()); },
+             [&](Carver& u) { o.big = inner(u, 3 * n); });          // union: both views share the start
+    o.tail = c.take<short>(7);
+    Carver size_of_sub;
+    inner(size_of_sub, 5);
+    o.sub = c.take_bytes(size_of_sub.used() + 1000);                // nested in a sub-range of known size
+    Carver s(o.sub);
+    o.in_sub = inner(s, 5);
+    return o;
+}
+static size_t off(const void* base, const void* p) { return (size_t)((const char*)p - (const char*)base); }
+int main(void) {
+    static char buf[1 << 16] __attribute__((aligned(256)));
+    for (size_t n = 1; n <= 301; n += 75) {
+        for (int with_opt = 0; with_opt < 2; ++with_opt) {
+            Carver size, carve(buf);
+            const Outer s = outer(size, n, with_opt), o = outer(carve, n, with_opt);
+            // a sizing pass hands out no pointer and agrees with the carving pass on the size
+            CHECK(!s.head && !s.zero && !s.opt && !s.in.a && !s.in.b && !s.small.x && !s.big.b && !s.tail && !s.sub &&
+                  !s.in_sub.a);
+            CHECK(size.used() == carve.used() && carve.used() <= sizeof(buf) && carve.used() % 256 == 0);
+            // the offsets, written out flat: every slot is its bytes rounded up to 256
+            auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+            size_t e = 0;
+            CHECK(off(buf, o.head) == e); e += up(n);
+            CHECK(off(buf, o.zero) == e);                            // a zero-count slot takes 0 bytes
+            if (with_opt) { CHECK(off(buf, o.opt) == e); e += up(4 * n); } else { CHECK(!o.opt); }   // optional: 0 bytes
+            CHECK(off(buf, o.in.a) == e); e += up(4 * n);
+            CHECK(off(buf, o.in.b) == e); e += up(4 * (n + 1));
+            CHECK(off(buf, o.small.x) == e && off(buf, o.big.a) == e);
+            CHECK(off(buf, o.small.y) == e + 4 * n);                 // alignment 4: no padding between the two
+            CHECK(off(buf, o.big.b) == e + up(12 * n));
+            const size_t sm = up(16 * n), bg = up(12 * n) + up(4 * (3 * n + 1));
+            CHECK(bg > sm); e += bg;                                 // the union takes the larger member
+            CHECK(off(buf, o.tail) == e); e += up(14);
+            CHECK(off(buf, o.sub) == e && off(buf, o.in_sub.a) == e && off(buf, o.in_sub.b) == e + 256);
+            e += up(256 + 256 + 1000);
+            CHECK(e == carve.used());
+            const void* all[] = {o.head, o.zero, o.in.a, o.in.b, o.small.x, o.big.a, o.big.b, o.tail, o.sub, o.in_sub.b};
+            for (const void* p : all) CHECK((uintptr_t)p % 256 == 0);
+            // the cover check
+            CHECK(carve.covers(buf, carve.used()) && carve.covers(buf, carve.used() + 1));
+            CHECK(!carve.covers(buf, carve.used() - 1) && !carve.covers(nullptr, carve.used()));
+            CHECK(!size.covers(nullptr, (size_t)-1));
+        }
+    }
+    Carver a4(buf, 4);                                               // a size exported in floats, unpadded
+    act(a4, 5);
+    CHECK(a4.used() == 4 * (5 + 15));
+    Carver ref;
+    outer(ref, 7, true);
+    CHECK(carved([](Carver& c) { outer(c, 7, true); }) == ref.used());   // the sizing shorthand
+    printf("carver ok\n");
+    return 0;
+}
+"""
+
+
+def test_carver_sizes_and_hands_out_the_same_layout(tmp_path):
+    """csrc/lidf_carve.h alone, through a stand-alone program built with g++ (no HIP): a sizing pass and a carving
+    pass of one layout agree on every offset and on used(); every slot is aligned; a zero-count and a switched-off
+    optional slot take 0 bytes; a union takes its larger member and both views share the start; a nested layout
+    lands where the flat one would; the cover check refuses NULL and used() - 1 and accepts used()."""
+    import subprocess
+    src = tmp_path / "carver_probe.cpp"
+    src.write_text(CARVER_PROBE)
+    exe = tmp_path / "carver_probe"
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "implicit_depth_amd", "csrc"),
+                    str(src), "-o", str(exe)], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0 and "carver ok" in r.stdout, r.stdout + r.stderr
+
+
 def test_launchers_are_declared_once_in_lidf_launch_h():
     """The kernel files' host launchers are extern "C": the linker matches them by name alone. Their
     only prototypes live in csrc/lidf_launch.h, which every .hip file includes, so that the compiler
@@ -418,22 +509,35 @@ def test_c_abi_argument_errors_without_gpu():
 
 
 def test_host_size_functions_keep_their_recorded_values():
-    """The size functions that make no HIP call (workspaces and pack blobs of the query, the training forward,
-    stage 2, the PointNet and the frame) against tests/golden/host_sizes.json: a list of {fn, args, bytes}
-    recorded from the library before the query's launch plan was unified. Callers size persistent blobs with
-    these, and the blobs' layouts are what the kernels read: a byte more or less is a layout change."""
+    """Every exported size function (none makes a HIP call) against tests/golden/host_sizes.json: a list of
+    {fn, args, bytes}. The first 20 records date from before the query's launch plan was unified, the rest from
+    before the layouts were written over one carver: per function all zeros, all ones, odd sizes, the workload's
+    shape, and tuples that move one dimension or switch one optional slot at a time. Callers size persistent blobs
+    with these, and the blobs' layouts are what the kernels read: a byte more or less is a layout change."""
     import ctypes as C
     import json
     from implicit_depth_amd import _lib
     L = _lib.lib()
     recs = json.load(open(os.path.join(ROOT, "tests", "golden", "host_sizes.json")))
-    assert {r["fn"] for r in recs} == {
+    assert {r["fn"] for r in recs[:20]} == {
         "lidf_query_workspace_bytes", "lidf_query_pack_bytes", "lidf_query_forward_train_workspace_bytes",
         "lidf_refine_pack_bytes", "lidf_pointnet_pack_bytes", "lidf_frame_pack_bytes", "lidf_frame_pack_guard_bytes",
         "lidf_frame_workspace_bytes"}
-    assert len(recs) == 20
+    sized = {n for n, (res, _) in _lib.SIGNATURES.items() if res is C.c_size_t}
+    assert {r["fn"] for r in recs} == sized and len(sized) == 50
+    assert len(recs) == 318 and all(sum(r["fn"] == n for r in recs) >= 4 or not _lib.SIGNATURES[n][1] for n in sized)
+
+    def marshal(a):   # a list: int32[] (the frame's res[3]); {"widths": [prob_gf, off_gf, refine_gf, pe_slab_pairs]}
+        if isinstance(a, list):
+            return (C.c_int32 * len(a))(*a)
+        if isinstance(a, dict):
+            w = _lib.LidfFrameWidths()
+            w.prob_gf, w.off_gf, w.refine_gf, w.pe_slab_pairs = a["widths"]
+            return C.byref(w)
+        return a
+
     for r in recs:
-        args = [(C.c_int32 * len(a))(*a) if isinstance(a, list) else a for a in r["args"]]   # (the frame's res[3])
+        args = [marshal(a) for a in r["args"]]
         assert getattr(L, r["fn"])(*args) == r["bytes"], (r["fn"], r["args"])
     assert [r["bytes"] for r in recs if r["fn"] == "lidf_refine_pack_bytes" and r["args"] == [17, 0]] == [0]
 

@@ -23,15 +23,15 @@ csrc/ before the first poisoned run; word = 4 bytes):
    (FrameWs.lb_head, lidf_frame_head_lb_bytes)  lb_ticket / lb_exclusive (spin)   lidf_launch_zero_segments seg 0     lb_head: lb_head, lb_pairs
   frame lb_pairs: ticket + status per 256     lidf_ray_aabb_onepass_kernel      the same segment (adjacent)         (both 256-aligned) and
    rays of CAPACITY (..._onepass_lb_bytes)      lb_ticket / lb_exclusive (spin)                                      cell_flag [C], contiguous
-  frame cell_flag [C]                         lidf_frame_cells_kernel (scan)    the same segment (f.cell_flag ==    C words
-                                                                                f.lb_bytes)
+  frame cell_flag [C]                         lidf_frame_cells_kernel (scan)    the same segment (frame_ws carves   C words
+                                                                                it right behind the f.lb_bytes)
   frame pool1 [C,64] / pool2 [C,128]          pointnet chains (integer max)     step 0 segs 1, 2; per refine        C*64, C*128 words
                                                                                 iteration lidf_launch_refine_step
                                                                                 (zero0 / zero1) or, split-f16,
                                                                                 zero_segments {end_voxel, pools}
-  frame query tile counter (QueryWs.counter)  lidf_points(_h) atomicAdd         step 0 seg 3                        1 word
-  frame box list length (box + grid_floats)   lidf_rayfeat(_border)_kernel      step 0 seg 4                        1 word
-  frame group counts (PnetFrameWs.sort, B>=2) lidf_group_count_kernel atomics   step 0 seg 5; lidf_group_scan_      C words
+  frame query tile counter (FrameWs.q.counter) lidf_points(_h) atomicAdd        step 0 seg 3                        1 word
+  frame box list length (q.box + grid_floats) lidf_rayfeat(_border)_kernel      step 0 seg 4                        1 word
+  frame group counts (FrameWs.pnet.sort, B>=2) lidf_group_count_kernel atomics  step 0 seg 5; lidf_group_scan_      C words
                                                                                 kernel leaves them zero again
   frame counts[0..7], pair_off[0..R]          every later launch (n_dev)        lidf_frame_head_kernel :205-209,    all eight / R + 1 entries
                                                                                 lidf_frame_cells_kernel :242,
