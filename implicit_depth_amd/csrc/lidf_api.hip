@@ -1270,7 +1270,7 @@ LIDF_API int lidf_pointnet_pack_guarded_f32(const LidfPointNet* w, void* packed,
 // ---- stage-2 refinement ----------------------------------------------------------------------
 // The weight streams of refine_ief_factorised (lidf_refine_pack_f32's blob): [layer-1 stream of the per-voxel launch |
 // of the per-ray launch (ROI + direction columns, sized for the widest direction embedding) | stream + aux of the
-// chain | stream | aux of the 16 x 16 x 4 decoder (lidf_ief16.hip): E <= 99 embed(pos) columns = 7 k-quads]
+// chain | stream | aux of the 16 x 16 x 4 decoder (lidf_chain16.hip): E <= 99 embed(pos) columns = 7 k-quads]
 struct RefineFact {
     float *s_vox, *s_ray;
     char* s_chain;
@@ -2278,20 +2278,17 @@ static int linear_impl(const float* x, int64_t ldx, int64_t n, int32_t k, const 
 }
 
 // ---- a whole decoder at gf_dim 32 / 64 / 128 as one register-chained launch (lidf_chain16.hip) ------------
-static size_t chain16_stream_bytes(int gf, int k) {
-    const int G = gf / 16;
-    return (size_t)(((k + 15) / 16) * 4 * G + lidf_chain16_pass_quads(G)) * 1024;
-}
 // (split: the f16x3 form — lidf_chain16_h.hip's stream, padded to that kernel's ring)
-static size_t chain16_any_stream_bytes(int gf, int k, bool split) {
-    if (!split) return chain16_stream_bytes(gf, k);
-    const int G = gf / 16;
-    return (size_t)(lidf_chain16h_l1_quads(G, k) + lidf_chain16h_pass_quads(G)) * 1024;
+static size_t chain16_stream_bytes(int gf, int k, bool split = false) {
+    const int G = gf / 16, kq = lidf_chain16_kq(k);
+    const int quads = split ? lidf_chain16h_l1_quads(G, kq) + lidf_chain16_pass_quads(G, lidf_chain16h_ring(G))
+                            : lidf_chain16_l1_quads(G, kq) + lidf_chain16_pass_quads(G, LIDF_CHAIN16_RING);
+    return (size_t)quads * 1024;
 }
 // one decoder's chain stream | layer-4 operands: lidf_decoder_chain_f32's workspace, a slot of the any-width pack blob
 static StreamAux chain16_ws(Carver& c, int gf, int k, bool split) {
     StreamAux w;
-    w.stream = (float*)c.take_bytes(chain16_any_stream_bytes(gf, k, split));
+    w.stream = (float*)c.take_bytes(chain16_stream_bytes(gf, k, split));
     w.aux = c.take<float>(lidf_chain16_aux_floats(gf / 16));
     return w;
 }
@@ -2327,7 +2324,7 @@ static int decoder_chain_impl(const LidfDecoder* dec, int32_t gf_dim, int32_t in
     if ((rc = cu_count(&cus))) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int G = gf_dim / 16;
-    const size_t sbytes = chain16_any_stream_bytes(gf_dim, k, split);
+    const size_t sbytes = chain16_stream_bytes(gf_dim, k, split);
     float *sbuf = w.stream, *aux = w.aux;
     StreamLayout lay = {};
     lay.nets = 1; lay.mode = split ? LIDF_MODE_CHAIN16_H : LIDF_MODE_CHAIN16;
@@ -2782,14 +2779,14 @@ static int run_chain_train(const LidfDecoder* dec, int dcore, const L1Map& m, co
 }
 
 #define REFINE_RAY_K (128 + 3 + 6 * 16)
-static size_t ief16_stream_bytes(int E) { return (size_t)(((E + 15) / 16) * 16 + IEF16_PASS_QUADS) * 1024; }
 static RefineFact refine_fact(Carver& c, int D) {
     RefineFact f;
     f.s_vox = (float*)c.take_bytes(linex_stream_bytes(128));
     f.s_ray = (float*)c.take_bytes(linex_stream_bytes(REFINE_RAY_K));
     f.s_chain = (char*)c.take_bytes(chain_stream_bytes(D - 128));
-    f.s16 = (float*)c.take_bytes(ief16_stream_bytes(3 + 6 * 16));
-    f.aux16 = c.take<float>(IEF16_AUX_FLOATS);
+    const StreamAux w16 = chain16_ws(c, LIDF_H3, 3 + 6 * 16, false);   // the chain at G = 4, the widest embed(pos)
+    f.s16 = w16.stream;
+    f.aux16 = w16.aux;
     return f;
 }
 // LIDF_IEF16=0 in the environment: the 32 x 32 rows kernel of rounds 2-3 instead (A/B measurements)
@@ -2835,13 +2832,13 @@ static int refine_ief_factorised(const LidfDecoder* off, int D, const float* vox
         Lr.n_dev = R_dev;
         if ((rc = run_linex(Lr, f.s_ray, cus, st, pack_mode))) return rc;
     }
-    // the decoder on 16-ray sub-tiles (lidf_ief16.hip): its stream rides behind the others
+    // the decoder on 16-ray sub-tiles (the chain of lidf_chain16.h at G = 4): its stream rides behind the others
     if (pack_mode != 2) {
         StreamLayout lay = {};
-        lay.nets = 1; lay.mode = LIDF_MODE_IEF16;
-        lay.total = (int)(ief16_stream_bytes(E) / 4);
+        lay.nets = 1; lay.mode = LIDF_MODE_CHAIN16;
+        lay.total = (int)(chain16_stream_bytes(LIDF_H3, E) / 4);
         L1Map m16 = {};
-        m16.n0 = E; m16.c0 = 256;
+        m16.n0 = E; m16.c0 = 256; m16.nt = LIDF_H3 / 16;
         const NetW nw = to_netw(off, D);
         CHECK_HIP(pack_stream(lay, nw, nw, m16, f.s16, f.aux16, st));
     }
@@ -2855,8 +2852,8 @@ static int refine_ief_factorised(const LidfDecoder* off, int D, const float* vox
     }
     if (R <= 0) return LIDF_OK;
     if (ev_rows && ev_rows[0]) CHECK_HIP(hipEventRecord((hipEvent_t)ev_rows[0], st));   // (benchmarks only)
-    Ief16Args ia = {};
-    ia.stream = f.s16; ia.aux = f.aux16; ia.KQ = (E + 15) / 16; ia.E = E;
+    Chain16Args ia = {};
+    ia.stream = f.s16; ia.aux = f.aux16; ia.KQ = lidf_chain16_kq(E); ia.E = E;
     ia.n = R; ia.n_dev = R_dev;
     ia.X = inp_embed + 256; ia.ldx = D;
     ia.vox = end_voxel; ia.voxpart = voxpart; ia.raypart = raypart;
@@ -2864,7 +2861,7 @@ static int refine_ief_factorised(const LidfDecoder* off, int D, const float* vox
     ia.init = off->is_ief ? off->init_offset : 0.f;
     ia.sigmoid = off->use_sigmoid;
     ia.out = out;
-    CHECK_HIP(lidf_launch_ief16(ia, cus, st));
+    CHECK_HIP(lidf_launch_chain16_stage2(ia, cus, st));
     if (ev_rows && ev_rows[1]) CHECK_HIP(hipEventRecord((hipEvent_t)ev_rows[1], st));
     return LIDF_OK;
 }

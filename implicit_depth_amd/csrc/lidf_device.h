@@ -75,12 +75,10 @@ enum { LIDF_MODE_FUSED = 0, LIDF_MODE_ROWS = 1, LIDF_MODE_L1ONLY = 2, LIDF_MODE_
        LIDF_MODE_TRAIN = 5,     // rows mode (stream of LIDF_MODE_ROWS) that keeps the activations
        LIDF_MODE_ROWS_GATHER = 6,    // rows mode whose layer-1 accumulators start from gathered rows
        LIDF_MODE_PNET_CHAIN = 7,     // pack jobs only: the per-point chain stream of a PointNet2Stage (PN_* below)
-       LIDF_MODE_IEF16 = 8,          // pack jobs only: the stage-2 decoder's 16 x 16 x 4 stream (lidf_ief16.hip)
+       // (8: the stage-2 decoder's own 16 x 16 x 4 stream until it became LIDF_MODE_CHAIN16 at nt = 4)
        LIDF_MODE_PNET_BWD = 9,       // pack jobs only: the backward chains' stream of a PointNet2Stage (PNB_* below)
        LIDF_MODE_CHAIN16 = 10,       // the any-width decoder chain's stream (lidf_chain16.hip; L1Map.nt = gf / 16)
        LIDF_MODE_CHAIN16_H = 11 };   // its split-f16 form (lidf_chain16_h.hip): every weight as its two f16 pieces
-#define IEF16_PASS_QUADS 168   // 2 + 1 bias quads, 4 u quads, 128 layer-2 quads, 32 layer-3 quads, 1 padding quad
-#define IEF16_AUX_FLOATS 72    // w4 [64] | b4 [1] (+ padding)
 
 // One decoder's parameters as the packer sees them.
 struct NetW {
@@ -465,28 +463,9 @@ struct RayStepArgs {
     const int* cell_table;
 };
 
-// Arguments of the stage-2 decoder on 16 x 16 x 4 tiles (lidf_ief16.hip).
-struct Ief16Args {
-    const float* stream;   // (16 KQ + IEF16_PASS_QUADS) KiB
-    const float* aux;      // IEF16_AUX_FLOATS
-    int KQ;                // layer-1 k-quads of 16 columns
-    int E;                 // embed(pos) columns (operand columns beyond it are zero)
-    long long n;           // rays
-    const int* n_dev;      // optional device-side count (n = capacity)
-    const float* X;        // [n, ldx]: embed(pos) columns start at X (the caller offsets the row)
-    long long ldx;
-    const int* vox;        // [n] row of voxpart (the end voxel)
-    const float* voxpart;  // [V, 256]  W1[:, vox feat] f + b1 (+ c)
-    const float* raypart;  // [n, 256]  W1[:, ROI | dir] rayfeat
-    int npass;
-    float init;
-    int sigmoid;
-    float* out;            // [n]
-};
-
 // Arguments of the any-width decoder chain (lidf_chain16.hip); G = gf / 16, table rows are 4 gf = 64 G floats.
 struct Chain16Args {
-    const float* stream;   // (KQ * 4 G + lidf_chain16_pass_quads(G)) KiB
+    const float* stream;   // lidf_chain16_l1_quads + lidf_chain16_pass_quads KiB (split: lidf_chain16h_l1_quads)
     const float* aux;      // w4 [16 G] | b4 [1] (lidf_chain16_aux_floats(G))
     int KQ;                // layer-1 k-quads of 16 columns
     int E;                 // per-row operand columns (columns beyond it are zero)
@@ -504,21 +483,23 @@ struct Chain16Args {
     const int* n_dev;      // optional device-side count: rows = clamp(*n_dev - row0, 0, n) (n = capacity of the launch)
     long long row0;        // first row of this launch in the counted list (the slabs of a frame's pairs)
 };
-static inline int lidf_chain16_pass_quads(int G) {
+// The chain's stream in 1 KiB quads, for the host size functions, the packers and the kernels alike (G = gf / 16,
+// kq = ceil(k / 16) groups of 16 operand columns, ring = weight quads in flight per wavefront):
+// the layer-1 section — f32: a quad per group and output tile; split f16: the groups in pairs, a quad of high and a
+// quad of low pieces per pair and output tile —
+constexpr int lidf_chain16_kq(int k) { return (k + 15) / 16; }
+constexpr int lidf_chain16_l1_quads(int G, int kq) { return kq * 4 * G; }
+constexpr int lidf_chain16h_l1_quads(int G, int kq) { return (kq + 1) / 2 * 8 * G; }
+// and the pass section (both forms): bias quads of layer 2, a u quad in front of every fourth input tile, layer 2,
+// bias quads of layer 3, layer 3, padded to a multiple of the ring (ring 1: the unpadded length)
+constexpr int lidf_chain16_pass_quads(int G, int ring) {
     const int T1 = 4 * G, T2 = 2 * G, T3 = G;
-    const int raw = (T2 + 3) / 4 + T1 * T2 + T1 / 4 + (T3 + 3) / 4 + T2 * T3;
-    return (raw + 7) / 8 * 8;
-}
-static inline int lidf_chain16_aux_floats(int G) { return 16 * G + 8; }
-// the split-f16 chain (lidf_chain16_h.hip): weight quads in flight per wavefront (a divisor of 8 G), the pass
-// section padded to it, and the layer-1 section of k columns (pairs of 16-column groups, two quads per output tile)
-static inline int lidf_chain16h_ring(int G) { return G >= 4 ? 16 : 8; }
-static inline int lidf_chain16h_l1_quads(int G, int k) { return ((k + 15) / 16 + 1) / 2 * 8 * G; }
-static inline int lidf_chain16h_pass_quads(int G) {
-    const int T1 = 4 * G, T2 = 2 * G, T3 = G, ring = lidf_chain16h_ring(G);
     const int raw = (T2 + 3) / 4 + T1 * T2 + T1 / 4 + (T3 + 3) / 4 + T2 * T3;
     return (raw + ring - 1) / ring * ring;
 }
+#define LIDF_CHAIN16_RING 8   // the f32 chain's ring; the split chain's is a divisor of 8 G:
+constexpr int lidf_chain16h_ring(int G) { return G >= 4 ? 16 : 8; }
+constexpr int lidf_chain16_aux_floats(int G) { return 16 * G + 8; }
 
 // Arguments of the two-layer per-voxel kernel (lidf_linear.hip: lidf_vox2_kernel).
 struct Vox2Args {

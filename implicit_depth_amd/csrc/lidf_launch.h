@@ -328,11 +328,10 @@ hipError_t lidf_launch_miss_window(const void* mask, int dtype, const float* int
                                    long long* bid64, long long* flat64, long long* pix64, int* window, int* n_rays,
                                    hipStream_t st);
 
-// ---- lidf_ief16.hip
-hipError_t lidf_launch_ief16(const Ief16Args& a, int cus, hipStream_t st);
-
 // ---- lidf_chain16.hip
 hipError_t lidf_launch_chain16(int gf, const Chain16Args& a, int cus, hipStream_t st);
+// (the stage-2 decoder: gf 64, both tables and vox present, raypart row r for row r)
+hipError_t lidf_launch_chain16_stage2(const Chain16Args& a, int cus, hipStream_t st);
 hipError_t lidf_launch_chain16h(int gf, const Chain16Args& a, int cus, hipStream_t st);   // lidf_chain16_h.hip
 hipError_t lidf_launch_chain16_bias_row(const float* b1, const float* w1enc, int ld1, const float* benc, int nout,
                                         float* out, hipStream_t st);

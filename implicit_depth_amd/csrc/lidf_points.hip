@@ -131,52 +131,20 @@ __device__ float stream_value(const StreamLayout& lay, const NetW& net0, const N
     }
 }
 
-// element e of the stage-2 decoder's 16 x 16 x 4 stream (layout: lidf_ief16.hip); m.n0 = E embed(pos)
-// columns starting at w1 column m.c0
-__device__ float ief16_stream_value(const NetW& n, const L1Map& m, int e) {
-    const int KQ = (m.n0 + 15) / 16;
-    int quad = e / 256;
-    const int lane = (e % 256) / 4, r = e & 3;
-    const int j = lane & 15, g = lane >> 4;
-    if (quad < KQ * 16) {
-        const int kq = quad / 16, To = quad % 16;
-        const int x = 16 * kq + 4 * g + r;
-        return x < m.n0 ? n.w1[(size_t)(16 * To + j) * n.ld1 + m.c0 + x] : 0.f;
-    }
-    quad -= KQ * 16;
-    if (quad < 2)   // bias quads of layer 2: component r = b2 of output tile 4 quad + r, in group 0
-        return g == 0 ? n.b2[16 * (4 * quad + r) + j] : 0.f;
-    quad -= 2;
-    if (quad < 132) {   // layer 2, k-major: a u quad in front of every fourth input tile
-        const int blk = quad / 33, in = quad % 33;
-        if (in == 0) return (g == 0 && n.is_ief) ? ief_u(n, 16 * (4 * blk + r) + j) : 0.f;
-        const int T = 4 * blk + (in - 1) / 8, To = (in - 1) % 8;
-        return n.w2[(size_t)(16 * To + j) * LIDF_H1 + 16 * T + 4 * g + r];
-    }
-    quad -= 132;
-    if (quad < 1) return g == 0 ? n.b3[16 * r + j] : 0.f;   // bias quad of layer 3
-    quad -= 1;
-    if (quad < 32) {
-        const int T = quad / 4, To = quad % 4;
-        return n.w3[(size_t)(16 * To + j) * LIDF_H2 + 16 * T + 4 * g + r];
-    }
-    return 0.f;
-}
-
-// element e of the any-width decoder chain's stream (layout: lidf_chain16.hip); G = m.nt = gf / 16, m.n0 = E per-row
-// columns starting at w1 column m.c0
+// element e of the decoder chain's stream (layout: lidf_chain16.h; the stage-2 decoder is G = 4); G = m.nt = gf / 16,
+// m.n0 = E per-row columns starting at w1 column m.c0
 __device__ float chain16_stream_value(const NetW& n, const L1Map& m, int e) {
     const int G = m.nt, T1 = 4 * G, T2 = 2 * G, T3 = G;
-    const int KQ = (m.n0 + 15) / 16;
+    const int l1_quads = lidf_chain16_l1_quads(G, lidf_chain16_kq(m.n0));
     int quad = e / 256;
     const int lane = (e % 256) / 4, r = e & 3;
     const int j = lane & 15, g = lane >> 4;
-    if (quad < KQ * T1) {
+    if (quad < l1_quads) {
         const int kq = quad / T1, To = quad % T1;
         const int x = 16 * kq + 4 * g + r;
         return x < m.n0 ? n.w1[(size_t)(16 * To + j) * n.ld1 + m.c0 + x] : 0.f;
     }
-    quad -= KQ * T1;
+    quad -= l1_quads;
     const int NB2 = (T2 + 3) / 4, NB3 = (T3 + 3) / 4;
     if (quad < NB2) {   // bias quads of layer 2: component r = b2 of output tile 4 quad + r, in group 0
         const int tile = 4 * quad + r;
@@ -215,17 +183,17 @@ __device__ float chain16h_pieces(float w0, float w1, int lo) {
 }
 __device__ float chain16h_stream_value(const NetW& n, const L1Map& m, int e) {
     const int G = m.nt, T1 = 4 * G, T2 = 2 * G, T3 = G;
-    const int KP = ((m.n0 + 15) / 16 + 1) / 2;
+    const int l1_quads = lidf_chain16h_l1_quads(G, lidf_chain16_kq(m.n0));
     int quad = e / 256;
     const int lane = (e % 256) / 4, c = e & 3;
     const int j = lane & 15, g = lane >> 4;
     const int f0 = 16 * (c >> 1) + 4 * g + 2 * (c & 1);   // first of the dword's two features, from the pair's tile 0
-    if (quad < KP * 2 * T1) {
+    if (quad < l1_quads) {
         const int kp = quad / (2 * T1), To = (quad % (2 * T1)) / 2, x = 32 * kp + f0;
         const float* w = n.w1 + (size_t)(16 * To + j) * n.ld1 + m.c0;
         return chain16h_pieces(x < m.n0 ? w[x] : 0.f, x + 1 < m.n0 ? w[x + 1] : 0.f, quad & 1);
     }
-    quad -= KP * 2 * T1;
+    quad -= l1_quads;
     const int NB2 = (T2 + 3) / 4, NB3 = (T3 + 3) / 4;
     if (quad < NB2) {
         const int tile = 4 * quad + c;
@@ -269,17 +237,11 @@ __device__ __forceinline__ void pack_body(const StreamLayout& lay, const NetW& n
         if (e < lay.total) stream[e] = pn_bwd_stream_value(w, e);
         return;
     }
-    if (lay.mode == LIDF_MODE_IEF16) {
-        if (e < lay.total) stream[e] = ief16_stream_value(net0, m, e);
-        if (e < IEF16_AUX_FLOATS)
-            aux[e] = e < 64 ? net0.w4[e] : (e == 64 ? net0.b4[0] : 0.f);
-        return;
-    }
     if (lay.mode == LIDF_MODE_CHAIN16 || lay.mode == LIDF_MODE_CHAIN16_H) {
         const int gf = 16 * m.nt;
         if (e < lay.total)
             stream[e] = lay.mode == LIDF_MODE_CHAIN16 ? chain16_stream_value(net0, m, e) : chain16h_stream_value(net0, m, e);
-        if (e < gf + 8) aux[e] = e < gf ? net0.w4[e] : (e == gf ? net0.b4[0] : 0.f);
+        if (e < lidf_chain16_aux_floats(m.nt)) aux[e] = e < gf ? net0.w4[e] : (e == gf ? net0.b4[0] : 0.f);
         return;
     }
     if (e < lay.total) stream[e] = stream_value(lay, net0, net1, m, e);

@@ -231,7 +231,10 @@ def test_matrix_shorthands_and_split_f16_pieces_have_one_copy():
     """The matrix-instruction shorthands, the output activation, the leaky ReLUs and the split-f16 pieces
     are numerical contracts (the float64 tests pin their arithmetic): csrc/lidf_mma.h holds the only
     definition of each, lidf_device.h the only revolution-reduced sin/cos, and every kernel file that
-    uses a shorthand includes the header (directly or through lidf_chain16.h)."""
+    uses a shorthand includes the header (directly or through lidf_chain16.h). The chained 16-row decoders likewise:
+    lidf_chain16.h holds the only fetch / range / ring step / tile body / kernel body / launch guard, lidf_device.h the
+    only length formulas of their stream (packers, host sizes and kernels must agree on them), and the stage-2
+    decoder's own copies of all of these are gone."""
     import glob
     csrc = os.path.join(ROOT, "implicit_depth_amd", "csrc")
 
@@ -244,9 +247,11 @@ def test_matrix_shorthands_and_split_f16_pieces_have_one_copy():
     assert len(files) >= 28
     macros = r"(?:MFMA|MFMA16|MFMAH|MFMA32H|SCHED_FENCE|LDQ)"
     owned = {"lidf_mma.h": r"out_act\w*|lrelu1|lrelu4|hpiece|pack2|split1|split2|tile_feature|prep_pairs\w*",
-             "lidf_device.h": r"to_rev\w*|rev_sincos\w*"}
-    n_defs = {"lidf_mma.h": 9, "lidf_device.h": 2}
-    literals = {"0.99f": [], "0.15915493667125702f": []}
+             "lidf_device.h": r"to_rev\w*|rev_sincos\w*|lidf_chain16h?_(?:kq|l1_quads|pass_quads|ring|aux_floats)",
+             "lidf_chain16.h": r"c16_\w+"}
+    n_defs = {"lidf_mma.h": 9, "lidf_device.h": 2 + 6, "lidf_chain16.h": 6}
+    literals = {"0.99f": [], "0.15915493667125702f": [], "T1 * T2 + T1 / 4": []}
+    gone = r"\b(?:Ief16Args|ief16_\w+|IEF16_\w+|lidf_launch_ief16|LIDF_MODE_IEF16|LIDF_IEF16_SLOTS|C16H?_NEXT)\b"
     dup, bare = [], []
     for p in files:
         s, name = code(p), os.path.basename(p)
@@ -264,12 +269,16 @@ def test_matrix_shorthands_and_split_f16_pieces_have_one_copy():
         for lit in literals:
             if lit in open(p).read():
                 literals[lit].append(name)
+        dup += ["%s: %s" % (name, g) for g in re.findall(gone, open(p).read())]
         if p.endswith(".hip") and re.search(r"\b%s\s*\(" % macros, s):
             if not re.search(r'#include "lidf_(?:mma|chain16)\.h"', s):
                 bare.append(name)
     assert not dup, dup
     assert os.path.join(csrc, "lidf_mma.h") in files and not bare, bare   # a shorthand used without the header
-    assert literals == {"0.99f": ["lidf_mma.h"], "0.15915493667125702f": ["lidf_device.h"]}, literals
+    assert literals == {"0.99f": ["lidf_mma.h"], "0.15915493667125702f": ["lidf_device.h"],
+                        "T1 * T2 + T1 / 4": ["lidf_device.h"]}, literals
+    kernels = re.findall(r"__global__[^;{]*?\b(lidf_(?:ief16|chain16h?)_kernel)\s*\(", "".join(code(p) for p in files))
+    assert sorted(kernels) == ["lidf_chain16_kernel", "lidf_chain16h_kernel", "lidf_ief16_kernel"], kernels
     assert '#include "lidf_mma.h"' in code(os.path.join(csrc, "lidf_chain16.h"))
     assert '#include "lidf_launch.h"' in code(os.path.join(csrc, "lidf_mma.h"))
 
