@@ -7,7 +7,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 SOURCES = ["lidf_points.hip", "lidf_points_h.hip", "lidf_rows_h.hip", "lidf_linear.hip", "lidf_linear_s.hip", "lidf_linear_x.hip", "lidf_linear_sx.hip", "lidf_aux.hip", "lidf_frame.hip", "lidf_refine.hip", "lidf_train.hip", "lidf_train_widths.hip", "lidf_dgrad.hip", "lidf_pointnet.hip", "lidf_pointnet_train.hip", "lidf_chain16.hip", "lidf_chain16_h.hip", "lidf_loss.hip", "lidf_select.hip", "lidf_sample.hip", "lidf_api.hip"]
-HEADERS = ["lidf_device.h", "lidf_launch.h", "lidf_carve.h", "lidf_mma.h", "lidf_chain16.h", "lidf_linear_kernel.inc", "lidf_api_refine_train.inc", "lidf_api_pointnet_train.inc", os.path.join(ROOT, "include", "lidf_hip.h")]
+HEADERS = ["lidf_device.h", "lidf_launch.h", "lidf_carve.h", "lidf_mma.h", "lidf_chain16.h", "lidf_split32.h", "lidf_linear_kernel.inc", "lidf_api_refine_train.inc", "lidf_api_pointnet_train.inc", os.path.join(ROOT, "include", "lidf_hip.h")]
 LIB = os.path.join(HERE, "liblidf_hip.so")
 
 

@@ -1,6 +1,6 @@
 // lidf_mma.h — what the matrix kernels' files share, one definition each: the matrix-instruction, scheduling-fence and
 // buffer-load shorthands, the decoders' output activation and leaky ReLUs, and the pieces of the split-f16 arithmetic
-// (w*x ~= wh*xh + wh*xl + wl*xh on f16 pieces with f32 accumulation; lidf_points_h.hip and lidf_rows_h.hip, whose
+// (w*x ~= wh*xh + wh*xl + wl*xh on f16 pieces with f32 accumulation; the kernels over lidf_split32.h, whose
 // float64 twin is tests/split_f16_ref.py). Several of these are numerical contracts that the float64 tests pin.
 #pragma once
 #include "lidf_launch.h"
@@ -20,7 +20,7 @@ typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 #define LDQ(rs, voff, soff) \
     __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128((rs), (voff), (soff), 0))
 
-// the weight stream of the two split-f16 feeds reaches the wavefronts through LDS in chunks
+// the weight stream of the split-f16 feed (lidf_split32.h) reaches the wavefronts through LDS in chunks
 #define CH_QUADS 16
 #define CH_ELEMS (CH_QUADS * 64)  // f32x4 elements per chunk buffer
 #define NBUF 3
@@ -68,11 +68,24 @@ __device__ __forceinline__ _Float16 hpiece(float w, int part) {
     return (_Float16)(r - (float)lo);
 }
 
-// element e of the split-f16 packers' aux array, LIDF_AUX_FLOATS floats per net: w4 by (half, register) of the two
-// layer-3 tiles, b4 at [64]
-__device__ __forceinline__ void pack_aux_h(const NetW* nets, const long long e, float* aux) {
+// the IEF term of layer 1, W1[:, D:D+16] (wenc*off + benc) = u*off + c: row `out` of u and of c (the packers)
+__device__ __forceinline__ float ief_u(const NetW& n, int out) {
+    float acc = 0.f;
+    for (int j = 0; j < 16; ++j) acc += n.w1[(size_t)out * n.ld1 + n.dcore + j] * n.wenc[j];
+    return acc;
+}
+__device__ __forceinline__ float ief_c(const NetW& n, int out) {
+    float acc = 0.f;
+    for (int j = 0; j < 16; ++j) acc += n.w1[(size_t)out * n.ld1 + n.dcore + j] * n.benc[j];
+    return acc;
+}
+
+// element e of the split-f16 packer's aux array, LIDF_AUX_FLOATS floats per net: w4 by (half, register) of the two
+// layer-3 tiles, b4 at [64]. (The two nets by reference, selected per element: a NetW[2] copy indexed by a runtime
+// value lives in scratch.)
+__device__ __forceinline__ void pack_aux_h(const NetW& net0, const NetW& net1, const long long e, float* aux) {
     const int sec = (int)e / LIDF_AUX_FLOATS, i = (int)e % LIDF_AUX_FLOATS;
-    const NetW& n = nets[sec];
+    const NetW& n = sec ? net1 : net0;
     float v = 0.f;
     if (i < 64) {
         const int half = i / 32, s = i % 32;

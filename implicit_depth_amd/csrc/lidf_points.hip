@@ -51,18 +51,7 @@ __device__ __forceinline__ int k_to_feature(int s, int half) {
     return 32 * T + (r & 3) + 8 * (r >> 2) + 4 * half;
 }
 
-__device__ __forceinline__ float ief_u(const NetW& n, int out) {
-    float acc = 0.f;
-    for (int j = 0; j < 16; ++j) acc += n.w1[(size_t)out * n.ld1 + n.dcore + j] * n.wenc[j];
-    return acc;
-}
-__device__ __forceinline__ float ief_c(const NetW& n, int out) {
-    float acc = 0.f;
-    for (int j = 0; j < 16; ++j) acc += n.w1[(size_t)out * n.ld1 + n.dcore + j] * n.benc[j];
-    return acc;
-}
-
-// (the two nets by reference, selected per element: a NetW[2] copy indexed by a runtime value lived in scratch —
+// (ief_u / ief_c: lidf_mma.h. The two nets by reference, selected per element: a NetW[2] copy indexed by a runtime value lived in scratch —
 // 208 bytes per lane in every pack launch)
 __device__ float stream_value(const StreamLayout& lay, const NetW& net0, const NetW& net1, const L1Map& m, int e) {
     const int net = e / (lay.net_quads * 256);

@@ -25,17 +25,17 @@
 // instead of holding 128 registers across the pass.
 //
 // Weight stream ("H" layout): one section of 288 quads (1 KiB: 64 lanes x 8 halves) per decoder,
-// in exactly the order pass_desc() gives; an IEF decoder's section is consumed once per
-// iteration. The four wavefronts of a workgroup consume the stream in lockstep; it is staged once
-// per workgroup through LDS in chunks of 16 quads (3 rotating buffers, one s_barrier per chunk,
-// global loads issued one chunk ahead), and each wavefront keeps a 4-quad register ring of
-// ds_read_b128 in flight.
+// in exactly the order PointsH::desc() gives; an IEF decoder's section is consumed once per
+// iteration. It reaches the matrix instructions through the feed of lidf_split32.h, which also holds
+// the section's tail, the steps of layers 2 to 4 and the packer that this kernel shares with
+// lidf_rows_h.hip.
 //
 // Three instantiations of one body (PointsForm): the two-net launch over all pairs, one net of the
 // two-net stream and tables over all pairs (offsets for the selected pairs only: prob_dec), and the
 // list form of that (offset_dec on the one-pair-per-ray list, where every row is its own ray).
 #include "lidf_launch.h"
 #include "lidf_mma.h"
+#include "lidf_split32.h"
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -65,193 +65,60 @@
 #define LIDF_H_GRAB 2
 
 // ------------------------------------------------------------------------------------------------
-// Order of a decoder's section (shared by the packer and the kernel)
+// The kernel's policy (lidf_split32.h): its feed, the order of a decoder's section, its layer-1 quads
 // ------------------------------------------------------------------------------------------------
-enum { K_B2 = 0, K_L1, K_XA, K_XB, K_L2, K_B3, K_L3, K_PAD };
-struct QD {
-    int kind;
-    int t;    // output tile
-    int T;    // layer 1 / u: the H1 tile produced; layers 2, 3: the input tile consumed
-    int sub;  // layer 1: k-step; layers 2, 3: k-sub-step inside the input tile
-    int lo;   // 0: high pieces of the weights, 1: low pieces
-    int j;    // ordinal of the (hi, lo) pair inside its segment
-};
-__host__ __device__ constexpr QD l1u_desc(int T, int r) {
-    if (r < 2 * NK1) return {K_L1, 0, T, r >> 1, r & 1, r >> 1};
-    return {r == 2 * NK1 ? K_XA : K_XB, 0, T, 0, 0, 0};
-}
-__host__ __device__ constexpr QD pass_desc(int s) {
-    constexpr int L1U = 2 * NK1 + 2;
-    if (s < 4) return {K_B2, s, 0, 0, 0, 0};
-    s -= 4;
-    if (s < L1U) return l1u_desc(0, s);
-    s -= L1U;
-    if (s < 7 * (L1U + 16)) {
-        const int T = s / (L1U + 16);
-        int r = s % (L1U + 16);
-        if (r < L1U) return l1u_desc(T + 1, r);  // layer 1 runs one tile ahead of layer 2
-        r -= L1U;
-        const int lo = r & 1, j = r >> 1;
-        return {K_L2, j & 3, T, j >> 2, lo, j};
-    }
-    s -= 7 * (L1U + 16);
-    if (s < 16) {
-        const int lo = s & 1, j = s >> 1;
-        return {K_L2, j >> 1, 7, j & 1, lo, j};  // last segment: tile-major, tiles finish one by one
-    }
-    s -= 16;
-    if (s < 2) return {K_B3, s, 0, 0, 0, 0};
-    s -= 2;
-    if (s < 32) {
-        const int T = s / 8, r = s % 8, lo = r & 1, j = r >> 1;
-        if (T < 3) return {K_L3, j & 1, T, j >> 1, lo, j};
-        return {K_L3, j >> 1, T, j & 1, lo, j};
-    }
-    return {K_PAD, 0, 0, 0, 0, 0};
-}
-static_assert(4 + 8 * (2 * NK1 + 2) + 8 * 16 + 2 + 32 <= PASS_QUADS, "section size");
-static_assert(PASS_QUADS % CH_QUADS == 0, "sections are whole chunks");
-static_assert(PASS_QUADS % RING_D == 0 && CH_QUADS - RING_D > 6, "ring slots are static; ring reads of the next chunk start after the barrier");
+struct PointsH {
+    static constexpr int PASS = PASS_QUADS, RING = RING_D;
+    // The staged chunk is published at position 4 and the barrier stands at position 6, behind lgkmcnt(2): the ring
+    // reads of positions 5 and 6 were issued after the four writes, so the writes have landed once at most two
+    // operations are outstanding, and the ring need not drain.
+    static constexpr int PUBLISH_Q = 4, BARRIER_Q = 6, BARRIER_LGKM = 2;
+    static constexpr bool L1_PREFIX = false, TILE_COUNTER = true;
+    static constexpr int L1U = 2 * NK1 + 2;   // quads of one layer-1 tile: NK1 (hi, lo) pairs and the two mixed steps
 
-// ------------------------------------------------------------------------------------------------
-// Packer: one thread per f16 element.
-// ------------------------------------------------------------------------------------------------
-__device__ _Float16 stream_value_h(const StreamLayout& lay, const NetW* nets, const L1Map& m,
-                                   long long e) {
-    const int per_net = lay.net_quads * 512;
-    const int net = (int)(e / per_net);
-    e %= per_net;
-    const NetW& n = nets[net];
-    const int quad = (int)(e / 512);
-    const int lane = (int)(e % 512) / 8, i = (int)(e & 7);
-    const int half = lane >> 5, o = lane & 31;
-    const QD d = pass_desc(quad);
-    switch (d.kind) {
-        case K_L1: {
-            // k-step ks: 4 (octave, coordinate) combos 4ks..4ks+3, element 2c' = sin, 2c'+1 = cos;
-            // lanes 0..31 weight the enter position's embedding, lanes 32..63 the leave position's
+    __host__ __device__ static constexpr QD l1u_desc(int T, int r) {
+        if (r < 2 * NK1) return {K_L1, 0, T, r >> 1, r & 1, r >> 1};
+        return {r == 2 * NK1 ? K_XA : K_XB, 0, T, 0, 0, 0};
+    }
+    __host__ __device__ static constexpr QD desc(int s) {
+        if (s < 4) return {K_B2, s, 0, 0, 0, 0};
+        s -= 4;
+        if (s < L1U) return l1u_desc(0, s);
+        s -= L1U;
+        if (s < 7 * (L1U + 16)) {
+            const int T = s / (L1U + 16), r = s % (L1U + 16);
+            if (r < L1U) return l1u_desc(T + 1, r);  // layer 1 runs one tile ahead of layer 2
+            return l2_desc(T, r - L1U);
+        }
+        return tail_desc(s - 7 * (L1U + 16));
+    }
+
+    __device__ static _Float16 l1_value(const NetW& n, const L1Map& m, const QD d, const int half, const int o,
+                                        const int i) {
+        const int col0 = half ? m.leave_c0 : m.enter_c0;   // lanes 0..31 weight the enter position, 32..63 the leave position
+        const float* w = n.w1 + (size_t)(32 * d.T + o) * n.ld1;
+        if (d.kind == K_L1) {
+            // k-step ks: 4 (octave, coordinate) combos 4ks..4ks+3, element 2c' = sin, 2c'+1 = cos
             const int c = 4 * d.sub + (i >> 1), oct = c / 3, dd = c % 3;
             if (oct >= m.L) return (_Float16)0.f;
-            const int col = (half ? m.leave_c0 : m.enter_c0) + 3 + 6 * oct + 3 * (i & 1) + dd;
-            return hpiece(n.w1[(size_t)(32 * d.T + o) * n.ld1 + col], d.lo);
+            return hpiece(w[col0 + 3 + 6 * oct + 3 * (i & 1) + dd], d.lo);
         }
-        case K_XA: {
-            // raw x, y, z: high weight pieces twice, against (xh, yh, zh, xl, yl, zl, 0, 0)
-            if (i >= 6) return (_Float16)0.f;
-            const int col = (half ? m.leave_c0 : m.enter_c0) + i % 3;
-            return hpiece(n.w1[(size_t)(32 * d.T + o) * n.ld1 + col], 0);
-        }
-        case K_XB: {
-            // (wlx, wly, wlz, uh, ray_hi, ray_lo, uh, ul) against (xh, yh, zh, vh, m, m, vl, vh):
-            // low weight pieces of x, y, z; the IEF term u*val (lanes 0..31 only); elements 4, 5
-            // are filled in by the kernel with the raypart row of this half's ray
-            if (i < 3) {
-                const int col = (half ? m.leave_c0 : m.enter_c0) + i;
-                return hpiece(n.w1[(size_t)(32 * d.T + o) * n.ld1 + col], 1);
-            }
-            if (i == 4 || i == 5 || half != 0 || !n.is_ief) return (_Float16)0.f;
-            const int out = 32 * d.T + o;
-            float u = 0.f;
-            for (int j = 0; j < 16; ++j) u += n.w1[(size_t)out * n.ld1 + n.dcore + j] * n.wenc[j];
-            return hpiece(u, i == 7 ? 1 : 0);
-        }
-        case K_B2:
-            return half == 0 && i < 3 ? hpiece(n.b2[32 * d.t + o], i) : (_Float16)0.f;
-        case K_B3:
-            return half == 0 && i < 3 ? hpiece(n.b3[32 * d.t + o], i) : (_Float16)0.f;
-        case K_L2:
-            return hpiece(n.w2[(size_t)(32 * d.t + o) * LIDF_H1 + 32 * d.T +
-                               tile_feature(8 * d.sub + i, half)], d.lo);
-        case K_L3:
-            return hpiece(n.w3[(size_t)(32 * d.t + o) * LIDF_H2 + 32 * d.T +
-                               tile_feature(8 * d.sub + i, half)], d.lo);
-        default:
-            return (_Float16)0.f;
+        if (d.kind == K_XA)   // raw x, y, z: high weight pieces twice, against (xh, yh, zh, xl, yl, zl, 0, 0)
+            return i < 6 ? hpiece(w[col0 + i % 3], 0) : (_Float16)0.f;
+        // K_XB: (wlx, wly, wlz, uh, ray_hi, ray_lo, uh, ul) against (xh, yh, zh, vh, m, m, vl, vh): low weight pieces
+        // of x, y, z; the IEF term u*val (lanes 0..31 only); elements 4, 5 are filled in by the kernel with the
+        // raypart row of this half's ray
+        if (i < 3) return hpiece(w[col0 + i], 1);
+        if (i == 4 || i == 5 || half != 0 || !n.is_ief) return (_Float16)0.f;
+        return hpiece(ief_u(n, 32 * d.T + o), i == 7 ? 1 : 0);
     }
-}
-
-__global__ void lidf_pack_h_kernel(StreamLayout lay, NetW net0, NetW net1, L1Map m,
-                                   _Float16* stream, float* aux) {
-    if (lay.guard && lay.guard->dirty == 0) return;   // guarded packing: fingerprint unchanged
-    NetW nets[2] = {net0, net1};
-    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < (long long)lay.total * 2) stream[e] = stream_value_h(lay, nets, m, e);
-    if (e < lay.nets * LIDF_AUX_FLOATS) pack_aux_h(nets, e, aux);
-    if (e == 0) ((int*)aux)[lay.nets * LIDF_AUX_FLOATS] = 0;  // tile counter of lidf_points_h_kernel
-}
+};
+static_assert(section_fits<PointsH>(4 + 8 * PointsH::L1U + 7 * 16), "section size");
 
 extern "C" hipError_t lidf_launch_pack_h(const StreamLayout& lay, const NetW& n0, const NetW& n1,
                                          const L1Map& m, float* stream, float* aux,
                                          hipStream_t st) {
-    const long long total = (long long)lay.total * 2;
-    const int blocks = (int)((total + 255) / 256);
-    hipLaunchKernelGGL(lidf_pack_h_kernel, dim3(blocks), dim3(256), 0, st, lay, n0, n1, m,
-                       (_Float16*)stream, aux);
-    return hipGetLastError();
-}
-
-// The stream feed of one wavefront.
-struct Feed {
-    f32x4 ring[RING_D];  // next RING_D quads
-    f32x4 stage[4];  // this wavefront's quarter of the chunk after the next one, in flight
-    int cur, nxt;    // element index (f32x4 units) of this lane in the current / next LDS buffer
-    int nb;          // index of the next buffer
-    int s_net, s_pass, s_idx;  // sequencer: which chunk the next global load fetches
-};
-
-struct FeedCfg {
-    __amdgpu_buffer_rsrc_t srs;
-    int vq;         // lane * 16
-    int wave, lane;
-    int net_bytes, nets;
-    int npass0, npass1;
-};
-
-__device__ __forceinline__ void feed_issue(Feed& f, const FeedCfg& c) {
-    const int off = f.s_net * c.net_bytes + f.s_idx * (CH_QUADS * 1024) + c.wave * 4096;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) f.stage[j] = LDQ(c.srs, c.vq + j * 1024, off);
-    // advance the sequencer: a decoder's section is consumed once per pass
-    if (++f.s_idx == PASS_QUADS / CH_QUADS) {
-        f.s_idx = 0;
-        const int np = f.s_net ? c.npass1 : c.npass0;
-        if (++f.s_pass == np) {
-            f.s_pass = 0;
-            if (++f.s_net == c.nets) f.s_net = 0;
-        }
-    }
-}
-
-// position Q (0..15) of the current chunk: returns the quad, refills the ring four quads ahead,
-// and at mid-chunk publishes the staged chunk to LDS and starts the next global fetch
-__device__ __forceinline__ f32x4 feed_take(Feed& f, const FeedCfg& c, f32x4* sb, const int Q,
-                                            const int slot) {
-    // slot = (position in the section) % RING_D; sections are multiples of RING_D quads
-    const f32x4 a = f.ring[slot];
-    if (Q + RING_D < CH_QUADS)
-        f.ring[slot] = sb[f.cur + (Q + RING_D) * 64];
-    else
-        f.ring[slot] = sb[f.nxt + (Q + RING_D - CH_QUADS) * 64];
-    if (Q == 4) {
-        // The buffer written here last held the chunk before the previous one: every wavefront
-        // finished reading it before it passed the previous barrier.
-#pragma unroll
-        for (int j = 0; j < 4; ++j) sb[f.nb * CH_ELEMS + (4 * c.wave + j) * 64 + c.lane] = f.stage[j];
-        feed_issue(f, c);
-    }
-    if (Q == 6) {
-        // LDS operations complete in order and at least two (the ring reads of positions 5 and 6)
-        // were issued after the four writes of position 4: once at most two are outstanding the
-        // writes have landed, and the ring need not drain. The first read of the next buffer
-        // comes at position CH_QUADS - RING_D > 6.
-        asm volatile("s_waitcnt lgkmcnt(2)\n\ts_barrier" ::: "memory");
-    }
-    if (Q == CH_QUADS - 1) {
-        f.cur = f.nxt;
-        f.nb = f.nb == NBUF - 1 ? 0 : f.nb + 1;
-        f.nxt = f.nb * CH_ELEMS + c.lane;
-    }
-    return a;
+    return launch_pack_h<PointsH>(lay, n0, n1, m, stream, aux, st);
 }
 
 // FORM_ALL: both nets of the stream, tables of nets * 256 floats per row (the default launch).
@@ -286,21 +153,16 @@ __device__ long long g_chunk_ticks[32];
 #define CHUNK_PROF(q, s_)
 #endif
 template <int FORM>
-__device__ __forceinline__ float decoder_pass_h(Feed& f, const FeedCfg& c, f32x4* sb,
+__device__ __forceinline__ float decoder_pass_h(Feed<PointsH>& f, const FeedCfg& c, f32x4* sb,
                                                 const TileCtx& tc, const f32x4 (&pbh)[NK1],
                                                 const f32x4 xaB, const float xyB, const _Float16 zh,
                                                 const float val, const int h, const int col,
                                                 const float* __restrict__ ax) {
-    const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f,
-                           0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    const _Float16 one = (_Float16)1.f, hz = (_Float16)0.f;
-    f32x4 onesB = zero4, xbB = zero4;
+    const _Float16 one = (_Float16)1.f;
+    const f32x4 onesB = ones_operand(h);
+    f32x4 xbB = zero4;
     xbB[0] = xyB;
-    if (!h) {
-        onesB[0] = pack2(one, one);
-        onesB[1] = pack2(one, hz);
-    }
     {
         // (xh, yh, zh, vh, m, m, vl, vh): raw position, IEF input value, ray membership
         const _Float16 vh = (_Float16)val;
@@ -312,13 +174,9 @@ __device__ __forceinline__ float decoder_pass_h(Feed& f, const FeedCfg& c, f32x4
 
     f32x16 a1[2];               // layer-1 tiles, ping-pong: accumulating / being split
     float rpv[2];               // raypart value of this lane's row, same ping-pong
-    f32x16 acc2[4], acc3[2];
     f32x4 bh[2], bl[2];         // split H1 tile, [k-sub-step] (single buffer, see below)
-    f32x4 gh[4][2], gl[4][2];   // split H2 tiles
     f32x4 pl_cur = zero4, pl_nxt = zero4;  // low pieces of the embedding operand, from LDS
-    f32x4 w4[8];
-    float b4 = 0.f;
-    float ys[4] = {0.f, 0.f, 0.f, 0.f};
+    TAIL32_STATE;               // layers 2 to 4
 
     // voxel part of tile T straight into the accumulator layout; ray part of this lane's row
     auto gather = [&](const int T) {
@@ -362,11 +220,9 @@ __device__ __forceinline__ float decoder_pass_h(Feed& f, const FeedCfg& c, f32x4
 #pragma unroll
     for (int s = 0; s < PASS_QUADS; ++s) {
         const int Q = s % CH_QUADS;
-        const QD d = pass_desc(s);
-        const f32x4 A = feed_take(f, c, sb, Q, s % RING_D);
-        if (d.kind == K_B2) {
-            acc2[d.t] = MFMAH(A, onesB, zero16);
-        } else if (d.kind == K_L1) {
+        const QD d = PointsH::desc(s);
+        const f32x4 A = feed_take(f, c, sb, Q);
+        if (d.kind == K_L1) {
             f32x16& acc = a1[d.T & 1];
             if (!d.lo) {
                 acc = MFMAH(A, pbh[d.sub], acc);
@@ -416,8 +272,8 @@ __device__ __forceinline__ float decoder_pass_h(Feed& f, const FeedCfg& c, f32x4
                     acc = MFMAH(xa, xb, acc);
                 }
             }
-        } else if (d.kind == K_L2) {
-            if (!d.lo) {
+        } else {
+            if (d.kind == K_L2 && !d.lo) {
                 // the tile after next can start loading: its accumulator is free once the split
                 // of tile T (same parity) is done
                 if (d.j == 0 && d.T + 2 < 8) {
@@ -428,46 +284,12 @@ __device__ __forceinline__ float decoder_pass_h(Feed& f, const FeedCfg& c, f32x4
                 // tile 7 has no layer-1 segment after it to hide its split behind, and a second
                 // operand buffer just for it would push the kernel into spilling
                 if (d.T == 7 && d.j == 0) prep_pairs(0, 8, a1[1], bh, bl);
-                acc2[d.t] = MFMAH(A, bh[d.sub], acc2[d.t]);
-                acc2[d.t] = MFMAH(A, bl[d.sub], acc2[d.t]);
-                if (d.T == 7) {
-                    // last segment (tile-major): output tiles complete one by one
-                    if (d.j >= 2 && d.j < 6) prep_pairs(2 * (d.j - 2), 2 * (d.j - 2) + 2, acc2[0], gh[0], gl[0]);
-                    if (d.j >= 6) prep_pairs(2 * (d.j - 6), 2 * (d.j - 6) + 2, acc2[1], gh[1], gl[1]);
-                }
-            } else {
-                acc2[d.t] = MFMAH(A, bh[d.sub], acc2[d.t]);
             }
-        } else if (d.kind == K_B3) {
-            acc3[d.t] = MFMAH(A, onesB, zero16);
-            if (d.t == 0) b4 = ax[64];
-        } else if (d.kind == K_L3) {
-            if (!d.lo) {
-                // operands of the tail (layer 4), fetched late and in two halves so that they do not
-                // hold 32 registers through layer 3; their latency still hides behind it
-                if (d.T == 2 && d.j == 0) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) w4[i] = *(const f32x4*)(ax + h * 32 + 4 * i);
-                }
-                if (d.T == 3 && d.j == 0) {
-#pragma unroll
-                    for (int i = 4; i < 8; ++i) w4[i] = *(const f32x4*)(ax + h * 32 + 4 * i);
-                }
-                acc3[d.t] = MFMAH(A, gh[d.T][d.sub], acc3[d.t]);
-                acc3[d.t] = MFMAH(A, gl[d.T][d.sub], acc3[d.t]);
-                // pending splits: segment T handles the second half of H2[T+1] (first two pairs)
-                // and the first half of H2[T+2] (last two pairs)
-                if (d.T < 3 && d.j < 2) prep_pairs(4 + 2 * d.j, 6 + 2 * d.j, acc2[d.T + 1], gh[d.T + 1], gl[d.T + 1]);
-                if (d.T < 2 && d.j >= 2) prep_pairs(2 * (d.j - 2), 2 * (d.j - 2) + 2, acc2[d.T + 2], gh[d.T + 2], gl[d.T + 2]);
-                if (d.T == 3 && d.j >= 2) {
-                    // acc3[0] is complete: its half of layer 4 runs behind acc3[1]'s last steps
-#pragma unroll
-                    for (int r = 8 * (d.j - 2); r < 8 * (d.j - 2) + 8; ++r)
-                        ys[r & 3] = fmaf(w4[r >> 2][r & 3], lrelu1(acc3[0][r]), ys[r & 3]);
-                }
-            } else {
-                acc3[d.t] = MFMAH(A, gh[d.T][d.sub], acc3[d.t]);
-            }
+            // operands of layer 4, fetched late and in two halves so that they do not hold 32 registers
+            // through layer 3; their latency still hides behind it
+            if (d.kind == K_L3 && !d.lo && d.j == 0 && d.T >= 2) tail_load_w4(w4, ax, h, 4 * (d.T - 2), 4 * (d.T - 1));
+            tail_step(TAIL32_ARGS, d, A, onesB, bh, bl);
+            if (d.kind == K_B3 && d.t == 0) b4 = ax[64];
         }
         CHUNK_PROF(Q, s)
         SCHED_FENCE();
@@ -475,15 +297,7 @@ __device__ __forceinline__ float decoder_pass_h(Feed& f, const FeedCfg& c, f32x4
 #ifdef LIDF_PROFILE_CHUNKS
     if (blockIdx.x == 0 && threadIdx.x == 0) { g_chunk_ticks[31] += 1; }
 #endif
-    // layer 4 (64 -> 1) on the VALU, second tile; halves combined with one cross-half shuffle
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int sidx = 16 + r;
-        ys[r & 3] = fmaf(w4[sidx >> 2][sidx & 3], lrelu1(acc3[1][r]), ys[r & 3]);
-    }
-    float y = (ys[0] + ys[1]) + (ys[2] + ys[3]);
-    y += __shfl_xor(y, 32);
-    return y + b4;
+    return tail_finish(TAIL32_ARGS, b4);
 }
 
 struct GeoH {
@@ -499,16 +313,7 @@ __global__ void __launch_bounds__(256, 2) lidf_points_h_kernel(PointsArgs a) {
     const int h = lane >> 5;
     const int col = lane & 31;
 
-    FeedCfg c;
-    c.srs = __builtin_amdgcn_make_buffer_rsrc((void*)a.stream, 0, a.nets * a.net_quads * 1024,
-                                              0x00020000);
-    c.vq = lane * 16;
-    c.wave = wave;
-    c.lane = lane;
-    c.net_bytes = a.net_quads * 1024;
-    c.nets = a.nets;
-    c.npass0 = a.npass[0];
-    c.npass1 = a.npass[1];
+    const FeedCfg c = feed_cfg(a, lane, wave);
 
     // 128-point tiles are handed out dynamically, LIDF_H_GRAB at a time, from a counter the packer
     // zeroes: the two workgroups of a CU do not progress at the same rate (the older one wins the
@@ -523,21 +328,8 @@ __global__ void __launch_bounds__(256, 2) lidf_points_h_kernel(PointsArgs a) {
     float* const stash = (float*)(sb + LDS_STREAM_ELEMS + 4 * NK1 * 64 + 1) +
                          wave * (LDS_STASH_FLOATS * 64) + lane;
 
-    // prologue: chunk 0 into buffer 0, chunk 1 in flight
-    Feed f;
-    f.s_net = 0;
-    f.s_pass = 0;
-    f.s_idx = 0;
-    feed_issue(f, c);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) sb[(4 * wave + j) * 64 + lane] = f.stage[j];
-    feed_issue(f, c);
-    __syncthreads();
-    f.cur = lane;
-    f.nb = 1;
-    f.nxt = CH_ELEMS + lane;
-#pragma unroll
-    for (int i = 0; i < RING_D; ++i) f.ring[i] = sb[f.cur + i * 64];
+    Feed<PointsH> f;
+    feed_start(f, c, sb);
 
     // addresses = wave-uniform base (SGPRs) + a 32-bit lane offset: no 64-bit pointer registers
     auto load_idx = [&](long long tile, GeoH& g) {

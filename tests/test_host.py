@@ -234,7 +234,8 @@ def test_matrix_shorthands_and_split_f16_pieces_have_one_copy():
     uses a shorthand includes the header (directly or through lidf_chain16.h). The chained 16-row decoders likewise:
     lidf_chain16.h holds the only fetch / range / ring step / tile body / kernel body / launch guard, lidf_device.h the
     only length formulas of their stream (packers, host sizes and kernels must agree on them), and the stage-2
-    decoder's own copies of all of these are gone."""
+    decoder's own copies of all of these are gone. The split-f16 decoders on 32 x 32 tiles likewise: lidf_split32.h holds
+    the only stream feed, tail of the section order, steps of layers 2 to 4 and packer."""
     import glob
     csrc = os.path.join(ROOT, "implicit_depth_amd", "csrc")
 
@@ -248,8 +249,10 @@ def test_matrix_shorthands_and_split_f16_pieces_have_one_copy():
     macros = r"(?:MFMA|MFMA16|MFMAH|MFMA32H|SCHED_FENCE|LDQ)"
     owned = {"lidf_mma.h": r"out_act\w*|lrelu1|lrelu4|hpiece|pack2|split1|split2|tile_feature|prep_pairs\w*",
              "lidf_device.h": r"to_rev\w*|rev_sincos\w*|lidf_chain16h?_(?:kq|l1_quads|pass_quads|ring|aux_floats)",
-             "lidf_chain16.h": r"c16_\w+"}
-    n_defs = {"lidf_mma.h": 9, "lidf_device.h": 2 + 6, "lidf_chain16.h": 6}
+             "lidf_chain16.h": r"c16_\w+",
+             "lidf_split32.h": r"feed_(?:cfg|issue|start|take)|tail_(?:desc|load_w4|step|finish)|stream_value_[hr]|"
+                               r"lidf_pack_[hr]_kernel|launch_pack_h"}
+    n_defs = {"lidf_mma.h": 9, "lidf_device.h": 2 + 6, "lidf_chain16.h": 6, "lidf_split32.h": 11}
     literals = {"0.99f": [], "0.15915493667125702f": [], "T1 * T2 + T1 / 4": []}
     gone = r"\b(?:Ief16Args|ief16_\w+|IEF16_\w+|lidf_launch_ief16|LIDF_MODE_IEF16|LIDF_IEF16_SLOTS|C16H?_NEXT)\b"
     dup, bare = [], []
@@ -280,6 +283,7 @@ def test_matrix_shorthands_and_split_f16_pieces_have_one_copy():
     kernels = re.findall(r"__global__[^;{]*?\b(lidf_(?:ief16|chain16h?)_kernel)\s*\(", "".join(code(p) for p in files))
     assert sorted(kernels) == ["lidf_chain16_kernel", "lidf_chain16h_kernel", "lidf_ief16_kernel"], kernels
     assert '#include "lidf_mma.h"' in code(os.path.join(csrc, "lidf_chain16.h"))
+    assert '#include "lidf_mma.h"' in code(os.path.join(csrc, "lidf_split32.h"))
     assert '#include "lidf_launch.h"' in code(os.path.join(csrc, "lidf_mma.h"))
 
 
